@@ -14,12 +14,18 @@ float64 data.  Inputs are synthetic band-limited Gaussian maps made on the GPU b
                          only the spectra are gathered.  Reports realisations/s with a per-stage breakdown.
   --config c2 / c1 / ref 3x(5400x10800) lmax 4000 / 1x(1024x2048) lmax 512 / the reference's benchmark shape 1x(900x1800) lmax 750
 
-Prints ONE JSON line on rank 0 (driver contract); human-readable detail goes to stderr.  Besides the contract fields:
+Prints ONE JSON line on rank 0 (driver contract); human-readable detail goes to stderr.  A plain run sets up, warms up, times --steps
+steps and prints the line; besides the contract fields it carries what the timed steps themselves yield:
   roofline      the dominant kernel family (Legendre, FP64 FMA) from hipEvent stage timers inside the library
   fft_chain     the HBM-bound kernel family of the step (ring FFTs + theta resampling): algorithmic bytes / time / 8 TB/s
+--full adds, after the timed loop (never in `value`):
+  analysis_other_forms  the same round trip with the other analysis forms (N = 1, single map)
   fft           enmap.fft / ifft of one map component on the GPU with numpy.fft.fftn on the host cores beside it (N = 1)
   h2d_inclusive the round trip with the PCIe transfers of map and alm added (measured pinned-memory rate; never `value`)
+  accuracy      the HIP path against ducc0 itself when importable
   cpu_baseline  oracle/sht_port.c (+ scipy.fft) on a bounded sample on the host cores, or ducc0 itself when importable
+  configs       the other BASELINE configurations, a few steps each (behind the default --config c3 only)
+--dump-outputs DIR writes what the last timed step computed (alm and map; C_l for c5) to DIR/<name>.npy, a fixed seeded sample where large.
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -69,6 +75,30 @@ def emit(res):
 		import ctypes; ctypes.CDLL(None).fflush(None)
 	except Exception: pass
 	print(json.dumps(res), flush=True)
+
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: elements kept of an output larger than this (a C3 map is 2.8e9 values)
+
+def dump_index(n, k=DUMP_SAMPLE, seed=1234):
+	"""the fixed, seeded sample --dump-outputs keeps of a flat array of n elements: None (all of it) when n <= k, else sorted distinct
+	flat indices drawn with a seeded generator -- the same for every run and every build"""
+	if n <= k: return None
+	return np.unique(np.random.default_rng(seed).integers(0, n, size=k))
+
+def dump_outputs(outdir, arrays):
+	"""--dump-outputs: each named device tensor of the last timed step to outdir/<name>.npy, float64 (float32 stays float32), complex
+	values as a trailing (re, im) axis.  Whole when small; otherwise the dump_index sample of the flattened tensor, its flat indices in
+	outdir/<name>_index.npy.  At most DUMP_SAMPLE x (16 + 8) bytes per array (24 MB)."""
+	import torch
+	os.makedirs(outdir, exist_ok=True)
+	for name, t in arrays.items():
+		idx = dump_index(t.numel())
+		if idx is not None:
+			t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+			np.save(os.path.join(outdir, name+"_index.npy"), idx.astype(np.float64))
+		a = t.detach().cpu().numpy()
+		if np.iscomplexobj(a): a = np.stack([a.real, a.imag], -1)
+		np.save(os.path.join(outdir, name+".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+	log("outputs of the last timed step written to %s: %s" % (outdir, ", ".join(sorted(arrays))))
 
 def nalm(lmax): return (lmax+1)*(lmax+2)//2
 
@@ -360,6 +390,7 @@ def run_c5(args, torch, dist, rank, world, local, device, backend):
 	if world > 1:
 		t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
 		dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
+	if rank == 0 and args.dump_outputs: dump_outputs(args.dump_outputs, {"cl": cls[:nloc]})
 	stage_ms = {k: 0.0 for k in stages}
 	for r in range(len(evs)//7):      # per batch: six marks (before rand_alm, after rand_alm, after alm2map, after the FFT / spectrum loop, after map2alm, after alm2cl) + the inner FFT events
 		e = evs[7*r:7*r+7]
@@ -396,8 +427,8 @@ def run_c5(args, torch, dist, rank, world, local, device, backend):
 
 def run_sht(args, ctx):
 	"""One SHT configuration (args.config, args.steps, args.warmup): K timed round trips of map2alm + alm2map on device-resident maps; returns the
-	result line.  args.primary (default True): with the legs that belong to the headline line only (other analysis forms; host arrays, 2-D FFT and
-	CPU baseline unless args.no_cpu)."""
+	result line.  args.full and args.primary (default True): with the legs that belong to the headline line only (other analysis forms; host arrays,
+	2-D FFT and CPU baseline unless args.no_cpu)."""
 	from pixell_amd import curvedsky, enmap, sht, dist as pdist
 	torch, dist, rank, world, local, device, backend, force_pg = ctx.torch, ctx.dist, ctx.rank, ctx.world, ctx.local, ctx.device, ctx.backend, ctx.force_pg
 	primary = getattr(args, "primary", True)
@@ -494,6 +525,7 @@ def run_sht(args, ctx):
 	if world > 1 or force_pg:
 		t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
 		dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
+	if rank == 0 and args.dump_outputs: dump_outputs(args.dump_outputs, {"alm": alm_pp[(nstep[0]-1) % len(alm_pp)], "map": dmap.tensor})
 	ms_step = dt/args.steps*1e3
 	maps_total = ntot if batched else world
 	value = maps_total*args.steps/dt
@@ -504,7 +536,7 @@ def run_sht(args, ctx):
 	#   "weights": ring quadrature weights + adjoint synthesis, the reference's cyl route (curvedsky.py:852-861, 1068-1084), where the
 	#              grid has >= 2 lmax + 2 rings: three theta-resampling stages instead of five.
 	ana_forms = None
-	if primary and world == 1 and not batched and not os.environ.get("PXS_BENCH_NO_WEIGHTS"):
+	if args.full and primary and world == 1 and not batched and not os.environ.get("PXS_BENCH_NO_WEIGHTS"):
 		ana_forms = {}
 		for form in ["interpolant"]+(["weights"] if ny >= 2*lmax+2 else []):
 			try:
@@ -577,7 +609,7 @@ def run_sht(args, ctx):
 	if ranks_seen is not None: res["rccl_ranks_seen"] = ranks_seen; res["collective"] = gather.describe()
 	if rank == 0:
 		log("stage ms/step:", res["stage_ms_per_step"], " total %.1f ms/step" % ms_step)
-		if not args.no_cpu and world == 1:
+		if args.full and not args.no_cpu and world == 1:
 			try:
 				h2d, d2h = pcie_rates(torch, device)
 				t_io = (map_bytes+alm_bytes)/(h2d*1e9)+(map_bytes+alm_bytes)/(d2h*1e9)    # map in + alm out, alm in + map out
@@ -649,7 +681,7 @@ def secondary_legs(args, ctx):
 		("ref", dict(config="ref", steps=40, warmup=2))]
 	for name, kw in plan:
 		t0 = time.time()
-		leg = argparse.Namespace(**vars(args)); leg.config = kw["config"]; leg.steps = kw["steps"]; leg.warmup = kw["warmup"]; leg.no_cpu = True; leg.primary = False
+		leg = argparse.Namespace(**vars(args)); leg.config = kw["config"]; leg.steps = kw["steps"]; leg.warmup = kw["warmup"]; leg.no_cpu = True; leg.primary = False; leg.dump_outputs = None
 		try:
 			sht.clear_plans(); torch.cuda.empty_cache()
 			if "nbatch" in kw: os.environ["PXS_BENCH_NBATCH"] = str(kw["nbatch"])
@@ -678,8 +710,11 @@ def main():
 	ap.add_argument("--steps", type=int, default=3)
 	ap.add_argument("--warmup", type=int, default=1)
 	ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))      # (tqu: 16 T/Q/U maps in one call -- the batched spin-2 Legendre kernels; not a BASELINE configuration)
-	ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / fft / h2d legs")
-	ap.add_argument("--no-legs", action="store_true", help="skip the secondary configurations (`configs` block) after the headline loop")
+	ap.add_argument("--full", action="store_true", help="after the headline loop also run everything beside it: the other analysis forms, the host-array / PCIe / "
+		"2-D FFT / ducc0 / cpu_baseline legs and the secondary configurations (`configs`); without it a run only sets up, warms up, times the steps and prints the line")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a fixed, seeded sample of it where it is large) to DIR/<name>.npy")
+	ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline / fft / h2d legs")
+	ap.add_argument("--no-legs", action="store_true", help="with --full: skip the secondary configurations (`configs` block) after the headline loop")
 	ap.add_argument("--no-gather", action="store_true", help="skip the alm all-gather (N>1)")
 	ap.add_argument("--dry", action="store_true", help="rank plumbing only (launch, sharding, gather), no transforms: runs without a GPU over gloo")
 	args = ap.parse_args()
@@ -728,10 +763,10 @@ def main():
 	try:
 		t_all = time.time()
 		res = run_c5(args, torch, dist, rank, world, local, device, backend) if args.config == "c5" else run_sht(args, ctx)
-		# the other BASELINE configurations, after the headline loop: only beside the default headline (c3), so that `--config X` stays a
+		# --full: the other BASELINE configurations, after the headline loop: only beside the default headline (c3), so that `--config X` stays a
 		# short single-configuration run for profiling
 		# (PXS_BENCH_REHEARSE_LEGS=1: the legs behind another headline configuration -- two-rank rehearsals of the N > 1 path on a one-GPU box)
-		if ((args.config == "c3" and res["config"]["lmax"] == CONFIGS["c3"]["lmax"]) or os.environ.get("PXS_BENCH_REHEARSE_LEGS") == "1") and not args.no_legs and not os.environ.get("PXS_BENCH_NO_LEGS"):
+		if args.full and ((args.config == "c3" and res["config"]["lmax"] == CONFIGS["c3"]["lmax"]) or os.environ.get("PXS_BENCH_REHEARSE_LEGS") == "1") and not args.no_legs and not os.environ.get("PXS_BENCH_NO_LEGS"):
 			res["configs"] = secondary_legs(args, ctx)
 			res["configs_note"] = "secondary configurations run after the timed loop of the headline configuration, each on freshly built plans; never part of `value`"
 		res["bench_wall_s"] = round(time.time()-t_all, 1)

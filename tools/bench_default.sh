@@ -1,7 +1,7 @@
 #!/bin/bash
 # the driver's command (python bench.py, defaults) with its wall time; prints the headline and the `configs` block in short
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-r05b}; mkdir -p $O; cd $R; shift
-t0=$(date +%s.%N); python bench.py "$@" > $O/bench_default.json 2> $O/bench_default.err; rc=$?; t1=$(date +%s.%N)
+t0=$(date +%s.%N); python bench.py --full "$@" > $O/bench_default.json 2> $O/bench_default.err; rc=$?; t1=$(date +%s.%N)
 python -c "print(\"rc $rc wall %.1f s\" % ($t1 - $t0))"
 grep -E "stage ms|failed|Error|error|Traceback" $O/bench_default.err | cut -c1-220 | tail -20
 python - <<PY

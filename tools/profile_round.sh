@@ -3,11 +3,11 @@
 TAG=${1:-r05}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 PXS_REQUIRE_FULL=1 timeout 1800 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; tail -2 $O/pytest_gpu.log
-timeout 900 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err; tail -1 $O/bench_c3.err
-timeout 600 python bench.py --config c2 --no-cpu --steps 10 --warmup 2 > $O/bench_c2.json 2> $O/bench_c2.err; tail -1 $O/bench_c2.err
+timeout 900 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err; tail -1 $O/bench_c3.err
+timeout 600 python bench.py --full --config c2 --no-cpu --steps 10 --warmup 2 > $O/bench_c2.json 2> $O/bench_c2.err; tail -1 $O/bench_c2.err
 timeout 900 python bench.py --config c4 --no-cpu > $O/bench_c4.json 2> $O/bench_c4.err; tail -1 $O/bench_c4.err
 timeout 900 python bench.py --config c5 --no-cpu --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err; tail -1 $O/bench_c5.err
-timeout 300 python bench.py --config ref --no-cpu --steps 40 > $O/bench_ref.json 2> $O/bench_ref.err; tail -1 $O/bench_ref.err
+timeout 300 python bench.py --full --config ref --no-cpu --steps 40 > $O/bench_ref.json 2> $O/bench_ref.err; tail -1 $O/bench_ref.err
 PXS_BENCH_FORCE_PG=1 timeout 600 python bench.py --config c4 --no-cpu > $O/bench_c4_forcepg.json 2> $O/bench_c4_forcepg.err; tail -1 $O/bench_c4_forcepg.err
 # the N-rank launch path end to end on this one-GPU box: two ranks share the device, the gather goes through gloo (times mean nothing)
 PXS_BENCH_BACKEND=gloo PXS_BENCH_NBATCH=8 timeout 600 python bench.py --gpus 2 --config c4 --no-cpu --steps 1 --warmup 1 > $O/rehearsal_c4_2ranks_gloo.json 2> $O/rehearsal_c4.err; tail -2 $O/rehearsal_c4.err
