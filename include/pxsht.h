@@ -163,6 +163,12 @@ int pxa_alm2cl(int lmax, int mmax, const uint64_t* d_mstart, int64_t lstride, co
 int pxa_lmatmul(int N, int M, int lmax, int mmax, const uint64_t* d_mstart, int64_t lstride,
                 const void* alm_in, int64_t in_cstride, void* alm_out, int64_t out_cstride, int alm_dtype,
                 const double* d_lmat, int nl, int device, void* stream);
+/* pxa_rotate_alm: rotation of ncomp alm (triangular, mmax = lmax, components ncomp apart by in_cstride / out_cstride elements) by the
+ * Euler angles psi, theta, phi (zyz, active: f'(n) = f(R^-1 n), R = R_z(phi) R_y(theta) R_z(psi); ducc0.sht.rotate_alm as called at
+ * curvedsky.py:717-740).  FP64 arithmetic for both dtypes; out may alias in.  Scratch of (1 + 2 min(ncomp, 4)) x 16 x nalm bytes is
+ * allocated and freed on `stream` (stream-ordered); no host synchronisation. */
+int pxa_rotate_alm(int lmax, int ncomp, const void* alm_in, int64_t in_cstride, void* alm_out, int64_t out_cstride, int alm_dtype,
+                   double psi, double theta, double phi, int device, void* stream);
 
 /* flat-sky harmonic helpers around the 2-D map FFT (pixell/enmap.py:1358-1400 map2harm / harm2map / queb_rotmat,
  * :1959-2011 calc_ps2d, :2526-2556 lbin).  d_ly[ny], d_lx[nx]: DEVICE f64 wavenumber axes (enmap.laxes); maps [ny][nx] contiguous.

@@ -142,3 +142,50 @@ def lmul(ainfo, alm, lfun, out=None):
 def _zero(x):
 	if _is_tensor(x): x.zero_()
 	else: x[...] = 0
+
+def rotate_alm(alm, lmax, psi, theta, phi, inplace=False):
+	"""Euler-angle (zyz) rotation of alm[..., nelem] in the triangular layout (mmax = lmax), every leading component in one
+	launch sequence of include/pxsht.h pxa_rotate_alm (FP64 arithmetic for complex64 and complex128 alike).  numpy alm are staged
+	through the device and the result is numpy; torch CUDA tensors are used where they are, on the current stream.  inplace: the
+	result is written into `alm`, which is returned; otherwise `alm` is left as it is and a new array is returned."""
+	tens = _is_tensor(alm)
+	if not tens: alm = np.asarray(alm)
+	ctype = _np_dtype(alm)
+	if ctype not in (np.dtype(np.complex64), np.dtype(np.complex128)): raise ValueError("rotate_alm requires complex64 or complex128 alm")
+	lmax = int(lmax)
+	nelem = (lmax+1)*(lmax+2)//2
+	if lmax < 0 or alm.ndim < 1 or alm.shape[-1] != nelem:
+		raise ValueError("rotate_alm: alm of %d elements is not the triangular layout of lmax %d (%d elements)" % (alm.shape[-1] if alm.ndim else 0, lmax, nelem))
+	shape = tuple(alm.shape); npre = int(np.prod(shape[:-1], dtype=int))
+	psi, theta, phi = float(psi), float(theta), float(phi)
+	if npre == 0: return alm if inplace else (alm.clone() if tens else alm.copy())
+	lib = _lib.load(); dtc = _DT[ctype]
+	def run(src_ptr, dst_ptr, dev, st):
+		_lib.check(lib.pxa_rotate_alm(lmax, npre, src_ptr, nelem, dst_ptr, nelem, dtc, psi, theta, phi, dev, st))
+	if _lib.is_hostsim():
+		# (host pointers: the simulator runs the kernels on the CPU)
+		if tens:
+			src = alm.contiguous(); dst = src if inplace else _torch().empty_like(src)
+			run(src.data_ptr(), dst.data_ptr(), 0, None)
+			if inplace and dst is not alm: alm.copy_(dst); return alm
+			return dst
+		work = alm if (inplace and alm.flags.c_contiguous and alm.dtype.isnative) else np.array(alm, dtype=ctype, order="C")
+		run(work.ctypes.data, work.ctypes.data, 0, None)
+		if inplace and work is not alm: alm[...] = work; return alm
+		return work
+	torch = _torch()
+	if tens:
+		if not alm.is_cuda: raise ValueError("torch tensors passed to pixell_amd must live on the GPU")
+		with torch.cuda.device(alm.device):
+			st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+			src = alm.contiguous()
+			dst = src if inplace else torch.empty_like(src, memory_format=torch.contiguous_format)
+			run(src.data_ptr(), dst.data_ptr(), alm.device.index, st)
+		if inplace and dst is not alm: alm.copy_(dst); return alm
+		return dst
+	dev = device_index(); st = current_stream()
+	work = torch.from_numpy(np.array(alm, dtype=ctype, order="C")).cuda()
+	run(work.data_ptr(), work.data_ptr(), dev, st)
+	res = work.cpu().numpy().reshape(shape)
+	if inplace: alm[...] = res; return alm
+	return res

@@ -2,7 +2,8 @@
 
 Same function names, argument meaning and error behaviour as the reference for the `2d` and
 `cyl` methods and the healpix / profile helpers (curvedsky.py:83-302, 312-403, 510-580, 756-1086, 1170-1446); the `general` method
-(non-cylindrical pixelisations) and rotate_alm are outside the accelerated path and raise NotImplementedError (prof2alm: without the rotation).
+(non-cylindrical pixelisations) is outside the accelerated path and raises NotImplementedError (prof2alm: without the rotation to `dir`).
+rotate_alm (curvedsky.py:714-740) runs on the GPU (almops.rotate_alm, triangular layout).
 
 Differences that matter for speed, not for results:
   * the flipped / padded copies of map2buffer / buffer2map (curvedsky.py:1384-1411) are not
@@ -795,6 +796,25 @@ def rand_alm(ps, ainfo=None, lmax=None, seed=None, dtype=np.complex128, m_major=
 		m0.imag = 0; m0.real *= np.sqrt(2.0)
 	alm = alm[0] if ps.ndim == 1 else alm
 	return (alm, ainfo) if return_ainfo else alm
+
+euler_angs = {}
+euler_angs[("gal", "equ")] = np.array([57.06793215, 62.87115487, -167.14056929])*degree
+euler_angs[("equ", "gal")] = -euler_angs[("gal", "equ")][::-1]
+
+def rotate_alm(alm, psi, theta, phi, lmax=None, method="auto", nthread=None, inplace=False):
+	"""Rotate alm[..., nelem] by the zyz Euler angles psi, theta, phi (curvedsky.py:717-740; see euler_angs): the field f becomes
+	f'(n) = f(R^-1 n), R = R_z(phi) R_y(theta) R_z(psi).  Triangular layout (mmax = lmax) only.  Every leading component goes through
+	one launch sequence on the GPU (almops.rotate_alm -> pxa_rotate_alm); "auto", "ducc0" and "healpy" all name that same rotation,
+	nthread is accepted and ignored.  inplace: alm is overwritten and returned; otherwise it is left as it is."""
+	if method is None: raise ValueError("No rotate_alm implementations found")
+	if method not in ("auto", "ducc0", "healpy"): raise ValueError("Unrecognized rotate_alm implementation '%s'" % str(method))
+	if not _is_tensor(alm): alm = np.asarray(alm)
+	nalm = alm.shape[-1] if alm.ndim else 0
+	if lmax is None:
+		lmax = nalm2lmax(nalm)
+		if (lmax+1)*(lmax+2)//2 != nalm: raise ValueError("rotate_alm: %d elements are not a triangular alm layout" % nalm)
+	from . import almops
+	return almops.rotate_alm(alm, lmax, psi, theta, phi, inplace=inplace)
 
 def transfer_alm(iainfo, ialm, oainfo, oalm=None, op=lambda a, b: b):
 	"""Copy alm between layouts / band limits (curvedsky.py:744-750 -> cmisc.pyx:131-151): for every (l,m) both

@@ -359,6 +359,13 @@ def adjoint_synthesis(*, map, theta, nphi, phi0, ringstart, lmax, mmax=None, mst
 	return alm
 
 _gridweights_cache = {}
+def rotate_alm(alm, lmax, psi, theta, phi, nthreads=1):
+	"""ducc0.sht.rotate_alm as called at curvedsky.py:731: alm[nelem] (or [ncomp, nelem]) of lmax in the triangular layout, rotated
+	by the zyz Euler angles psi, theta, phi; returns a new array (numpy in, numpy out; a CUDA tensor stays on its device).
+	nthreads is accepted and ignored."""
+	from . import almops
+	return almops.rotate_alm(alm, lmax, psi, theta, phi, inplace=False)
+
 def get_gridweights(geometry, ntheta):
 	"""ducc0.sht.experimental.get_gridweights (curvedsky.py:501, 855); sum = 4 pi.  The last few results are kept: quad_weights asks
 	for the same grid on every map2alm of a declination band"""
