@@ -59,6 +59,20 @@ int pxs_plan_grid2d(pxs_plan** plan, const char* geometry, int ntheta, int nphi,
                     int flip_y, int flip_x, int lmax, int mmax, const uint64_t* mstart,
                     int64_t lstride, int device);
 
+/* Plan for transforms at arbitrary points (ducc0.sht.experimental.synthesis_general / adjoint_synthesis_general, curvedsky.py:993-1016,
+ * 1088-1120).  cc_grid_plan: a pxs_plan_grid2d plan of geometry "CC", unflipped, phi0 = 0, ntheta >= lmax + 2, nphi even and >= 2 mmax + 2,
+ * both 2 ntheta - 2 and nphi transformable by the FFT engine; it carries lmax, mmax and the alm layout, the caller keeps it alive as long as
+ * the points plan.  d_loc: DEVICE f64[npts][2] = (theta in [0, pi], phi any finite value), read while the plan is made (sorted into the
+ * plan).  epsilon in [1e-13, 0.1]: relative L2 accuracy of the result.  Transforms run through pxs_synthesis on this plan with the map
+ * [comp][npts] (map_cstride = npts): synthesis onto the CC grid, mirror onto the doubled sphere, 2-D FFT, deapodisation and zero padding
+ * to the fine grid (oversampling 2), inverse FFT, interpolation with the exponential-of-semicircle kernel; the adjoint is the exact
+ * transpose.  The spreading of the adjoint sums in a fixed order (bitwise repeatable); the Legendre stage follows the grid plan's own
+ * "deterministic" option.  pxs_plan_query: "kernel_width", "fine_ntheta", "fine_nphi", "npts", "plan_us" (host wall time of
+ * making the plan), "stage_us_cc_sht" / "_fft" / "_grid" / "_interp" / "_spread" (device-event microseconds per stage, summed over the
+ * calls since pxs_plan_option(plan, "profile", 1), which resets them; each profiled call synchronises its stream).  A plan serves any
+ * number of calls, of either direction and of any spin.  Synchronises `stream` once. */
+int pxs_plan_points(pxs_plan** plan, const pxs_plan* cc_grid_plan, int64_t npts, const double* d_loc, double epsilon, int device, void* stream);
+
 void pxs_plan_destroy(pxs_plan* plan);
 
 /* alm -> map (adjoint = 0: synthesis[_2d]) or map -> alm (adjoint = 1: adjoint_synthesis[_2d]).

@@ -22,6 +22,7 @@ def _declare(lib):
 	lib.pxs_version.restype = c.c_char_p
 	lib.pxs_plan_rings.argtypes = [c.POINTER(vp), i32, vp, vp, vp, vp, i64, i32, i32, vp, i64, i32]
 	lib.pxs_plan_grid2d.argtypes = [c.POINTER(vp), c.c_char_p, i32, i32, dbl, i32, i32, i32, i32, vp, i64, i32]
+	lib.pxs_plan_points.argtypes = [c.POINTER(vp), vp, i64, vp, dbl, i32, vp]
 	lib.pxs_plan_destroy.argtypes = [vp]; lib.pxs_plan_destroy.restype = None
 	lib.pxs_synthesis.argtypes = [vp, i32, i32, i32, i32, vp, i32, i64, i64, vp, i32, i64, i64, vp]
 	lib.pxs_analysis.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, vp, i32, i64, i64, vp]
@@ -45,12 +46,12 @@ def _declare(lib):
 	lib.pxf_fft_nd.argtypes = [i32, vp, vp, vp, i32, vp, i32, i32, dbl, i32, i32, vp, vp, i32, vp]
 	lib.pxf_fft_supported.argtypes = [i64]
 	lib.pxf_fft_good_size.argtypes = [i64]; lib.pxf_fft_good_size.restype = i64
-	for name in ["pxs_plan_rings", "pxs_plan_grid2d", "pxs_synthesis", "pxs_analysis", "pxs_gridweights",
+	for name in ["pxs_plan_rings", "pxs_plan_grid2d", "pxs_plan_points", "pxs_synthesis", "pxs_analysis", "pxs_gridweights",
 			"pxs_grid_maxlmax", "pxs_plan_info", "pxs_plan_option", "pxs_plan_query", "pxf_fft_nd", "pxf_fft_supported", "pxs_profile", "pxs_profile_read", "pxs_profile_flops", "pxs_debug_theta_plan", "pxs_debug_chain", "pxs_memory", "pxa_alm2cl", "pxa_lmatmul", "pxa_rotate_alm", "pxm_rotate_queb", "pxm_ps2d", "pxm_lbin", "pxm_bin_index", "pxm_mul_axis"]:
 		getattr(lib, name).restype = i32
 	return lib
 
-EXPORTS = ["pxs_plan_rings", "pxs_plan_grid2d", "pxs_plan_destroy", "pxs_synthesis", "pxs_analysis",
+EXPORTS = ["pxs_plan_rings", "pxs_plan_grid2d", "pxs_plan_points", "pxs_plan_destroy", "pxs_synthesis", "pxs_analysis",
 	"pxs_gridweights", "pxs_grid_maxlmax", "pxs_plan_info", "pxs_plan_option", "pxs_plan_query", "pxf_fft_nd", "pxf_fft_supported",
 	"pxf_fft_good_size", "pxs_last_error", "pxs_version", "pxs_profile", "pxs_profile_read", "pxs_profile_flops", "pxs_debug_theta_plan", "pxs_debug_chain", "pxs_memory", "pxa_alm2cl", "pxa_lmatmul", "pxa_rotate_alm", "pxm_rotate_queb", "pxm_ps2d", "pxm_lbin", "pxm_bin_index", "pxm_mul_axis"]
 

@@ -28,6 +28,14 @@ FftContext& fft_context(int device);
 void fft_dense_lines(int device, hipStream_t st, long n, bool forward, long nlines, const double2* in, double2* out);   // api_fft.hip
 void fft_release_stream(int device, hipStream_t st);                                                                  // api_fft.hip
 const char* get_last_error();
+// points plans (points.hip)
+struct PointsState;
+PointsState* points_create(int ntheta, int nphi, int lmax, int mmax, int device, long npts, const double* d_loc, double eps, hipStream_t st);
+void points_free(PointsState* s);
+void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint, int nb, void* alm, int alm_dtype, long alm_cstride, long alm_bstride,
+                void* map, int map_dtype, long map_cstride, long map_bstride, hipStream_t st);
+int64_t points_query(const PointsState* s, const std::string& name);
+void points_profile(PointsState* s, bool on);
 
 typedef long double LDb;
 static const LDb PIl = 3.141592653589793238462643383279502884L;
@@ -338,7 +346,10 @@ struct pxs_plan {
 	bool general = false; std::vector<GenGroup> groups; long npixz = 0;
 	DevBuf g_blk_ring, g_blk_k0, g_nphi, g_zoff, g_rstart, g_phi0, gz; long g_nblk = 0;
 	std::vector<hipStream_t> gstreams; std::vector<hipEvent_t> gjoin; hipEvent_t gfork = nullptr;
+	// points plans (pxs_plan_points): the CC grid plan they were made from (owned by the caller) and the per-point state
+	pxs_plan* pgrid = nullptr; PointsState* pts = nullptr;
 	~pxs_plan() {
+		if (pts) points_free(pts);
 		for (auto s_ : gstreams) { pxs::fft_release_stream(device, s_); (void)hipStreamDestroy(s_); }
 		for (auto e : gjoin) (void)hipEventDestroy(e);
 		if (gfork) (void)hipEventDestroy(gfork);
@@ -935,12 +946,37 @@ int pxs_plan_rings(pxs_plan** plan, int nring, const double* theta, const uint64
 	PXS_CATCH
 }
 
+int pxs_plan_points(pxs_plan** plan, const pxs_plan* g, int64_t npts, const double* d_loc, double epsilon, int device, void* stream)
+{
+	PXS_TRY
+	PXS_REQUIRE(plan && g && npts >= 0 && (d_loc || npts == 0), "pxs_plan_points: bad arguments");
+	PXS_REQUIRE(g->is_grid && g->geometry == "CC" && !g->pts && g->phi0 == 0 && g->ring_stride == g->nphi && g->pix_stride == 1,
+		"pxs_plan_points: needs an unflipped CC grid plan with phi0 = 0");
+	PXS_REQUIRE(g->nring >= g->lmax + 2 && g->nphi % 2 == 0 && g->nphi >= 2*g->mmax + 2, "pxs_plan_points: the CC grid needs ntheta >= lmax + 2 and an even nphi >= 2 mmax + 2");
+	PXS_REQUIRE(FftContext::supported(2L*g->nring - 2) && FftContext::supported(g->nphi), "pxs_plan_points: CC grid sizes the FFT engine cannot transform");
+	PXS_REQUIRE(epsilon >= 1e-13 && epsilon <= 0.1, "pxs_plan_points: epsilon must lie in [1e-13, 0.1]");
+	PXS_REQUIRE(device == g->device, "pxs_plan_points: the grid plan lives on another device");
+	PXS_HIP(hipSetDevice(device));
+	std::unique_ptr<pxs_plan> p(new pxs_plan());
+	p->device = device; p->lmax = g->lmax; p->mmax = g->mmax; p->lstride = g->lstride; p->pgrid = const_cast<pxs_plan*>(g);
+	p->pts = points_create(g->nring, g->nphi, g->lmax, g->mmax, device, (long)npts, d_loc, epsilon, (hipStream_t)stream);
+	*plan = p.release();
+	PXS_CATCH
+}
+
 void pxs_plan_destroy(pxs_plan* plan) { delete plan; }
 
 int pxs_plan_option(pxs_plan* p, const char* name, int64_t value) {
 	PXS_TRY
 	PXS_REQUIRE(p && name, "pxs_plan_option: null argument");
 	std::lock_guard<std::mutex> plan_lock(p->call_mu);
+	if (p->pts) {      // a points plan: its spreading is always ordered; the Legendre stage follows the grid plan's own option
+		const std::string n(name);
+		PXS_REQUIRE((n == "deterministic" || n == "profile") && (value == 0 || value == 1), "pxs_plan_option: a points plan takes 'deterministic' or 'profile' (0 or 1)");
+		if (n == "deterministic") p->wk.deterministic = value != 0;
+		else points_profile(p->pts, value != 0);
+		return 0;
+	}
 	if (std::string(name) == "analysis") {
 		PXS_REQUIRE(value >= 0 && value <= 2, "pxs_plan_option: analysis takes 0 (interpolant), 1 (weights) or 2 (ducc0)");
 		p->ana_weights = (int)value;
@@ -961,7 +997,8 @@ int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	PXS_TRY
 	PXS_REQUIRE(p && name && value, "pxs_plan_query: null argument");
 	const std::string n(name);
-	if (n == "analysis_form") *value = ana_form_now(p);
+	if (p->pts) *value = points_query(p->pts, n);
+	else if (n == "analysis_form") *value = ana_form_now(p);
 	else if (n == "ncc_circle") *value = p->ncc > 0 ? p->Ncc : 0;
 	else if (n == "ducc_ncc_circle") *value = FftChain::ducc_ncc(p->lmax);
 	else if (n == "theta_line") *value = theta_line_now(p);
@@ -1274,6 +1311,7 @@ int pxs_synthesis(pxs_plan* p, int spin, int mode, int adjoint, int nbatch,
 	PXS_REQUIRE(nbatch >= 1, "pxs_synthesis: nbatch must be >= 1");
 	PXS_HIP(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream;
+	if (p->pts) { points_run(p->pts, p->pgrid, spin, mode, adjoint, nbatch, alm, alm_dtype, alm_cstride, alm_bstride, map, map_dtype, map_cstride, map_bstride, st); return 0; }
 	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16, mesz = map_dtype == PX_F32 ? 4 : 8;
 	// (a grid whose ring FFTs are chained but whose theta resampling is not -- 2 ntheta with a prime factor >= 7 -- takes the
 	// CC detour through the unfused resampling, one map at a time)

@@ -1,8 +1,10 @@
 """Drop-in for the spherical-harmonic-transform API of pixell/curvedsky.py on MI355X.
 
 Same function names, argument meaning and error behaviour as the reference for the `2d` and
-`cyl` methods and the healpix / profile helpers (curvedsky.py:83-302, 312-403, 510-580, 756-1086, 1170-1446); the `general` method
-(non-cylindrical pixelisations) is outside the accelerated path and raises NotImplementedError (prof2alm: without the rotation to `dir`).
+`cyl` methods and the healpix / profile helpers (curvedsky.py:83-302, 312-403, 510-580, 756-1086, 1170-1446).  Transforms at arbitrary
+positions run on the GPU: alm2map_pos, alm2map_raw_general and map2alm_raw_general (curvedsky.py:174-207, 993-1016, 1088-1120; sht.synthesis_general).
+The `general` method for whole maps (non-cylindrical pixelisations) is outside the accelerated path and raises NotImplementedError (prof2alm:
+without the rotation to `dir`).
 rotate_alm (curvedsky.py:714-740) runs on the GPU (almops.rotate_alm, triangular layout).
 
 Differences that matter for speed, not for results:
@@ -588,6 +590,109 @@ def map2alm_healpix(healmap, alm=None, ainfo=None, lmax=None, spin=[0, 2], weigh
 			if adjoint: map_full[Ij] = jacobi_inverse(YT, WY, _contig(alm_full[Ij]), niter=niter)
 			else:       alm_full[Ij] = jacobi_inverse(Y, YTW, map_full[Ij], niter=niter)
 	return healmap if adjoint else alm
+
+# ---------------------------------------------------------------------------------------
+# arbitrary positions: the point transforms of sht.synthesis_general (curvedsky.py:174-207, 993-1016, 1088-1120)
+# ---------------------------------------------------------------------------------------
+def _copy(x): return None if x is None else (x.clone() if _is_tensor(x) else x.copy())
+
+def _loc_from_pos(pos):
+	"""pos [{dec,ra}, ...] -> loc [..., {codec, ra}] with ra made positive (curvedsky.py:185-193)"""
+	if _is_tensor(pos):
+		loc = pos.movedim(0, -1).to(_torch().float64).clone()
+		loc[..., 0] = np.pi/2 - loc[..., 0]
+		loc[..., 1] = _torch().where(loc[..., 1] < 0, loc[..., 1]+2*np.pi, loc[..., 1])
+		return loc
+	loc = np.moveaxis(np.asarray(pos, np.float64), 0, -1).copy(order="C")
+	loc[..., 0] *= -1; loc[..., 0] += np.pi/2
+	loc[loc[..., 1] < 0, 1] += 2*np.pi
+	return loc
+
+def alm2map_pos(alm, pos=None, loc=None, ainfo=None, map=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, epsilon=None):
+	"""alm -> values at arbitrary positions (curvedsky.alm2map_pos, curvedsky.py:174-207).  pos: [{dec,ra}, ...] in radians, or
+	loc: [..., {codec,ra}].  The pre-dimensions of pos / loc come back as trailing dimensions of the map: alm [..., nelem] ->
+	map [..., npts...] (deriv: [..., 2, npts...], the declination derivative first).  adjoint: map -> alm, returns alm (with deriv
+	the exact transpose: the sign of the declination component is applied before the transform and the input is left alone)."""
+	if adjoint:
+		if copy and alm is not None: alm = _copy(alm)
+	else:
+		if copy and map is not None: map = _copy(map)
+	if loc is None: loc = _loc_from_pos(pos)
+	lpre = tuple(loc.shape[:-1])
+	loc = loc.reshape(-1, 2)
+	npts = int(loc.shape[0])
+	if map is None:
+		oshape = tuple(alm.shape[:-1])+((2, npts) if deriv else (npts,))
+		mflat = _zeros_like_kind(oshape, real_dtype(_np_dtype(alm)), alm)
+	else: mflat = map.reshape(tuple(map.shape[:map.ndim-len(lpre)])+(npts,))
+	res = alm2map_raw_general(alm, mflat, loc, ainfo=ainfo, spin=spin, deriv=deriv, nthread=nthread, verbose=verbose, epsilon=epsilon, adjoint=adjoint)
+	if adjoint: return res
+	return mflat.reshape(tuple(mflat.shape[:-1])+lpre)
+
+def alm2map_raw_general(alm, map, loc, ainfo=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, epsilon=None):
+	"""alm [..., ncomp, nelem] -> map [..., ncomp, npts] at loc [npts, 2] (curvedsky.alm2map_raw_general, curvedsky.py:993-1016); adjoint: the
+	transpose.  deriv: alm [..., nelem] -> map [..., 2, npts] = (d/ddec, d/dra / cos dec)."""
+	if copy:
+		if adjoint: alm = _copy(alm)
+		else: map = _copy(map)
+	alm_full, map_full, ainfo, nthread = prepare_raw(alm, map, ainfo=ainfo, deriv=deriv, nthread=nthread, pixdims=1, convert_alm=not adjoint)
+	if epsilon is None: epsilon = 1e-10 if _np_dtype(map_full) == np.float64 else 1e-6
+	kw = dict(loc=loc, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride, epsilon=epsilon)
+	kw["plan"] = sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon)     # one binning of the points for every spin group
+	func = sht.adjoint_synthesis_general if adjoint else sht.synthesis_general
+	for I in nditer(map_full.shape[:-2]):
+		if deriv:
+			a = _contig(alm_full[I][None])
+			if adjoint:
+				m = map_full[I]*_dec_flip(map_full)
+				func(alm=a, map=_contig(m), mode="DERIV1", spin=1, **kw); alm_full[I] = a[0]
+			else:
+				func(alm=a, map=map_full[I], mode="DERIV1", spin=1, **kw)
+				map_full[I+(0,)] *= -1                   # d/dtheta -> d/ddec
+		else:
+			for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
+				Ij = I+(slice(j1, j2),)
+				v = alm_full[Ij]; a = _contig(v)
+				func(alm=a, map=_contig(map_full[Ij]) if adjoint else map_full[Ij], spin=int(s), **kw)
+				if adjoint and a is not v: v[...] = a
+	return alm if adjoint else map
+
+def _dec_flip(like):
+	f = np.array([-1.0, 1.0])[:, None]
+	return _torch().as_tensor(f, dtype=like.dtype, device=like.device) if _is_tensor(like) else f.astype(like.dtype)
+
+def map2alm_raw_general(map, loc, alm=None, ainfo=None, lmax=None, spin=[0, 2], weights=None, deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, niter=0, epsilon=None):
+	"""values at loc [npts, 2] -> alm: weighted adjoint synthesis (pixel weights `weights`, default 1) with `niter` Jacobi refinements
+	(curvedsky.map2alm_raw_general, curvedsky.py:1088-1120).  adjoint: the transpose of that operator, alm -> map."""
+	if adjoint:
+		if copy and map is not None: map = _copy(map)
+	else:
+		if copy and alm is not None: alm = _copy(alm)
+	if epsilon is None: epsilon = 1e-10 if _np_dtype(_mdata(map)) == np.float64 else 1e-6
+	alm_full, map_full, ainfo, nthread = prepare_raw(alm, map, ainfo=ainfo, lmax=lmax, deriv=deriv, nthread=nthread, pixdims=1, convert_alm=adjoint)
+	kw = dict(loc=loc, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride, epsilon=epsilon)
+	kw["plan"] = sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon)     # shared by the spin groups and the Jacobi steps
+	if weights is None: weights = 1.0
+	if _is_tensor(map_full) and not np.isscalar(weights): weights = _torch().as_tensor(np.asarray(weights), device=map_full.device)
+	for I in nditer(map_full.shape[:-2]):
+		if deriv:
+			def Y(a):   return sht.synthesis_general(alm=_contig(a), mode="DERIV1", spin=1, **kw)
+			def YT(m):  return sht.adjoint_synthesis_general(map=_contig(m), mode="DERIV1", spin=1, **kw)
+			def YTW(m): return YT(m*weights)
+			def WY(a):  return Y(a)*weights
+			flip = _dec_flip(map_full)
+			if adjoint: map_full[I] = jacobi_inverse(YT, WY, _contig(alm_full[I][None]), niter=niter)*flip
+			else:       alm_full[I] = jacobi_inverse(Y, YTW, map_full[I]*flip, niter=niter)[0]
+		else:
+			for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
+				Ij = I+(slice(j1, j2),)
+				def Y(a, s=s):   return sht.synthesis_general(alm=_contig(a), spin=int(s), **kw)
+				def YT(m, s=s):  return sht.adjoint_synthesis_general(map=_contig(m), spin=int(s), **kw)
+				def YTW(m): return YT(m*weights)
+				def WY(a):  return Y(a)*weights
+				if adjoint: map_full[Ij] = jacobi_inverse(YT, WY, _contig(alm_full[Ij]), niter=niter)
+				else:       alm_full[Ij] = jacobi_inverse(Y, YTW, map_full[Ij], niter=niter)
+	return map if adjoint else alm
 
 # ---------------------------------------------------------------------------------------
 # 1-D transforms: radial profiles <-> functions of l, as m = 0 transforms on rings of one pixel (curvedsky.py:510-554)

@@ -358,6 +358,117 @@ def adjoint_synthesis(*, map, theta, nphi, phi0, ringstart, lmax, mmax=None, mst
 	adjoint_synthesis.last_plan = plan
 	return alm
 
+# ---- transforms at arbitrary points (pxs_plan_points; ducc0.sht.experimental.synthesis_general / adjoint_synthesis_general,
+# curvedsky.py:993-1016, 1088-1120) ----------------------------------------------------------------------------------------------
+EPS_MIN, EPS_MAX = 1e-13, 0.1
+
+def points_grid_shape(lmax, mmax):
+	"""(ntheta, nphi) of the Clenshaw-Curtis grid the point transforms synthesise onto: 2 ntheta - 2 and nphi/2 good FFT sizes,
+	ntheta >= lmax + 2, nphi >= 2 mmax + 2"""
+	g = _lib.load().pxf_fft_good_size
+	return int(g(lmax+1))+1, 2*int(g(mmax+1))
+
+def _loc_device(loc):
+	"""loc [npts, 2] f64 -> (device array the library reads, npts); ValueError for theta outside [0, pi] or a non-finite phi"""
+	if _is_tensor(loc):
+		torch = _torch()
+		if loc.ndim != 2 or loc.shape[1] != 2: raise ValueError("loc must have shape [npts, 2]")
+		loc = loc.to(torch.float64).contiguous()
+		if loc.shape[0] and not bool(((loc[:, 0] >= 0) & (loc[:, 0] <= np.pi) & torch.isfinite(loc[:, 1])).all()):
+			raise ValueError("loc: theta must lie in [0, pi] and phi be finite")
+		if _lib.is_hostsim(): return loc, loc.shape[0]
+		return (loc if loc.is_cuda else loc.cuda()), loc.shape[0]
+	loc = np.ascontiguousarray(loc, dtype=np.float64)
+	if loc.ndim != 2 or loc.shape[1] != 2: raise ValueError("loc must have shape [npts, 2]")
+	if loc.shape[0] and not (np.all((loc[:, 0] >= 0) & (loc[:, 0] <= np.pi)) and np.all(np.isfinite(loc[:, 1]))):
+		raise ValueError("loc: theta must lie in [0, pi] and phi be finite")
+	if _lib.is_hostsim(): return loc, loc.shape[0]
+	return _torch().from_numpy(loc).cuda(), loc.shape[0]
+
+def points_plan(loc, lmax, mmax=None, mstart=None, lstride=1, epsilon=1e-10):
+	"""a pxs_plan of the points loc [npts, 2] (theta, phi) on the cached CC grid plan of (lmax, mmax, layout); not cached itself"""
+	if mmax is None: mmax = lmax
+	if mstart is None: mstart = tri_mstart(lmax, mmax)
+	epsilon = float(epsilon)
+	if not (EPS_MIN <= epsilon <= EPS_MAX): raise ValueError("epsilon must lie in [%g, %g], got %g" % (EPS_MIN, EPS_MAX, epsilon))
+	nt, nph = points_grid_shape(lmax, mmax)
+	grid = grid_plan("CC", nt, nph, 0.0, (False, False), lmax, mmax, mstart, lstride)
+	dloc, npts = _loc_device(loc)
+	ptr = dloc.data_ptr() if _is_tensor(dloc) else dloc.ctypes.data
+	h = ctypes.c_void_p()
+	_lib.check(_lib.load().pxs_plan_points(ctypes.byref(h), grid.handle, int(npts), ptr if npts else None, epsilon, device_index(), current_stream()))
+	p = Plan(h); p.grid = grid; p.npts = int(npts)
+	return p
+
+def points_profile(plan, enable=True):
+	"""stage timers of a point plan (pxs_plan_option "profile"): enable resets them"""
+	plan.set_option("profile", int(bool(enable)))
+
+def points_profile_read(plan):
+	"""{stage: ms} summed over the calls since points_profile(plan): cc_sht (CC synthesis / its adjoint), fft (2-D FFTs), grid (doubling,
+	fold, padding, truncation), interp, spread (spreading + slab gather); plan: host wall time of making the plan"""
+	out = {k: plan.query("stage_us_"+k)*1e-3 for k in ("cc_sht", "fft", "grid", "interp", "spread")}
+	out["plan"] = plan.query("plan_us")*1e-3
+	return out
+
+def _default_eps(epsilon, map_dtype):
+	if epsilon is not None: return epsilon
+	return 1e-6 if np.dtype(map_dtype) == np.float32 else 1e-10
+
+def _run_points(plan, alm, map, spin, mode, adjoint):
+	with plan.grid.lock:      # the grid plan's deterministic option applies to the Legendre stage of this call
+		_apply_mode(plan.grid)
+		_run_syn(plan, alm, map, spin, mode, adjoint, map_overwrite=True)
+
+def _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, map_dtype):
+	"""the point plan of a call: the caller's (made by points_plan for the same loc, band limit, layout and epsilon: the binning and sort
+	of the points are then shared by several calls, e.g. the spin groups of one alm2map_pos) or a new one"""
+	if plan is not None:
+		if plan.npts != int(loc.shape[0]): raise ValueError("plan was made for %d points, loc has %d" % (plan.npts, int(loc.shape[0])))
+		return plan
+	return points_plan(loc, lmax, mmax, mstart, lstride, _default_eps(epsilon, map_dtype))
+
+def synthesis_general(*, alm, loc, spin, lmax, mmax=None, mstart=None, lstride=1, epsilon=None, mode="STANDARD", map=None, nthreads=0, plan=None):
+	"""ducc0.sht.experimental.synthesis_general as called at curvedsky.py:1004, 1098: alm [nca, nelem] (or a batch [nb, nca, nelem]) ->
+	map [ncm, npts] (or [nb, ncm, npts]) at loc [npts, 2] = (theta, phi).  numpy in, numpy out; a CUDA tensor stays on its device.
+	epsilon: relative L2 accuracy (default 1e-10 for float64 maps, 1e-6 for float32), within [1e-13, 0.1].
+	plan (ours): a points_plan of these points to reuse (its epsilon and layout apply)."""
+	nca, ncm = _ncomp(spin, mode)
+	if mode not in ("STANDARD", "DERIV1"): raise ValueError("unknown mode '%s'" % str(mode))
+	npts = int(loc.shape[0])
+	if map is None:
+		rdt = np.float32 if _np_dtype(alm) == np.complex64 else np.float64
+		shape = tuple(alm.shape[:-2])+(ncm, npts)
+		map = _torch().zeros(shape, dtype=getattr(_torch(), np.dtype(rdt).name), device=alm.device) if _is_tensor(alm) else np.zeros(shape, rdt)
+	_check_pair(alm, map, spin, mode, 1)
+	if map.shape[-1] != npts: raise ValueError("map has %d points, loc %d" % (map.shape[-1], npts))
+	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, _np_dtype(map))
+	if npts == 0: return map
+	_run_points(plan, alm, map, spin, mode, False)
+	return map
+
+def adjoint_synthesis_general(*, map, loc, spin, lmax, mmax=None, mstart=None, lstride=1, epsilon=None, mode="STANDARD", alm=None, nthreads=0, plan=None):
+	"""ducc0.sht.experimental.adjoint_synthesis_general as called at curvedsky.py:1104-1115: the exact transpose of synthesis_general,
+	map [ncm, npts] -> alm [nca, nelem] (overwritten; allocated when None)"""
+	nca, ncm = _ncomp(spin, mode)
+	if mode not in ("STANDARD", "DERIV1"): raise ValueError("unknown mode '%s'" % str(mode))
+	if mmax is None: mmax = lmax
+	if mstart is None: mstart = tri_mstart(lmax, mmax)
+	npts = int(loc.shape[0])
+	if alm is None:
+		nelem = int(np.max(np.asarray(mstart).astype(np.int64))+lmax*lstride+1)
+		cdt = np.complex64 if _np_dtype(map) == np.float32 else np.complex128
+		shape = tuple(map.shape[:-2])+(nca, nelem)
+		alm = _torch().zeros(shape, dtype=getattr(_torch(), np.dtype(cdt).name), device=map.device) if _is_tensor(map) else np.zeros(shape, cdt)
+	_check_pair(alm, map, spin, mode, 1)
+	if map.shape[-1] != npts: raise ValueError("map has %d points, loc %d" % (map.shape[-1], npts))
+	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, _np_dtype(map))
+	if npts == 0:      # (no map to read: the transpose of an empty synthesis is zero)
+		alm[...] = 0
+		return alm
+	_run_points(plan, alm, map, spin, mode, True)
+	return alm
+
 _gridweights_cache = {}
 def rotate_alm(alm, lmax, psi, theta, phi, nthreads=1):
 	"""ducc0.sht.rotate_alm as called at curvedsky.py:731: alm[nelem] (or [ncomp, nelem]) of lmax in the triangular layout, rotated
