@@ -10,7 +10,18 @@
  *  - all data pointers are DEVICE pointers (hipMalloc / torch.cuda tensors) on the plan's
  *    device; the caller owns them.  `stream` is a hipStream_t (NULL = default stream); calls
  *    are asynchronous with respect to the host.
- *  - plans own their device scratch and tables; a plan may be used by one call at a time.
+ *  - plans own their device scratch and tables, so a plan serves one call at a time.  On the
+ *    device the library sees to that itself: calls on one plan run in the order they were
+ *    issued, whatever their streams (each call records an event after its last launch, and
+ *    a call that comes on another stream waits for it; a points plan orders against the
+ *    grid plan it borrows in the same way).  Streams are told apart by their handles: a
+ *    stream must be idle with respect to a plan (synchronised, or its last call on the plan
+ *    followed by one on another stream) before it is destroyed.  The calls themselves take the plan's own host
+ *    lock, so two host threads on one plan queue up; a thread that sets a plan option and
+ *    relies on it in the next call must hold a lock of its own around the pair.
+ *  - device memory a plan releases (pxs_plan_destroy, a scratch buffer that grows) may still
+ *    be in use by queued work on any stream: the library synchronises the device before
+ *    such a block serves another plan or returns to the driver (pxs_memory).
  *  - return value: 0 = OK, <0 = error (pxs_last_error() returns a thread-local message).
  *    No C++ exception crosses the boundary.
  *  - dtype codes: 0 = float32, 1 = float64, 2 = complex64, 3 = complex128.  All arithmetic is

@@ -151,10 +151,12 @@ int pxa_alm2cl(int lmax, int mmax, const uint64_t* d_mstart, int64_t lstride, co
 		hipLaunchKernelGGL(alm2cl_kernel, dim3((lmax+256)/256), dim3(256), 0, (hipStream_t)stream, lmax, mmax, d_mstart, (long)lstride,
 			alm1, alm2, alm_dtype, cl, cl_dtype, acc_f32 ? 1 : 0);
 	} else {
-		static std::mutex mu; static std::map<int, DevBuf> scratch;
+		// partial sums per m chunk: scratch per (device, stream), like the FFT scratch (api_fft.hip) -- calls on two streams must not share it,
+		// and calls on one stream are ordered by the stream.  (A torch process has at most a few dozen streams; entries are 8 (lmax + 1) nch bytes.)
+		static std::mutex mu; static std::map<std::pair<int, void*>, DevBuf> scratch;
 		const int nch = mmax/ALM2CL_MCH + 1;
 		double* part;
-		{ std::lock_guard<std::mutex> g(mu); DevBuf& b = scratch[device]; b.ensure(sizeof(double)*(size_t)nch*(lmax+1)); part = b.as<double>(); }
+		{ std::lock_guard<std::mutex> g(mu); DevBuf& b = scratch[std::make_pair(device, stream)]; b.ensure(sizeof(double)*(size_t)nch*(lmax+1)); part = b.as<double>(); }
 		hipLaunchKernelGGL(alm2cl_part_kernel, dim3((lmax+256)/256, nch), dim3(256), 0, (hipStream_t)stream, lmax, mmax, d_mstart, (long)lstride,
 			alm1, alm2, alm_dtype, part);
 		hipLaunchKernelGGL(alm2cl_sum_kernel, dim3((lmax+256)/256), dim3(256), 0, (hipStream_t)stream, lmax, mmax, (const double*)part, cl, cl_dtype);

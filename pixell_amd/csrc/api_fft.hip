@@ -68,7 +68,9 @@ static void fft_axis(FftContext& fc, hipStream_t st, long n, bool forward, std::
 static std::mutex g_blue_mu; static std::map<std::pair<int, hipStream_t>, std::unique_ptr<DevBuf>> g_blue_scratch;
 // chain engine (and its scratch) of the 2-D real -> complex fast path, per stream like the other scratch
 // (each entry owns the transposed intermediate of its last transform -- 15 GB for a complex 21600 x 43200 map -- so the table is
-// bounded: beyond PXF_F2_MAX_STREAMS (4) the entry used longest ago is dropped; hipFree waits for the kernels that may still use it)
+// bounded: beyond PXF_F2_MAX_STREAMS (4) the entry used longest ago is dropped.  Its kernels may still be queued on its stream: its
+// blocks go to the arena, which synchronises the device before one of them serves anybody else (arena.hip); smaller blocks go through
+// hipFree, which waits for the device)
 // Entries are shared_ptr: the caller holds one for the duration of its transform, so an eviction (or fft_release_stream) on another
 // thread only drops the table's reference -- the chain and its scratch go when the last user is done.  The cap counts the streams of
 // ONE device (a process driving 8 GPUs keeps 4 per GPU), and an entry somebody holds is never the one evicted.
@@ -115,7 +117,8 @@ static void bluestein_axis(FftContext& fc, int device, hipStream_t st, long n, b
 	std::vector<AxisDim> d1 = dims, d2 = dims;
 	long lines = 1;
 	for (size_t k = dims.size(); k-- > 0;) { d1[k].os = lines*M; d2[k].is = lines*M; lines *= dims[k].n; }
-	// scratch per stream, grown on demand and kept (growing frees the old block: hipFree waits for the device); owners of private
+	// scratch per stream, grown on demand and kept (growing gives the old block to the arena, which synchronises the device before the
+	// block is used again, or to hipFree, which waits for the device: the stream's earlier transforms may still read it); owners of private
 	// streams give it back with fft_release_stream before they destroy the stream
 	DevBuf* sp;
 	{ std::lock_guard<std::mutex> g(g_blue_mu); auto& u = g_blue_scratch[std::make_pair(device, st)]; if (!u) u.reset(new DevBuf()); sp = u.get(); }

@@ -30,6 +30,7 @@ void set_last_error(const std::string& msg);
 // workloads (bench.py's legs, sht.clear_plans()) paid for it again each time.  pxs_memory() reports and releases.
 void* dev_alloc(size_t bytes);
 void dev_free(void* p, size_t bytes);
+size_t dev_capacity(void* p);      // true size of a live arena block (it may exceed what its user asked for), 0 for anything else
 
 // simple owning device buffer
 struct DevBuf {
@@ -41,7 +42,11 @@ struct DevBuf {
 	DevBuf& operator=(DevBuf&& o) noexcept { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; return *this; }
 	~DevBuf() { release(); }
 	void alloc(size_t n) { release(); if (n) { p = dev_alloc(n); bytes = n; } }
-	void ensure(size_t n) { if (n > bytes) alloc(n); }
+	void ensure(size_t n) {
+		if (n <= bytes) return;
+		if (p && dev_capacity(p) >= n) { bytes = n; return; }      // a reused block with room to spare: grow in place (releasing it would hand the same block back after a device synchronisation)
+		alloc(n);
+	}
 	void release() { if (p) { dev_free(p, bytes); p = nullptr; bytes = 0; } }
 	template<class T> T* as() const { return reinterpret_cast<T*>(p); }
 };

@@ -1107,7 +1107,9 @@ void FftChain::from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_c
 // transform as a complex one over both axes.  false: no usable factorisation (the caller takes the generic engine).
 bool FftChain::fft2_real(hipStream_t st, const void* in, int in_dtype, double2* out, long npre, long ny, long nx, bool forward, double scale) {
 	Split sy;
-	if (nx < 4 || ny < 4 || !split_balanced(ny, sy) || (nphi_ != nx && !plan_rings(nx))) return false;
+	// (plan_rings notes the width before it knows whether it can split it: a chain kept per stream must not take a width it refused
+	// in an earlier transform for a planned one)
+	if (nx < 4 || ny < 4 || !split_balanced(ny, sy) || ((nphi_ != nx || !rings_ok()) && !plan_rings(nx))) return false;
 	const long nm = nx/2 + 1, ldF = pad8(ny), a = std::min(sy.a, sy.b), b = ny/a, ldY = pad8(b);
 	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] fft2_real %ld x %ld x %ld: rows %s, columns %ld x %ld\n", npre, ny, nx, describe().c_str(), a, b);
 	PXS_REQUIRE(npre*nm < (1L << 31)/std::max<long>(a, b), "fft2_real: too many lines");

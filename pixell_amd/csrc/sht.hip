@@ -323,6 +323,10 @@ struct pxs_plan {
 	// a plan serves one call at a time (it owns the scratch of the call, and the analysis option is read several times in a call):
 	// the entry points that run or reconfigure it take this lock, so two host threads on one cached plan queue up instead of interleaving
 	std::mutex call_mu;
+	// ... on the device too: the calls are asynchronous, so the lock orders only their issue.  Every call records `used` on its stream
+	// after its last launch, and a call that comes on another stream waits for it before its first (PlanUse below): calls on one plan
+	// run in the order they were issued, whatever their streams.
+	hipEvent_t used = nullptr; hipStream_t used_stream = nullptr; bool used_any = false;
 	int device = 0;
 	bool is_grid = false;
 	std::string geometry;
@@ -350,6 +354,7 @@ struct pxs_plan {
 	pxs_plan* pgrid = nullptr; PointsState* pts = nullptr;
 	~pxs_plan() {
 		if (pts) points_free(pts);
+		if (used) (void)hipEventDestroy(used);
 		for (auto s_ : gstreams) { pxs::fft_release_stream(device, s_); (void)hipStreamDestroy(s_); }
 		for (auto e : gjoin) (void)hipEventDestroy(e);
 		if (gfork) (void)hipEventDestroy(gfork);
@@ -391,6 +396,22 @@ struct pxs_plan {
 };
 
 namespace {
+
+// One call on a plan (call_mu held, the plan's device selected): waits, on the call's stream, for the plan's previous call where that
+// ran on another stream, and records the plan's last use when the call has issued its launches (also when it ends in an exception:
+// what it launched up to there uses the scratch all the same).
+struct PlanUse {
+	pxs_plan* p; hipStream_t st;
+	PlanUse(pxs_plan* p_, hipStream_t st_) : p(p_), st(st_) {
+		if (p->used_any && st != p->used_stream) PXS_HIP(hipStreamWaitEvent(st, p->used, 0));
+	}
+	~PlanUse() {
+		if (!p->used && hipEventCreateWithFlags(&p->used, hipEventDisableTiming) != hipSuccess) p->used = nullptr;
+		if (p->used && hipEventRecord(p->used, st) == hipSuccess) { p->used_stream = st; p->used_any = true; }
+		else { (void)hipStreamSynchronize(st); p->used_any = false; }      // (no event: the call is complete before the next one starts)
+	}
+	PlanUse(const PlanUse&) = delete; PlanUse& operator=(const PlanUse&) = delete;
+};
 
 void plan_common(pxs_plan* p, int lmax, int mmax, const uint64_t* mstart, int64_t lstride, int device) {
 	PXS_REQUIRE(lmax >= 0 && mmax >= 0 && mmax <= lmax, "need 0 <= mmax <= lmax");
@@ -1029,6 +1050,8 @@ int pxs_debug_chain(pxs_plan* p, int kind, int nc, int spin, int reps, double* m
 	PXS_REQUIRE(p && ms && nc >= 1 && reps >= 1 && kind >= 0 && kind <= 4, "pxs_debug_chain: bad arguments");
 	PXS_REQUIRE(p->chain_rings && (kind < 2 || p->chain_theta()), "pxs_debug_chain: the plan has no fused chain for this stage");
 	PXS_HIP(hipSetDevice(p->device));
+	std::lock_guard<std::mutex> plan_lock(p->call_mu);
+	PlanUse use(p, nullptr);      // (runs on the NULL stream, on the plan's scratch)
 	const size_t nm = (size_t)p->mmax + 1, nr = (size_t)p->nring, c16 = sizeof(double2);
 	const long ldm = FftChain::pad8(p->nring), ldc = p->ld_cc(), ldh = p->ld_h();
 	DevBuf dmap;
@@ -1236,7 +1259,9 @@ static void synthesis_core(pxs_plan* p, int spin, int mode, int adjoint, int nb,
 // Scratch of a call is sized HERE, before its first launch (the fused-chain paths every BASELINE configuration takes; a plan's
 // buffers only grow, so this allocates on the first call of a kind and when a later call brings a larger batch).  The `ensure`
 // calls further down are then no-ops; they remain as the allocation points of the rarely taken paths (general ring sets,
-// unfused FFTs, the deterministic analysis), where a growing buffer is freed between launches through hipFree's device sync.
+// unfused FFTs, the deterministic analysis).  A buffer that grows gives its old block to the arena while the launches that use it may
+// still be queued (of this call, or of the plan's previous call on another stream): the arena synchronises the device before that
+// block serves anybody else (arena.hip), and a block below the arena's threshold goes through hipFree, which waits for the device.
 static void reserve_call(pxs_plan* p, int spin, int mode, bool synthesis, bool adjoint, int nb) {
 	if (p->general || !p->chain_rings) return;
 	const int ncm = synthesis ? ncomp_of(spin, mode, false) : (spin == 0 ? 1 : 2), nct = nb*ncm;
@@ -1311,6 +1336,7 @@ int pxs_synthesis(pxs_plan* p, int spin, int mode, int adjoint, int nbatch,
 	PXS_REQUIRE(nbatch >= 1, "pxs_synthesis: nbatch must be >= 1");
 	PXS_HIP(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream;
+	PlanUse use(p, st);      // (a points plan: its own scratch here, the grid plan's in the pxs_synthesis calls points_run makes on it)
 	if (p->pts) { points_run(p->pts, p->pgrid, spin, mode, adjoint, nbatch, alm, alm_dtype, alm_cstride, alm_bstride, map, map_dtype, map_cstride, map_bstride, st); return 0; }
 	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16, mesz = map_dtype == PX_F32 ? 4 : 8;
 	// (a grid whose ring FFTs are chained but whose theta resampling is not -- 2 ntheta with a prime factor >= 7 -- takes the
@@ -1435,6 +1461,7 @@ int pxs_analysis(pxs_plan* p, int spin, int adjoint, int nbatch,
 	if (p->lmax > grid_maxlmax(p->geometry, p->nring)) throw Error(PXS_ERR_ARG, "too few rings for analysis up to requested lmax");
 	PXS_HIP(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream;
+	PlanUse use(p, st);
 	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16, mesz = map_dtype == PX_F32 ? 4 : 8;
 	const int chunk = ana_path(p, adjoint) == ANA_UNFUSED ? 1 : batch_chunk(p, nbatch, spin == 0 ? 1 : 2);
 	reserve_call(p, spin, PXS_MODE_STANDARD, false, adjoint != 0, std::min(chunk, nbatch));

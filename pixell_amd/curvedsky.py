@@ -102,7 +102,8 @@ def quad_weights(shape, wcs, pix_tol=1e-6, row_order="reference"):
 # array plumbing
 # ---------------------------------------------------------------------------------------
 def _mdata(map):
-	return map.tensor if isinstance(map, enmap.dmap) else np.asarray(map)
+	if isinstance(map, enmap.dmap): return map.tensor
+	return map if _is_tensor(map) else np.asarray(map)      # (a bare device tensor stays where it is: alm2map_pos makes one for a tensor alm)
 
 def _zeros_like_kind(shape, dtype, like):
 	if _is_tensor(like):

@@ -140,7 +140,8 @@ class Plan:
 class _PlanCache:
 	"""least-recently-used cache of pxs_plan handles: a plan owns device scratch (tens of GB at the largest configurations), so a
 	sweep over geometries or band limits must not keep every plan alive.  PIXELL_AMD_MAX_PLANS (default 4) bounds the count; an
-	evicted plan is destroyed (its kernels are stream-ordered before the free)."""
+	evicted plan is destroyed.  Its kernels may still be queued, on any stream: the library's arena synchronises the device before a
+	block of the plan's scratch serves another plan or goes back to the driver (csrc/arena.hip)."""
 	def __init__(self):
 		import collections
 		self.d = collections.OrderedDict()
@@ -191,7 +192,8 @@ def tri_mstart(lmax, mmax=None):
 	return (m*(2*lmax+1-m)//2).astype(np.uint64)
 
 def grid_plan(geometry, ntheta, nphi, phi0, flip, lmax, mmax, mstart, lstride=1):
-	"""cached pxs_plan (a plan owns its device scratch: one call at a time per plan)"""
+	"""cached pxs_plan, shared by every stream of its device (a plan owns its device scratch: the library runs the calls on one plan in
+	the order they were issued, whatever their streams -- include/pxsht.h)"""
 	ms = np.ascontiguousarray(np.asarray(mstart)[:mmax+1], dtype=np.uint64)
 	key = ("g", geometry, int(ntheta), int(nphi), float(phi0), bool(flip[0]), bool(flip[1]), int(lmax), int(mmax), ms.tobytes(), int(lstride), device_index())
 	p = _plans.get(key)
