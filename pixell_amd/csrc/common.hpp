@@ -67,6 +67,13 @@ inline FastDiv make_fastdiv(uint32_t d) {
 
 enum DType : int { PX_F32 = 0, PX_F64 = 1, PX_C64 = 2, PX_C128 = 3 };
 
+// the alm and the maps of an SHT call as the C ABI hands them over: component c of batch member b starts at element
+// b*bstride + c*cstride of `dtype`; from(b): the same arrays from batch member b on
+struct AlmArg { void* ptr; int dtype; long cstride, bstride;
+	AlmArg from(long b) const { return AlmArg{(char*)ptr + (dtype == PX_C64 ? 8 : 16)*(size_t)b*bstride, dtype, cstride, bstride}; } };
+struct MapArg { void* ptr; int dtype; long cstride, bstride;
+	MapArg from(long b) const { return MapArg{(char*)ptr + (dtype == PX_F32 ? 4 : 8)*(size_t)b*bstride, dtype, cstride, bstride}; } };
+
 // Tuning and experiment switches (tile shapes, ring pairs per lane, planner overrides, alternative paths kept for A/B runs) are read
 // from the environment in LAB builds only (-DPXS_LAB, tools/build_variants.sh); the product build compiles their defaults in.  What
 // the product reads from the environment is listed in DESIGN.md ("Environment switches").

@@ -424,13 +424,10 @@ static void fft2(PointsState* s, hipStream_t st, long na, long nb, double2* data
 }
 
 // one call of pxs_synthesis on a points plan; grid: the CC plan it was made from
-void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint, int nb,
-                void* alm, int alm_dtype, long alm_cstride, long alm_bstride,
-                void* map, int map_dtype, long map_cstride, long map_bstride, hipStream_t st)
+void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint, int nb, const AlmArg& alm, const MapArg& map, hipStream_t st)
 {
 	const int ncm = (spin == 0 && mode == PXS_MODE_STANDARD) ? 1 : 2;
 	const long npix = (long)s->ntheta*s->nphi, nfield = (long)nb*ncm;
-	const size_t mesz = map_dtype == PX_F32 ? 4 : 8;
 	const double sgn = (spin & 1) ? -1.0 : 1.0;
 	const double scale = 1.0/((double)s->N1*s->nphi);
 	const int P = PT_T + s->W - 1;
@@ -455,10 +452,10 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 		}
 		evs.clear();
 	};
-	auto field = [&](long q) -> char* { const long b = q/ncm, c = q - b*ncm; return (char*)map + mesz*(b*map_bstride + c*map_cstride); };
+	auto field = [&](long q) -> char* { const long b = q/ncm, c = q - b*ncm; return (char*)map.from(b).ptr + (map.dtype == PX_F32 ? 4 : 8)*c*map.cstride; };
 	if (!adjoint) {
 		timed(PT_ST_CC, [&] {
-			const int rc = pxs_synthesis(grid, spin, mode, 0, nb, alm, alm_dtype, alm_cstride, alm_bstride, f, PX_F64, npix, ncm*npix, st);
+			const int rc = pxs_synthesis(grid, spin, mode, 0, nb, alm.ptr, alm.dtype, alm.cstride, alm.bstride, f, PX_F64, npix, ncm*npix, st);
 			if (rc != 0) throw Error(rc, pxs_last_error()); });
 		if (s->npts == 0) { collect(); return; }
 		for (long q = 0; q < nfield; q += 2) {
@@ -469,7 +466,7 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 				s->cbuf.as<double2>(), s->d1.as<double>(), s->d2.as<double>(), scale, s->fine.as<double2>()); });
 			timed(PT_ST_FFT, [&] { fft2(s, st, s->n1, s->n2, s->fine.as<double2>(), false); });
 			timed(PT_ST_INTERP, [&] { hipLaunchKernelGGL(pt_interp, dim3(nblocks(s->npts, 256)), dim3(256), 0, st, s->npts, s->xs.as<double2>(), s->perm.as<int64_t>(),
-				s->fine.as<double2>(), s->n1, s->n2, s->W, s->beta, (void*)field(q), two ? (void*)field(q+1) : nullptr, map_dtype); });
+				s->fine.as<double2>(), s->n1, s->n2, s->W, s->beta, (void*)field(q), two ? (void*)field(q+1) : nullptr, map.dtype); });
 			PXS_HIP(hipGetLastError());
 		}
 	} else {
@@ -480,7 +477,7 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 				if (s->npts > 0) {
 					const size_t shm = sizeof(double)*(2*(size_t)P*P + 64*(2*s->W + 4));
 					hipLaunchKernelGGL(pt_spread, dim3((unsigned)ntiles), dim3(64), shm, st, s->off.as<int64_t>(), s->xs.as<double2>(), s->perm.as<int64_t>(),
-						(const void*)field(q), two ? (const void*)field(q+1) : nullptr, map_dtype, s->n1, s->n2, s->nt2, s->W, s->beta, P, s->slab.as<double2>());
+						(const void*)field(q), two ? (const void*)field(q+1) : nullptr, map.dtype, s->n1, s->n2, s->nt2, s->W, s->beta, P, s->slab.as<double2>());
 					hipLaunchKernelGGL(pt_gather, dim3(nblocks(nfine, 256)), dim3(256), 0, st, s->n1, s->n2, s->nt1, s->nt2, P, s->slab.as<double2>(), s->fine.as<double2>());
 				} else PXS_HIP(hipMemsetAsync(s->fine.p, 0, sizeof(double2)*nfine, st)); });
 			timed(PT_ST_FFT, [&] { fft2(s, st, s->n1, s->n2, s->fine.as<double2>(), true); });
@@ -491,7 +488,7 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 			PXS_HIP(hipGetLastError());
 		}
 		timed(PT_ST_CC, [&] {
-			const int rc = pxs_synthesis(grid, spin, mode, 1, nb, alm, alm_dtype, alm_cstride, alm_bstride, f, PX_F64, npix, ncm*npix, st);
+			const int rc = pxs_synthesis(grid, spin, mode, 1, nb, alm.ptr, alm.dtype, alm.cstride, alm.bstride, f, PX_F64, npix, ncm*npix, st);
 			if (rc != 0) throw Error(rc, pxs_last_error()); });
 	}
 	collect();

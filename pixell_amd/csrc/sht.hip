@@ -32,8 +32,7 @@ const char* get_last_error();
 struct PointsState;
 PointsState* points_create(int ntheta, int nphi, int lmax, int mmax, int device, long npts, const double* d_loc, double eps, hipStream_t st);
 void points_free(PointsState* s);
-void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint, int nb, void* alm, int alm_dtype, long alm_cstride, long alm_bstride,
-                void* map, int map_dtype, long map_cstride, long map_bstride, hipStream_t st);
+void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint, int nb, const AlmArg& alm, const MapArg& map, hipStream_t st);
 int64_t points_query(const PointsState* s, const std::string& name);
 void points_profile(PointsState* s, bool on);
 
@@ -319,6 +318,40 @@ __global__ __launch_bounds__(256) void split_pair_transposed(const double2* __re
 
 using namespace pxs;
 
+// How one pxs_synthesis / pxs_analysis call runs.  route_of() decides it ONCE per call, from the plan and the call's arguments; the
+// scratch of the call (reserve_call), its batching, the stages it launches (run_core) and the queries all read this one object.
+enum RouteKind {
+	R_DIRECT,             // synthesis / its adjoint: Legendre stage on the map's own rings
+	R_VIA_CC,             // ... on the minimal CC grid, fused theta chain between that grid and the map's rings (grids, bands of F1 grids)
+	R_VIA_CC_UNFUSED,     // ... theta resampling through the generic FFT engine (no fused theta chain for this size), one map at a time
+	R_VIA_CC_UNFUSED_H,   // ... whose last stage writes the ring-major h directly (plans without a ring chain)
+	R_RING_WEIGHTS,       // analysis: quadrature weights on the map's rings + adjoint synthesis there (DH / F2; the weights form off the CC detour)
+	R_CC_WEIGHTS,         // analysis: ring weights, transposed theta upsampling, Legendre stage on the CC grid (the weights form with fused chains)
+	R_CHAIN,              // analysis: exact quadrature of the theta-interpolant through the fused chains (to_cc / to_cc_adjoint)
+	R_UNFUSED };          // analysis: ... through the generic FFT engine on dense rows, one map at a time
+static const char* const ROUTE_NAMES[] = {"direct", "via-cc", "via-cc-unfused", "via-cc-unfused-h", "ring-weights", "cc-weights", "chain", "unfused"};
+// the theta operation of a route; the values are the `kind` of FftChain::theta_scratch
+enum ThetaOp { TH_NONE = -1, TH_TO_CC = 0, TH_FROM_CC_ADJ = 1, TH_FROM_CC = 2, TH_TO_CC_ADJ = 3 };
+struct Route {
+	RouteKind kind = R_DIRECT;
+	bool to_map = true;            // alm -> map (synthesis, adjoint analysis) or map -> alm
+	bool batched = true;           // may take several maps per pass (batch_chunk); false: one map at a time
+	int nc = 1, deriv1 = 0;        // map components per map
+	const LegTables* tb = nullptr;       // (null in the routes the queries make: they size nothing)
+	const RingSet* rs = nullptr;         // ring set of the Legendre stage: the plan's rs_map (buffer leg) or rs_cc (buffer leg2)
+	// row strides of leg[c][m][ring], leg2[c][m][cc ring], h[c][ring][m] (padded to whole 128-byte lines on the fused routes, dense on
+	// the unfused ones; 0: the route does not touch that buffer) and the rings of h per component
+	long ld_leg = 0, ld_leg2 = 0, ld_h = 0; int nr_h = 0;
+	long ld_leg_alloc = 0;         // leg is SIZED for rows of this stride: ld_leg but for the CC-grid synthesis, see route_of
+	// theta operation between the map's grid (nr_th rings: the whole grid for a band) and the CC grid, with the tables of its form
+	ThetaOp theta = TH_NONE; bool theta_fused = false, line = false;      // line: the single-kernel engine takes it (thetaline.hip; no intermediates)
+	int nr_th = 0; const ThetaPlan* tp = nullptr; const double2 *sigma = nullptr, *wcc = nullptr, *whalf = nullptr; long M = 0; bool fine = false;
+	bool reserve_chain = false;    // the call reserves the ping-pong scratch of the plan's FFT chains
+	// bytes the call needs for nb maps per pass: the plan's leg / leg2 / hbuf, the Legendre work arrays, the chain's ping-pong scratch
+	struct Scratch { size_t leg = 0, leg2 = 0, h = 0, almt = 0, mom = 0, c1 = 0, c2 = 0, r1 = 0; };
+	Scratch scratch(const pxs_plan* p, int nb) const;
+};
+
 struct pxs_plan {
 	// a plan serves one call at a time (it owns the scratch of the call, and the analysis option is read several times in a call):
 	// the entry points that run or reconfigure it take this lock, so two host threads on one cached plan queue up instead of interleaving
@@ -373,16 +406,16 @@ struct pxs_plan {
 	bool ring_pairs = true;      // transform two real rings per complex FFT (PXS_RING_PAIRS=0 disables)
 	FftContext* fc = nullptr;
 	// fused FFT chains (fftchain.hip).  chain_rings: ring FFTs through MA1/MA2, MS1/MS2; tp.ok: theta resampling through RA1-5 / RS1-3.
-	// The chain paths use row strides padded to whole 128-byte lines for leg / leg_cc / h; the older unfused paths (kept for
-	// aliased rings, lengths without a usable factorisation, the adjoint of the analysis) use dense rows.  A stride is chosen per call.
+	// These say what the plan CAN do; which of it a call uses, and with which row strides (padded to whole 128-byte lines on the chain
+	// routes, dense on the unfused ones kept for aliased rings and lengths without a usable factorisation), is the call's Route.
 	std::unique_ptr<FftChain> chain; ThetaPlan tp; bool chain_rings = false;
 	bool chain_theta() const { return chain_rings && tp.ok; }
 	long ld_map() const { return chain_rings ? FftChain::pad8(nring) : nring; }
 	long ld_cc()  const { return chain_theta() ? FftChain::pad8(ncc) : ncc; }
 	long ld_h()   const { return chain_rings ? FftChain::pad8(mmax + 1) : mmax + 1; }
-	FftChain::MapDesc map_desc(const void* map, int dtype, long cstride, long bstride = 0, int ncb = 0) const {
-		FftChain::MapDesc m; m.ptr = map; m.dtype = dtype; m.cstride = cstride; m.ring_off0 = ring_off0; m.ring_stride = ring_stride; m.pix_stride = pix_stride; m.nring = nring; m.nphi = nphi;
-		m.bstride = bstride; m.ncb = ncb;
+	FftChain::MapDesc map_desc(const MapArg& a, int ncb = 0) const {
+		FftChain::MapDesc m; m.ptr = a.ptr; m.dtype = a.dtype; m.cstride = a.cstride; m.ring_off0 = ring_off0; m.ring_stride = ring_stride; m.pix_stride = pix_stride; m.nring = nring; m.nphi = nphi;
+		m.bstride = a.bstride; m.ncb = ncb;
 		return m; }
 	LegProfile prof;
 	size_t resample_chunk_bytes = size_t(1) << 40;    // per intermediate buffer of the theta-FFT chain (chunking to stay in the
@@ -393,7 +426,41 @@ struct pxs_plan {
 		if (!p) { p.reset(new LegTables()); p->build(lmax, mmax, spin); }
 		return *p;
 	}
+	// Legendre stage of a route for nb maps: alm -> the route's buffer on its ring set with its row stride (rs_map: leg, rs_cc: leg2) ...
+	DevBuf& leg_buf(const Route& r) { return r.rs == &rs_cc ? leg2 : leg; }
+	void leg_syn(hipStream_t st, const Route& r, const AlmArg& a, int nb) {
+		const long ld = r.rs == &rs_cc ? r.ld_leg2 : r.ld_leg;
+		leg_synthesis(st, *r.rs, *r.tb, wk, a.ptr, a.dtype, a.cstride, d_mstart.as<uint64_t>(), lstride, leg_buf(r).as<double2>(), r.deriv1, &prof, ld, nb, a.bstride, (long)r.nc*(mmax + 1)*ld);
+	}
+	// ... and its transpose
+	void leg_ana(hipStream_t st, const Route& r, const AlmArg& a, int nb) {
+		const long ld = r.rs == &rs_cc ? r.ld_leg2 : r.ld_leg;
+		leg_analysis(st, *r.rs, *r.tb, wk, leg_buf(r).as<double2>(), a.ptr, a.dtype, a.cstride, d_mstart.as<uint64_t>(), lstride, r.deriv1, &prof, ld, nb, a.bstride, (long)r.nc*(mmax + 1)*ld);
+	}
+	// the fused theta operation of a route on nct components: leg <-> leg2 (analysis side), leg2 -> h (synthesis side); wring: optional weight per ring of the map
+	void run_theta(hipStream_t st, const Route& r, int nct, int spin, const double2* wring) {
+		const int nm = mmax + 1;
+		double2 *l1 = leg.as<double2>(), *l2 = leg2.as<double2>(), *h = hbuf.as<double2>();
+		prof.begin(st, PXS_STAGE_RESAMPLE);
+		switch (r.theta) {
+		case TH_TO_CC:       chain->to_cc(st, *r.tp, l1, r.ld_leg, r.nr_th, mir_c, l2, r.ld_leg2, ncc, nct, nm, spin, lmax, ph_shift.as<double2>(), r.sigma, r.wcc); break;
+		case TH_FROM_CC_ADJ: chain->from_cc_adjoint(st, *r.tp, l1, r.ld_leg, r.nr_th, mir_c, l2, r.ld_leg2, ncc, nct, nm, spin, lmax, ph_shift.as<double2>(), wadj.as<double2>(), wring); break;
+		case TH_FROM_CC:     chain->from_cc(st, *r.tp, l2, r.ld_leg2, ncc, h, r.ld_h, r.nr_h, mir_c, nct, nm, spin, lmax, ph_up.as<double2>(), phase.as<double2>(), 1.0/(double)Ncc, wring); break;
+		case TH_TO_CC_ADJ:   chain->to_cc_adjoint(st, *r.tp, l2, r.ld_leg2, ncc, h, r.ld_h, r.nr_h, mir_c, nct, nm, spin, lmax, ph_shift.as<double2>(), r.sigma, r.whalf, phase.as<double2>(), 2.0); break;
+		case TH_NONE: break;
+		}
+		prof.end(st, PXS_STAGE_RESAMPLE);
+	}
 };
+
+Route::Scratch Route::scratch(const pxs_plan* p, int nb) const {
+	Scratch s; const size_t nct = (size_t)nb*nc, nm = (size_t)p->mmax + 1, c16 = sizeof(double2);
+	s.leg = c16*nct*nm*ld_leg_alloc; s.leg2 = c16*nct*nm*ld_leg2; s.h = c16*nct*nr_h*ld_h;
+	if (to_map) s.almt = sizeof(double)*4*(tb->nrows + 4)*nb; else s.mom = sizeof(double)*4*std::max<long>(tb->nrows, 1)*nb;
+	if (theta_fused && !line) FftChain::theta_scratch(*tp, (int)nm, (int)nct, theta, s.c1, s.c2);
+	if (reserve_chain) p->chain->ring_scratch(p->nring, (int)nct, !to_map, s.r1, p->mmax);
+	return s;
+}
 
 namespace {
 
@@ -591,18 +658,19 @@ int ncomp_of(int spin, int mode, bool alm_side) {
 	return spin == 0 ? 1 : 2;
 }
 
-// ring FFT: user map -> hbuf[c][ring][m] -> leg[c][m][ring] * e^{-i m phi0} * scale
-// (ld: row stride of leg; the unfused path below only writes dense rows, ld == nring)
-void map2leg(pxs_plan* p, hipStream_t st, const void* map, int map_dtype, long map_cstride, int nc, double2* leg, double scale, long ldl, long map_bstride = 0, int ncb = 0) {
+// ring FFT of the nb maps of a pass: user map -> hbuf[c][ring][m] -> leg[c][m][ring] * e^{-i m phi0}
+// (row stride of leg: the route's ld_leg; the unfused path below only writes dense rows, ld_leg == nring)
+void map2leg(pxs_plan* p, hipStream_t st, const Route& r, const MapArg& m, int nb, double2* leg) {
 	p->prof.begin(st, PXS_STAGE_RING_FFT);
-	const int nm = p->mmax+1, nr = p->nring;
+	const int nm = p->mmax+1, nr = p->nring, nc = nb*r.nc, ncb = nb > 1 ? r.nc : 0;
+	const long ldl = r.ld_leg;
 	if (p->general) {
 		PXS_REQUIRE(ncb == 0, "internal: general ring sets take one map per call");
-		p->gz.ensure(sizeof(double2)*(size_t)nc*p->npixz);
-		const GenK g = gen_args(p, nc, ldl, map_cstride, scale);
+		p->gz.ensure(sizeof(double2)*(size_t)nc*p->npixz);      // (general ring sets size their own z here)
+		const GenK g = gen_args(p, nc, ldl, m.cstride, 1.0);
 		const dim3 grid((unsigned)p->g_nblk, nc);
-		if (map_dtype == PX_F32) hipLaunchKernelGGL(gen_gather<float>, grid, dim3(256), 0, st, g, (const float*)map, p->gz.as<double2>());
-		else                     hipLaunchKernelGGL(gen_gather<double>, grid, dim3(256), 0, st, g, (const double*)map, p->gz.as<double2>());
+		if (m.dtype == PX_F32) hipLaunchKernelGGL(gen_gather<float>, grid, dim3(256), 0, st, g, (const float*)m.ptr, p->gz.as<double2>());
+		else                     hipLaunchKernelGGL(gen_gather<double>, grid, dim3(256), 0, st, g, (const double*)m.ptr, p->gz.as<double2>());
 		gen_ffts(p, st, nc, true);
 		hipLaunchKernelGGL(gen_unfold, dim3((nr + 255)/256, std::min(nm, 4096), nc), dim3(256), 0, st, g, (const double2*)p->gz.p, leg);
 		p->prof.end(st, PXS_STAGE_RING_FFT);
@@ -610,79 +678,79 @@ void map2leg(pxs_plan* p, hipStream_t st, const void* map, int map_dtype, long m
 		return;
 	}
 	if (p->chain_rings) {
-		p->chain->map2leg(st, p->map_desc(map, map_dtype, map_cstride, map_bstride, ncb), nc, p->mmax, leg, ldl, p->phase.as<double2>(), scale);
+		p->chain->map2leg(st, p->map_desc(m, ncb), nc, p->mmax, leg, ldl, p->phase.as<double2>(), 1.0);
 		p->prof.end(st, PXS_STAGE_RING_FFT);
 		return;
 	}
 	PXS_REQUIRE(ldl == nr && ncb == 0, "internal: unfused ring FFT needs dense rows and single maps");
 	auto esz = [](int dt) { return dt == PX_F32 ? 4 : 8; };
+	// (the unfused ring FFT of a map sizes its own packed spectra in hbuf, here and below)
 	if (2L*p->mmax < p->nphi && p->ring_pairs) {
 		// two real rings per complex transform; the pruned two-sided spectrum (|k| <= mmax) is unpacked in the transpose
 		const int npair = (nr + 1)/2; const long rowlen = 2L*p->mmax + 1;
 		p->hbuf.ensure(sizeof(double2)*(size_t)nc*std::max<size_t>((size_t)npair*rowlen, (size_t)nr*nm));
-		FftDims d; d.n_i = npair; d.is_i = p->ring_stride; d.os_i = rowlen; d.n_o1 = nc; d.is_o1 = map_cstride; d.os_o1 = (long)npair*rowlen;
+		FftDims d; d.n_i = npair; d.is_i = p->ring_stride; d.os_i = rowlen; d.n_o1 = nc; d.is_o1 = m.cstride; d.os_o1 = (long)npair*rowlen;
 		d.is_e = p->pix_stride; d.os_e = 1;
-		FftLoad ld; ld.ptr = (const char*)map + esz(map_dtype)*p->ring_off0; ld.dtype = map_dtype; ld.mode = LD_REAL_PAIR; ld.pair_lines = nr;
+		FftLoad ld; ld.ptr = (const char*)m.ptr + esz(m.dtype)*p->ring_off0; ld.dtype = m.dtype; ld.mode = LD_REAL_PAIR; ld.pair_lines = nr;
 		FftStore sf; sf.ptr = p->hbuf.p; sf.two_sided_k = p->mmax; sf.compact_two_sided = 1;
 		p->fc->exec(st, p->nphi, true, d, ld, sf);
 		dim3 grid((nm+31)/32, (npair+31)/32, nc);
 		hipLaunchKernelGGL(unpack_pair_transpose, grid, dim3(256), sizeof(double2)*2*32*33, st, (const double2*)p->hbuf.p, leg, nr, nm,
-			(long)npair*rowlen, (long)nr*nm, (const double2*)p->phase.p, scale);
+			(long)npair*rowlen, (long)nr*nm, (const double2*)p->phase.p, 1.0);
 		p->prof.end(st, PXS_STAGE_RING_FFT);
 		PXS_HIP(hipGetLastError());
 		return;
 	}
 	const int ncin = std::min(nm, p->nphi);           // distinct FFT bins needed (m >= nphi alias onto m mod nphi)
 	p->hbuf.ensure(sizeof(double2)*(size_t)nc*nr*nm);
-	FftDims d; d.n_i = nr; d.is_i = p->ring_stride; d.os_i = ncin; d.n_o1 = nc; d.is_o1 = map_cstride; d.os_o1 = (long)nr*ncin;
+	FftDims d; d.n_i = nr; d.is_i = p->ring_stride; d.os_i = ncin; d.n_o1 = nc; d.is_o1 = m.cstride; d.os_o1 = (long)nr*ncin;
 	d.is_e = p->pix_stride; d.os_e = 1;
-	FftLoad ld; ld.ptr = (const char*)map + esz(map_dtype)*p->ring_off0; ld.dtype = map_dtype;
+	FftLoad ld; ld.ptr = (const char*)m.ptr + esz(m.dtype)*p->ring_off0; ld.dtype = m.dtype;
 	FftStore sf; sf.ptr = p->hbuf.p; sf.ne = ncin;
 	p->fc->exec(st, p->nphi, true, d, ld, sf);
 	if (ncin == nm) {
 		dim3 grid((nm+31)/32, (nr+31)/32, nc);
 		hipLaunchKernelGGL(transpose_mul, grid, dim3(256), sizeof(double2)*32*33, st, (const double2*)p->hbuf.p, leg, nr, nm,
-			(long)nr*nm, (long)nr*nm, (const double2*)p->phase.p, 0, scale);
+			(long)nr*nm, (long)nr*nm, (const double2*)p->phase.p, 0, 1.0);
 	} else {
 		dim3 grid((unsigned)(((long)nr*nm + 255)/256), nc);
 		hipLaunchKernelGGL(gather_alias, grid, dim3(256), 0, st, (const double2*)p->hbuf.p, leg, nr, nm, ncin, p->nphi,
-			(long)nr*ncin, (long)nr*nm, (const double2*)p->phase.p, scale);
+			(long)nr*ncin, (long)nr*nm, (const double2*)p->phase.p, 1.0);
 	}
 	p->prof.end(st, PXS_STAGE_RING_FFT);
 	PXS_HIP(hipGetLastError());
 }
 
-// leg[c][m][ring] * e^{+i m phi0} -> hbuf[c][ring][m] -> c2r ring FFT -> user map
-// (ldleg: row stride of leg; hbuf rows are ld_h() long)
-void leg2map(pxs_plan* p, hipStream_t st, const double2* leg, long ldleg, void* map, int map_dtype, long map_cstride, int nc, bool have_h = false, long map_bstride = 0, int ncb = 0) {
+// the nb maps of a pass: leg[c][m][ring] * e^{+i m phi0} -> hbuf[c][ring][m] -> c2r ring FFT -> user map
+// (leg: rows of stride ldleg; null: the route's theta stage has written hbuf already.  hbuf: the route's ld_h and nr_h, sized by reserve_call)
+void leg2map(pxs_plan* p, hipStream_t st, const Route& r, const double2* leg, long ldleg, const MapArg& m, int nb) {
 	p->prof.begin(st, PXS_STAGE_RING_FFT);
-	const int nm = p->mmax+1, nr = p->nring;
+	const int nm = p->mmax+1, nr = p->nring, nc = nb*r.nc, ncb = nb > 1 ? r.nc : 0;
+	const bool have_h = leg == nullptr;
 	if (p->general) {
 		PXS_REQUIRE(ncb == 0 && !have_h, "internal: general ring sets take one map per call");
-		p->gz.ensure(sizeof(double2)*(size_t)nc*p->npixz);
-		const GenK g = gen_args(p, nc, ldleg, map_cstride, 1.0);
+		p->gz.ensure(sizeof(double2)*(size_t)nc*p->npixz);      // (general ring sets size their own z here)
+		const GenK g = gen_args(p, nc, ldleg, m.cstride, 1.0);
 		const dim3 grid((unsigned)p->g_nblk, nc);
 		hipLaunchKernelGGL(gen_fold, grid, dim3(256), 0, st, g, leg, p->gz.as<double2>());
 		gen_ffts(p, st, nc, false);
-		if (map_dtype == PX_F32) hipLaunchKernelGGL(gen_scatter<float>, grid, dim3(256), 0, st, g, (const double2*)p->gz.p, (float*)map);
-		else                     hipLaunchKernelGGL(gen_scatter<double>, grid, dim3(256), 0, st, g, (const double2*)p->gz.p, (double*)map);
+		if (m.dtype == PX_F32) hipLaunchKernelGGL(gen_scatter<float>, grid, dim3(256), 0, st, g, (const double2*)p->gz.p, (float*)m.ptr);
+		else                     hipLaunchKernelGGL(gen_scatter<double>, grid, dim3(256), 0, st, g, (const double2*)p->gz.p, (double*)m.ptr);
 		p->prof.end(st, PXS_STAGE_RING_FFT);
 		PXS_HIP(hipGetLastError());
 		(void)nm;
 		return;
 	}
-	const long ldh = p->ld_h();
-	p->hbuf.ensure(sizeof(double2)*(size_t)nc*(have_h && p->band ? p->nfull : nr)*ldh);
-	if (!have_h) {      // (the CC synthesis path has written hbuf already, see resample_from_cc / FftChain::from_cc)
+	const long ldh = r.ld_h;
+	if (!have_h) {
 		dim3 grid((nm+31)/32, (nr+31)/32, nc);
 		hipLaunchKernelGGL(transpose_mul_outcol, grid, dim3(256), sizeof(double2)*32*33, st, leg, (double2*)p->hbuf.p, nr, nm,
 			(long)nm*ldleg, (long)nr*ldh, (const double2*)p->phase.p, 1, 1.0, ldleg, ldh);
 	}
 	if (p->chain_rings) {
-		// (have_h on a band plan: h holds all nfull rings of the grid, the map's rings start at row0)
-		const bool full_h = have_h && p->band;
-		p->chain->h2map(st, p->hbuf.as<double2>() + (full_h ? (size_t)p->row0*ldh : 0), ldh, p->map_desc(map, map_dtype, map_cstride, map_bstride, ncb), nc, p->mmax,
-			full_h ? p->nfull : 0);
+		// (the CC detour of a band plan: h holds all nfull rings of the grid, the map's rings start at row0)
+		const bool full_h = r.nr_h > nr;
+		p->chain->h2map(st, p->hbuf.as<double2>() + (full_h ? (size_t)p->row0*ldh : 0), ldh, p->map_desc(m, ncb), nc, p->mmax, full_h ? r.nr_h : 0);
 		p->prof.end(st, PXS_STAGE_RING_FFT);
 		return;
 	}
@@ -690,16 +758,16 @@ void leg2map(pxs_plan* p, hipStream_t st, const double2* leg, long ldleg, void* 
 	auto esz = [](int dt) { return dt == PX_F32 ? 4 : 8; };
 	if (2L*p->mmax < p->nphi && p->ring_pairs) {
 		// two rings per complex transform: Z = X_a + i X_b, real part -> ring 2q, imaginary part -> ring 2q+1
-		FftDims d; d.n_i = (nr + 1)/2; d.is_i = nm; d.os_i = p->ring_stride; d.n_o1 = nc; d.is_o1 = (long)nr*nm; d.os_o1 = map_cstride;
+		FftDims d; d.n_i = (nr + 1)/2; d.is_i = nm; d.os_i = p->ring_stride; d.n_o1 = nc; d.is_o1 = (long)nr*nm; d.os_o1 = m.cstride;
 		d.is_e = 1; d.os_e = p->pix_stride;
 		FftLoad ld; ld.ptr = p->hbuf.p; ld.mode = LD_HERM_PAIR; ld.ne = nm; ld.pair_lines = nr;
-		FftStore sf; sf.ptr = (char*)map + esz(map_dtype)*p->ring_off0; sf.dtype = map_dtype; sf.real_pair = 1; sf.pair_lines = nr;
+		FftStore sf; sf.ptr = (char*)m.ptr + esz(m.dtype)*p->ring_off0; sf.dtype = m.dtype; sf.real_pair = 1; sf.pair_lines = nr;
 		p->fc->exec(st, p->nphi, false, d, ld, sf);
 	} else {
-		FftDims d; d.n_i = nr; d.is_i = nm; d.os_i = p->ring_stride; d.n_o1 = nc; d.is_o1 = (long)nr*nm; d.os_o1 = map_cstride;
+		FftDims d; d.n_i = nr; d.is_i = nm; d.os_i = p->ring_stride; d.n_o1 = nc; d.is_o1 = (long)nr*nm; d.os_o1 = m.cstride;
 		d.is_e = 1; d.os_e = p->pix_stride;
 		FftLoad ld; ld.ptr = p->hbuf.p; ld.mode = LD_HERM; ld.ne = nm; ld.herm_fold = 1;
-		FftStore sf; sf.ptr = (char*)map + esz(map_dtype)*p->ring_off0; sf.dtype = map_dtype;
+		FftStore sf; sf.ptr = (char*)m.ptr + esz(m.dtype)*p->ring_off0; sf.dtype = m.dtype;
 		p->fc->exec(st, p->nphi, false, d, ld, sf);
 	}
 	p->prof.end(st, PXS_STAGE_RING_FFT);
@@ -1012,25 +1080,33 @@ int pxs_plan_option(pxs_plan* p, const char* name, int64_t value) {
 	PXS_CATCH
 }
 
-static int ana_form_now(const pxs_plan* p);
-static int theta_line_now(const pxs_plan* p);
+// tables of the interpolating forms of the analysis (fused chains or the unfused engine): the fine-CC form (the default; the weights option
+// on a grid below 2 lmax + 2 rings takes it too), else the interpolant form
+struct AnaSet { const ThetaPlan* tp; const double2* sigma; const double2* wcc; const double2* whalf; long M; bool fine; };
+static AnaSet ana_set(const pxs_plan* p, bool allow_fine = true) {
+	if (allow_fine && p->ana_weights != 0 && p->Mf > 0) return AnaSet{&p->tpf, p->sigma_f.as<double2>(), p->wcc_f.as<double2>(), p->whalf_f.as<double2>(), p->Mf, true};
+	return AnaSet{&p->tp, p->sigma.as<double2>(), p->wcc.as<double2>(), p->whalf.as<double2>(), p->M, false};
+}
+static Route route_of(const pxs_plan* p, bool analysis, int spin, int mode, bool adjoint, const LegTables* tb);
+static Route analysis_route_now(const pxs_plan* p) { return route_of(p, true, 0, PXS_MODE_STANDARD, false, nullptr); }      // pxs_analysis under the plan's current option
 int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	PXS_TRY
 	PXS_REQUIRE(p && name && value, "pxs_plan_query: null argument");
 	const std::string n(name);
 	if (p->pts) *value = points_query(p->pts, n);
-	else if (n == "analysis_form") *value = ana_form_now(p);
+	else if (n == "analysis_form") { const Route r = analysis_route_now(p); *value = (r.kind == R_RING_WEIGHTS || r.kind == R_CC_WEIGHTS) ? 1 : (r.fine ? 2 : 0); }
 	else if (n == "ncc_circle") *value = p->ncc > 0 ? p->Ncc : 0;
 	else if (n == "ducc_ncc_circle") *value = FftChain::ducc_ncc(p->lmax);
-	else if (n == "theta_line") *value = theta_line_now(p);
+	else if (n == "theta_line") *value = analysis_route_now(p).line ? 1 : 0;      // 1: its theta resampling runs as ONE kernel per call (thetaline.hip), 0: as the stage chain
 	else throw Error(PXS_ERR_ARG, std::string("pxs_plan_query: unknown name '") + name + "'");
 	PXS_CATCH
 }
 
 int pxs_plan_info(const pxs_plan* p, int* nsyn, int* nana, int64_t* scratch) {
 	if (!p) return PXS_ERR_ARG;
-	if (nsyn) *nsyn = (p->syn_via_cc && p->ncc > 0) ? p->ncc : p->nring;
-	if (nana) *nana = p->ncc > 0 ? p->ncc : p->nring;
+	// rings of the Legendre stage of a spin-2 synthesis (the call's route) and of the interpolating analysis
+	if (nsyn) *nsyn = route_of(p, false, 2, PXS_MODE_STANDARD, false, nullptr).rs->nring;
+	if (nana) *nana = p->ncc > 0 ? p->ncc : p->nring;      // (the CC grid where the plan has one, whatever the analysis option: what this has always reported)
 	if (scratch) *scratch = (int64_t)(p->leg.bytes + p->leg2.bytes + p->hbuf.bytes + p->b1.bytes + p->b2.bytes + p->wk.almt.bytes + p->wk.part.bytes + p->wk.mom.bytes);
 	return 0;
 }
@@ -1060,13 +1136,13 @@ int pxs_debug_chain(pxs_plan* p, int kind, int nc, int spin, int reps, double* m
 	PXS_HIP(hipMemset(p->leg.p, 0, p->leg.bytes)); PXS_HIP(hipMemset(p->leg2.p, 0, p->leg2.bytes)); PXS_HIP(hipMemset(p->hbuf.p, 0, p->hbuf.bytes));
 	hipStream_t st = nullptr;
 	auto run = [&]() {
-		const FftChain::MapDesc md = p->map_desc(dmap.p, PX_F64, (long)nr*p->nphi);
+		const FftChain::MapDesc md = p->map_desc(MapArg{dmap.p, PX_F64, (long)nr*p->nphi, 0});
 		switch (kind) {
 		case 0: p->chain->map2leg(st, md, nc, p->mmax, p->leg.as<double2>(), ldm, p->phase.as<double2>(), 1.0); break;
 		case 1: p->chain->h2map(st, p->hbuf.as<double2>(), ldh, md, nc, p->mmax); break;
-		case 2: { const bool f = p->ana_weights != 0 && p->Mf > 0 && p->tpf.ok;      // (the form the plan's analysis option selects)
-			p->chain->to_cc(st, f ? p->tpf : p->tp, p->leg.as<double2>(), ldm, p->nring, p->mir_c, p->leg2.as<double2>(), ldc, p->ncc, nc, (int)nm, spin, p->lmax,
-				p->ph_shift.as<double2>(), (f ? p->sigma_f : p->sigma).as<double2>(), (f ? p->wcc_f : p->wcc).as<double2>()); } break;
+		case 2: { AnaSet as = ana_set(p); if (!as.tp->ok) as = ana_set(p, false);      // (the form the plan's analysis option selects, where the chains hold it)
+			p->chain->to_cc(st, *as.tp, p->leg.as<double2>(), ldm, p->nring, p->mir_c, p->leg2.as<double2>(), ldc, p->ncc, nc, (int)nm, spin, p->lmax,
+				p->ph_shift.as<double2>(), as.sigma, as.wcc); } break;
 		case 3: p->chain->from_cc(st, p->tp, p->leg2.as<double2>(), ldc, p->ncc, p->hbuf.as<double2>(), ldh, p->nring, p->mir_c, nc, (int)nm, spin, p->lmax,
 				p->ph_up.as<double2>(), p->phase.as<double2>(), 1.0/(double)p->Ncc); break;
 		default: p->chain->from_cc_adjoint(st, p->tp, p->leg.as<double2>(), ldm, p->nring, p->mir_c, p->leg2.as<double2>(), ldc, p->ncc, nc, (int)nm, spin, p->lmax,
@@ -1113,42 +1189,64 @@ int pxs_profile_read(pxs_plan* p, double* ms, int* counts, int reset) {
 	PXS_CATCH
 }
 
-// How a pxs_analysis call runs.  Decided HERE, once, for reserve_call, the batch chunking and analysis_core.
-enum AnaPath {
-	ANA_RING_WEIGHTS,   // quadrature weights on the map's rings + (adjoint) synthesis there: DH / F2 grids; the weights option on grids without the CC detour
-	ANA_CC_WEIGHTS,     // the weights option on F1 grids with fused chains: ring weights, transposed theta upsampling, Legendre stage on the CC grid
-	ANA_CHAIN,          // exact quadrature of the theta-interpolant through the fused chains (to_cc / to_cc_adjoint)
-	ANA_UNFUSED };      // ... through the generic FFT engine on dense rows, one map at a time
-static bool adj_ana_fused() { const char* e = getenv("PXS_ADJ_ANA_FUSED"); return e ? atoi(e) != 0 : true; }      // (read per call: the tests switch it)
-static AnaPath ana_path(const pxs_plan* p, int adjoint) {
-	if (p->wring.p) return ANA_RING_WEIGHTS;
+// THE route decision of a call: every test of what the plan can do and of the lab switches is here and nowhere else.
+// analysis: pxs_analysis (else pxs_synthesis); tb: the recurrence tables of the spin (null: a query, which sizes nothing)
+static Route route_of(const pxs_plan* p, bool analysis, int spin, int mode, bool adjoint, const LegTables* tb) {
+	Route r;
+	const int nr = p->nring;
+	const bool th = p->chain_theta();
+	const long ldm = p->ld_map(), ldc = p->ld_cc(), ldh = p->ld_h();
+	r.to_map = analysis ? adjoint : !adjoint; r.tb = tb;
+	r.nc = analysis ? (spin == 0 ? 1 : 2) : ncomp_of(spin, mode, false); r.deriv1 = mode == PXS_MODE_DERIV1;
+	r.rs = &p->rs_map; r.nr_th = nr; r.tp = &p->tp;
+	auto use_h = [&](int rows) { r.nr_h = rows; r.ld_h = ldh; };
+	auto form = [&](const AnaSet& as) { r.tp = as.tp; r.sigma = as.sigma; r.wcc = as.wcc; r.whalf = as.whalf; r.M = as.M; r.fine = as.fine; };
+	if (!analysis) {
+		// Legendre stage on the minimal CC grid + exact Fourier resampling in theta where the map has clearly more rings (the thresholds of
+		// setup_resampling): grids, and bands of F1 grids (their rows outside the band are zero)
+		const bool cc = (p->is_grid || (p->band && th)) && (spin == 0 ? p->syn_via_cc0 : p->syn_via_cc) && p->ncc > 0;
+		static const bool adj_cc = [] { const char* e = lab_getenv("PXS_ADJ_VIA_CC"); return e ? atoi(e) != 0 : true; }();
+		static const bool fuse = [] { const char* e = lab_getenv("PXS_FUSE_SPLIT"); return e ? atoi(e) != 0 : true; }();
+		r.ld_leg = r.ld_leg_alloc = ldm;
+		if (!cc || (adjoint && !(th && adj_cc))) { r.kind = R_DIRECT; if (!adjoint && !p->general) use_h(nr); }
+		else {
+			r.rs = &p->rs_cc; r.ld_leg2 = ldc; r.nr_th = p->band ? p->nfull : nr;      // (a band: the theta stage works on every ring of its grid)
+			if (adjoint) { r.kind = R_VIA_CC; r.theta = TH_FROM_CC_ADJ; r.ld_leg = r.ld_leg_alloc = p->band ? FftChain::pad8(p->nfull) : ldm; }
+			else if (th) { r.kind = R_VIA_CC; r.theta = TH_FROM_CC; use_h(r.nr_th); r.ld_leg = 0; }      // (leg: unused, but sized as it always was -- a plan's scratch_bytes are part of what it reports)
+			// (a grid whose ring FFTs are chained but whose theta resampling is not -- 2 ntheta with a prime factor >= 7 -- and one without any chain)
+			else { r.kind = (fuse && !p->chain_rings) ? R_VIA_CC_UNFUSED_H : R_VIA_CC_UNFUSED; r.theta = TH_FROM_CC; use_h(nr); r.ld_leg = nr; }      // (the unfused split writes dense rows)
+		}
+	} else if (p->wring.p) { r.kind = R_RING_WEIGHTS; }
 	// ring weights on the map's own rings: the weights option, and ducc0's route on CC grids with >= 2 lmax + 2 rings (its
 	// resample_to_prepared_CC multiplies such a grid by its weights directly: need_first_resample is false for it)
-	if ((p->ana_weights == 1 || (p->ana_weights == 2 && p->geometry == "CC")) && (long)p->nring >= 2L*p->lmax + 2)
-		return (p->chain_theta() && p->ncc > 0) ? ANA_CC_WEIGHTS : ANA_RING_WEIGHTS;
-	const bool fine = p->ana_weights != 0 && p->Mf > 0;        // the fine-CC form (default; the weights option on a grid below 2 lmax + 2 rings takes it too)
-	if (p->chain_theta() && (fine ? p->tpf.ok : (!adjoint || adj_ana_fused()))) return ANA_CHAIN;
-	return ANA_UNFUSED;      // (also: the fine-CC form on a plan whose chains cannot hold the circle of 2 N_cc points)
+	else if ((p->ana_weights == 1 || (p->ana_weights == 2 && p->geometry == "CC")) && (long)nr >= 2L*p->lmax + 2)
+		r.kind = (th && p->ncc > 0) ? R_CC_WEIGHTS : R_RING_WEIGHTS;
+	else {
+		form(ana_set(p));
+		// (the adjoint of the interpolant form: PXS_ADJ_ANA_FUSED=0 sends it through the unfused engine; read per call, the tests switch it.
+		//  Unfused also: the fine-CC form on a plan whose chains cannot hold the circle of 2 N_cc points)
+		auto adj_ana_fused = [] { const char* e = getenv("PXS_ADJ_ANA_FUSED"); return e ? atoi(e) != 0 : true; };
+		r.kind = (th && (r.fine ? r.tp->ok : (!adjoint || adj_ana_fused()))) ? R_CHAIN : R_UNFUSED;
+	}
+	if (analysis) {      // buffers of the analysis routes: map -> leg [-> leg2] -> alm, or alm -> leg -> h -> map / alm -> leg2 -> h -> map
+		if (r.kind == R_RING_WEIGHTS) { r.ld_leg = ldm; if (adjoint) use_h(nr); }
+		else {
+			r.rs = &p->rs_cc; r.ld_leg2 = r.kind == R_UNFUSED ? p->ncc : ldc;
+			if (!adjoint || r.kind == R_UNFUSED) r.ld_leg = r.kind == R_UNFUSED ? nr : ldm;
+			if (adjoint) use_h(nr);
+			r.theta = r.kind == R_CC_WEIGHTS ? (adjoint ? TH_FROM_CC : TH_FROM_CC_ADJ) : (adjoint ? TH_TO_CC_ADJ : TH_TO_CC);
+		}
+		r.ld_leg_alloc = r.ld_leg;
+	}
+	const bool unfused = r.kind == R_VIA_CC_UNFUSED || r.kind == R_VIA_CC_UNFUSED_H || r.kind == R_UNFUSED;
+	r.batched = !unfused;
+	r.theta_fused = r.theta != TH_NONE && !unfused;
+	r.line = r.theta_fused && r.theta <= TH_FROM_CC_ADJ && FftChain::line_takes(*r.tp, r.theta == TH_TO_CC);
+	// the ring chain's scratch is reserved with the call (the unfused analysis leaves it to the chain's own launches, as it always did)
+	r.reserve_chain = p->chain_rings && r.kind != R_UNFUSED;
+	return r;
 }
-// tables of the interpolating forms of the analysis (fused chains or the unfused engine): the fine-CC form, else the interpolant form
-struct AnaSet { const ThetaPlan* tp; const double2* sigma; const double2* wcc; const double2* whalf; long M; bool fine; };
-static AnaSet ana_set(const pxs_plan* p) {
-	if (p->ana_weights != 0 && p->Mf > 0) return AnaSet{&p->tpf, p->sigma_f.as<double2>(), p->wcc_f.as<double2>(), p->whalf_f.as<double2>(), p->Mf, true};
-	return AnaSet{&p->tp, p->sigma.as<double2>(), p->wcc.as<double2>(), p->whalf.as<double2>(), p->M, false};
-}
-// 1: the theta resampling of pxs_analysis (the plan's current form) runs as ONE kernel per call (thetaline.hip), 0: as the stage chain
-static int theta_line_now(const pxs_plan* p) {
-	if (!p->chain_theta()) return 0;
-	const AnaPath path = ana_path(p, 0);
-	if (path == ANA_CHAIN) return FftChain::line_takes(*ana_set(p).tp, true) ? 1 : 0;
-	if (path == ANA_CC_WEIGHTS) return FftChain::line_takes(p->tp, false) ? 1 : 0;
-	return 0;
-}
-static int ana_form_now(const pxs_plan* p) {
-	const AnaPath path = ana_path(p, 0);
-	if (path == ANA_RING_WEIGHTS || path == ANA_CC_WEIGHTS) return 1;
-	return ana_set(p).fine ? 2 : 0;
-}
+
 // per-ring weight / nphi of the ring-weights paths (DH / F2: fixed at plan time; the weights option: built on first use)
 static const double2* ring_weights(pxs_plan* p) {
 	if (p->wring.p) return p->wring.as<double2>();
@@ -1187,118 +1285,74 @@ static const double2* unit_weights_ext(pxs_plan* p) {
 	return p->wunit_ext.as<double2>();
 }
 
-// nb maps of one call (nb > 1 only on the fused-chain paths): ring FFTs of all maps in one launch each, theta chains and
-// Legendre kernels map by map on the plan's scratch
-static void synthesis_core(pxs_plan* p, int spin, int mode, int adjoint, int nb, void* alm, int alm_dtype, long alm_cstride, long alm_bstride,
-                           void* map, int map_dtype, long map_cstride, long map_bstride, hipStream_t st)
+// The nb maps of one pass of a call (nb > 1 only on the batched routes): ring FFTs of all maps in one launch each, theta chains and
+// Legendre kernels map by map on the plan's scratch.  Every route is one of two stage sequences, alm -> [leg2 ->] leg / h -> map or its
+// mirror image; the strides, ring sets and tables are the route's.
+static void run_core(pxs_plan* p, const Route& r, int spin, int nb, const AlmArg& alm, const MapArg& map, hipStream_t st)
 {
-	const int ncm = ncomp_of(spin, mode, false), nca = ncomp_of(spin, mode, true), nct = nb*ncm;
-	const int nm = p->mmax+1, nr = p->nring;
-	LegTables& tb = p->table(spin);
-	const bool th = p->chain_theta();
-	const long ldm = p->chain_rings ? FftChain::pad8(nr) : nr;
-	const int ncb = nb > 1 ? ncm : 0;
-	(void)nca;
-	p->leg.ensure(sizeof(double2)*(size_t)nct*nm*ldm);
-	if (!adjoint) {
-		if ((p->is_grid || (p->band && th)) && (spin == 0 ? p->syn_via_cc0 : p->syn_via_cc) && p->ncc > 0) {
-			const long ldc = p->ld_cc();
-			p->leg2.ensure(sizeof(double2)*(size_t)nct*nm*ldc);
-			leg_synthesis(st, p->rs_cc, tb, p->wk, alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-				p->leg2.as<double2>(), mode == PXS_MODE_DERIV1, &p->prof, ldc, nb, alm_bstride, (long)ncm*nm*ldc);
-			if (th) {	// fused chain: CC grid -> ring spectra of the map's rings, written ring-major for the ring FFT
-				const long ldh = p->ld_h();
-				const int nrh = p->band ? p->nfull : nr;          // (a band: h for every ring of the grid, the ring FFTs take its rows)
-				p->hbuf.ensure(sizeof(double2)*(size_t)nct*nrh*ldh);
-				p->prof.begin(st, PXS_STAGE_RESAMPLE);
-				p->chain->from_cc(st, p->tp, p->leg2.as<double2>(), ldc, p->ncc, p->hbuf.as<double2>(), ldh, nrh, p->mir_c, nct, nm, spin, p->lmax,
-					p->ph_up.as<double2>(), p->phase.as<double2>(), 1.0/(double)p->Ncc);
-				p->prof.end(st, PXS_STAGE_RESAMPLE);
-				leg2map(p, st, nullptr, nr, map, map_dtype, map_cstride, nct, true, map_bstride, ncb);
-			} else {
-				PXS_REQUIRE(nb == 1, "internal: batched call on an unfused path");
-				static const bool fuse = [] { const char* e = lab_getenv("PXS_FUSE_SPLIT"); return e ? atoi(e) != 0 : true; }();
-				const bool via_h = fuse && !p->chain_rings;     // (the unfused transposing split writes dense h rows)
-				if (via_h) p->hbuf.ensure(sizeof(double2)*(size_t)ncm*nr*nm);
-				resample_from_cc(p, st, p->leg2.as<double2>(), p->leg.as<double2>(), ncm, spin, via_h ? p->hbuf.as<double2>() : nullptr);
-				leg2map(p, st, p->leg.as<double2>(), nr, map, map_dtype, map_cstride, ncm, via_h);
-			}
+	const int nct = nb*r.nc, nr = p->nring, nm = p->mmax + 1;
+	double2* leg = p->leg.as<double2>();
+	switch (r.kind) {
+	case R_VIA_CC_UNFUSED: case R_VIA_CC_UNFUSED_H: {      // (synthesis only; the unfused resamplers size their own b1 / b2)
+		PXS_REQUIRE(nb == 1, "internal: batched call on an unfused path");
+		const bool to_h = r.kind == R_VIA_CC_UNFUSED_H;
+		p->leg_syn(st, r, alm, 1);
+		resample_from_cc(p, st, p->leg2.as<double2>(), leg, r.nc, spin, to_h ? p->hbuf.as<double2>() : nullptr);
+		leg2map(p, st, r, to_h ? nullptr : leg, r.ld_leg, map, 1);
+		return; }
+	case R_UNFUSED:      // analysis_2d / adjoint_analysis_2d stage by stage through the generic FFT engine
+		PXS_REQUIRE(nb == 1, "internal: batched call on an unfused path");
+		if (r.to_map) {
+			p->leg_syn(st, r, alm, 1);
+			resample_to_cc_adjoint(p, st, p->leg2.as<double2>(), leg, r.nc, spin, r.M, r.sigma, r.wcc);
+			leg2map(p, st, r, leg, r.ld_leg, map, 1);
 		} else {
-			leg_synthesis(st, p->rs_map, tb, p->wk, alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-				p->leg.as<double2>(), mode == PXS_MODE_DERIV1, &p->prof, ldm, nb, alm_bstride, (long)ncm*nm*ldm);
-			leg2map(p, st, p->leg.as<double2>(), ldm, map, map_dtype, map_cstride, nct, false, map_bstride, ncb);
+			map2leg(p, st, r, map, 1, leg);
+			resample_to_cc(p, st, leg, p->leg2.as<double2>(), r.nc, spin, r.M, r.sigma, r.wcc);
+			p->leg_ana(st, r, alm, 1);
 		}
+		return;
+	default: break;
+	}
+	// the fused routes.  Weights: of the rings in the weights forms of the analysis (R_RING_WEIGHTS: on leg itself; R_CC_WEIGHTS: folded into
+	// the theta stage, self-mirrored rings doubled where it is the transposed upsampling); the adjoint of the CC-grid synthesis on grids
+	// with self-mirrored rings (CC / MW / MWflip) counts those double in the reflection that stands for the zero extension
+	const double2* wleg = r.kind == R_RING_WEIGHTS ? ring_weights(p) : nullptr;
+	const double2* wth = r.kind == R_CC_WEIGHTS ? (r.to_map ? ring_weights(p) : ring_weights_ext(p)) : (r.kind == R_VIA_CC && !r.to_map ? unit_weights_ext(p) : nullptr);
+	auto weigh = [&] {
+		if (!wleg) return;
+		const long tot = (long)nct*nm*nr;
+		hipLaunchKernelGGL(scale_rings, dim3((unsigned)((tot+255)/256)), dim3(256), 0, st, leg, (long)nct*nm, nr, r.ld_leg, wleg);
+		PXS_HIP(hipGetLastError()); };
+	if (r.to_map) {
+		p->leg_syn(st, r, alm, nb);
+		weigh();
+		if (r.theta != TH_NONE) p->run_theta(st, r, nct, spin, wth);      // (writes h ring-major for the ring FFT)
+		leg2map(p, st, r, r.theta != TH_NONE ? nullptr : leg, r.ld_leg, map, nb);
 	} else {
-		// the transpose of the synthesis through the CC grid, where that is the cheaper synthesis: grids (self-mirrored rings of
-		// CC / MW / MWflip count double in the reflection that stands for the zero extension, unit_weights_ext) and bands of F1 grids
-		// (rows outside the band are zero)
-		static const bool adj_cc = [] { const char* e = lab_getenv("PXS_ADJ_VIA_CC"); return e ? atoi(e) != 0 : true; }();
-		const bool via = adj_cc && (p->is_grid || p->band) && th && (p->is_grid || p->geometry == "F1") && (spin == 0 ? p->syn_via_cc0 : p->syn_via_cc) && p->ncc > 0;
-		if (via && p->band) {
-			const long ldf = FftChain::pad8(p->nfull);
-			p->leg.ensure(sizeof(double2)*(size_t)nct*nm*ldf);
-			PXS_HIP(hipMemsetAsync(p->leg.p, 0, sizeof(double2)*(size_t)nct*nm*ldf, st));
-			map2leg(p, st, map, map_dtype, map_cstride, nct, p->leg.as<double2>() + p->row0, 1.0, ldf, map_bstride, ncb);
-		} else map2leg(p, st, map, map_dtype, map_cstride, nct, p->leg.as<double2>(), 1.0, ldm, map_bstride, ncb);
-		if (via) {
-			const long ldc = p->ld_cc(), ldin = p->band ? FftChain::pad8(p->nfull) : ldm;
-			p->leg2.ensure(sizeof(double2)*(size_t)nct*nm*ldc);
-			p->prof.begin(st, PXS_STAGE_RESAMPLE);
-			p->chain->from_cc_adjoint(st, p->tp, p->leg.as<double2>(), ldin, p->band ? p->nfull : nr, p->mir_c, p->leg2.as<double2>(), ldc, p->ncc, nct, nm, spin, p->lmax,
-				p->ph_shift.as<double2>(), p->wadj.as<double2>(), unit_weights_ext(p));
-			p->prof.end(st, PXS_STAGE_RESAMPLE);
-			leg_analysis(st, p->rs_cc, tb, p->wk, p->leg2.as<double2>(), alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-				mode == PXS_MODE_DERIV1, &p->prof, ldc, nb, alm_bstride, (long)ncm*nm*ldc);
-			return;
+		if (r.nr_th > nr) {      // a band through the CC grid: leg holds every ring of the grid, zero outside the band's rows
+			PXS_HIP(hipMemsetAsync(p->leg.p, 0, sizeof(double2)*(size_t)nct*nm*r.ld_leg, st));
+			leg += p->row0;
 		}
-		leg_analysis(st, p->rs_map, tb, p->wk, p->leg.as<double2>(), alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-			mode == PXS_MODE_DERIV1, &p->prof, ldm, nb, alm_bstride, (long)ncm*nm*ldm);
+		map2leg(p, st, r, map, nb, leg);
+		weigh();
+		if (r.theta != TH_NONE) p->run_theta(st, r, nct, spin, wth);
+		p->leg_ana(st, r, alm, nb);
 	}
 }
 
-// Scratch of a call is sized HERE, before its first launch (the fused-chain paths every BASELINE configuration takes; a plan's
-// buffers only grow, so this allocates on the first call of a kind and when a later call brings a larger batch).  The `ensure`
-// calls further down are then no-ops; they remain as the allocation points of the rarely taken paths (general ring sets,
-// unfused FFTs, the deterministic analysis).  A buffer that grows gives its old block to the arena while the launches that use it may
-// still be queued (of this call, or of the plan's previous call on another stream): the arena synchronises the device before that
-// block serves anybody else (arena.hip), and a block below the arena's threshold goes through hipFree, which waits for the device.
-static void reserve_call(pxs_plan* p, int spin, int mode, bool synthesis, bool adjoint, int nb) {
-	if (p->general || !p->chain_rings) return;
-	const int ncm = synthesis ? ncomp_of(spin, mode, false) : (spin == 0 ? 1 : 2), nct = nb*ncm;
-	const size_t nm = (size_t)p->mmax + 1, nr = (size_t)p->nring, c16 = sizeof(double2);
-	const bool th = p->chain_theta();
-	const size_t ldm = (size_t)FftChain::pad8(p->nring), ldc = (size_t)p->ld_cc(), ldh = (size_t)p->ld_h();
-	const bool via_cc = (p->is_grid || (p->band && th)) && (spin == 0 ? p->syn_via_cc0 : p->syn_via_cc) && p->ncc > 0;
-	LegTables& tb = p->table(spin);
-	size_t c1 = 0, c2 = 0, r1 = 0;
-	auto theta = [&](int kind) {
-		if (!th) return;
-		const ThetaPlan& tpk = (kind == 0 || kind == 3) ? *ana_set(p).tp : p->tp;
-		if (kind <= 1 && FftChain::line_takes(tpk, kind == 0)) return;      // the single-kernel engine (thetaline.hip) has no intermediates
-		FftChain::theta_scratch(tpk, (int)nm, nct, kind, c1, c2); };
-	if (synthesis && !adjoint) {                        // alm -> map
-		p->wk.almt.ensure(sizeof(double)*4*(tb.nrows + 4)*nb);
-		p->leg.ensure(c16*nct*nm*ldm);
-		if (via_cc) { p->leg2.ensure(c16*nct*nm*ldc); if (th) { p->hbuf.ensure(c16*nct*(p->band ? (size_t)p->nfull : nr)*ldh); theta(2); } }
-		else p->hbuf.ensure(c16*nct*nr*ldh);
-		p->chain->ring_scratch(p->nring, nct, false, r1, p->mmax);
-	} else if (synthesis) {                             // map -> alm, transpose of the synthesis
-		p->wk.mom.ensure(sizeof(double)*4*std::max<long>(tb.nrows, 1)*nb);
-		const bool via = (p->is_grid || p->band) && th && (p->is_grid || p->geometry == "F1") && via_cc;
-		p->leg.ensure(c16*nct*nm*(via && p->band ? (size_t)FftChain::pad8(p->nfull) : ldm));
-		if (via) { p->leg2.ensure(c16*nct*nm*ldc); theta(1); }
-		p->chain->ring_scratch(p->nring, nct, true, r1);
-	} else {                                            // pxs_analysis: the same path decision as analysis_core
-		const AnaPath path = ana_path(p, adjoint);
-		if (path == ANA_UNFUSED) return;
-		if (adjoint) p->wk.almt.ensure(sizeof(double)*4*(tb.nrows + 4)*nb); else p->wk.mom.ensure(sizeof(double)*4*std::max<long>(tb.nrows, 1)*nb);
-		if (path == ANA_RING_WEIGHTS) { p->leg.ensure(c16*nct*nm*ldm); if (adjoint) p->hbuf.ensure(c16*nct*nr*ldh); }
-		else if (path == ANA_CC_WEIGHTS) { p->leg2.ensure(c16*nct*nm*ldc); if (adjoint) { p->hbuf.ensure(c16*nct*nr*ldh); theta(2); } else { p->leg.ensure(c16*nct*nm*ldm); theta(1); } }
-		else if (!adjoint) { p->leg.ensure(c16*nct*nm*ldm); p->leg2.ensure(c16*nct*nm*ldc); theta(0); }      // analysis_2d
-		else { p->leg2.ensure(c16*nct*nm*ldc); p->hbuf.ensure(c16*nct*nr*ldh); theta(3); }                   // adjoint_analysis_2d (fused transposed chain)
-		p->chain->ring_scratch(p->nring, nct, !adjoint, r1, p->mmax);
-	}
-	p->chain->reserve(std::max(c1, r1), c2);
+// Scratch of a call is sized HERE and only here, from its route, before its first launch (a plan's buffers only grow, so this
+// allocates on the first call of a kind and when a later call brings a larger batch).  What is sized elsewhere, at the point of use,
+// belongs to the rarely taken paths: gz of the general ring sets and the packed spectra of the unfused ring FFT (map2leg, leg2map),
+// b1 / b2 of the unfused theta resamplers, the partial moments of the deterministic analysis (legendre.hip).  A buffer that grows gives
+// its old block to the arena while the launches that use it may still be queued (of the plan's previous call on another stream): the
+// arena synchronises the device before that block serves anybody else (arena.hip), and a block below the arena's threshold goes
+// through hipFree, which waits for the device.
+static void reserve_call(pxs_plan* p, const Route& r, int nb) {
+	const Route::Scratch s = r.scratch(p, nb);
+	p->wk.almt.ensure(s.almt); p->wk.mom.ensure(s.mom);
+	p->leg.ensure(s.leg); p->leg2.ensure(s.leg2); p->hbuf.ensure(s.h);
+	if (r.reserve_chain) p->chain->reserve(std::max(s.c1, s.r1), s.c2);
 }
 
 // maps per pass of a batched call: bounded by the scratch the plan may hold (leg + leg_cc + h per map, and the chain scratch)
@@ -1323,6 +1377,15 @@ static int batch_chunk(const pxs_plan* p, int nbatch, int ncm) {
 	return (nbatch + npass - 1)/npass;      // equal passes (64 maps at 15 per pass: 13 x 4 + 12, not 15 x 4 + 4 with a last pass at 27 % of the batch dimension)
 }
 
+// a call after its argument checks (call_mu held, the plan's device selected): route, scratch, then the maps in passes
+static void run_call(pxs_plan* p, bool analysis, int spin, int mode, int adjoint, int nbatch, const AlmArg& alm, const MapArg& map, hipStream_t st) {
+	const Route r = route_of(p, analysis, spin, mode, adjoint != 0, &p->table(spin));
+	const int chunk = r.batched ? batch_chunk(p, nbatch, r.nc) : 1;
+	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] %s route %s, adjoint %d, spin %d, analysis option %d, %d maps in passes of %d\n", analysis ? "analysis" : "synthesis", ROUTE_NAMES[r.kind], adjoint, spin, p->ana_weights, nbatch, chunk);
+	reserve_call(p, r, std::min(chunk, nbatch));
+	for (int b0 = 0; b0 < nbatch; b0 += chunk) run_core(p, r, spin, std::min(chunk, nbatch - b0), alm.from(b0), map.from(b0), st);
+}
+
 int pxs_synthesis(pxs_plan* p, int spin, int mode, int adjoint, int nbatch,
                   void* alm, int alm_dtype, int64_t alm_cstride, int64_t alm_bstride,
                   void* map, int map_dtype, int64_t map_cstride, int64_t map_bstride, void* stream)
@@ -1337,115 +1400,10 @@ int pxs_synthesis(pxs_plan* p, int spin, int mode, int adjoint, int nbatch,
 	PXS_HIP(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream;
 	PlanUse use(p, st);      // (a points plan: its own scratch here, the grid plan's in the pxs_synthesis calls points_run makes on it)
-	if (p->pts) { points_run(p->pts, p->pgrid, spin, mode, adjoint, nbatch, alm, alm_dtype, alm_cstride, alm_bstride, map, map_dtype, map_cstride, map_bstride, st); return 0; }
-	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16, mesz = map_dtype == PX_F32 ? 4 : 8;
-	// (a grid whose ring FFTs are chained but whose theta resampling is not -- 2 ntheta with a prime factor >= 7 -- takes the
-	// CC detour through the unfused resampling, one map at a time)
-	const bool cc_unfused = !adjoint && (p->is_grid || p->band) && (spin == 0 ? p->syn_via_cc0 : p->syn_via_cc) && p->ncc > 0 && !p->chain_theta();
-	const int chunk = cc_unfused ? 1 : batch_chunk(p, nbatch, ncomp_of(spin, mode, false));
-	reserve_call(p, spin, mode, true, adjoint != 0, std::min(chunk, nbatch));
-	for (int b0 = 0; b0 < nbatch; b0 += chunk) {
-		const int nb = std::min(chunk, nbatch - b0);
-		synthesis_core(p, spin, mode, adjoint, nb, (char*)alm + aesz*(size_t)b0*alm_bstride, alm_dtype, alm_cstride, alm_bstride,
-			(char*)map + mesz*(size_t)b0*map_bstride, map_dtype, map_cstride, map_bstride, st);
-	}
+	const AlmArg a{alm, alm_dtype, (long)alm_cstride, (long)alm_bstride}; const MapArg m{map, map_dtype, (long)map_cstride, (long)map_bstride};
+	if (p->pts) points_run(p->pts, p->pgrid, spin, mode, adjoint, nbatch, a, m, st);
+	else run_call(p, false, spin, mode, adjoint, nbatch, a, m, st);
 	PXS_CATCH
-}
-
-static void analysis_core(pxs_plan* p, int spin, int adjoint, int nb, void* map, int map_dtype, long map_cstride, long map_bstride,
-                          void* alm, int alm_dtype, long alm_cstride, long alm_bstride, hipStream_t st)
-{
-	const int nc = spin == 0 ? 1 : 2, nct = nb*nc;
-	const int nm = p->mmax+1, nr = p->nring;
-	LegTables& tb = p->table(spin);
-	const AnaPath path = ana_path(p, adjoint);
-	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] analysis path %d (0 ring weights, 1 weights via the CC grid, 2 chain, 3 unfused), option %d, adjoint %d\n", (int)path, p->ana_weights, adjoint);
-	if (path == ANA_RING_WEIGHTS) {	// DH / F2 (and the weights option off the CC detour): analysis = adjoint synthesis of the weighted map (its adjoint: synthesis, then the weights)
-		const double2* wr = ring_weights(p);
-		const long ldw = p->chain_rings ? FftChain::pad8(nr) : nr;
-		const int ncbw = nb > 1 ? nc : 0;
-		p->leg.ensure(sizeof(double2)*(size_t)nct*nm*ldw);
-		const long tot = (long)nct*nm*nr;
-		if (!adjoint) {
-			map2leg(p, st, map, map_dtype, map_cstride, nct, p->leg.as<double2>(), 1.0, ldw, map_bstride, ncbw);
-			hipLaunchKernelGGL(scale_rings, dim3((unsigned)((tot+255)/256)), dim3(256), 0, st, p->leg.as<double2>(), (long)nct*nm, nr, ldw, wr);
-			leg_analysis(st, p->rs_map, tb, p->wk, p->leg.as<double2>(), alm, alm_dtype, alm_cstride,
-				p->d_mstart.as<uint64_t>(), p->lstride, 0, &p->prof, ldw, nb, alm_bstride, (long)nc*nm*ldw);
-		} else {
-			leg_synthesis(st, p->rs_map, tb, p->wk, alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-				p->leg.as<double2>(), 0, &p->prof, ldw, nb, alm_bstride, (long)nc*nm*ldw);
-			hipLaunchKernelGGL(scale_rings, dim3((unsigned)((tot+255)/256)), dim3(256), 0, st, p->leg.as<double2>(), (long)nct*nm, nr, ldw, wr);
-			leg2map(p, st, p->leg.as<double2>(), ldw, map, map_dtype, map_cstride, nct, false, map_bstride, ncbw);
-		}
-		PXS_HIP(hipGetLastError());
-		return;
-	}
-	if (path == ANA_CC_WEIGHTS) {
-		// the weights form on an F1 grid with at least 2 lmax + 2 rings, Legendre stage on the ~lmax + 2 rings of the CC grid: the
-		// synthesis there is (theta upsampling) o (Legendre on the CC grid), exactly, so its transpose applied to the weighted
-		// ring spectra is the reference's adjoint_synthesis(map * weights) (curvedsky.py:852-861, 1068-1084) -- three chain stages
-		// (FftChain::from_cc_adjoint, the ring weights folded into its first one) instead of the five of the interpolant (to_cc)
-		const double2* wr = ring_weights(p);
-		const long ldm = FftChain::pad8(nr), ldc = p->ld_cc(), ldh = p->ld_h();
-		const int ncb = nb > 1 ? nc : 0;
-		p->leg2.ensure(sizeof(double2)*(size_t)nct*nm*ldc);
-		if (!adjoint) {
-			p->leg.ensure(sizeof(double2)*(size_t)nct*nm*ldm);
-			map2leg(p, st, map, map_dtype, map_cstride, nct, p->leg.as<double2>(), 1.0, ldm, map_bstride, ncb);
-			p->prof.begin(st, PXS_STAGE_RESAMPLE);
-			p->chain->from_cc_adjoint(st, p->tp, p->leg.as<double2>(), ldm, nr, p->mir_c, p->leg2.as<double2>(), ldc, p->ncc, nct, nm, spin, p->lmax,
-				p->ph_shift.as<double2>(), p->wadj.as<double2>(), ring_weights_ext(p));
-			p->prof.end(st, PXS_STAGE_RESAMPLE);
-			leg_analysis(st, p->rs_cc, tb, p->wk, p->leg2.as<double2>(), alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride, 0, &p->prof, ldc, nb, alm_bstride, (long)nc*nm*ldc);
-		} else {
-			p->hbuf.ensure(sizeof(double2)*(size_t)nct*nr*ldh);
-			leg_synthesis(st, p->rs_cc, tb, p->wk, alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-				p->leg2.as<double2>(), 0, &p->prof, ldc, nb, alm_bstride, (long)nc*nm*ldc);
-			p->prof.begin(st, PXS_STAGE_RESAMPLE);
-			p->chain->from_cc(st, p->tp, p->leg2.as<double2>(), ldc, p->ncc, p->hbuf.as<double2>(), ldh, nr, p->mir_c, nct, nm, spin, p->lmax,
-				p->ph_up.as<double2>(), p->phase.as<double2>(), 1.0/(double)p->Ncc, wr);
-			p->prof.end(st, PXS_STAGE_RESAMPLE);
-			leg2map(p, st, nullptr, nr, map, map_dtype, map_cstride, nct, true, map_bstride, ncb);
-		}
-		return;
-	}
-	if (path == ANA_CHAIN && adjoint) {
-		// adjoint_analysis_2d through the fused transposed chain: Legendre synthesis on the CC grid, FftChain::to_cc_adjoint straight
-		// into the ring-major spectra, ring FFTs -- all maps of the call in every launch
-		const long ldc = p->ld_cc(), ldh = p->ld_h();
-		p->leg2.ensure(sizeof(double2)*(size_t)nct*nm*ldc); p->hbuf.ensure(sizeof(double2)*(size_t)nct*nr*ldh);
-		leg_synthesis(st, p->rs_cc, tb, p->wk, alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride,
-			p->leg2.as<double2>(), 0, &p->prof, ldc, nb, alm_bstride, (long)nc*nm*ldc);
-		p->prof.begin(st, PXS_STAGE_RESAMPLE);
-		const AnaSet as = ana_set(p);
-		p->chain->to_cc_adjoint(st, *as.tp, p->leg2.as<double2>(), ldc, p->ncc, p->hbuf.as<double2>(), ldh, nr, p->mir_c, nct, nm, spin, p->lmax,
-			p->ph_shift.as<double2>(), as.sigma, as.whalf, p->phase.as<double2>(), 2.0);
-		p->prof.end(st, PXS_STAGE_RESAMPLE);
-		leg2map(p, st, nullptr, nr, map, map_dtype, map_cstride, nct, true, map_bstride, nb > 1 ? nc : 0);
-		return;
-	}
-	const bool th = path == ANA_CHAIN;                  // (ANA_UNFUSED: the generic FFT engine on dense rows, one map per call)
-	const long ldm = th ? FftChain::pad8(nr) : nr, ldc = th ? p->ld_cc() : p->ncc;
-	const int ncb = nb > 1 ? nc : 0;
-	p->leg.ensure(sizeof(double2)*(size_t)nct*nm*ldm);
-	p->leg2.ensure(sizeof(double2)*(size_t)nct*nm*ldc);
-	if (!adjoint) {
-		map2leg(p, st, map, map_dtype, map_cstride, nct, p->leg.as<double2>(), 1.0, ldm, map_bstride, ncb);
-		if (th) {
-			p->prof.begin(st, PXS_STAGE_RESAMPLE);
-			const AnaSet as = ana_set(p);
-			p->chain->to_cc(st, *as.tp, p->leg.as<double2>(), ldm, nr, p->mir_c, p->leg2.as<double2>(), ldc, p->ncc, nct, nm, spin, p->lmax,
-				p->ph_shift.as<double2>(), as.sigma, as.wcc);
-			p->prof.end(st, PXS_STAGE_RESAMPLE);
-		} else { PXS_REQUIRE(nb == 1, "internal: batched call on an unfused path"); const AnaSet as = ana_set(p); resample_to_cc(p, st, p->leg.as<double2>(), p->leg2.as<double2>(), nc, spin, as.M, as.sigma, as.wcc); }
-		leg_analysis(st, p->rs_cc, tb, p->wk, p->leg2.as<double2>(), alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride, 0, &p->prof, ldc, nb, alm_bstride, (long)nc*nm*ldc);
-	} else {
-		// adjoint_analysis_2d: the exact transpose, stage by stage in reverse
-		PXS_REQUIRE(nb == 1, "internal: batched call on an unfused path");
-		leg_synthesis(st, p->rs_cc, tb, p->wk, alm, alm_dtype, alm_cstride, p->d_mstart.as<uint64_t>(), p->lstride, p->leg2.as<double2>(), 0, &p->prof, ldc);
-		{ const AnaSet as = ana_set(p); resample_to_cc_adjoint(p, st, p->leg2.as<double2>(), p->leg.as<double2>(), nc, spin, as.M, as.sigma, as.wcc); }
-		leg2map(p, st, p->leg.as<double2>(), nr, map, map_dtype, map_cstride, nc);
-	}
 }
 
 int pxs_analysis(pxs_plan* p, int spin, int adjoint, int nbatch,
@@ -1462,14 +1420,7 @@ int pxs_analysis(pxs_plan* p, int spin, int adjoint, int nbatch,
 	PXS_HIP(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)stream;
 	PlanUse use(p, st);
-	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16, mesz = map_dtype == PX_F32 ? 4 : 8;
-	const int chunk = ana_path(p, adjoint) == ANA_UNFUSED ? 1 : batch_chunk(p, nbatch, spin == 0 ? 1 : 2);
-	reserve_call(p, spin, PXS_MODE_STANDARD, false, adjoint != 0, std::min(chunk, nbatch));
-	for (int b0 = 0; b0 < nbatch; b0 += chunk) {
-		const int nb = std::min(chunk, nbatch - b0);
-		analysis_core(p, spin, adjoint, nb, (char*)map + mesz*(size_t)b0*map_bstride, map_dtype, map_cstride, map_bstride,
-			(char*)alm + aesz*(size_t)b0*alm_bstride, alm_dtype, alm_cstride, alm_bstride, st);
-	}
+	run_call(p, true, spin, PXS_MODE_STANDARD, adjoint, nbatch, AlmArg{alm, alm_dtype, (long)alm_cstride, (long)alm_bstride}, MapArg{map, map_dtype, (long)map_cstride, (long)map_bstride}, st);
 	PXS_CATCH
 }
 
