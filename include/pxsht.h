@@ -213,6 +213,23 @@ int pxm_bin_index(int64_t n, const int32_t* d_bin, int nbin, const void* map, in
  * (the per-axis phase ramps of pixell.fft.shift, fft.py:347-368) */
 int pxm_mul_axis(int64_t total, int64_t n, int64_t inner, void* data, int dtype, const void* d_vec, int device, void* stream);
 
+/* curved-sky lensing between the gradient synthesis and the point synthesis of lensing.lens_map_curved (pixell/lensing.py:367-503).
+ * pxm_deflect: the observed positions offset by the gradient of the lensing potential (lensing.offset_by_grad, lensing.py:552-589), one
+ *   thread per pixel.  Positions: d_pos = NULL -> pixel i of the separable CAR band [ny][nx] (ny*nx = npts) sits at dec0 + (i / nx) ddec,
+ *   ra0 + (i % nx) dra (radians; enmap.posmap without the map); otherwise d_pos: DEVICE f64 [{dec, ra}(, psi0)][npts], pos_ncomp = 2 | 3.
+ *   d_grad: [2][npts] = (d/ddec, (d/dra)/cos dec) as alm2map(deriv=True) returns it, f32 | f64, components grad_cstride elements apart.
+ *   geodesic != 0: the point moves |grad| along the great circle that leaves it in the direction of the gradient, psi = psi0 minus twice
+ *   the change of that direction's angle in the local (e_theta, e_phi) basis (the spin-2 rotation of parallel transport); a zero
+ *   gradient is the identity.  geodesic = 0: dec + g0, ra + g1/cos dec, reflected at the poles (lensing.pole_wrap, :623-632), psi = 0.
+ *   d_loc: DEVICE f64 [npts][2] = (colatitude in [0, pi], ra in [0, 2 pi)), what pxs_plan_points reads; d_psi: DEVICE f64 [npts] or NULL.
+ *   FP64 arithmetic for both gradient dtypes.
+ * pxm_rotate_pol: in place (a, b) <- (c a - s b, s a + c b), c + i s = exp(i spin psi) (enmap.rotate_pol, enmap.py:1402-1416), for npair
+ *   pairs of maps (f32 | f64, npts contiguous pixels each) that share d_psi (DEVICE f64 [npts]): pair p is a + p*pair_stride,
+ *   b + p*pair_stride (elements).  spin = 0 does nothing. */
+int pxm_deflect(int64_t npts, int ny, int nx, double dec0, double ddec, double ra0, double dra, const double* d_pos, int pos_ncomp,
+                const void* d_grad, int grad_dtype, int64_t grad_cstride, int geodesic, double* d_loc, double* d_psi, int device, void* stream);
+int pxm_rotate_pol(int64_t npts, int npair, void* a, void* b, int64_t pair_stride, int dtype, const double* d_psi, int spin, int device, void* stream);
+
 /* 1 if the engine can transform this length (2,3,5-smooth or prime factors small enough) */
 int pxf_fft_supported(int64_t n);
 int64_t pxf_fft_good_size(int64_t n);

@@ -95,6 +95,11 @@ __global__ __launch_bounds__(256) void lmatmul_kernel(int N, int M, int lmax, in
 		const void* __restrict__ in, long in_cstride, void* __restrict__ out, long out_cstride, int dtype,
 		const double* __restrict__ lmat, int nl)
 {
+	// products and sums rounded separately, in the reference's order: a seed's coloured alm are then the reference's bit for bit.  (The
+	// pragma, not __fmul_rn / __dadd_rn and their like: those are a plain product and sum that the compiler still fuses into an fma.)
+#ifndef PXS_HOST_SIM
+	#pragma clang fp contract(off)
+#endif
 	const int l = blockIdx.x*blockDim.x + threadIdx.x;
 	const int m = blockIdx.y;
 	if (l > lmax || l < m) return;
@@ -109,7 +114,8 @@ __global__ __launch_bounds__(256) void lmatmul_kernel(int N, int M, int lmax, in
 			float re = 0, im = 0;
 			for (int b = 0; b < M; b++) {
 				const float f = l < nl ? (float)lmat[((long)a*M + b)*nl + l] : 0.0f;
-				re = __fadd_rn(re, __fmul_rn(f, v[b].x)); im = __fadd_rn(im, __fmul_rn(f, v[b].y));
+				const float tr = f*v[b].x, ti = f*v[b].y;
+				re = re + tr; im = im + ti;
 			}
 			pout[a*out_cstride + i] = make_float2(re, im);
 		}
@@ -122,7 +128,8 @@ __global__ __launch_bounds__(256) void lmatmul_kernel(int N, int M, int lmax, in
 		double re = 0, im = 0;
 		for (int b = 0; b < M; b++) {
 			const double f = l < nl ? lmat[((long)a*M + b)*nl + l] : 0.0;
-			re += f*v[b].x; im += f*v[b].y;
+			const double tr = f*v[b].x, ti = f*v[b].y;
+			re = re + tr; im = im + ti;
 		}
 		pout[a*out_cstride + i] = make_double2(re, im);
 	}

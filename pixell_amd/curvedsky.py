@@ -808,11 +808,13 @@ def prepare_ps(ps, ainfo=None, lmax=None):
 
 def _multi_sqrt(wps):
 	"""enmap.multi_pow(wps, 0.5) (enmap.py:2021-2024 -> utils.eigpow): matrix square root of each
-	[ncomp,ncomp] slice through its eigen-decomposition, negative eigenvalues set to zero"""
+	[ncomp,ncomp] slice through its eigen-decomposition, negative eigenvalues set to zero.  The power and the product are taken in
+	the reference's order of operations (E**0.5, then (V E) V^T), so that the coloured alm of a seed are the reference's bit for bit"""
 	A = np.moveaxis(np.asarray(wps, dtype=np.float64), (0, 1), (-2, -1))
 	E, V = np.linalg.eigh(A)
-	E = np.where(E < 0, 0, np.sqrt(np.abs(E)))
-	res = np.einsum("...ij,...j,...kj->...ik", V, E, V)
+	neg = E < 0
+	E[~neg] **= 0.5; E[neg] = 0
+	res = np.einsum("...ij,...kj->...ik", V*E[..., None, :], V)
 	return np.moveaxis(res, (-2, -1), (0, 1))
 
 def fill_gauss(arr, bsize=0x10000):
@@ -899,7 +901,7 @@ def rand_alm(ps, ainfo=None, lmax=None, seed=None, dtype=np.complex128, m_major=
 		alm[:, :ainfo.lmax+1] = (alm[:, :ainfo.lmax+1].real*np.sqrt(2.0)).to(alm.dtype)
 	else:
 		m0 = alm[:, :ainfo.lmax+1]                        # the m = 0 column comes first in the m-major layout
-		m0.imag = 0; m0.real *= np.sqrt(2.0)
+		m0.imag = 0; m0.real *= 2**0.5      # (a Python float: single precision alm are scaled in single precision, as the reference's are)
 	alm = alm[0] if ps.ndim == 1 else alm
 	return (alm, ainfo) if return_ainfo else alm
 

@@ -444,6 +444,82 @@ def posaxes(shape, wcs):
 	ra  = pix2sky(shape, wcs, [np.zeros(shape[-1]), np.arange(shape[-1])])[1]
 	return dec, ra
 
+def posmap(shape, wcs, safe=True, corner=False, separable="auto", dtype=np.float64, device=None):
+	"""[{dec,ra},ny,nx] coordinates of every pixel centre (corner: of its lower corner) in radians, for separable cylindrical
+	geometries: the outer sum of posaxes (enmap.posmap, enmap.py:435-465).  device: a torch device -> a dmap there, filled by
+	broadcasting the two axes on the device.  (lensing.lens_map_curved never makes this map: pxm_deflect takes the axes' numbers.)"""
+	if separable == "auto": separable = wcsutils.is_separable(wcs)
+	if not separable: raise NotImplementedError("posmap: only separable cylindrical geometries")
+	dec, ra = posaxes(shape, wcs)
+	if corner:
+		w = wcs.wcs; dec = dec-0.5*w.cdelt[1]*degree; ra = ra-0.5*w.cdelt[0]*degree
+	ny, nx = int(shape[-2]), int(shape[-1])
+	if device is not None:
+		torch = _torch()
+		res = torch.empty((2, ny, nx), dtype=getattr(torch, np.dtype(dtype).name), device=device)
+		res[0] = torch.as_tensor(dec, device=device)[:, None]; res[1] = torch.as_tensor(ra, device=device)[None, :]
+		return dmap(res, wcs)
+	res = np.empty((2, ny, nx), dtype)
+	res[0] = dec[:, None]; res[1] = ra[None, :]
+	return ndmap(res, wcs)
+
+def _rotate_pairs_by(data, psi, c0, c1, spin):
+	"""in place: components (c0, c1) of the contiguous real array data [npre, ncomp, npix...] (numpy in the simulator, a tensor next to
+	psi otherwise) rotated by spin*psi, psi f64 [npix...] contiguous -- every pre-dimension entry in one pxm_rotate_pol call"""
+	from . import sht
+	npre, nc = int(data.shape[0]), int(data.shape[1])
+	npix = int(np.prod(data.shape[2:], dtype=np.int64))
+	dt = sht._np_dtype(data)
+	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
+	base = _ptr(data)
+	sht._lib.check(lib.pxm_rotate_pol(npix, npre, base+int(c0)*npix*dt.itemsize, base+int(c1)*npix*dt.itemsize, nc*npix, sht._DT[dt], _ptr(psi), int(spin), dev, st))
+
+def rotate_pol(emap, angle, comps=[-2, -1], spin=2, axis=-3):
+	"""A copy of emap with the components `comps` of `axis` rotated by spin*angle (radians): (a, b) -> (c a - s b, s a + c b),
+	c + i s = exp(i spin angle) (enmap.rotate_pol, enmap.py:1402-1416).  angle: a scalar or an array (host or device) that broadcasts
+	against emap with `axis` removed.  Host arrays, dmaps and CUDA tensors; the rotation runs on the GPU (pxm_rotate_pol), all leading
+	entries in one call when the angle does not depend on them."""
+	from . import sht
+	if spin == 0: return emap
+	data = _data(emap)
+	tens = hasattr(data, "data_ptr")
+	rdt = sht._np_dtype(data)
+	if rdt not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("rotate_pol needs a real float32 or float64 map")
+	axis %= data.ndim
+	nc = int(data.shape[axis]); c0, c1 = int(comps[0]) % nc, int(comps[1]) % nc
+	if c0 == c1: raise ValueError("rotate_pol: the two components must differ")
+	pre, post = tuple(data.shape[:axis]), tuple(data.shape[axis+1:])
+	sim = sht._lib.is_hostsim()
+	if tens:
+		torch = _torch()
+		work = data.clone(memory_format=torch.contiguous_format)
+		if not sim and not work.is_cuda: raise ValueError("torch tensors passed to pixell_amd must live on the GPU")
+		ang = _data(angle)
+		ang = ang.to(device=work.device, dtype=torch.float64) if hasattr(ang, "data_ptr") else torch.as_tensor(np.asarray(ang, np.float64), device=work.device)
+		full = torch.broadcast_shapes(tuple(ang.shape), pre+post)
+	else:
+		if sim: work = np.array(data, dtype=rdt, order="C")
+		else:
+			sht.device_index(); torch = _torch()
+			work = torch.from_numpy(np.ascontiguousarray(data)).cuda()
+		ang = np.asarray(_to_host(angle) if isinstance(angle, dmap) else (angle.cpu().numpy() if hasattr(angle, "data_ptr") else angle), np.float64)
+		full = np.broadcast_shapes(ang.shape, pre+post)
+		if not sim: ang = torch.from_numpy(np.ascontiguousarray(ang)).cuda()
+	if tuple(full) != pre+post: raise ValueError("rotate_pol: angle of shape %s does not broadcast against the map" % (tuple(ang.shape),))
+	lead = tuple(ang.shape)[:max(ang.ndim-len(post), 0)]
+	w3 = work.reshape((int(np.prod(pre, dtype=np.int64)), nc)+post)
+	if hasattr(ang, "data_ptr"): spread = lambda a, sh: a.broadcast_to(sh).contiguous()
+	else: spread = lambda a, sh: np.ascontiguousarray(np.broadcast_to(a, sh))
+	if all(n == 1 for n in lead):
+		_rotate_pairs_by(w3, spread(ang.reshape(tuple(ang.shape)[len(lead):]), post), c0, c1, spin)
+	else:
+		afull = spread(ang, pre+post).reshape((w3.shape[0],)+post)
+		for p in range(w3.shape[0]): _rotate_pairs_by(w3[p:p+1], afull[p], c0, c1, spin)
+	if not tens and not sim: work = work.cpu().numpy()
+	if isinstance(emap, dmap): return dmap(work, emap.wcs)
+	if tens: return work
+	return ndmap(work, emap.wcs) if isinstance(emap, ndmap) else work
+
 def center(shape, wcs):
 	"""[dec, ra] of the middle of the pixel grid (enmap.center, enmap.py:1254-1256)"""
 	return pix2sky(shape, wcs, (np.array(shape[-2:])-1)/2.0)
@@ -496,3 +572,4 @@ for _cls in (ndmap, dmap):
 	_cls.lmap     = lambda self, **kw: lmap(self.shape, self.wcs, **kw)
 	_cls.modlmap  = lambda self, **kw: modlmap(self.shape, self.wcs, **kw)
 	_cls.lbin     = lambda self, *a, **kw: lbin(self, *a, **kw)
+	_cls.posmap   = lambda self, **kw: posmap(self.shape, self.wcs, **kw)
