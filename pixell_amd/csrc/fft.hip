@@ -386,7 +386,7 @@ static void launch_tiles(const KArgs& k, long nblk, size_t sh, hipStream_t st, i
 // host side
 // ------------------------------------------------------------------------------------
 struct FftSub {
-	int n; std::vector<int> fac; bool generic = false;
+	int n; std::vector<int> fac, hperm; bool generic = false;
 	DevBuf perm, tw, d_pass;
 	PassDesc pass[FFT_MAXFAC]; int nfac = 0;
 };
@@ -523,7 +523,7 @@ std::shared_ptr<FftSub> FftContext::sub(long n, bool comp, int maxr) {
 		perm[j] = (int)pos;
 	}
 	std::vector<double2> tw; twiddles(n, tw);
-	s->perm = upload(perm); s->tw = upload(tw);
+	s->perm = upload(perm); s->tw = upload(tw); s->hperm = perm;
 	s->d_pass = upload(std::vector<PassDesc>(s->pass, s->pass + FFT_MAXFAC));
 	subs_[key] = s;
 	return s;
@@ -532,7 +532,7 @@ std::shared_ptr<FftSub> FftContext::sub(long n, bool comp, int maxr) {
 FftContext::SubView FftContext::view(long n, int maxr) {
 	auto s = sub(n, true, maxr);
 	SubView v; v.n = s->n; v.nfac = s->nfac; v.ns = s->n | 1; v.generic = s->generic ? 1 : 0;
-	v.pass = s->d_pass.p; v.perm = s->perm.as<int>(); v.tw = s->tw.as<double2>();
+	v.pass = s->d_pass.p; v.perm = s->perm.as<int>(); v.tw = s->tw.as<double2>(); v.hfac = s->fac.data(); v.hperm = s->hperm.data();
 	return v;
 }
 

@@ -62,7 +62,7 @@ public:
 	static bool supported(long n, std::string* why = nullptr);
 	// views for the fused chain kernels (fftchain.hip): LDS sub-transform tables of length n (radices 2,3,4,5 only:
 	// `ok` false otherwise) and the four-step twiddle table e^{-2 pi i k/n}, k < n
-	struct SubView { int n, nfac, ns, generic; const void* pass; const int* perm; const double2* tw; };
+	struct SubView { int n, nfac, ns, generic; const void* pass; const int* perm; const double2* tw; const int* hfac; const int* hperm; };      // hfac, hperm: host copies of the radices and of perm
 	SubView view(long n, int maxr = 1000);      // maxr: largest composite register radix the calling kernel has compiled in
 	const double2* twiddle_table(long n) { return bigtw(n); }
 	void release_stream(hipStream_t st) { std::lock_guard<std::mutex> g(mu_); temps_.erase(st); }   // four-step scratch of a stream that is going away

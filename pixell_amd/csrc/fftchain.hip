@@ -21,6 +21,7 @@
 // Replaces ducc0's ring FFTs / resample_theta inside synthesis_2d / analysis_2d (pixell/curvedsky.py:907-924, 1032-1046).
 #include "fftchain.hpp"
 #include "fft_dev.hpp"
+#include "fft_static_dev.hpp"
 #include "chain_dev.hpp"
 #include <algorithm>
 #include <set>
@@ -229,6 +230,7 @@ struct StFirst : StageBase {
 
 // ... of the 2-D FFTs (plain mode; lengths are 2-3-5-smooth there, split_balanced)
 struct StFirst2D : StFirst {
+	static constexpr int SID = 10;      // (its own kernel: a stage id of its own in the static table and the per-stage switches)
 	static constexpr bool R7 = false;
 	// the tile's samples are runs of nl elements at j = b e + t0 of row q0: every 8th element names a 128-byte line
 	static constexpr int PFI = 2;
@@ -573,6 +575,146 @@ struct StColOut : StageBase {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The same kernel with its transforms planned at compile time (fft_static_dev.hpp): na, nb, T, the radix sequences and the digit
+// reversal are constants, every index split divides by a constant, every loop has a constant trip count.  The stage functors (load,
+// mid, store, decode, row, pfaddr), the tables (W_n, tws, btw), the prefetch-ahead and the shared W_n of two equal lengths are
+// those of chain_kernel; partial tiles (c.nl < T) stay a run-time condition inside the functors.  Launched for the stage shapes of
+// STATIC_TABLE below; chain_kernel serves every other shape.
+template<class S, class FA, class FB, int T, int NT> __global__ PXS_CH_BOUNDS void chain_kernel_static(const S s)
+{
+	PXS_SHARED(double2, lds);
+	constexpr int na = FA::n, nb = FB::n;
+	static_assert(S::TWO == (nb > 0), "chain_kernel_static: second transform");
+	constexpr int nlast = S::TWO ? nb : na, nslast = S::TWO ? FB::ns : FA::ns;
+	constexpr bool same_tw = S::TWO && nb == na;
+	constexpr int LA = (T*na + NT - 1)/NT, LB = (T*nb + NT - 1)/NT, LS = (T*nlast + NT - 1)/NT;
+	static_assert(LA*NT <= SDIV_MAX && LB*NT <= SDIV_MAX && LS*NT <= SDIV_MAX, "chain_kernel_static: index range of sdiv");
+	double2* twa = lds; double2* twb = same_tw ? lds : lds + na; double2* twx = lds + na + (same_tw ? 0 : nb); double2* buf = twx + (S::HAS_TW ? nlast : 0);
+	TileC c;
+	if (!s.decode((int)blockIdx.x, c)) return;
+	const bool have_tw = S::HAS_TW && s.btw != nullptr;
+	int pf_val = 0;
+	{	// ---- load: every global load of the tile is in flight before the first LDS write
+		double2 v[LA]; int pos[LA];
+#pragma unroll
+		for (int u = 0; u < LA; u++) {
+			const uint32_t idx = threadIdx.x + u*NT; pos[u] = -1;
+			if ((T*na) % NT == 0 || idx < (uint32_t)(T*na)) {
+				uint32_t li, e;
+				if (S::LOAD_LINE_FAST) { e = sdiv<T>(idx); li = idx - e*T; }
+				else { li = sdiv<na>(idx); e = idx - li*na; }
+				v[u] = s.load(c, (int)li, (int)e);
+				if (S::INV_A) v[u].y = -v[u].y;
+				pos[u] = (int)(li*FA::ns + FA::perm(e));
+			}
+		}
+		if ((S::LOADK == 0 || S::PFI > 0) && s.pf > 0 && (long)blockIdx.x + s.pf < (long)gridDim.x) {
+			TileC c2;
+			if (s.decode((int)blockIdx.x + s.pf, c2)) {
+				if (S::LOADK == 0) {
+					constexpr int per = (na*16 + 127) >> 7; const uint32_t i = threadIdx.x;
+					if (i < (uint32_t)(T*per)) {
+						const uint32_t li = sdiv<per>(i), seg = i - li*per;
+						const double2* r = s.row(c2, (int)li);
+						if (r) pf_val = *reinterpret_cast<const int*>(reinterpret_cast<const char*>(r) + seg*128);
+					}
+				} else {
+#pragma unroll
+					for (int it = 0; it < S::PFI; it++) {
+						const void* q = s.pfaddr(c2, (int)threadIdx.x + it*NT);
+						if (q) pf_val += *reinterpret_cast<const int*>(q);
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int k0 = 0; k0 < na; k0 += NT) { const int k = k0 + (int)threadIdx.x; if (k < na) twa[k] = s.fa.tw[k]; }
+		if constexpr (S::TWO && !same_tw) {
+#pragma unroll
+			for (int k0 = 0; k0 < nb; k0 += NT) { const int k = k0 + (int)threadIdx.x; if (k < nb) twb[k] = s.fb.tw[k]; }
+		}
+		if (have_tw) {
+#pragma unroll
+			for (int k0 = 0; k0 < nlast; k0 += NT) { const int k = k0 + (int)threadIdx.x; if (k < nlast) twx[k] = s.btw[(long)c.t0*k]; }
+		}
+#pragma unroll
+		for (int u = 0; u < LA; u++) if (pos[u] >= 0) buf[pos[u]] = v[u];
+	}
+	PXS_LDS_BARRIER();
+	lds_fft_static<FA, NT, T>(buf, twa);
+	if constexpr (S::TWO) {	// ---- second transform on the same lines
+		double2 v[LB]; int pos[LB];
+#pragma unroll
+		for (int u = 0; u < LB; u++) {
+			const uint32_t idx = threadIdx.x + u*NT; pos[u] = -1;
+			if ((T*nb) % NT == 0 || idx < (uint32_t)(T*nb)) {
+				const uint32_t e = sdiv<T>(idx), li = idx - e*T;
+				{ const double2* Al = buf + li*FA::ns; v[u] = s.mid(c, (int)li, (int)e, [&](int k) { return Al[k]; }); }
+				if (S::INV_B) v[u].y = -v[u].y;
+				pos[u] = (int)(li*FB::ns + FB::perm(e));
+			}
+		}
+		PXS_LDS_BARRIER();
+#pragma unroll
+		for (int u = 0; u < LB; u++) if (pos[u] >= 0) buf[pos[u]] = v[u];
+		PXS_LDS_BARRIER();
+		lds_fft_static<FB, NT, T>(buf, twb);
+	}
+	{	// ---- store
+#pragma unroll
+		for (int u = 0; u < LS; u++) {
+			const uint32_t idx = threadIdx.x + u*NT;
+			if ((T*nlast) % NT == 0 || idx < (uint32_t)(T*nlast)) {
+				uint32_t li, e;
+				if (S::STORE_LINE_FAST) { e = sdiv<T>(idx); li = idx - e*T; } else { li = sdiv<nlast>(idx); e = idx - li*nlast; }
+				double2 w = make_double2(1, 0);
+				if (have_tw) w = cmul(twx[e], s.tws[S::STORE_LINE_FAST ? idx : e*T + li]);
+				s.store(c, (int)li, (int)e, [&](int l2, int e2) { return buf[l2*nslast + e2]; }, w);
+			}
+		}
+	}
+#ifndef PXS_HOST_SIM
+	if (S::LOADK == 0 || S::PFI > 0) asm volatile("" :: "v"(pf_val));
+#endif
+}
+
+// ---- the compiled table ---------------------------------------------------------------------------------------------------------
+// One StaticFft per length and radix set (F<n>: the theta stages and the 2-D FFT stages, radices up to 9; G<n>: the ring stages,
+// radices up to 8), one PXS_CS line per stage shape (stage, first transform, second transform or NoFft, lines per tile).
+// To add a shape: run the workload with PXS_CHAIN_VERBOSE=1, which prints every stage shape it launches ("chain stage <sid>:
+// na= nb= T= ... static 0|1") and the radices FftContext::sub plans for its lengths; add the StaticFft if the length is new,
+// with exactly those radices in that order (static_check refuses anything else), then the PXS_CS line; check the kernel's
+// registers against its stage's budget (tools/kres.py: ring stages <= 64 VGPRs, no scratch anywhere) and leave it out if it
+// does not fit.
+struct StaticEntry {
+	int sid, na, nb, T, maxr; std::vector<int> ra, rb; std::vector<int> pa, pb;
+	void (*launch)(const void* s, long nblk, size_t sh, hipStream_t st);
+};
+template<class S, class FA, class FB, int T> static void launch_static(const void* sp, long nblk, size_t sh, hipStream_t st) {
+	const S& s = *static_cast<const S*>(sp);
+#ifndef PXS_HOST_SIM
+	static const bool once = [] { (void)hipFuncSetAttribute((const void*)chain_kernel_static<S, FA, FB, T, S::NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }();
+	(void)once;
+#endif
+	hipLaunchKernelGGL((chain_kernel_static<S, FA, FB, T, S::NT>), dim3((unsigned)nblk), dim3(S::NT), sh, st, s);
+}
+template<class F> static std::vector<int> radices_of() { std::vector<int> r; for (int p = 0; p < F::nfac; p++) r.push_back(F::radix(p)); return r; }
+template<class F> static std::vector<int> perm_of() { std::vector<int> r; for (int j = 0; j < F::n; j++) r.push_back(F::perm_host(j)); return r; }
+template<class S, class FA, class FB, int T> static StaticEntry static_entry() {
+	static_assert((long)T*(FA::n > FB::n ? FA::n : FB::n) <= S::PTS, "static chain stage: tile too large");
+	return StaticEntry{S::SID, FA::n, FB::n, T, S::MAXR, radices_of<FA>(), radices_of<FB>(), perm_of<FA>(), perm_of<FB>(), &launch_static<S, FA, FB, T>};
+}
+#define PXS_CS(S, FA, FB, T) static_entry<S, FA, FB, T>(),
+#include "chain_static_table.hpp"
+#undef PXS_CS
+static const StaticEntry* static_find(int sid, int na, int nb, int T) {
+	for (const StaticEntry& e : static_table()) if (e.sid == sid && e.na == na && e.nb == nb && e.T == T) return &e;
+	return nullptr;
+}
+// PXS_CHAIN_STATIC=0 keeps the run-time kernel for every shape (read per call: the tests compare the two paths on one plan)
+static bool static_enabled() { const char* e = getenv("PXS_CHAIN_STATIC"); return e ? atoi(e) != 0 : true; }
+
+// ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 static bool smooth235(long n) { if (n < 1) return false; for (int p : {2, 3, 5}) while (n % p == 0) n /= p; return n == 1; }
@@ -588,6 +730,13 @@ static LdsFft mk(FftContext* fc, long n, int maxr = 9) {
 	constexpr int nofft = 0;
 #endif
 	static const int nspad = [] { const char* e = lab_getenv("PXS_CH_NS_PAD"); return e ? atoi(e) : 0; }();     // experiments: line stride (n | 1) + pad
+	if (getenv("PXS_CHAIN_VERBOSE")) {
+		static std::mutex mu; static std::set<std::pair<long, int>> seen; std::lock_guard<std::mutex> g(mu);
+		if (seen.insert(std::make_pair(n, maxr)).second) {
+			std::string r; for (int p = 0; p < v.nfac; p++) r += " " + std::to_string(v.hfac[p]);
+			fprintf(stderr, "[pxsht] chain fft n=%ld maxr=%d: radices%s\n", n, maxr, r.c_str());
+		}
+	}
 	f.n = v.n; f.nfac = nofft ? 0 : v.nfac; f.ns = v.ns + nspad; f.generic = v.generic; f.pass = (const PassDesc*)v.pass; f.perm = v.perm; f.tw = v.tw; f.dn = make_fastdiv((uint32_t)n);
 	return f;
 }
@@ -653,8 +802,19 @@ static const int F2_RADICES[] = {2, 3, 4, 5, 6, 8, 9};
 // n as a product of at most three register radices: fewest passes, then the smallest largest radix; ascending order (the first
 // pass works on the longest rows, which wastes the least padding).  maxfirst: cap on the first radix (passes that pull their inputs
 
-template<class S> static void launch_stage(const S& s, long nblk, hipStream_t st) {
+// the static instance of a stage as planned, or null: its shape is not in the table, or the stage uses what the static kernel leaves
+// out (blocked input, a padded line stride or a plan with no passes: experiments)
+template<class S> static const StaticEntry* static_for(const S& s) {
+	const StaticEntry* e = static_find(S::SID, s.fa.n, s.fb.n, s.T);
+	if (!e || s.bin.Tw > 0 || s.fa.ns != (s.fa.n | 1) || s.fa.nfac != (int)e->ra.size()) return nullptr;
+	if (S::TWO && (s.fb.ns != (s.fb.n | 1) || s.fb.nfac != (int)e->rb.size())) return nullptr;
+	return e;
+}
+template<class S> static void launch_stage(const S& s, long nblk, hipStream_t st, std::vector<ChainShape>* dry) {
 	if (nblk <= 0) return;
+	const StaticEntry* se = static_for(s);
+	if (dry) { dry->push_back(ChainShape{S::SID, s.fa.n, s.fb.n, s.T, se != nullptr}); return; }
+	if (!static_enabled()) se = nullptr;
 	PXS_REQUIRE((long)s.T*std::max(s.fa.n, s.fb.n) <= S::PTS, "internal: chain tile too large");
 	PXS_REQUIRE(nblk < (1L << 31), "internal: chain grid too large");
 	size_t sh = sizeof(double2)*((size_t)s.fa.n + (S::TWO && s.fb.n == s.fa.n ? 0 : s.fb.n) + (S::HAS_TW ? std::max(s.fa.n, s.fb.n) : 0) + (size_t)s.T*std::max(s.fa.ns, s.fb.ns) + 2);
@@ -666,8 +826,9 @@ template<class S> static void launch_stage(const S& s, long nblk, hipStream_t st
 	if (getenv("PXS_CHAIN_VERBOSE")) {
 		static std::mutex mu; static std::set<std::tuple<int, int, int, int>> seen; std::lock_guard<std::mutex> g(mu);
 		if (seen.insert(std::make_tuple(S::SID, s.fa.n, s.fb.n, s.T)).second)
-			fprintf(stderr, "[pxsht] chain stage %d: na=%d nb=%d T=%d LDS %.1f KiB -> %d WG/CU by LDS, %ld workgroups\n", S::SID, s.fa.n, s.fb.n, s.T, sh/1024.0, (int)((160*1024)/sh), nblk);
+			fprintf(stderr, "[pxsht] chain stage %d: na=%d nb=%d T=%d LDS %.1f KiB -> %d WG/CU by LDS, %ld workgroups, static %d\n", S::SID, s.fa.n, s.fb.n, s.T, sh/1024.0, (int)((160*1024)/sh), nblk, se ? 1 : 0);
 	}
+	if (se) { se->launch(&s, nblk, sh, st); return; }
 #ifndef PXS_HOST_SIM
 #ifdef PXS_CH_NT2      /* experiment builds: stages whose bit SID is set in PXS_CH_NT2_MASK run with PXS_CH_NT2 threads per workgroup */
 	static const long mask2 = [] { const char* e = lab_getenv("PXS_CH_NT2_MASK"); return e ? strtol(e, nullptr, 0) : 0L; }();
@@ -692,7 +853,34 @@ template<class S> int FftChain::tile_lines_for(long n_a, long n_b, long nlines, 
 	if (S::PTS > CH_TILE_PTS && T < mult && (long)mult*std::max(n_a, n_b) <= S::PTS && nlines >= mult) T = mult;
 	return T;
 }
-template<class S> void FftChain::launch_any(S& s, long nblk, hipStream_t st) { launch_stage(s, nblk, st); }
+template<class S> void FftChain::launch_any(S& s, long nblk, hipStream_t st) {
+	if (!dry_) static_check(S::MAXR);
+	launch_stage(s, nblk, st, dry_);
+}
+
+// every table entry against the run-time plans of its lengths (once per radix set of a chain): radices, order and digit reversal
+// must be those of FftContext::sub, whose W_n tables the static kernels read.  Returns the number of entries.
+int FftChain::static_check(int maxr) {
+	std::lock_guard<std::mutex> g(mu_);
+	if (maxr > 0 && checked_.count(maxr)) return (int)static_table().size();
+	for (const StaticEntry& e : static_table()) {
+		if (maxr > 0 && e.maxr != maxr) continue;
+		for (int which = 0; which < 2; which++) {
+			const int n = which ? e.nb : e.na; if (n <= 0) continue;
+			const std::vector<int>& r = which ? e.rb : e.ra; const std::vector<int>& pm = which ? e.pb : e.pa;
+			const auto v = fc_->view(n, e.maxr);
+			bool ok = !v.generic && v.nfac == (int)r.size() && v.ns == (n | 1);
+			for (int p = 0; ok && p < v.nfac; p++) ok = v.hfac[p] == r[p];
+			for (int j = 0; ok && j < n; j++) ok = v.hperm[j] == pm[j];
+			PXS_REQUIRE(ok, "static chain table: the plan compiled for length " + std::to_string(n) + " (stage " + std::to_string(e.sid) + ") is not the one the FFT engine plans");
+		}
+	}
+	if (maxr > 0) checked_.insert(maxr);
+	return (int)static_table().size();
+}
+// is (stage id, na, nb, T) in the compiled table
+bool FftChain::static_has(int sid, int na, int nb, int T) { return static_find(sid, na, nb, T) != nullptr; }
+void FftChain::static_shapes(std::vector<ChainShape>& out) { for (const StaticEntry& e : static_table()) out.push_back(ChainShape{e.sid, e.na, e.nb, e.T, true}); }
 
 // balanced split n = a*b with both factors usable
 static bool split_balanced(long n, Split& s, long amax = 320) {
@@ -810,7 +998,7 @@ void FftChain::map2leg(hipStream_t st, const MapDesc& m, int nc, int mmax, doubl
 	const long npair_all = (m.nring + 1)/2, a = ra_.a, b = ra_.b, ldY = pad8(b);
 	int T2 = tile_lines_for<StRingA2>(b, 0, 2*npair_all, 8, b); if (T2 < 2) T2 = 2; T2 -= T2 % 2;
 	const long qchunk = ring_chunk(npair_all, (long)sizeof(double2)*nc*a*ldY, T2/2);
-	s1_.ensure(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
+	ensure1(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
 	for (long q_lo = 0; q_lo < npair_all; q_lo += qchunk) {
 		const long npair = std::min(qchunk, npair_all - q_lo);
 		const int nring = m.nring - (int)(2*q_lo);           // rings from the first pair of this pass on (the odd-last-ring tests are local)
@@ -831,16 +1019,16 @@ void FftChain::map2leg(hipStream_t st, const MapDesc& m, int nc, int mmax, doubl
 			launch_any(s, (long)nc*s.groups*a, st);
 		}
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 void FftChain::h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& m, int nc, int mmax, long hcomp) {
 	PXS_REQUIRE(rings_ok() && m.nphi == nphi_, "internal: ring chain not planned");
-	if (line_h2map(st, h, ldh, m, nc, mmax, hcomp)) return;      // (ring lengths compiled into ringline.hip: one kernel, no intermediate)
+	if (dry_ ? line_h2map_takes(nphi_, mmax) : line_h2map(st, h, ldh, m, nc, mmax, hcomp)) return;      // (ring lengths compiled into ringline.hip: one kernel, no intermediate)
 	const long npair_all = (m.nring + 1)/2, a = rs_.a, b = rs_.b, ldY = pad8(b);
 	const long qchunk = ring_chunk(npair_all, (long)sizeof(double2)*nc*a*ldY, 1);
 	const int T1 = tile_lines_for<StRingS1>(a, 0, b, 8, 2*a), T2 = tile_lines_for<StRingS2>(b, 0, a, 16, b);
-	s1_.ensure(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
+	ensure1(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
 	for (long q_lo = 0; q_lo < npair_all; q_lo += qchunk) {
 		const long npair = std::min(qchunk, npair_all - q_lo);
 		const int nring = m.nring - (int)(2*q_lo);
@@ -859,7 +1047,7 @@ void FftChain::h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& 
 			launch_any(s, (long)nc*npair*s.ntile, st);
 		}
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 // components per pass of a theta chain: all of them unless the two ping-pong buffers would exceed PXS_CHAIN_SCRATCH_GB (12) each
@@ -889,14 +1077,14 @@ void FftChain::ring_scratch(long nring, int nc, bool analysis, size_t& b1, int m
 void FftChain::to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
                      int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* wcc)
 {
-	if (line_analysis(st, tp, true, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, sigma, wcc, nullptr)) return;
+	if (dry_ ? line_takes(tp, true) : line_analysis(st, tp, true, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, sigma, wcc, nullptr)) return;
 	const long npair = (nm + 1)/2;
 	const long g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
 	const long ldY1 = pad8(bN), ldZ2 = pad8(g), ldV3 = pad8(g2), ldU4 = pad8(g);
 	const size_t need1 = (size_t)npair*std::max(g*ldY1, g*ldV3), need2 = (size_t)npair*std::max(g2*ldZ2, ac*ldU4);
 	const int cchunk = theta_comp_chunk(nc, need1, need2);
 	const int T1 = tile_lines_for<StFirst>(g, 0, bN, 8), T2 = tile_lines_for<StResize>(bN, g2, g, 8), T3 = tile_lines_for<StSigma>(g, g, g2, 8), T4 = tile_lines_for<StResize>(g2, ac, g, 8);
-	s1_.ensure(sizeof(double2)*need1*cchunk); s2_.ensure(sizeof(double2)*need2*cchunk);
+	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
 	for (int c0 = 0; c0 < nc; c0 += cchunk) {
 		const long ncl = std::min(cchunk, nc - c0);
 		{	StFirst s; memset(&s, 0, sizeof(s));
@@ -945,7 +1133,7 @@ void FftChain::to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, lo
 			launch_any(s, ncl*npair*s.ntile, st);
 		}
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 // exact transpose of from_cc (theta upsampling CC grid -> map rings): leg on the map's rings -> leg on the CC grid, for grids
@@ -956,14 +1144,14 @@ void FftChain::to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, lo
 void FftChain::from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
                                int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* w, const double2* wring)
 {
-	if (line_analysis(st, tp, false, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, nullptr, w, wring)) return;
+	if (dry_ ? line_takes(tp, false) : line_analysis(st, tp, false, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, nullptr, w, wring)) return;
 	const long npair = (nm + 1)/2;
 	const long g = tp.g, bN = tp.bN, ac = tp.ac;
 	const long ldY1 = pad8(bN), ldU = pad8(g);
 	const size_t need1 = (size_t)npair*g*ldY1, need2 = (size_t)npair*ac*ldU;
 	const int cchunk = theta_comp_chunk(nc, need1, need2);
 	const int T1 = tile_lines_for<StFirst>(g, 0, bN, 8), T2 = tile_lines_for<StResize>(bN, ac, g, 8);
-	s1_.ensure(sizeof(double2)*need1*cchunk); s2_.ensure(sizeof(double2)*need2*cchunk);
+	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
 	for (int c0 = 0; c0 < nc; c0 += cchunk) {
 		const long ncl = std::min(cchunk, nc - c0);
 		{	StFirst s; memset(&s, 0, sizeof(s));
@@ -994,7 +1182,7 @@ void FftChain::from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double
 			launch_any(s, ncl*npair*s.ntile, st);
 		}
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 // exact adjoint of to_cc (adjoint_analysis_2d): leg on the CC grid -> ring spectra h[c][ring][m] on the map's rings.
@@ -1013,7 +1201,7 @@ void FftChain::to_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2*
 	const size_t need1 = (size_t)npair*std::max(g*ldY, g*ldV), need2 = (size_t)npair*std::max(g2*ldZ, bN*ldZ);
 	const int cchunk = theta_comp_chunk(nc, need1, need2);
 	const int T1 = tile_lines_for<StFirst>(g, 0, ac, 8), T2 = tile_lines_for<StResize>(ac, g2, g, 8), T3 = tile_lines_for<StSigma>(g, g, g2, 8), T4 = tile_lines_for<StResize>(g2, bN, g, 8);
-	s1_.ensure(sizeof(double2)*need1*cchunk); s2_.ensure(sizeof(double2)*need2*cchunk);
+	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
 	for (int c0 = 0; c0 < nc; c0 += cchunk) {
 		const long ncl = std::min(cchunk, nc - c0);
 		{	StFirst s; memset(&s, 0, sizeof(s));      // weighted mirror-pair extension on the CC circle, pass 1 of FFT_Ncc
@@ -1056,7 +1244,7 @@ void FftChain::to_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2*
 			launch_any(s, ncl*groups*bN, st);
 		}
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 void FftChain::from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
@@ -1068,7 +1256,7 @@ void FftChain::from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_c
 	const size_t need1 = (size_t)npair*gs*ldY, need2 = (size_t)npair*aN*ldZ;
 	const int cchunk = theta_comp_chunk(nc, need1, need2);
 	const int T1 = tile_lines_for<StFirst>(gs, 0, bs, 8), T2 = tile_lines_for<StResize>(bs, aN, gs, 8);
-	s1_.ensure(sizeof(double2)*need1*cchunk); s2_.ensure(sizeof(double2)*need2*cchunk);
+	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
 	for (int c0 = 0; c0 < nc; c0 += cchunk) {
 		const long ncl = std::min(cchunk, nc - c0);
 		{	StFirst s; memset(&s, 0, sizeof(s));
@@ -1097,7 +1285,7 @@ void FftChain::from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_c
 			launch_any(s, ncl*groups*aN, st);
 		}
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 // 2-D FFT of real maps [npre][ny][nx] -> complex [npre][ny][nx] (enmap.fft of a map, pixell/enmap.py:1307-1323), through the
@@ -1114,10 +1302,10 @@ bool FftChain::fft2_real(hipStream_t st, const void* in, int in_dtype, double2* 
 	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] fft2_real %ld x %ld x %ld: rows %s, columns %ld x %ld\n", npre, ny, nx, describe().c_str(), a, b);
 	PXS_REQUIRE(npre*nm < (1L << 31)/std::max<long>(a, b), "fft2_real: too many lines");
 	// F (half spectrum, transposed) lives in s2_, the four-step intermediates of both axes in s1_
-	s2_.ensure(sizeof(double2)*(size_t)npre*nm*ldF);
+	ensure2(sizeof(double2)*(size_t)npre*nm*ldF);
 	MapDesc m; m.ptr = in; m.dtype = in_dtype; m.cstride = ny*nx; m.ring_off0 = 0; m.ring_stride = nx; m.pix_stride = 1; m.nring = (int)ny; m.nphi = nx;
 	map2leg(st, m, (int)npre, (int)(nm - 1), s2_.as<double2>(), ldF, nullptr, 1.0);
-	s1_.ensure(sizeof(double2)*(size_t)npre*nm*a*ldY);
+	ensure1(sizeof(double2)*(size_t)npre*nm*a*ldY);
 	{	StFirst2D s; memset(&s, 0, sizeof(s));
 		s.fa = mk(fc_, a); s.fb = mk(fc_, 0);
 		s.src.leg = s2_.as<double2>(); s.src.cstride = nm*ldF; s.src.ld = ldF; s.src.nr = (int)ny; s.src.N = (int)ny; s.src.ncol = (int)nm; s.src.plain = 1;
@@ -1134,7 +1322,7 @@ bool FftChain::fft2_real(hipStream_t st, const void* in, int in_dtype, double2* 
 		s.groups = (int)((nm + T - 1)/T); s.dgr = make_fastdiv((uint32_t)s.groups);
 		launch_any(s, npre*s.groups*a, st);
 	}
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 	return true;
 }
 
@@ -1147,8 +1335,8 @@ bool FftChain::fft2_c2c(hipStream_t st, const double2* in, double2* out, long np
 	const long ax = std::min(sx.a, sx.b), bx = nx/ax, ay = std::min(sy.a, sy.b), by = ny/ay, ldF = pad8(ny);
 	if (npre*std::max(nx, ny) >= (1L << 31)/512) return false;
 	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] fft2_c2c %ld x %ld x %ld: rows %ld x %ld, columns %ld x %ld\n", npre, ny, nx, ax, bx, ay, by);
-	s1_.ensure(sizeof(double2)*(size_t)npre*std::max(ny*ax*pad8(bx), nx*ay*pad8(by)));
-	s2_.ensure(sizeof(double2)*(size_t)npre*nx*ldF);
+	ensure1(sizeof(double2)*(size_t)npre*std::max(ny*ax*pad8(bx), nx*ay*pad8(by)));
+	ensure2(sizeof(double2)*(size_t)npre*nx*ldF);
 	auto first = [&](const double2* src, long nlines, long ld, long n, long a, long b, int conj) {
 		StFirst2D s; memset(&s, 0, sizeof(s));
 		s.fa = mk(fc_, a); s.fb = mk(fc_, 0);
@@ -1170,7 +1358,7 @@ bool FftChain::fft2_c2c(hipStream_t st, const double2* in, double2* out, long np
 	second(s2_.as<double2>(), ny, ldF, nx*ldF, ax, bx, 0, 1.0);               // -> F[kx][y]
 	first(s2_.as<double2>(), nx, ldF, ny, ay, by, 0);                         // columns kx: contiguous lines of ny points
 	second(out, nx, nx, ny*nx, ay, by, forward ? 0 : 1, scale);               // -> out[ky][kx]
-	PXS_HIP(hipGetLastError());
+	if (!dry_) PXS_HIP(hipGetLastError());
 	return true;
 }
 

@@ -5,6 +5,8 @@
 #include "fft.hpp"
 #include <tuple>
 #include <map>
+#include <set>
+#include <vector>
 #include <mutex>
 #include <memory>
 
@@ -15,6 +17,8 @@ struct Lds2;
 // factorisation N = a*b of a four-step transform: pass 1 = a-point transforms over the residues mod b,
 // pass 2 = b-point transforms producing the residues mod a
 struct Split { long a = 0, b = 0; };
+// a stage as launched: stage id (S::SID), lengths of its one or two LDS transforms, lines per tile; in the compiled table?
+struct ChainShape { int sid, na, nb, T; bool is_static; };
 
 struct ThetaPlan {            // sizes of the theta chains of a grid plan
 	bool ok = false;
@@ -74,7 +78,18 @@ public:
 	static void theta_scratch(const ThetaPlan& tp, int nm, int nc, int kind, size_t& b1, size_t& b2);
 	void ring_scratch(long nring, int nc, bool analysis, size_t& b1, int mmax = -1) const;      // (mmax given: 0 for a synthesis that ringline.hip takes)
 	void reserve(size_t b1, size_t b2) { s1_.ensure(b1); s2_.ensure(b2); }
+	// Compile-time-planned stage kernels (chain_kernel_static, chain_static_table.hpp).  A dry run: between dry_begin and dry_end the
+	// calls above launch and allocate nothing and list the stage shapes they would launch, with whether the table holds each.
+	void dry_begin(std::vector<ChainShape>* out) { dry_ = out; }
+	void dry_end() { dry_ = nullptr; }
+	int static_check(int maxr = 0);      // table entries (of the stages with this largest radix; 0: all) against the engine's plans; throws on a mismatch
+	static bool static_has(int sid, int na, int nb, int T);
+	static void static_shapes(std::vector<ChainShape>& out);
 private:
+	void ensure1(size_t b) { if (!dry_) s1_.ensure(b); }
+	void ensure2(size_t b) { if (!dry_) s2_.ensure(b); }
+	std::vector<ChainShape>* dry_ = nullptr;
+	std::set<int> checked_;
 	const double2* small_tw(long X, int n, int T);
 	template<class S> void set_tiles(S& s, int T, long nlines, long X);
 	template<class S> int tile_lines_for(long n_a, long n_b, long nlines, int mult, long tab_pts = -1);

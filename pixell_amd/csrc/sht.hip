@@ -1089,6 +1089,41 @@ static AnaSet ana_set(const pxs_plan* p, bool allow_fine = true) {
 }
 static Route route_of(const pxs_plan* p, bool analysis, int spin, int mode, bool adjoint, const LegTables* tb);
 static Route analysis_route_now(const pxs_plan* p) { return route_of(p, true, 0, PXS_MODE_STANDARD, false, nullptr); }      // pxs_analysis under the plan's current option
+// The chain stage shapes of the plan's standard calls (analysis under its current option, synthesis of spin 0 and spin 2), each once:
+// a dry run of the very calls (FftChain::dry_begin), so the list cannot drift from what they launch.
+static std::vector<ChainShape> chain_shapes(const pxs_plan* cp) {
+	pxs_plan* p = const_cast<pxs_plan*>(cp);
+	std::vector<ChainShape> all, out;
+	if (!p->chain || !p->chain_rings) return out;
+	std::lock_guard<std::mutex> plan_lock(p->call_mu);
+	const int nm = p->mmax + 1;
+	FftChain::MapDesc md; memset(&md, 0, sizeof(md)); md.dtype = PX_F64; md.cstride = (long)p->nring*p->nphi; md.ring_stride = p->nphi; md.pix_stride = 1; md.nring = p->nring; md.nphi = p->nphi;
+	p->chain->dry_begin(&all);
+	try {
+		for (int which = 0; which < 3; which++) {
+			const bool ana = which == 0; const int spin = which == 2 ? 2 : 0;
+			const Route r = route_of(p, ana, spin, PXS_MODE_STANDARD, false, nullptr);
+			if (!r.reserve_chain) continue;
+			if (ana) p->chain->map2leg(nullptr, md, r.nc, p->mmax, nullptr, r.ld_leg, nullptr, 1.0);
+			else p->chain->h2map(nullptr, nullptr, r.ld_h, md, r.nc, p->mmax, 0);
+			if (!r.theta_fused || r.line) continue;
+			switch (r.theta) {
+			case TH_TO_CC:       p->chain->to_cc(nullptr, *r.tp, nullptr, r.ld_leg, r.nr_th, p->mir_c, nullptr, r.ld_leg2, p->ncc, r.nc, nm, spin, p->lmax, nullptr, nullptr, nullptr); break;
+			case TH_FROM_CC_ADJ: p->chain->from_cc_adjoint(nullptr, *r.tp, nullptr, r.ld_leg, r.nr_th, p->mir_c, nullptr, r.ld_leg2, p->ncc, r.nc, nm, spin, p->lmax, nullptr, nullptr, nullptr); break;
+			case TH_FROM_CC:     p->chain->from_cc(nullptr, *r.tp, nullptr, r.ld_leg2, p->ncc, nullptr, r.ld_h, r.nr_h, p->mir_c, r.nc, nm, spin, p->lmax, nullptr, nullptr, 1.0, nullptr); break;
+			case TH_TO_CC_ADJ:   p->chain->to_cc_adjoint(nullptr, *r.tp, nullptr, r.ld_leg2, p->ncc, nullptr, r.ld_h, r.nr_h, p->mir_c, r.nc, nm, spin, p->lmax, nullptr, nullptr, nullptr, nullptr, 2.0); break;
+			case TH_NONE: break;
+			}
+		}
+	} catch (...) { p->chain->dry_end(); throw; }
+	p->chain->dry_end();
+	for (const ChainShape& c : all) {
+		bool seen = false;
+		for (const ChainShape& o : out) seen = seen || (o.sid == c.sid && o.na == c.na && o.nb == c.nb && o.T == c.T);
+		if (!seen) out.push_back(c);
+	}
+	return out;
+}
 int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	PXS_TRY
 	PXS_REQUIRE(p && name && value, "pxs_plan_query: null argument");
@@ -1098,6 +1133,15 @@ int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	else if (n == "ncc_circle") *value = p->ncc > 0 ? p->Ncc : 0;
 	else if (n == "ducc_ncc_circle") *value = FftChain::ducc_ncc(p->lmax);
 	else if (n == "theta_line") *value = analysis_route_now(p).line ? 1 : 0;      // 1: its theta resampling runs as ONE kernel per call (thetaline.hip), 0: as the stage chain
+	else if (n == "chain_stages" || n == "chain_static") {      // distinct chain stage shapes of the plan's standard calls / those with a compile-time-planned kernel
+		int64_t k = 0;
+		for (const ChainShape& c : chain_shapes(p)) {
+			if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] plan stage %d: na=%d nb=%d T=%d static %d\n", c.sid, c.na, c.nb, c.T, c.is_static ? 1 : 0);
+			k += (n == "chain_stages" || c.is_static) ? 1 : 0;
+		}
+		*value = k;
+	}
+	else if (n == "chain_static_table") *value = p->chain ? p->chain->static_check(0) : 0;      // entries of the compiled table, each checked against the FFT engine's plan of its lengths (throws on a mismatch)
 	else throw Error(PXS_ERR_ARG, std::string("pxs_plan_query: unknown name '") + name + "'");
 	PXS_CATCH
 }
