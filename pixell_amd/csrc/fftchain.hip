@@ -46,38 +46,21 @@ static constexpr int CH_NMAX = 512;           // longest LDS sub-transform of a 
 
 struct TileC { int outer, t0, nl, comp, q0; };
 
-// Tile-blocked intermediates (an option, see blocked_on()).  A stage whose lines are the fast index of its output ("line-fast"
-// store) writes runs of T*16 bytes (T = 8-16 lines: 128-256 bytes) at a row stride, and the next stage reads whole rows.  With the
-// blocked layout a writer's tile -- lines [t0, t0 + w) x all n outputs -- is ONE contiguous chunk [e][line in tile] of n*w points
-// at offset t0*n of its outer slab, and a reader, whose tile is Tr consecutive rows e, finds Tr*w points of every chunk contiguous
-// (1-2 KB).  BlkIn describes the chunks to the reader: width Tw of the full ones, their number, the width of the last one.
-struct BlkIn {
-	int Tw, nBf, wL; FastDiv dTTw, dTw, dwL;      // Tw = 0: plain rows of stride ld
-	// offset of (row `line` of nrows, element e of na) within the outer slab
-	__device__ __forceinline__ long off(int line, int e, int nrows) const {
-		const uint32_t B = fdiv((uint32_t)e, dTw);
-		const int w = (int)B < nBf ? Tw : wL;
-		return (long)B*Tw*nrows + (long)line*w + (e - (int)B*Tw);
-	}
-	// load order of a reader tile of T rows: chunk, row, element in chunk -- consecutive lanes read consecutive memory
-	__device__ __forceinline__ void split(int idx, int T, uint32_t& li, uint32_t& e) const {
-		uint32_t B = fdiv((uint32_t)idx, dTTw);
-		if ((int)B < nBf) { const uint32_t rem = idx - B*T*Tw; li = fdiv(rem, dTw); e = B*Tw + (rem - li*Tw); }
-		else { const uint32_t rem = idx - (uint32_t)nBf*T*Tw; li = fdiv(rem, dwL); e = (uint32_t)nBf*Tw + (rem - li*wL); }
-	}
-};
-
-struct StageBase {
+// alignas(64): a stage's own fields start on a 64-byte boundary whatever the base holds.  The compiler merges the scalar loads of the
+// kernel arguments into aligned 16- to 64-byte loads, so the fields' offsets modulo 64 decide which loads merge and, through the
+// schedule, the registers: with the base 40 bytes shorter and unaligned StResize 112/150 T = 16 went from 64 to 66 VGPRs (8 -> 7 waves)
+// and StColOut 120 T = 16 from 54 to 55 with their own text unchanged; aligned, both are back (profiles/chain_static_kernel_resources.txt).
+// The alignment does not protect against other changes: rerun tools/kres.py on this file whenever a stage struct changes.
+struct alignas(64) StageBase {
 	// radix 7 compiled into the stage's kernel (MAXR = 9 stages): the theta stages, for ducc0's ring counts.  Its code costs the kernels
 	// that hold it 2-4 % (same box, tools/fft2_ab.sh: enmap.fft 17.3 -> 17.7 ms, enmap.ifft 32.2 -> 33.7), so the 2-D FFT stages leave it out
 	static constexpr bool R7 = true;
-	// threads per workgroup.  Per-stage A/B at C3 (tools/gpu_ntlab.sh, profiles/r04b_ntlab_c3.txt): 512 wins for every stage (256: ring stages
+	// threads per workgroup.  Per-stage A/B at C3 (profiles/r04b_ntlab_c3.txt): 512 wins for every stage (256: ring stages
 	// +15-25 %, StResize / StSigma +5-9 %; 384: 0 to +10 %) except the transposing split StSplit<1>: from_cc 12.27 -> 11.45 ms with 256
 	static constexpr int NT = CH_NT;
 	// most points a tile of the stage may hold (the kernel's per-thread element count follows from it)
 	static constexpr int PTS = CH_TILE_PTS;
 	LdsFft fa, fb;
-	BlkIn bin; int bout;       // input in the blocked layout (bin.Tw > 0); write the output blocked
 	int T; int ntile;
 	FastDiv dT, dna, dnb, dnt;
 	// four-step twiddle of the stage's output, W_X^{(t0 + li) e} = W_X^{t0 e} * W_X^{li e}: the first factor is gathered once per tile
@@ -135,7 +118,6 @@ template<class S, int NT, int MAXE> __global__ PXS_CH_BOUNDS void chain_kernel(c
 			if (idx < total) {
 				uint32_t li, e;
 				if (S::LOAD_LINE_FAST) { e = fdiv(idx, s.dT); li = idx - e*T; }
-				else if (s.bin.Tw > 0) s.bin.split(idx, T, li, e);
 				else { li = fdiv(idx, s.dna); e = idx - li*na; }
 				v[u] = s.load(c, (int)li, (int)e);
 				if (S::INV_A) v[u].y = -v[u].y;
@@ -224,8 +206,7 @@ struct StFirst : StageBase {
 	template<class AF> __device__ __forceinline__ double2 mid(const TileC&, int, int, AF&&) const { return make_double2(0, 0); }
 	template<class VF> __device__ __forceinline__ void store(const TileC& c, int li, int e, VF&& val, double2 w) const {
 		if (li >= c.nl) return;
-		const long o = bout ? ((long)c.outer*b + c.t0)*fa.n + (long)e*c.nl + li : ((long)c.outer*fa.n + e)*ldY + c.t0 + li;
-		Y[o] = cmul(val(li, e), w); }
+		Y[((long)c.outer*fa.n + e)*ldY + c.t0 + li] = cmul(val(li, e), w); }
 };
 
 // ... of the 2-D FFTs (plain mode; lengths are 2-3-5-smooth there, split_balanced)
@@ -251,9 +232,6 @@ struct StResize : StageBase {
 #define PXS_RESIZE_MINW 1      /* 8 (at most 64 VGPRs, 20 bytes of scratch per lane, four workgroups per CU where the LDS allows) measured: to_cc 29.9 -> 34.1 ms at C3, 11.4 -> 13.0 at C4 */
 #endif
 	static constexpr int MAXR = 9, MINW = PXS_RESIZE_MINW;
-#ifdef PXS_RESIZE_PTS      /* experiment: a larger tile cap (2880) so that lines of 321 ... 360 points still get 8 per tile: to_cc 11.2 -> 12.45 ms at C4, 4.3 -> 4.8 at C2 (74 VGPRs, more LDS per workgroup), nothing at C3 / C5 */
-	static constexpr int PTS = PXS_RESIZE_PTS;
-#endif
 	const double2* Y; long ldY; double2* Z; long ldZ;
 	int g, X1, X2, kmax, nyq; const double2* ph; FastDiv dg;
 	int adj;      // transposed padding rule (X1 > X2): conjugate phase, and the Nyquist slot of X2 collects 1/2 of both +-X2/2 bins of X1
@@ -263,7 +241,7 @@ struct StResize : StageBase {
 		c.outer = fdiv(bx, dnt); c.t0 = (bx - c.outer*ntile)*T; c.nl = min(T, g - c.t0); return true; }
 	__device__ __forceinline__ double2 load(const TileC& c, int li, int e) const {
 		if (li >= c.nl) return make_double2(0, 0);
-		return bin.Tw > 0 ? Y[(long)c.outer*g*fa.n + bin.off(c.t0 + li, e, g)] : Y[((long)c.outer*g + c.t0 + li)*ldY + e]; }
+		return Y[((long)c.outer*g + c.t0 + li)*ldY + e]; }
 	template<class AF> __device__ __forceinline__ double2 mid(const TileC& c, int li, int e, AF&& A) const {
 		if (li >= c.nl) return make_double2(0, 0);
 		const int k1 = c.t0 + li;
@@ -289,8 +267,7 @@ struct StResize : StageBase {
 		return v; }
 	template<class VF> __device__ __forceinline__ void store(const TileC& c, int li, int e, VF&& val, double2 w) const {
 		if (li >= c.nl) return;
-		const long o = bout ? ((long)c.outer*g + c.t0)*fb.n + (long)e*c.nl + li : ((long)c.outer*fb.n + e)*ldZ + c.t0 + li;
-		Z[o] = cmul(cconj(val(li, e)), cconj(w)); }
+		Z[((long)c.outer*fb.n + e)*ldZ + c.t0 + li] = cmul(cconj(val(li, e)), cconj(w)); }
 };
 
 // pass 2 of IFFT_M (g points), pointwise product with the |sin| series samples, pass 1 of FFT_M (g points)
@@ -304,16 +281,17 @@ struct StSigma : StageBase {
 	__device__ __forceinline__ const double2* row(const TileC& c, int li) const { return li < c.nl ? Z + ((long)c.outer*g2 + c.t0 + li)*ldZ : nullptr; }
 	__device__ __forceinline__ bool decode(int bx, TileC& c) const {
 		c.outer = fdiv(bx, dnt); c.t0 = (bx - c.outer*ntile)*T; c.nl = min(T, g2 - c.t0); return true; }
+	// (c.t0 + li grouped, here and in store: the 32-bit line index that row() and mid() use too; summed into the 64-bit outer*g2 first
+	// it cost StSigma 48/48 T = 48 two more VGPRs, 72 against 70 and 68)
 	__device__ __forceinline__ double2 load(const TileC& c, int li, int e) const {
 		if (li >= c.nl) return make_double2(0, 0);
-		return bin.Tw > 0 ? Z[(long)c.outer*g2*fa.n + bin.off(c.t0 + li, e, g2)] : Z[((long)c.outer*g2 + c.t0 + li)*ldZ + e]; }
+		return Z[((long)c.outer*g2 + (c.t0 + li))*ldZ + e]; }
 	template<class AF> __device__ __forceinline__ double2 mid(const TileC& c, int li, int e, AF&& A) const {
 		if (li >= c.nl) return make_double2(0, 0);
 		return cmul(cconj(A(e)), sigma[(c.t0 + li) + g2*e]); }
 	template<class VF> __device__ __forceinline__ void store(const TileC& c, int li, int e, VF&& val, double2 w) const {
 		if (li >= c.nl) return;
-		const long o = bout ? ((long)c.outer*g2 + c.t0)*fb.n + (long)e*c.nl + li : ((long)c.outer*g + e)*ldV + c.t0 + li;
-		V[o] = cmul(val(li, e), w); }
+		V[((long)c.outer*g + e)*ldV + (c.t0 + li)] = cmul(val(li, e), w); }
 };
 
 // last pass of a backward chain (IFFT over r < g for the lines k1 < a, circle index t = k1 + a*k2) + separation of the packed pair
@@ -366,7 +344,6 @@ template<int MODE> struct StSplit : StageBase {
 	__device__ __forceinline__ double2 load(const TileC& c, int li, int e) const {
 		int line, pair; slot(c, li, line, pair);
 		if (line < 0) return make_double2(0, 0);
-		if (MODE == 0 && bin.Tw > 0) return U[((long)c.comp*npair + pair)*a*fa.n + bin.off(line, e, a)];
 		return U[(((long)c.comp*npair + pair)*a + line)*ldU + e]; }
 	template<class AF> __device__ __forceinline__ double2 mid(const TileC&, int, int, AF&&) const { return make_double2(0, 0); }
 	template<class VF> __device__ __forceinline__ void store(const TileC& c, int li, int e, VF&& val, double2) const {
@@ -512,8 +489,7 @@ struct StRingS1 : StageBase {
 	template<class AF> __device__ __forceinline__ double2 mid(const TileC&, int, int, AF&&) const { return make_double2(0, 0); }
 	template<class VF> __device__ __forceinline__ void store(const TileC& c, int li, int e, VF&& val, double2 w) const {
 		if (li >= c.nl) return;
-		const long o = bout ? ((long)c.outer*b + c.t0)*fa.n + (long)e*c.nl + li : ((long)c.outer*fa.n + e)*ldY + c.t0 + li;
-		Y[o] = cmul(cconj(val(li, e)), cconj(w)); }
+		Y[((long)c.outer*fa.n + e)*ldY + c.t0 + li] = cmul(cconj(val(li, e)), cconj(w)); }
 };
 
 // MS2: backward b-point transform over j2 for the lines k1; pixel x = k1 + a*k2: real part -> ring 2q, imaginary part -> ring 2q+1
@@ -529,7 +505,7 @@ struct StRingS2 : StageBase {
 		c.comp = fdiv(c.outer, dnp); c.q0 = c.outer - c.comp*npair; return true; }
 	__device__ __forceinline__ double2 load(const TileC& c, int li, int e) const {
 		if (li >= c.nl) return make_double2(0, 0);
-		return bin.Tw > 0 ? Y[(long)c.outer*a*fa.n + bin.off(c.t0 + li, e, a)] : Y[((long)c.outer*a + c.t0 + li)*ldY + e]; }
+		return Y[((long)c.outer*a + c.t0 + li)*ldY + e]; }
 	template<class AF> __device__ __forceinline__ double2 mid(const TileC&, int, int, AF&&) const { return make_double2(0, 0); }
 	template<class VF> __device__ __forceinline__ void store(const TileC& c, int li, int e, VF&& val, double2) const {
 		if (li >= c.nl) return;
@@ -729,7 +705,6 @@ static LdsFft mk(FftContext* fc, long n, int maxr = 9) {
 #else
 	constexpr int nofft = 0;
 #endif
-	static const int nspad = [] { const char* e = lab_getenv("PXS_CH_NS_PAD"); return e ? atoi(e) : 0; }();     // experiments: line stride (n | 1) + pad
 	if (getenv("PXS_CHAIN_VERBOSE")) {
 		static std::mutex mu; static std::set<std::pair<long, int>> seen; std::lock_guard<std::mutex> g(mu);
 		if (seen.insert(std::make_pair(n, maxr)).second) {
@@ -737,7 +712,7 @@ static LdsFft mk(FftContext* fc, long n, int maxr = 9) {
 			fprintf(stderr, "[pxsht] chain fft n=%ld maxr=%d: radices%s\n", n, maxr, r.c_str());
 		}
 	}
-	f.n = v.n; f.nfac = nofft ? 0 : v.nfac; f.ns = v.ns + nspad; f.generic = v.generic; f.pass = (const PassDesc*)v.pass; f.perm = v.perm; f.tw = v.tw; f.dn = make_fastdiv((uint32_t)n);
+	f.n = v.n; f.nfac = nofft ? 0 : v.nfac; f.ns = v.ns; f.generic = v.generic; f.pass = (const PassDesc*)v.pass; f.perm = v.perm; f.tw = v.tw; f.dn = make_fastdiv((uint32_t)n);
 	return f;
 }
 
@@ -761,19 +736,15 @@ const double2* FftChain::small_tw(long X, int n, int T) {
 }
 
 // lines per tile: as many as fit CH_TILE_PTS, in multiples of `mult`
-// tab_pts >= 0 (ring stages, which run at <= 64 VGPRs) and PXS_RING_TILE_KB = k > 0: shrink the tile until tile + tab_pts table
-// entries fit k KiB of LDS (k = 39.5: four workgroups per CU).  Off by default -- measured at C3 / C4 / C2: ring FFT stages
-// 47.4 / 60.6 / 2.85 ms with 39.5 KiB tiles against 46.4 / 60.8 / 2.83 ms with the full 2560-point tiles.
-static int tile_lines(long n_a, long n_b, long nlines, int mult, long tab_pts = -1) {
+// (Tried for the ring stages, which run at <= 64 VGPRs: tiles shrunk until tile + tables fit 39.5 KiB of LDS, four workgroups per CU.
+// Measured at C3 / C4 / C2: ring FFT stages 47.4 / 60.6 / 2.85 ms against 46.4 / 60.8 / 2.83 ms with the full 2560-point tiles.  Removed.)
+static int tile_lines(long n_a, long n_b, long nlines, int mult) {
 	const long n = std::max(n_a, n_b);
 	long T = CH_TILE_PTS / n;
 	if (T >= mult) T -= T % mult;
 	if (T < 1) T = 1;
 	const long cap = ((nlines + mult - 1)/mult)*mult;
 	if (T > cap) T = cap;
-	static const long limit = [] { const char* e = lab_getenv("PXS_RING_TILE_KB"); return e ? (long)(atof(e)*1024) : 0L; }();
-	if (tab_pts >= 0 && limit > 0)
-		while (T > mult && (long)sizeof(double2)*(tab_pts + T*(n | 1) + 2) > limit) T -= mult;
 	return (int)T;
 }
 // tiles of T consecutive lines; X > 0: the stage applies the four-step twiddle of a length-X transform to its output
@@ -783,31 +754,10 @@ template<class S> void FftChain::set_tiles(S& s, int T, long nlines, long X) {
 	s.btw = nullptr; s.tws = nullptr;
 	if (X > 0) { s.tws = small_tw(X, S::TWO ? s.fb.n : s.fa.n, T); s.btw = s.tws ? fc_->twiddle_table(X) : nullptr; }
 }
-// blocked intermediates: OFF by default.  Measured (tools/chain_lab.py, same box): C3 chain stages 106.9 ms with rows, 108.1 ms
-// blocked; C4 26.6 / 26.6 -- the 128-byte runs of the intermediates are not what holds the chain kernels at ~3 TB/s (a bare
-// load-tile / LDS / store-tile kernel on contiguous 40 KB tiles reaches 5.3 TB/s with 2, 3 or 4 workgroups per CU, and an LDS-DMA
-// double-buffered persistent variant of it only 4.6: tools/dma_skel.hip).  PXS_CH_BLOCKED=1 turns the layout on for experiments.
-static bool blocked_on() { static const bool on = [] { const char* e = lab_getenv("PXS_CH_BLOCKED"); return e ? atoi(e) != 0 : false; }(); return on; }
-// reader side of a blocked intermediate: the writer made chunks of Tw lines out of na, the reader's tile has T rows
-static BlkIn mk_blk(int Tw, long na, int T) {
-	BlkIn b; memset(&b, 0, sizeof(b));
-	if (!blocked_on()) return b;
-	b.Tw = Tw; b.nBf = (int)(na/Tw); b.wL = (int)(na - (long)b.nBf*Tw);
-	b.dTTw = make_fastdiv((uint32_t)(T*Tw)); b.dTw = make_fastdiv((uint32_t)Tw); b.dwL = make_fastdiv((uint32_t)std::max(b.wL, 1));
-	return b;
-}
-// ---- second-generation kernel: transform plans and launch -------------------------------------------------------------------
-
-static const int F2_RADICES[] = {2, 3, 4, 5, 6, 8, 9};
-// n as a product of at most three register radices: fewest passes, then the smallest largest radix; ascending order (the first
-// pass works on the longest rows, which wastes the least padding).  maxfirst: cap on the first radix (passes that pull their inputs
-
-// the static instance of a stage as planned, or null: its shape is not in the table, or the stage uses what the static kernel leaves
-// out (blocked input, a padded line stride or a plan with no passes: experiments)
+// the static instance of a stage as planned, or null: its shape is not in the table, or the plan has no passes (PXS_CH_NOFFT, lab builds)
 template<class S> static const StaticEntry* static_for(const S& s) {
 	const StaticEntry* e = static_find(S::SID, s.fa.n, s.fb.n, s.T);
-	if (!e || s.bin.Tw > 0 || s.fa.ns != (s.fa.n | 1) || s.fa.nfac != (int)e->ra.size()) return nullptr;
-	if (S::TWO && (s.fb.ns != (s.fb.n | 1) || s.fb.nfac != (int)e->rb.size())) return nullptr;
+	if (!e || s.fa.nfac != (int)e->ra.size() || (S::TWO && s.fb.nfac != (int)e->rb.size())) return nullptr;
 	return e;
 }
 template<class S> static void launch_stage(const S& s, long nblk, hipStream_t st, std::vector<ChainShape>* dry) {
@@ -830,16 +780,6 @@ template<class S> static void launch_stage(const S& s, long nblk, hipStream_t st
 	}
 	if (se) { se->launch(&s, nblk, sh, st); return; }
 #ifndef PXS_HOST_SIM
-#ifdef PXS_CH_NT2      /* experiment builds: stages whose bit SID is set in PXS_CH_NT2_MASK run with PXS_CH_NT2 threads per workgroup */
-	static const long mask2 = [] { const char* e = lab_getenv("PXS_CH_NT2_MASK"); return e ? strtol(e, nullptr, 0) : 0L; }();
-	if ((mask2 >> S::SID) & 1) {
-		constexpr int NT2 = PXS_CH_NT2, MAXE2 = (S::PTS + NT2 - 1)/NT2;
-		static const bool once2 = [] { (void)hipFuncSetAttribute((const void*)chain_kernel<S, NT2, MAXE2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }();
-		(void)once2;
-		hipLaunchKernelGGL((chain_kernel<S, NT2, MAXE2>), dim3((unsigned)nblk), dim3(NT2), sh, st, s);
-		return;
-	}
-#endif
 	static const bool once = [] { (void)hipFuncSetAttribute((const void*)chain_kernel<S, S::NT, (S::PTS + S::NT - 1)/S::NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }();
 	(void)once;
 #endif
@@ -847,8 +787,8 @@ template<class S> static void launch_stage(const S& s, long nblk, hipStream_t st
 }
 
 // lines per tile of a stage
-template<class S> int FftChain::tile_lines_for(long n_a, long n_b, long nlines, int mult, long tab_pts) {
-	int T = tile_lines(n_a, n_b, nlines, mult, tab_pts);
+template<class S> int FftChain::tile_lines_for(long n_a, long n_b, long nlines, int mult) {
+	int T = tile_lines(n_a, n_b, nlines, mult);
 	// a stage with a larger cap takes it only to reach `mult` lines (whole 128-byte lines on its strided side)
 	if (S::PTS > CH_TILE_PTS && T < mult && (long)mult*std::max(n_a, n_b) <= S::PTS && nlines >= mult) T = mult;
 	return T;
@@ -993,28 +933,98 @@ static long ring_chunk(long npair, long bytes_per_pair, int mult) {
 	return std::min(q, npair);
 }
 
+// ---- one builder per stage kind -------------------------------------------------------------------------------------------------
+// A builder takes what varies between the calls of its stage and owns the rest: the zeroed stage and its transforms (new_stage), the
+// lines per tile (tile_lines_for; pair_lines where a tile holds pairs of lines), set_tiles, the FastDivs of its own arguments, and
+// where the intermediates live: a chain ping-pongs between s1_ and s2_, and a row of n points has the leading dimension pad8(n).
+template<class S> S FftChain::new_stage(long na, long nb) {
+	S s; memset(&s, 0, sizeof(s));
+	s.fa = mk(fc_, na, S::MAXR); s.fb = mk(fc_, nb, S::MAXR);
+	return s;
+}
+template<class S> int FftChain::pair_lines(long n, long nlines) { int T = tile_lines_for<S>(n, 0, nlines, 8); if (T < 2) T = 2; return T - T % 2; }
+
+// columns (m, m+1) of leg[comp][m][ring] packed by parity and mirror-extended to the circle of N points (w: optional weight per ring)
+static PairSrc pair_src(const double2* leg, long ld, int nr, long N, int mir_c, int spin, int nm, const double2* w) {
+	PairSrc p; memset(&p, 0, sizeof(p));
+	p.leg = leg; p.cstride = (long)nm*ld; p.ld = ld; p.nr = nr; p.N = (int)N; p.mir_c = mir_c; p.a_odd = spin & 1; p.ncol = nm; p.w = w;
+	return p;
+}
+// `nlines` plain lines of n points per component (the 2-D FFTs)
+static PairSrc plain_src(const double2* src, long nlines, long ld, long n, int conj) {
+	PairSrc p; memset(&p, 0, sizeof(p));
+	p.leg = src; p.cstride = nlines*ld; p.ld = ld; p.nr = (int)n; p.N = (int)n; p.ncol = (int)nlines; p.plain = 1; p.conj = conj;
+	return p;
+}
+// StFirst / StFirst2D: pass 1 of the a*b-point transform of `npair` lines per component: src -> s1_[outer][k1 < a][j2 < b]
+template<class S> void FftChain::run_first(hipStream_t st, const PairSrc& src, long ncomp, long npair, long a, long b) {
+	S s = new_stage<S>(a, 0);
+	s.src = src; s.b = (int)b; s.Y = s1_.as<double2>(); s.ldY = pad8(b); s.npair = (int)npair; s.dnp = make_fastdiv((uint32_t)npair);
+	set_tiles(s, tile_lines_for<S>(a, 0, b, 8), b, a*b);
+	launch_any(s, ncomp*npair*s.ntile, st);
+}
+// StResize: pass 2 of the forward transform of X1 = g*fa points, resize, pass 1 of the backward one of X2 = g*fb points:
+// s1_[outer][k1 < g][j2 < fa] -> s2_[outer][k1' < fb][k1 < g]
+void FftChain::run_resize(hipStream_t st, long nouter, long fa, long fb, long g, int kmax, int nyq, int adj, const double2* ph) {
+	StResize s = new_stage<StResize>(fa, fb);
+	s.Y = s1_.as<double2>(); s.ldY = pad8(fa); s.Z = s2_.as<double2>(); s.ldZ = pad8(g);
+	s.g = (int)g; s.X1 = (int)(g*fa); s.X2 = (int)(g*fb); s.kmax = kmax; s.nyq = nyq; s.adj = adj; s.ph = ph; s.dg = make_fastdiv((uint32_t)g);
+	set_tiles(s, tile_lines_for<StResize>(fa, fb, g, 8), g, g*fb);
+	launch_any(s, nouter*s.ntile, st);
+}
+// StSigma: s2_[outer][k1' < g2][r < g] -> s1_[outer][k1'' < g][k1' < g2] on the fine circle of M = g*g2 points
+void FftChain::run_sigma(hipStream_t st, long nouter, long g, long g2, const double2* sigma) {
+	StSigma s = new_stage<StSigma>(g, g);
+	s.Z = s2_.as<double2>(); s.ldZ = pad8(g); s.V = s1_.as<double2>(); s.ldV = pad8(g2); s.g = (int)g; s.g2 = (int)g2; s.sigma = sigma;
+	set_tiles(s, tile_lines_for<StSigma>(g, g, g2, 8), g2, g*g2);
+	launch_any(s, nouter*s.ntile, st);
+}
+// StSplit<MODE>: last pass of the backward transform of X = a*g points from s2_[comp][pair][k1 < a][r < g], the pair apart, rings t < nr_out:
+// MODE 0 -> out[comp][col][t] * w[t]; MODE 1 -> out[comp][t][col] * conj(tab[col]) * w[t] * scale.  ocstride: elements of out per component
+template<int MODE> void FftChain::run_split(hipStream_t st, long ncomp, long npair, int nm, int spin, long a, long g, int mir_c, int nr_out,
+                                            double2* out, long ld, long ocstride, const double2* w, const double2* tab, double scale, int self_half) {
+	using S = StSplit<MODE>;
+	S s = new_stage<S>(g, 0);
+	const int T = pair_lines<S>(g, MODE == 0 ? 2*a : 2*npair), TH = T/2;
+	// MODE 0: tiles of TH primary lines (of a/2 + 1) and their mirror lines; MODE 1: one tile per line and group of TH pairs (ntile = a)
+	set_tiles(s, T, MODE == 0 ? (long)((a/2 + 1 + TH - 1)/TH)*T : a*T, 0);
+	s.TH = MODE == 0 ? TH : 0; s.groups = MODE == 0 ? 1 : (int)((npair + TH - 1)/TH);
+	s.U = s2_.as<double2>(); s.ldU = pad8(g); s.a = (int)a; s.g = (int)g; s.X = (int)(a*g); s.mir_c = mir_c; s.nr_out = nr_out; s.a_odd = spin & 1; s.ncol = nm; s.npair = (int)npair;
+	s.out = out; s.ocstride = ocstride; s.ld = ld; s.w = w; s.tab = tab; s.scale = scale; s.self_half = self_half;
+	s.da = make_fastdiv((uint32_t)a); s.dnp = make_fastdiv((uint32_t)npair); s.dgr = make_fastdiv((uint32_t)s.groups);
+	launch_any(s, ncomp*(MODE == 0 ? npair : (long)s.groups)*s.ntile, st);
+}
+// StColOut: last pass of the a*b-point transform of `nlines` lines per component from s1_, transposed into out[k][line] (row stride ldo,
+// ocomp elements per component); herm_nx > 0: the lines are the half spectrum of herm_nx real points, write the Hermitian image too
+void FftChain::run_colout(hipStream_t st, long npre, long nlines, long a, long b, double2* out, long ldo, long ocomp, int conj, double scale, long herm_ny, long herm_nx) {
+	StColOut s = new_stage<StColOut>(b, 0);
+	const int T = tile_lines_for<StColOut>(b, 0, nlines, 8);
+	set_tiles(s, T, a*T, 0);          // one tile per line: ntile = a
+	s.Y = s1_.as<double2>(); s.ldY = pad8(b); s.a = (int)a; s.nm = (int)nlines; s.ny = (int)herm_ny; s.nx = (int)herm_nx; s.herm = herm_nx > 0 ? 1 : 0;
+	s.conj_out = conj; s.out = out; s.ldo = ldo; s.ocomp = ocomp; s.scale = scale;
+	s.groups = (int)((nlines + T - 1)/T); s.dgr = make_fastdiv((uint32_t)s.groups);
+	launch_any(s, npre*s.groups*a, st);
+}
+
 void FftChain::map2leg(hipStream_t st, const MapDesc& m, int nc, int mmax, double2* leg, long ldleg, const double2* tab, double scale) {
 	PXS_REQUIRE(rings_ok() && m.nphi == nphi_, "internal: ring chain not planned");
 	const long npair_all = (m.nring + 1)/2, a = ra_.a, b = ra_.b, ldY = pad8(b);
-	int T2 = tile_lines_for<StRingA2>(b, 0, 2*npair_all, 8, b); if (T2 < 2) T2 = 2; T2 -= T2 % 2;
+	const int T2 = pair_lines<StRingA2>(b, 2*npair_all);
 	const long qchunk = ring_chunk(npair_all, (long)sizeof(double2)*nc*a*ldY, T2/2);
 	ensure1(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
 	for (long q_lo = 0; q_lo < npair_all; q_lo += qchunk) {
 		const long npair = std::min(qchunk, npair_all - q_lo);
 		const int nring = m.nring - (int)(2*q_lo);           // rings from the first pair of this pass on (the odd-last-ring tests are local)
-		{	StRingA1 s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, a, 8); s.fb = mk(fc_, 0, 8);
+		{	StRingA1 s = new_stage<StRingA1>(a, 0);
 			s.m = map_addr(m); s.m.off0 += 2*q_lo*m.ring_stride; s.m.nring = nring;
 			s.b = (int)b; s.npair = (int)npair; s.Y = s1_.as<double2>(); s.ldY = ldY; s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, tile_lines_for<StRingA1>(a, 0, b, 16, 2*a), b, nphi_);
+			set_tiles(s, tile_lines_for<StRingA1>(a, 0, b, 16), b, nphi_);
 			launch_any(s, (long)nc*npair*s.ntile, st);
 		}
-		{	StRingA2 s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, b, 8); s.fb = mk(fc_, 0, 8);
-			const int T = T2;
-			set_tiles(s, T, a*T, 0);          // one tile per line: ntile = a
+		{	StRingA2 s = new_stage<StRingA2>(b, 0);
+			set_tiles(s, T2, a*T2, 0);          // one tile per line: ntile = a
 			s.Y = s1_.as<double2>(); s.ldY = ldY; s.a = (int)a; s.X = (int)nphi_; s.npair = (int)npair; s.nring = nring; s.mmax = mmax;
-			s.groups = (int)((npair + T/2 - 1)/(T/2)); s.da = make_fastdiv((uint32_t)a); s.dgr = make_fastdiv((uint32_t)s.groups);
+			s.groups = (int)((npair + T2/2 - 1)/(T2/2)); s.da = make_fastdiv((uint32_t)a); s.dgr = make_fastdiv((uint32_t)s.groups);
 			s.leg = leg + 2*q_lo; s.ldleg = ldleg; s.nm = mmax + 1; s.tab = tab; s.scale = scale;
 			launch_any(s, (long)nc*s.groups*a, st);
 		}
@@ -1027,23 +1037,20 @@ void FftChain::h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& 
 	if (dry_ ? line_h2map_takes(nphi_, mmax) : line_h2map(st, h, ldh, m, nc, mmax, hcomp)) return;      // (ring lengths compiled into ringline.hip: one kernel, no intermediate)
 	const long npair_all = (m.nring + 1)/2, a = rs_.a, b = rs_.b, ldY = pad8(b);
 	const long qchunk = ring_chunk(npair_all, (long)sizeof(double2)*nc*a*ldY, 1);
-	const int T1 = tile_lines_for<StRingS1>(a, 0, b, 8, 2*a), T2 = tile_lines_for<StRingS2>(b, 0, a, 16, b);
 	ensure1(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
 	for (long q_lo = 0; q_lo < npair_all; q_lo += qchunk) {
 		const long npair = std::min(qchunk, npair_all - q_lo);
 		const int nring = m.nring - (int)(2*q_lo);
-		{	StRingS1 s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, a, 8); s.fb = mk(fc_, 0, 8);
+		{	StRingS1 s = new_stage<StRingS1>(a, 0);
 			s.h = h + 2*q_lo*ldh; s.ldh = ldh; s.hcomp = hcomp > 0 ? hcomp : m.nring; s.b = (int)b; s.X = (int)nphi_; s.npair = (int)npair; s.nring = nring; s.mmax = mmax;
 			s.Y = s1_.as<double2>(); s.ldY = ldY; s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, T1, b, nphi_); s.bout = blocked_on();
+			set_tiles(s, tile_lines_for<StRingS1>(a, 0, b, 8), b, nphi_);
 			launch_any(s, (long)nc*npair*s.ntile, st);
 		}
-		{	StRingS2 s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, b, 8); s.fb = mk(fc_, 0, 8);
+		{	StRingS2 s = new_stage<StRingS2>(b, 0);
 			s.Y = s1_.as<double2>(); s.ldY = ldY; s.a = (int)a; s.npair = (int)npair; s.m = map_addr(m); s.m.off0 += 2*q_lo*m.ring_stride; s.m.nring = nring;
 			s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, T2, a, 0); s.bin = mk_blk(T1, b, T2);
+			set_tiles(s, tile_lines_for<StRingS2>(b, 0, a, 16), a, 0);
 			launch_any(s, (long)nc*npair*s.ntile, st);
 		}
 	}
@@ -1056,13 +1063,16 @@ static int theta_comp_chunk(int nc, size_t need1_per_comp, size_t need2_per_comp
 	const size_t per = sizeof(double2)*std::max(need1_per_comp, need2_per_comp);
 	return (int)std::max<size_t>(1, std::min<size_t>((size_t)nc, budget/std::max<size_t>(per, 1)));
 }
-void FftChain::theta_scratch(const ThetaPlan& tp, int nm, int nc, int kind, size_t& b1, size_t& b2) {
+// points per component that a theta chain keeps in s1_ (n1) and s2_ (n2): the largest of the intermediates its builders put there
+static void theta_need(const ThetaPlan& tp, int nm, int kind, size_t& n1, size_t& n2) {
 	const size_t npair = (size_t)(nm + 1)/2;
-	size_t n1, n2;
-	if (kind == 0)      { n1 = npair*std::max(tp.g*pad8(tp.bN), tp.g*pad8(tp.g2)); n2 = npair*std::max(tp.g2*pad8(tp.g), tp.ac*pad8(tp.g)); }   // to_cc
-	else if (kind == 1) { n1 = npair*tp.g*pad8(tp.bN); n2 = npair*tp.ac*pad8(tp.g); }                                                    // from_cc_adjoint
-	else if (kind == 2) { n1 = npair*tp.gs*pad8(tp.bs); n2 = npair*tp.aNs*pad8(tp.gs); }                                                  // from_cc
-	else                { n1 = npair*std::max(tp.g*pad8(tp.ac), tp.g*pad8(tp.g2)); n2 = npair*std::max(tp.g2*pad8(tp.g), tp.bN*pad8(tp.g)); }   // to_cc_adjoint
+	if (kind == 0)      { n1 = npair*std::max(tp.g*FftChain::pad8(tp.bN), tp.g*FftChain::pad8(tp.g2)); n2 = npair*std::max(tp.g2*FftChain::pad8(tp.g), tp.ac*FftChain::pad8(tp.g)); }   // to_cc
+	else if (kind == 1) { n1 = npair*tp.g*FftChain::pad8(tp.bN); n2 = npair*tp.ac*FftChain::pad8(tp.g); }                                                    // from_cc_adjoint
+	else if (kind == 2) { n1 = npair*tp.gs*FftChain::pad8(tp.bs); n2 = npair*tp.aNs*FftChain::pad8(tp.gs); }                                                  // from_cc
+	else                { n1 = npair*std::max(tp.g*FftChain::pad8(tp.ac), tp.g*FftChain::pad8(tp.g2)); n2 = npair*std::max(tp.g2*FftChain::pad8(tp.g), tp.bN*FftChain::pad8(tp.g)); }   // to_cc_adjoint
+}
+void FftChain::theta_scratch(const ThetaPlan& tp, int nm, int nc, int kind, size_t& b1, size_t& b2) {
+	size_t n1, n2; theta_need(tp, nm, kind, n1, n2);
 	const int cc = theta_comp_chunk(nc, n1, n2);
 	b1 = sizeof(double2)*n1*cc; b2 = sizeof(double2)*n2*cc;
 }
@@ -1071,69 +1081,36 @@ void FftChain::ring_scratch(long nring, int nc, bool analysis, size_t& b1, int m
 	const long npair = (nring + 1)/2, a = analysis ? ra_.a : rs_.a, b = analysis ? ra_.b : rs_.b;
 	b1 = sizeof(double2)*(size_t)nc*npair*a*pad8(b);       // (ring_chunk only shrinks it)
 }
-
-// All components of a call go through each stage in ONE launch (outer index = component * npair + pair; batched maps are
+// the loop of a theta chain (kind as in theta_scratch) over the component chunks that fit its scratch: stages(c0, ncl) runs the chain for
+// the ncl components from c0 on.
+// All components of a chunk go through each stage in ONE launch (outer index = component * npair + pair; batched maps are
 // components here): 64 maps of 5400 rings are 5 launches of ~150 000 workgroups instead of 320 of ~10 000 with their tails.
+template<class F> void FftChain::theta_chunks(const ThetaPlan& tp, int nm, int nc, int kind, F&& stages) {
+	size_t n1, n2; theta_need(tp, nm, kind, n1, n2);
+	const int cchunk = theta_comp_chunk(nc, n1, n2);
+	ensure1(sizeof(double2)*n1*cchunk); ensure2(sizeof(double2)*n2*cchunk);
+	for (int c0 = 0; c0 < nc; c0 += cchunk) stages(c0, (long)std::min(cchunk, nc - c0));
+	if (!dry_) PXS_HIP(hipGetLastError());
+}
+
 void FftChain::to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
                      int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* wcc)
 {
 	if (dry_ ? line_takes(tp, true) : line_analysis(st, tp, true, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, sigma, wcc, nullptr)) return;
-	const long npair = (nm + 1)/2;
-	const long g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
-	const long ldY1 = pad8(bN), ldZ2 = pad8(g), ldV3 = pad8(g2), ldU4 = pad8(g);
-	const size_t need1 = (size_t)npair*std::max(g*ldY1, g*ldV3), need2 = (size_t)npair*std::max(g2*ldZ2, ac*ldU4);
-	const int cchunk = theta_comp_chunk(nc, need1, need2);
-	const int T1 = tile_lines_for<StFirst>(g, 0, bN, 8), T2 = tile_lines_for<StResize>(bN, g2, g, 8), T3 = tile_lines_for<StSigma>(g, g, g2, 8), T4 = tile_lines_for<StResize>(g2, ac, g, 8);
-	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
-	for (int c0 = 0; c0 < nc; c0 += cchunk) {
-		const long ncl = std::min(cchunk, nc - c0);
-		{	StFirst s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, g); s.fb = mk(fc_, 0);
-			s.src.leg = leg + (size_t)c0*nm*ldleg; s.src.cstride = (long)nm*ldleg; s.src.ld = ldleg; s.src.nr = nr; s.src.N = (int)tp.N; s.src.mir_c = mir_c; s.src.a_odd = spin & 1; s.src.ncol = nm;
-			s.b = (int)bN; s.Y = s1_.as<double2>(); s.ldY = ldY1; s.npair = (int)npair; s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, T1, bN, tp.N); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StResize s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, bN); s.fb = mk(fc_, g2);
-			s.Y = s1_.as<double2>(); s.ldY = ldY1; s.Z = s2_.as<double2>(); s.ldZ = ldZ2; s.g = (int)g; s.X1 = (int)tp.N; s.X2 = (int)tp.M;
-			// M > N (the interpolant form; the fine-CC form on grids below ~2 lmax rings): zero padding, Nyquist bin of N split;
-			// M <= N (the fine-CC form on larger grids): low pass, |k| < M/2 kept
-			s.kmax = tp.M > tp.N ? -1 : (int)(tp.M/2 - 1); s.nyq = tp.M > tp.N ? 1 : 0;
-			s.ph = ph_shift; s.dg = make_fastdiv((uint32_t)g);
+	const long npair = (nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
+	const double2* ph = ph_shift;
 #ifdef PXS_LAB
-			{ static const int noph = [] { const char* e = getenv("PXS_CH_NOPH"); return e ? atoi(e) : 0; }(); if (noph) s.ph = nullptr; }     // timing experiments only (wrong results)
+	{ static const int noph = [] { const char* e = getenv("PXS_CH_NOPH"); return e ? atoi(e) : 0; }(); if (noph) ph = nullptr; }     // timing experiments only (wrong results)
 #endif
-			set_tiles(s, T2, g, tp.M); s.bin = mk_blk(T1, bN, T2); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StSigma s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, g); s.fb = mk(fc_, g);
-			s.Z = s2_.as<double2>(); s.ldZ = ldZ2; s.V = s1_.as<double2>(); s.ldV = ldV3; s.g = (int)g; s.g2 = (int)g2; s.sigma = sigma;
-			set_tiles(s, T3, g2, tp.M); s.bin = mk_blk(T2, g, T3); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StResize s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, g2); s.fb = mk(fc_, ac);
-			s.Y = s1_.as<double2>(); s.ldY = ldV3; s.Z = s2_.as<double2>(); s.ldZ = ldU4; s.g = (int)g; s.X1 = (int)tp.M; s.X2 = (int)tp.Ncc; s.kmax = lmax; s.nyq = 0;
-			s.ph = nullptr; s.dg = make_fastdiv((uint32_t)g);
-			set_tiles(s, T4, g, tp.Ncc); s.bin = mk_blk(T3, g2, T4); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StSplit<0> s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, g); s.fb = mk(fc_, 0);
-			int T = tile_lines_for<StSplit<0>>(g, 0, 2*ac, 8); if (T < 2) T = 2; T -= T % 2;
-			const int TH = T/2;
-			set_tiles(s, T, (long)((ac/2 + 1 + TH - 1)/TH)*T, 0);
-			s.TH = TH;
-			s.U = s2_.as<double2>(); s.ldU = ldU4; s.a = (int)ac; s.g = (int)g; s.X = (int)tp.Ncc; s.mir_c = 0; s.nr_out = ncc; s.a_odd = spin & 1; s.ncol = nm; s.npair = (int)npair;
-			s.out = leg_cc + (size_t)c0*nm*ldcc; s.ocstride = (long)nm*ldcc; s.dnp = make_fastdiv((uint32_t)npair); s.groups = 1; s.dgr = make_fastdiv(1);
-			s.ld = ldcc; s.w = wcc; s.tab = nullptr; s.scale = 1.0; s.da = make_fastdiv((uint32_t)ac);
-			s.bin = mk_blk(T4, g, T);
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-	}
-	if (!dry_) PXS_HIP(hipGetLastError());
+	theta_chunks(tp, nm, nc, 0, [&](int c0, long ncl) {
+		run_first<StFirst>(st, pair_src(leg + (size_t)c0*nm*ldleg, ldleg, nr, tp.N, mir_c, spin, nm, nullptr), ncl, npair, g, bN);      // RA1
+		// RA2.  M > N (the interpolant form; the fine-CC form on grids below ~2 lmax rings): zero padding, Nyquist bin of N split;
+		// M <= N (the fine-CC form on larger grids): low pass, |k| < M/2 kept
+		run_resize(st, ncl*npair, bN, g2, g, tp.M > tp.N ? -1 : (int)(tp.M/2 - 1), tp.M > tp.N ? 1 : 0, 0, ph);
+		run_sigma(st, ncl*npair, g, g2, sigma);      // RA3
+		run_resize(st, ncl*npair, g2, ac, g, lmax, 0, 0, nullptr);      // RA4: keep |k| <= lmax
+		run_split<0>(st, ncl, npair, nm, spin, ac, g, 0, ncc, leg_cc + (size_t)c0*nm*ldcc, ldcc, (long)nm*ldcc, wcc, nullptr, 1.0, 0);      // RA5
+	});
 }
 
 // exact transpose of from_cc (theta upsampling CC grid -> map rings): leg on the map's rings -> leg on the CC grid, for grids
@@ -1145,44 +1122,13 @@ void FftChain::from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double
                                int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* w, const double2* wring)
 {
 	if (dry_ ? line_takes(tp, false) : line_analysis(st, tp, false, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, nullptr, w, wring)) return;
-	const long npair = (nm + 1)/2;
-	const long g = tp.g, bN = tp.bN, ac = tp.ac;
-	const long ldY1 = pad8(bN), ldU = pad8(g);
-	const size_t need1 = (size_t)npair*g*ldY1, need2 = (size_t)npair*ac*ldU;
-	const int cchunk = theta_comp_chunk(nc, need1, need2);
-	const int T1 = tile_lines_for<StFirst>(g, 0, bN, 8), T2 = tile_lines_for<StResize>(bN, ac, g, 8);
-	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
-	for (int c0 = 0; c0 < nc; c0 += cchunk) {
-		const long ncl = std::min(cchunk, nc - c0);
-		{	StFirst s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, g); s.fb = mk(fc_, 0);
-			s.src.leg = leg + (size_t)c0*nm*ldleg; s.src.cstride = (long)nm*ldleg; s.src.ld = ldleg; s.src.nr = nr; s.src.N = (int)tp.N; s.src.mir_c = mir_c; s.src.a_odd = spin & 1; s.src.ncol = nm;
-			s.src.w = wring;      // (quadrature weights of the map's rings: the weights form of the analysis)
-			s.b = (int)bN; s.Y = s1_.as<double2>(); s.ldY = ldY1; s.npair = (int)npair; s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, T1, bN, tp.N); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StResize s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, bN); s.fb = mk(fc_, ac);
-			s.Y = s1_.as<double2>(); s.ldY = ldY1; s.Z = s2_.as<double2>(); s.ldZ = ldU; s.g = (int)g; s.X1 = (int)tp.N; s.X2 = (int)tp.Ncc; s.kmax = lmax; s.nyq = 0;
-			s.ph = ph_shift; s.dg = make_fastdiv((uint32_t)g);
-			set_tiles(s, T2, g, tp.Ncc); s.bin = mk_blk(T1, bN, T2); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StSplit<0> s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, g); s.fb = mk(fc_, 0);
-			int T = tile_lines_for<StSplit<0>>(g, 0, 2*ac, 8); if (T < 2) T = 2; T -= T % 2;
-			const int TH = T/2;
-			set_tiles(s, T, (long)((ac/2 + 1 + TH - 1)/TH)*T, 0);
-			s.TH = TH;
-			s.U = s2_.as<double2>(); s.ldU = ldU; s.a = (int)ac; s.g = (int)g; s.X = (int)tp.Ncc; s.mir_c = 0; s.nr_out = ncc; s.a_odd = spin & 1; s.ncol = nm; s.npair = (int)npair;
-			s.out = leg_cc + (size_t)c0*nm*ldcc; s.ocstride = (long)nm*ldcc; s.dnp = make_fastdiv((uint32_t)npair); s.groups = 1; s.dgr = make_fastdiv(1);
-			s.ld = ldcc; s.w = w; s.tab = nullptr; s.scale = 1.0; s.da = make_fastdiv((uint32_t)ac);
-			s.bin = mk_blk(T2, g, T);
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-	}
-	if (!dry_) PXS_HIP(hipGetLastError());
+	const long npair = (nm + 1)/2, g = tp.g, bN = tp.bN, ac = tp.ac;
+	theta_chunks(tp, nm, nc, 1, [&](int c0, long ncl) {
+		// (wring: quadrature weights of the map's rings: the weights form of the analysis)
+		run_first<StFirst>(st, pair_src(leg + (size_t)c0*nm*ldleg, ldleg, nr, tp.N, mir_c, spin, nm, wring), ncl, npair, g, bN);
+		run_resize(st, ncl*npair, bN, ac, g, lmax, 0, 0, ph_shift);
+		run_split<0>(st, ncl, npair, nm, spin, ac, g, 0, ncc, leg_cc + (size_t)c0*nm*ldcc, ldcc, (long)nm*ldcc, w, nullptr, 1.0, 0);
+	});
 }
 
 // exact adjoint of to_cc (adjoint_analysis_2d): leg on the CC grid -> ring spectra h[c][ring][m] on the map's rings.
@@ -1195,97 +1141,31 @@ void FftChain::from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double
 void FftChain::to_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
                              int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* whalf, const double2* tab, double scale)
 {
-	const long npair = (nm + 1)/2;
-	const long g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
-	const long ldY = pad8(ac), ldZ = pad8(g), ldV = pad8(g2);
-	const size_t need1 = (size_t)npair*std::max(g*ldY, g*ldV), need2 = (size_t)npair*std::max(g2*ldZ, bN*ldZ);
-	const int cchunk = theta_comp_chunk(nc, need1, need2);
-	const int T1 = tile_lines_for<StFirst>(g, 0, ac, 8), T2 = tile_lines_for<StResize>(ac, g2, g, 8), T3 = tile_lines_for<StSigma>(g, g, g2, 8), T4 = tile_lines_for<StResize>(g2, bN, g, 8);
-	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
-	for (int c0 = 0; c0 < nc; c0 += cchunk) {
-		const long ncl = std::min(cchunk, nc - c0);
-		{	StFirst s; memset(&s, 0, sizeof(s));      // weighted mirror-pair extension on the CC circle, pass 1 of FFT_Ncc
-			s.fa = mk(fc_, g); s.fb = mk(fc_, 0);
-			s.src.leg = leg_cc + (size_t)c0*nm*ldcc; s.src.cstride = (long)nm*ldcc; s.src.ld = ldcc; s.src.nr = ncc; s.src.N = (int)tp.Ncc; s.src.mir_c = 0; s.src.a_odd = spin & 1; s.src.ncol = nm;
-			s.src.w = whalf;
-			s.b = (int)ac; s.Y = s1_.as<double2>(); s.ldY = ldY; s.npair = (int)npair; s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, T1, ac, tp.Ncc); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StResize s; memset(&s, 0, sizeof(s));     // pass 2 of FFT_Ncc, |k| <= lmax embedded in the M spectrum, pass 1 of IFFT_M
-			s.fa = mk(fc_, ac); s.fb = mk(fc_, g2);
-			s.Y = s1_.as<double2>(); s.ldY = ldY; s.Z = s2_.as<double2>(); s.ldZ = ldZ; s.g = (int)g; s.X1 = (int)tp.Ncc; s.X2 = (int)tp.M; s.kmax = lmax; s.nyq = 0;
-			s.ph = nullptr; s.dg = make_fastdiv((uint32_t)g);
-			set_tiles(s, T2, g, tp.M); s.bin = mk_blk(T1, ac, T2); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StSigma s; memset(&s, 0, sizeof(s));      // pass 2 of IFFT_M, x |sin| series, pass 1 of FFT_M
-			s.fa = mk(fc_, g); s.fb = mk(fc_, g);
-			s.Z = s2_.as<double2>(); s.ldZ = ldZ; s.V = s1_.as<double2>(); s.ldV = ldV; s.g = (int)g; s.g2 = (int)g2; s.sigma = sigma;
-			set_tiles(s, T3, g2, tp.M); s.bin = mk_blk(T2, g, T3); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StResize s; memset(&s, 0, sizeof(s));     // pass 2 of FFT_M, transposed padding M -> N (conjugate phase, Nyquist bins combined), pass 1 of IFFT_N
-			s.fa = mk(fc_, g2); s.fb = mk(fc_, bN);
-			s.Y = s1_.as<double2>(); s.ldY = ldV; s.Z = s2_.as<double2>(); s.ldZ = ldZ; s.g = (int)g; s.X1 = (int)tp.M; s.X2 = (int)tp.N; s.kmax = tp.M > tp.N ? -1 : (int)(tp.M/2 - 1); s.nyq = 0; s.adj = 1;      // (M <= N: transpose of the low pass = zero padding of |k| < M/2)
-			s.ph = ph_shift; s.dg = make_fastdiv((uint32_t)g);
-			set_tiles(s, T4, g, tp.N); s.bin = mk_blk(T3, g2, T4);      // (plain rows out: the transposing split takes one line of many pairs)
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StSplit<1> s; memset(&s, 0, sizeof(s));   // pass 2 of IFFT_N, the two parities apart, rings of the map, ring-major
-			s.fa = mk(fc_, g); s.fb = mk(fc_, 0);
-			int T = tile_lines_for<StSplit<1>>(g, 0, 2*npair, 8); if (T < 2) T = 2; T -= T % 2;
-			set_tiles(s, T, bN*T, 0);         // one tile per line: ntile = bN
-			s.TH = 0;
-			s.U = s2_.as<double2>(); s.ldU = ldZ; s.a = (int)bN; s.g = (int)g; s.X = (int)tp.N; s.mir_c = mir_c; s.nr_out = nr; s.a_odd = spin & 1; s.ncol = nm; s.npair = (int)npair;
-			const long groups = (npair + T/2 - 1)/(T/2);
-			s.out = h + (size_t)c0*nr*ldh; s.ocstride = (long)nr*ldh; s.dnp = make_fastdiv((uint32_t)npair); s.groups = (int)groups; s.dgr = make_fastdiv((uint32_t)groups);
-			s.ld = ldh; s.w = nullptr; s.tab = tab; s.scale = scale; s.da = make_fastdiv((uint32_t)bN); s.self_half = 1;
-			launch_any(s, ncl*groups*bN, st);
-		}
-	}
-	if (!dry_) PXS_HIP(hipGetLastError());
+	const long npair = (nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
+	theta_chunks(tp, nm, nc, 3, [&](int c0, long ncl) {
+		// weighted mirror-pair extension on the CC circle, pass 1 of FFT_Ncc
+		run_first<StFirst>(st, pair_src(leg_cc + (size_t)c0*nm*ldcc, ldcc, ncc, tp.Ncc, 0, spin, nm, whalf), ncl, npair, g, ac);
+		// pass 2 of FFT_Ncc, |k| <= lmax embedded in the M spectrum, pass 1 of IFFT_M
+		run_resize(st, ncl*npair, ac, g2, g, lmax, 0, 0, nullptr);
+		// pass 2 of IFFT_M, x |sin| series, pass 1 of FFT_M
+		run_sigma(st, ncl*npair, g, g2, sigma);
+		// pass 2 of FFT_M, transposed padding M -> N (conjugate phase, Nyquist bins combined), pass 1 of IFFT_N
+		// (M <= N: transpose of the low pass = zero padding of |k| < M/2)
+		run_resize(st, ncl*npair, g2, bN, g, tp.M > tp.N ? -1 : (int)(tp.M/2 - 1), 0, 1, ph_shift);
+		// pass 2 of IFFT_N, the two parities apart, rings of the map, ring-major
+		run_split<1>(st, ncl, npair, nm, spin, bN, g, mir_c, nr, h + (size_t)c0*nr*ldh, ldh, (long)nr*ldh, nullptr, tab, scale, 1);
+	});
 }
 
 void FftChain::from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
                        int nc, int nm, int spin, int lmax, const double2* ph_up, const double2* tab, double scale, const double2* wring)
 {
-	const long npair = (nm + 1)/2;
-	const long gs = tp.gs, bs = tp.bs, aN = tp.aNs;
-	const long ldY = pad8(bs), ldZ = pad8(gs);
-	const size_t need1 = (size_t)npair*gs*ldY, need2 = (size_t)npair*aN*ldZ;
-	const int cchunk = theta_comp_chunk(nc, need1, need2);
-	const int T1 = tile_lines_for<StFirst>(gs, 0, bs, 8), T2 = tile_lines_for<StResize>(bs, aN, gs, 8);
-	ensure1(sizeof(double2)*need1*cchunk); ensure2(sizeof(double2)*need2*cchunk);
-	for (int c0 = 0; c0 < nc; c0 += cchunk) {
-		const long ncl = std::min(cchunk, nc - c0);
-		{	StFirst s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, gs); s.fb = mk(fc_, 0);
-			s.src.leg = leg_cc + (size_t)c0*nm*ldcc; s.src.cstride = (long)nm*ldcc; s.src.ld = ldcc; s.src.nr = ncc; s.src.N = (int)tp.Ncc; s.src.mir_c = 0; s.src.a_odd = spin & 1; s.src.ncol = nm;
-			s.b = (int)bs; s.Y = s1_.as<double2>(); s.ldY = ldY; s.npair = (int)npair; s.dnp = make_fastdiv((uint32_t)npair);
-			set_tiles(s, T1, bs, tp.Ncc); s.bout = blocked_on();
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StResize s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, bs); s.fb = mk(fc_, aN);
-			s.Y = s1_.as<double2>(); s.ldY = ldY; s.Z = s2_.as<double2>(); s.ldZ = ldZ; s.g = (int)gs; s.X1 = (int)tp.Ncc; s.X2 = (int)tp.N; s.kmax = lmax; s.nyq = 0;
-			s.ph = ph_up; s.dg = make_fastdiv((uint32_t)gs);
-			set_tiles(s, T2, gs, tp.N); s.bin = mk_blk(T1, bs, T2);      // (plain rows out, see to_cc_adjoint)
-			launch_any(s, ncl*npair*s.ntile, st);
-		}
-		{	StSplit<1> s; memset(&s, 0, sizeof(s));
-			s.fa = mk(fc_, gs); s.fb = mk(fc_, 0);
-			int T = tile_lines_for<StSplit<1>>(gs, 0, 2*npair, 8); if (T < 2) T = 2; T -= T % 2;
-			set_tiles(s, T, aN*T, 0);         // one tile per line: ntile = aN
-			s.TH = 0;
-			s.U = s2_.as<double2>(); s.ldU = ldZ; s.a = (int)aN; s.g = (int)gs; s.X = (int)tp.N; s.mir_c = mir_c; s.nr_out = nr; s.a_odd = spin & 1; s.ncol = nm; s.npair = (int)npair;
-			const long groups = (npair + T/2 - 1)/(T/2);
-			s.out = h + (size_t)c0*nr*ldh; s.ocstride = (long)nr*ldh; s.dnp = make_fastdiv((uint32_t)npair); s.groups = (int)groups; s.dgr = make_fastdiv((uint32_t)groups);
-			s.ld = ldh; s.w = wring; s.tab = tab; s.scale = scale; s.da = make_fastdiv((uint32_t)aN);
-			launch_any(s, ncl*groups*aN, st);
-		}
-	}
-	if (!dry_) PXS_HIP(hipGetLastError());
+	const long npair = (nm + 1)/2, gs = tp.gs, bs = tp.bs, aN = tp.aNs;
+	theta_chunks(tp, nm, nc, 2, [&](int c0, long ncl) {
+		run_first<StFirst>(st, pair_src(leg_cc + (size_t)c0*nm*ldcc, ldcc, ncc, tp.Ncc, 0, spin, nm, nullptr), ncl, npair, gs, bs);      // RS1
+		run_resize(st, ncl*npair, bs, aN, gs, lmax, 0, 0, ph_up);      // RS2
+		run_split<1>(st, ncl, npair, nm, spin, aN, gs, mir_c, nr, h + (size_t)c0*nr*ldh, ldh, (long)nr*ldh, wring, tab, scale, 0);      // RS3
+	});
 }
 
 // 2-D FFT of real maps [npre][ny][nx] -> complex [npre][ny][nx] (enmap.fft of a map, pixell/enmap.py:1307-1323), through the
@@ -1298,30 +1178,16 @@ bool FftChain::fft2_real(hipStream_t st, const void* in, int in_dtype, double2* 
 	// (plan_rings notes the width before it knows whether it can split it: a chain kept per stream must not take a width it refused
 	// in an earlier transform for a planned one)
 	if (nx < 4 || ny < 4 || !split_balanced(ny, sy) || ((nphi_ != nx || !rings_ok()) && !plan_rings(nx))) return false;
-	const long nm = nx/2 + 1, ldF = pad8(ny), a = std::min(sy.a, sy.b), b = ny/a, ldY = pad8(b);
+	const long nm = nx/2 + 1, ldF = pad8(ny), a = std::min(sy.a, sy.b), b = ny/a;
 	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] fft2_real %ld x %ld x %ld: rows %s, columns %ld x %ld\n", npre, ny, nx, describe().c_str(), a, b);
 	PXS_REQUIRE(npre*nm < (1L << 31)/std::max<long>(a, b), "fft2_real: too many lines");
 	// F (half spectrum, transposed) lives in s2_, the four-step intermediates of both axes in s1_
 	ensure2(sizeof(double2)*(size_t)npre*nm*ldF);
 	MapDesc m; m.ptr = in; m.dtype = in_dtype; m.cstride = ny*nx; m.ring_off0 = 0; m.ring_stride = nx; m.pix_stride = 1; m.nring = (int)ny; m.nphi = nx;
 	map2leg(st, m, (int)npre, (int)(nm - 1), s2_.as<double2>(), ldF, nullptr, 1.0);
-	ensure1(sizeof(double2)*(size_t)npre*nm*a*ldY);
-	{	StFirst2D s; memset(&s, 0, sizeof(s));
-		s.fa = mk(fc_, a); s.fb = mk(fc_, 0);
-		s.src.leg = s2_.as<double2>(); s.src.cstride = nm*ldF; s.src.ld = ldF; s.src.nr = (int)ny; s.src.N = (int)ny; s.src.ncol = (int)nm; s.src.plain = 1;
-		s.b = (int)b; s.Y = s1_.as<double2>(); s.ldY = ldY; s.npair = (int)nm; s.dnp = make_fastdiv((uint32_t)nm);
-		set_tiles(s, tile_lines_for<StFirst2D>(a, 0, b, 8), b, ny);
-		launch_any(s, npre*nm*s.ntile, st);
-	}
-	{	StColOut s; memset(&s, 0, sizeof(s));
-		s.fa = mk(fc_, b); s.fb = mk(fc_, 0);
-		int T = tile_lines_for<StColOut>(b, 0, nm, 8);
-		set_tiles(s, T, a*T, 0);          // one tile per line: ntile = a
-		s.Y = s1_.as<double2>(); s.ldY = ldY; s.a = (int)a; s.nm = (int)nm; s.ny = (int)ny; s.nx = (int)nx; s.conj_out = forward ? 0 : 1; s.out = out; s.scale = scale;
-		s.herm = 1; s.ldo = nx; s.ocomp = ny*nx;
-		s.groups = (int)((nm + T - 1)/T); s.dgr = make_fastdiv((uint32_t)s.groups);
-		launch_any(s, npre*s.groups*a, st);
-	}
+	ensure1(sizeof(double2)*(size_t)npre*nm*a*pad8(b));
+	run_first<StFirst2D>(st, plain_src(s2_.as<double2>(), nm, ldF, ny, 0), npre, nm, a, b);
+	run_colout(st, npre, nm, a, b, out, nx, ny*nx, forward ? 0 : 1, scale, ny, nx);
 	if (!dry_) PXS_HIP(hipGetLastError());
 	return true;
 }
@@ -1337,27 +1203,11 @@ bool FftChain::fft2_c2c(hipStream_t st, const double2* in, double2* out, long np
 	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] fft2_c2c %ld x %ld x %ld: rows %ld x %ld, columns %ld x %ld\n", npre, ny, nx, ax, bx, ay, by);
 	ensure1(sizeof(double2)*(size_t)npre*std::max(ny*ax*pad8(bx), nx*ay*pad8(by)));
 	ensure2(sizeof(double2)*(size_t)npre*nx*ldF);
-	auto first = [&](const double2* src, long nlines, long ld, long n, long a, long b, int conj) {
-		StFirst2D s; memset(&s, 0, sizeof(s));
-		s.fa = mk(fc_, a); s.fb = mk(fc_, 0);
-		s.src.leg = src; s.src.cstride = nlines*ld; s.src.ld = ld; s.src.nr = (int)n; s.src.N = (int)n; s.src.ncol = (int)nlines; s.src.plain = 1; s.src.conj = conj;
-		s.b = (int)b; s.Y = s1_.as<double2>(); s.ldY = pad8(b); s.npair = (int)nlines; s.dnp = make_fastdiv((uint32_t)nlines);
-		set_tiles(s, tile_lines_for<StFirst2D>(a, 0, b, 8), b, n);
-		launch_any(s, npre*nlines*s.ntile, st);
-	};
-	auto second = [&](double2* dst, long nlines, long ldo, long ocomp, long a, long b, int conj, double sc) {
-		StColOut s; memset(&s, 0, sizeof(s));
-		s.fa = mk(fc_, b); s.fb = mk(fc_, 0);
-		int T = tile_lines_for<StColOut>(b, 0, nlines, 8);
-		set_tiles(s, T, a*T, 0);
-		s.Y = s1_.as<double2>(); s.ldY = pad8(b); s.a = (int)a; s.nm = (int)nlines; s.ny = 0; s.nx = 0; s.conj_out = conj; s.herm = 0; s.out = dst; s.ldo = ldo; s.ocomp = ocomp; s.scale = sc;
-		s.groups = (int)((nlines + T - 1)/T); s.dgr = make_fastdiv((uint32_t)s.groups);
-		launch_any(s, npre*s.groups*a, st);
-	};
-	first(in, ny, nx, nx, ax, bx, forward ? 0 : 1);                           // rows y: lines of nx points
-	second(s2_.as<double2>(), ny, ldF, nx*ldF, ax, bx, 0, 1.0);               // -> F[kx][y]
-	first(s2_.as<double2>(), nx, ldF, ny, ay, by, 0);                         // columns kx: contiguous lines of ny points
-	second(out, nx, nx, ny*nx, ay, by, forward ? 0 : 1, scale);               // -> out[ky][kx]
+	const int conj = forward ? 0 : 1;
+	run_first<StFirst2D>(st, plain_src(in, ny, nx, nx, conj), npre, ny, ax, bx);                  // rows y: lines of nx points
+	run_colout(st, npre, ny, ax, bx, s2_.as<double2>(), ldF, nx*ldF, 0, 1.0);                      // -> F[kx][y]
+	run_first<StFirst2D>(st, plain_src(s2_.as<double2>(), nx, ldF, ny, 0), npre, nx, ay, by);     // columns kx: contiguous lines of ny points
+	run_colout(st, npre, nx, ay, by, out, nx, ny*nx, conj, scale);                                 // -> out[ky][kx]
 	if (!dry_) PXS_HIP(hipGetLastError());
 	return true;
 }

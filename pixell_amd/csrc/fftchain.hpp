@@ -13,6 +13,7 @@
 namespace pxs {
 
 struct Lds2;
+struct PairSrc;
 
 // factorisation N = a*b of a four-step transform: pass 1 = a-point transforms over the residues mod b,
 // pass 2 = b-point transforms producing the residues mod a
@@ -92,8 +93,18 @@ private:
 	std::set<int> checked_;
 	const double2* small_tw(long X, int n, int T);
 	template<class S> void set_tiles(S& s, int T, long nlines, long X);
-	template<class S> int tile_lines_for(long n_a, long n_b, long nlines, int mult, long tab_pts = -1);
+	template<class S> int tile_lines_for(long n_a, long n_b, long nlines, int mult);
+	template<class S> int pair_lines(long n, long nlines);
 	template<class S> void launch_any(S& s, long nblk, hipStream_t st);
+	// one builder per stage kind (fftchain.hip): each plans, fills in and launches its stage; theta_chunks: the chunk loop of a theta chain
+	template<class S> S new_stage(long na, long nb);
+	template<class S> void run_first(hipStream_t st, const PairSrc& src, long ncomp, long npair, long a, long b);
+	void run_resize(hipStream_t st, long nouter, long fa, long fb, long g, int kmax, int nyq, int adj, const double2* ph);
+	void run_sigma(hipStream_t st, long nouter, long g, long g2, const double2* sigma);
+	template<int MODE> void run_split(hipStream_t st, long ncomp, long npair, int nm, int spin, long a, long g, int mir_c, int nr_out,
+	                                  double2* out, long ld, long ocstride, const double2* w, const double2* tab, double scale, int self_half);
+	void run_colout(hipStream_t st, long npre, long nlines, long a, long b, double2* out, long ldo, long ocomp, int conj, double scale, long herm_ny = 0, long herm_nx = 0);
+	template<class F> void theta_chunks(const ThetaPlan& tp, int nm, int nc, int kind, F&& stages);
 	std::mutex mu_;
 	std::map<std::tuple<long, int, int>, DevBuf> stw_;
 	FftContext* fc_;

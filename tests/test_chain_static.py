@@ -12,7 +12,8 @@ The oracle's values are fixtures (tests/golden/chain_static/: 8192 sampled pixel
 analysis_2d of a white-noise map, per grid and spin; the oracle itself takes minutes at these sizes).
 
 The tests print each measured figure before they assert it.  Measured so far: in the host simulator (1 and 64 lanes per workgroup) the two
-paths agree bit for bit, 0.0 in every case; no figure from an MI355X yet."""
+paths agree bit for bit, 0.0 in every case; on an MI355X alm2map 0.0 in every case, map2alm 4e-17 ... 2.3e-15, against the oracle 1.2e-14 ... 1.4e-13,
+the adjoint pairs 0 ... 1.9e-18."""
 import os, numpy as np, pytest
 from pixell_amd import sht, _lib
 from oracle import sht_oracle as so
@@ -137,6 +138,69 @@ def test_off_table_grid_against_the_oracle_gpu():
 	ref = np.zeros((1, nt, nph)); so.synthesis_2d(alm=alm, map=ref, **kw)
 	out = np.zeros((1, nt, nph)); sht.synthesis_2d(alm=alm, map=out, **kw)
 	assert np.abs(out - ref).max() < ORACLE_TOL*np.abs(ref).max()
+
+# ---- 4b. all four theta chains: every transform against its adjoint ------------------------------------------------------------------
+# run_paths exercises to_cc and from_cc only.  With PXS_THETA_LINE=0 analysis_2d goes through to_cc and adjoint_analysis_2d through
+# to_cc_adjoint on both grids.  Synthesis takes the CC grid only where the map has clearly more rings than it (the thresholds of
+# setup_resampling in sht.hip): on 1024 x 2048 with lmax 511 (513 CC rings) synthesis_2d goes through from_cc and adjoint_synthesis_2d
+# through from_cc_adjoint; on 900 x 1800 with lmax 750 (757 CC rings) both run on the map's rings and only the ring stages are chain
+# stages.  The 900 x 1800 plan has partial tiles in every stage kind it launches and an odd last column (see the list at the top).
+# The route is asserted from the plan's own stage list: StSplit<0> (stage 3) ends to_cc / from_cc_adjoint, StSplit<1> (stage 4) ends
+# from_cc / to_cc_adjoint.
+# Tolerance: 1e-11 of the product of the norms, the bound and the normalisation of the adjoint inner-product test check_adjointness
+# (tests/test_baseline_configs.py: test_adjointness_*; tests/test_sht_parity.py pins the same transforms to the oracle with the same TOL = 1e-11).
+ADJ_TOL = 1e-11
+ADJ_GRIDS = [((900, 1800, 750), False), ((1024, 2048, 511), True)]      # (grid, synthesis through the CC grid)
+
+def alm_dot(a, b, lmax):
+	"""real inner product of two alm sets, m = 0 (the first lmax + 1 coefficients) once, m > 0 twice"""
+	w = np.full(a.shape[-1], 2.0); w[:lmax + 1] = 1.0
+	return float(np.sum((a.real*b.real + a.imag*b.imag)*w))
+
+def planned_stage_ids(plan, monkeypatch, capfd):
+	"""stage ids of the chain stages of the plan's analysis and synthesis, from the list the plan prints with PXS_CHAIN_VERBOSE=1"""
+	monkeypatch.setenv("PXS_CHAIN_VERBOSE", "1"); capfd.readouterr()
+	plan.query("chain_stages")
+	monkeypatch.delenv("PXS_CHAIN_VERBOSE")
+	return {int(l.split("plan stage ")[1].split(":")[0]) for l in capfd.readouterr().err.splitlines() if "plan stage " in l}
+
+def check_adjoint_pairs(monkeypatch, capfd, grid, via_cc, mmax, spin, static):
+	nt, nph, lmax = grid
+	nc = 1 if spin == 0 else 2
+	monkeypatch.setenv("PXS_THETA_LINE", "0"); monkeypatch.setenv("PXS_CHAIN_STATIC", static)
+	ms = sht.tri_mstart(lmax, mmax); nalm = int(ms[-1]) + lmax + 1
+	sids = planned_stage_ids(sht.grid_plan("F1", nt, nph, 0.3, (False, False), lmax, mmax, ms, 1), monkeypatch, capfd)
+	assert 3 in sids and (4 in sids) == via_cc, sids      # to_cc as the stage chain; from_cc where the synthesis goes through the CC grid
+	kw = dict(spin=spin, lmax=lmax, mmax=mmax, geometry="F1", phi0=0.3, mstart=ms)
+	rng = np.random.default_rng(21 + spin)
+	x = rng.standard_normal((nc, nt, nph))      # (not band-limited)
+	a = rng.standard_normal((nc, nalm)) + 1j*rng.standard_normal((nc, nalm)); a[:, :lmax + 1] = a[:, :lmax + 1].real
+	l_of = np.concatenate([np.arange(m, lmax + 1) for m in range(mmax + 1)]); a[:, l_of < spin] = 0
+	nrm = lambda t: float(np.sqrt(np.sum(t*t))); an = np.sqrt(alm_dot(a, a, lmax)); xn = nrm(x)
+	ax = np.zeros_like(a); sht.analysis_2d(alm=ax, map=x, **kw)
+	aa = np.zeros_like(x); sht.adjoint_analysis_2d(alm=a, map=aa, **kw)
+	lhs, rhs = alm_dot(ax, a, lmax), float(np.sum(x*aa)); n1 = max(np.sqrt(alm_dot(ax, ax, lmax))*an, xn*nrm(aa)); e1 = abs(lhs - rhs)/n1
+	sa = np.zeros_like(x); sht.synthesis_2d(alm=a, map=sa, **kw)
+	sx = np.zeros_like(a); sht.adjoint_synthesis_2d(alm=sx, map=x, **kw)
+	lhs2, rhs2 = float(np.sum(sa*x)), alm_dot(a, sx, lmax); n2 = max(nrm(sa)*xn, an*np.sqrt(alm_dot(sx, sx, lmax))); e2 = abs(lhs2 - rhs2)/n2
+	print("chain adjoint pairs %dx%d lmax %d mmax %d spin %d static %s: analysis %.3e synthesis %.3e" % (nt, nph, lmax, mmax, spin, static, e1, e2))
+	assert abs(lhs) > 1e-7*n1 and abs(lhs2) > 1e-7*n2, "degenerate inner products"
+	assert e1 < ADJ_TOL and e2 < ADJ_TOL, (e1, e2)
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("static", ["1", "0"])
+@pytest.mark.parametrize("spin", [0, 2])
+@pytest.mark.parametrize("grid,via_cc", ADJ_GRIDS)
+def test_theta_chains_against_their_adjoints_gpu(monkeypatch, capfd, grid, via_cc, spin, static):
+	check_adjoint_pairs(monkeypatch, capfd, grid, via_cc, grid[2], spin, static)
+
+@pytest.mark.hostsim
+@pytest.mark.parametrize("static", ["1", "0"])
+@pytest.mark.parametrize("spin", [0, 2])
+@pytest.mark.parametrize("grid,via_cc", ADJ_GRIDS)
+def test_theta_chains_against_their_adjoints_hostsim(monkeypatch, capfd, grid, via_cc, spin, static):
+	"""the same grids with 4 columns, as test_static_against_run_time_hostsim"""
+	check_adjoint_pairs(monkeypatch, capfd, grid, via_cc, 3, spin, static)
 
 # ---- 5. enmap.fft / ifft ---------------------------------------------------------------------------------------------------------
 def fft_round_trip(monkeypatch):
