@@ -78,7 +78,6 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 		// phase C: fast loop, two steps per iteration (lam1/lam2 swap roles, no register moves),
 		// coefficients of the next iteration prefetched with scalar loads (tables are padded by 2 rows)
 		double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1), a0 = LDC(at, k), a1 = LDC(at, k+1);
-#ifndef PXS_NO_PHASEC_UNROLL
 		// two pairs per iteration on alternating row sets: the prefetched rows are consumed where they landed (the single-pair loop
 		// rotated them with 8-16 s_mov_b64 per pair; SALU was 27-45 % of the VALU count, profiles/r04_leg_sq_counters_c3.txt)
 		while (k + 3 < nk) {
@@ -89,7 +88,6 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 			S0_SYN_PAIR(n0, n1, m0, m1)
 			k += 2;
 		}
-#endif
 		for (; k + 1 < nk; k += 2) {
 			const double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3), m0 = LDC(at, k+2), m1 = LDC(at, k+3);
 			S0_SYN_PAIR(c0, c1, a0, a1)
@@ -203,7 +201,6 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 	}
 	// phase C: every lane at scale 0 (or without data): next coefficients prefetched with scalar loads
 	double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1);
-#ifndef PXS_NO_PHASEC_UNROLL
 	while (k + 3 < nk) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
 		double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3);
 		S0_ANA_PAIR(c0, c1)
@@ -212,7 +209,6 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 		S0_ANA_PAIR(n0, n1)
 		k += 2;
 	}
-#endif
 	for (; k + 1 < nk; k += 2) {
 		const double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3);
 		S0_ANA_PAIR(c0, c1)
@@ -247,26 +243,47 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 //  * The ring data reach the B registers through the LDS: the 512 threads read the rows leg[map][m][ring] of 4 maps coalesced (one
 //    ring pair per thread), park (sum, difference x cos) as 16 doubles per pair (17-double entries: lane (j, kk) of MFMA q then reads
 //    entry 64 w + 16 kk + q, double j, conflict-free), and every lane picks its 16 operands.  (First form: per-lane gathers straight
-//    from global memory -- 16 % of the kernel's wave time, tools/mm_time.sh.)
+//    from global memory -- 16 % of the kernel's wave time.)
 //  * Step coefficients come from a compact table (a, b) resp. (a, a + b) per step (LegTables::coef2), the 16 steps of the NEXT tile
 //    requested with four s_load_dwordx16 before the MFMAs of the current one (first form: the 32-byte rows of the VALU kernels,
 //    requested and awaited group by group -- four scalar-load round trips per tile, 38 % of the wave time).
-// lab build (-DPXS_LAB_MMTIME): shader-clock time of the phases of leg_ana_s0_mm, summed over the waves (tools/mm_time.sh)
-#if defined(PXS_LAB_MMTIME) && !defined(PXS_HOST_SIM)
-__device__ unsigned long long mm_prof[16];
-#define MM_T0 long long tprev_ = clock64(); unsigned long long tacc_[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define MM_TICK(i) { const long long tn_ = clock64(); tacc_[i] += (unsigned long long)(tn_ - tprev_); tprev_ = tn_; }
-#define MM_TDUMP if (lane == 0) { for (int i_ = 0; i_ < 14; i_++) atomicAdd(&mm_prof[i_], tacc_[i_]); atomicAdd(&mm_prof[15], 1ull); }
-#else
-#define MM_T0
-#define MM_TICK(i)
-#define MM_TDUMP
-#endif
+// one Ishioka recurrence in extended-exponent form (the chain of the MFMA kernels, cf. SpinChain): p_{k+1} = (a x^2 + b) p_k + p_{k-1}, lam2 the current value
+struct S0Chain {
+	double csq, lam1, lam2; int sc;
+	__device__ __forceinline__ double step(double ca, double cb) { const double p = lam2, nx = fma(mm_coef(ca, csq, cb), lam2, lam1); lam1 = p; lam2 = nx; return p; }
+	__device__ __forceinline__ void rescale() { if (fabs(lam2) > SC_BIG) { lam1 *= SC_SMALL; lam2 *= SC_SMALL; sc++; } }
+	__device__ __forceinline__ void park_sign(int, double*) const {}
+};
+// start value of ring pair p at m; returns whether the pair carries signal at this m
+__device__ __forceinline__ bool s0_chain_init(const LegK& a, int p, int m, bool polar, S0Chain& C) {
+	const bool valid = p < a.npairs;
+	const double x = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0;
+	C.csq = polar ? -sth*sth : x*x;
+	const bool alive = valid && ((double)m <= a.lmax*sth + a.ofs);
+	C.lam1 = 0; C.lam2 = 0; C.sc = 0;
+	if (alive) { double mt; int e; pow_scaled(sth, m, mt, e); to_scaled(mt, e, C.lam2, C.sc); }
+	return alive;
+}
+// phase A (S0_PHASE_A for one chain): recurrence only until the first lane of the wave is at scale 0; returns the step reached
+__device__ __forceinline__ int s0_chain_phase_a(S0Chain& C, const double4_t* __restrict__ coef, bool polar, int nk) {
+	int k = 0;
+	while (k + 4 <= nk) {
+		if (__any(C.sc == 0 && C.lam2 != 0.0)) break;
+		const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3);
+		const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b;
+		C.lam1 = fma(fma(q0.a, C.csq, b0), C.lam2, C.lam1);
+		C.lam2 = fma(fma(q1.a, C.csq, b1), C.lam1, C.lam2);
+		C.lam1 = fma(fma(q2.a, C.csq, b2), C.lam2, C.lam1);
+		C.lam2 = fma(fma(q3.a, C.csq, b3), C.lam1, C.lam2);
+		if (C.sc < 0) C.rescale();
+		k += 4;
+	}
+	return k;
+}
+
 template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm(const LegK a)
 {
 	PXS_SHARED(double, sh);
-	constexpr int K = 1;
-	MM_T0
 	double* __restrict__ ptile = sh;                              // [W][16][MM_PSTRIDE]
 	double* __restrict__ red = sh + W*16*MM_PSTRIDE;              // [2][4 NG][64]: the accumulators of a tile summed over the waves
 	int* __restrict__ s_kmin = reinterpret_cast<int*>(sh + mm_lds_doubles(NG, W));
@@ -275,34 +292,19 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 	if (!leg_block(a, wv, m, bb)) return;
 	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
 	const int nk = (a.lmax - m)/2 + 1;
-	const double4_t* __restrict__ coef = a.coef + row0;
 	const int pbase = wv*64*W;
-	const bool polar = [&] { const double c = a.cth[min(pbase + 64*(w + 1), a.npairs) - 1]; return c*c > PXS_POLAR_COS2; }();      // (per wave: its own 64 pairs, its own coefficient stream)
-	double csq[K], lam1[K], lam2[K]; int sc[K];
-	bool alive;
-	{
-		const int p = pbase + tid;      // pair of this recurrence lane: wave w owns the pairs [64 w, 64 w + 64) of the chunk
-		const bool valid = p < a.npairs;
-		const double x = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0;
-		csq[0] = polar ? -sth*sth : x*x;
-		alive = valid && ((double)m <= a.lmax*sth + a.ofs);
-		lam1[0] = 0; lam2[0] = 0; sc[0] = 0;
-		if (alive) { double mt; int e; pow_scaled(sth, m, mt, e); to_scaled(mt, e, lam2[0], sc[0]); }
-	}
+	const bool polar = mm_wave_polar(a, pbase + 64*(w + 1));      // (per wave: its own 64 pairs, its own coefficient stream)
+	S0Chain C;
+	const bool alive = s0_chain_init(a, pbase + tid, m, polar, C);      // wave w owns the pairs [64 w, 64 w + 64) of the chunk
 	if (tid == 0) *s_kmin = nk;
 	__syncthreads();
-	MM_TICK(0)
 	// phase A, per wave: recurrence only until the first lane of the wave is at scale 0; kw = the first step this wave contributes to
-	int k = 0;
 	const bool wave_alive = __any(alive);
-	if (wave_alive) { S0_PHASE_A }
-	const int kw = wave_alive ? PXS_UNIFORM_INT(k) : nk + 16;
-	MM_TICK(1)
+	const int kw = wave_alive ? PXS_UNIFORM_INT(s0_chain_phase_a(C, a.coef + row0, polar, nk)) : nk + 16;
 	if (lane == 0) atomicMin(s_kmin, kw);
 	__syncthreads();
 	const int kmin = PXS_UNIFORM_INT(*s_kmin);
-	MM_TICK(2)
-	if (kmin >= nk) { MM_TDUMP return; }      // (workgroup-uniform) no ring of this chunk carries signal at this m
+	if (kmin >= nk) return;      // (workgroup-uniform) no ring of this chunk carries signal at this m
 	// B operands through the LDS: thread = ring pair, 4 maps per round
 	double breg[NG][16];
 	{
@@ -310,7 +312,6 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 		const bool ok = p < a.npairs;
 		const int rn = ok ? a.ring_n[p] : -1, rs = ok ? a.ring_s[p] : -1;
 		const double x = ok ? a.cth[p] : 0.0;
-		MM_TICK(8)
 		double* __restrict__ ent = sh + tid*MM_ESTRIDE;
 		const double* __restrict__ rd = sh + (64*w + 16*(lane >> 4))*MM_ESTRIDE + (lane & 15);
 #pragma unroll
@@ -323,7 +324,6 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 				const bool okm = map < a.nmaps;
 				vn[mm] = (okm && rn >= 0) ? in[rn] : make_double2(0, 0); vs[mm] = (okm && rs >= 0) ? in[rs] : make_double2(0, 0);
 			}
-			MM_TICK(9)
 			if (g > 0) __syncthreads();      // the reads of the previous round
 #pragma unroll
 			for (int mm = 0; mm < 4; mm++) {
@@ -331,87 +331,35 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 				ent[4*mm + 2] = (vn[mm].x - vs[mm].x)*x; ent[4*mm + 3] = (vn[mm].y - vs[mm].y)*x;
 			}
 			__syncthreads();
-			MM_TICK(10)
 #pragma unroll
 			for (int q = 0; q < 16; q++) breg[g][q] = rd[q*MM_ESTRIDE];
 			MM_WAVE_SYNC();
-			MM_TICK(11)
 		}
 		__syncthreads();
 		for (int i = tid; i < 2*NG*4*64; i += 64*W) red[i] = 0.0;
 		__syncthreads();
 	}
-	MM_TICK(3)
 	const double* __restrict__ tab = reinterpret_cast<const double*>(polar ? a.coef2p : a.coef2) + 2*row0;      // (a, b') of step k at tab[2 k]
-	bool pend = __any(sc[0] < 0);
+	bool pend = __any(C.sc < 0);
 	double* __restrict__ pmine = ptile + w*16*MM_PSTRIDE;
 	const double* __restrict__ pread = pmine + (lane & 15)*MM_PSTRIDE + 16*(lane >> 4);
 	double cf[32]; int cf_tile = -1;      // coefficients of the 16 steps of tile cf_tile, requested a tile ahead
 	long ntile = 0;
-	// flush of tile tf (after the barrier that ends it): register r of group g holds rows 4 r + lane / 16 of the tile, column lane % 16 =
-	// 4 (map in the group) + side.  It is issued behind the MFMAs of the NEXT tile (the two reduction tiles alternate), off the path
-	// from the barrier to that tile's recurrence.
-	auto mm_flush = [&](int tf) {
-		double* __restrict__ redf = red + (tf & 1)*NG*4*64;
-		for (int c = w; c < 4*NG; c += W) {
-			const int g = c >> 2, r = c & 3;
-			double* rp = redf + c*64 + lane;
-			const double v = *rp; *rp = 0.0;
-			const int krow = 16*tf + 4*r + (lane >> 4), map = (bb*NG + g)*4 + ((lane & 15) >> 2);
-			if (krow < nk && map < a.nmaps) {
-				double* dst = a.mom + (long)map*a.mom_bs + 4*(row0 + krow) + (lane & 3);
-#ifdef PXS_HOST_SIM
-				atomicAdd(dst, v);
-#elif defined(PXS_LAB_NOATOM)
-				if (v == 12345.678) *dst = v;      // timing experiment (wrong results)
-#else
-				unsafeAtomicAdd(dst, v);
-#endif
-			}
-		}
-	};
+	auto flush = [&](int tf) { mm_flush<NG, W, false>(a, red, tf, w, lane, bb, nk, row0, 0); };
 	int tlast = -1;
 	for (int t = kmin >> 4; 16*t < nk; t++) {
 		const int k0 = 16*t;
 		double* __restrict__ redt = red + (t & 1)*NG*4*64;
 		if (k0 + 16 > kw) {      // (wave-uniform) this wave has steps in the tile
 			ntile++;
-			if (cf_tile != t) {
-#pragma unroll
-				for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*k0 + i);
-			}
-#pragma unroll
-			for (int q4 = 0; q4 < 4; q4++) {
-				const int kq = k0 + 4*q4;
-				double p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-				if (kq >= kw && kq < nk) {
-					p0 = lam2[0]; lam1[0] = fma(mm_coef(cf[8*q4 + 0], csq[0], cf[8*q4 + 1]), lam2[0], lam1[0]);
-					p1 = lam1[0]; lam2[0] = fma(mm_coef(cf[8*q4 + 2], csq[0], cf[8*q4 + 3]), lam1[0], lam2[0]);
-					p2 = lam2[0]; lam1[0] = fma(mm_coef(cf[8*q4 + 4], csq[0], cf[8*q4 + 5]), lam2[0], lam1[0]);
-					p3 = lam1[0]; lam2[0] = fma(mm_coef(cf[8*q4 + 6], csq[0], cf[8*q4 + 7]), lam1[0], lam2[0]);
-					if (pend) {      // phase B: lanes below scale 0 contribute nothing yet; rescale them every 4 steps
-						if (sc[0] < 0) { p0 = p1 = p2 = p3 = 0.0; if (fabs(lam2[0]) > SC_BIG) { lam1[0] *= SC_SMALL; lam2[0] *= SC_SMALL; sc[0]++; } }
-						pend = __any(sc[0] < 0);
-					}
-					// rows beyond the last step of this m stay out of the sums (their table rows belong to the next m)
-					if (kq + 1 >= nk) p1 = 0.0;
-					if (kq + 2 >= nk) p2 = 0.0;
-					if (kq + 3 >= nk) p3 = 0.0;
-				}
-				pmine[(4*q4 + 0)*MM_PSTRIDE + lane] = p0; pmine[(4*q4 + 1)*MM_PSTRIDE + lane] = p1;
-				pmine[(4*q4 + 2)*MM_PSTRIDE + lane] = p2; pmine[(4*q4 + 3)*MM_PSTRIDE + lane] = p3;
-			}
+			if (cf_tile != t) mm_load_cf(cf, tab, k0);
+			mm_park_tile<MM_PSTRIDE>(C, cf, k0, kw, nk, pend, pmine, lane);
 			MM_WAVE_SYNC();
-			MM_TICK(4)
 			double av[4];
 #pragma unroll
 			for (int q = 0; q < 4; q++) av[q] = pread[q];
 			MM_WAVE_SYNC();
-			if (k0 + 16 < nk) {      // the rows of the next tile, on their way during the MFMAs (requested after the first A operands have landed)
-#pragma unroll
-				for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*(k0 + 16) + i);
-				cf_tile = t + 1;
-			}
+			if (k0 + 16 < nk) { mm_load_cf(cf, tab, k0 + 16); cf_tile = t + 1; }      // the rows of the next tile, on their way during the MFMAs (requested after the first A operands have landed)
 			mm_acc acc[NG];
 #pragma unroll
 			for (int g = 0; g < NG; g++) { acc[g][0] = 0; acc[g][1] = 0; acc[g][2] = 0; acc[g][3] = 0; }
@@ -421,20 +369,17 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 #pragma unroll
 				for (int g = 0; g < NG; g++) acc[g] = mm_mfma(aq, breg[g][q], acc[g]);
 			}
-			if (tlast >= 0) { mm_flush(tlast); tlast = -1; }
+			if (tlast >= 0) { flush(tlast); tlast = -1; }
 #pragma unroll
 			for (int g = 0; g < NG; g++)
 #pragma unroll
 				for (int r = 0; r < 4; r++) mm_lds_add(redt + (g*4 + r)*64 + lane, acc[g][r]);
-			MM_TICK(5)
 		}
-		if (tlast >= 0) mm_flush(tlast);
+		if (tlast >= 0) flush(tlast);
 		tlast = t;
 		__syncthreads();
-		MM_TICK(6)
 	}
-	if (tlast >= 0) mm_flush(tlast);
-	MM_TDUMP
+	if (tlast >= 0) flush(tlast);
 	PXS_COUNT(1, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
 }
 
@@ -452,26 +397,15 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const LegK a)
 {
 	PXS_SHARED(double, pmine);      // [16][MMS_PSTRIDE]
-	constexpr int K = 1;
 	const int lane = threadIdx.x;
 	int wv, m, bb;
 	if (!leg_block(a, wv, m, bb)) return;
 	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
 	const int nk = (a.lmax - m)/2 + 1;
-	const double4_t* __restrict__ coef = a.coef + row0;
 	const int pbase = wv*64;
-	const bool polar = [&] { const double c = a.cth[min(pbase + 64, a.npairs) - 1]; return c*c > PXS_POLAR_COS2; }();
-	double csq[K], lam1[K], lam2[K]; int sc[K];
-	bool alive;
-	{
-		const int p = pbase + lane;
-		const bool valid = p < a.npairs;
-		const double x = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0;
-		csq[0] = polar ? -sth*sth : x*x;
-		alive = valid && ((double)m <= a.lmax*sth + a.ofs);
-		lam1[0] = 0; lam2[0] = 0; sc[0] = 0;
-		if (alive) { double mt; int e; pow_scaled(sth, m, mt, e); to_scaled(mt, e, lam2[0], sc[0]); }
-	}
+	const bool polar = mm_wave_polar(a, pbase + 64);
+	S0Chain C;
+	const bool alive = s0_chain_init(a, pbase + lane, m, polar, C);
 	mm_acc acc[NG][4];
 #pragma unroll
 	for (int g = 0; g < NG; g++)
@@ -479,70 +413,27 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const Le
 		for (int rb = 0; rb < 4; rb++) { acc[g][rb][0] = 0; acc[g][rb][1] = 0; acc[g][rb][2] = 0; acc[g][rb][3] = 0; }
 	long ntile = 0;
 	// phase A: recurrence only until the first lane of the wave is at scale 0 (a wave without a live ring skips the loop below)
-	int k = 0;
 	const bool wave_alive = __any(alive);
-	if (wave_alive) { S0_PHASE_A }
-	const int kw = PXS_UNIFORM_INT(wave_alive ? k : nk + 16);      // (explicitly wave-uniform: left as a select, the loop below was compiled as divergent and the prefetched coefficient rows went to VGPRs)
-	coef = (const double4_t*)PXS_UNIFORM_LONG((long)coef);
+	const int kw = PXS_UNIFORM_INT(wave_alive ? s0_chain_phase_a(C, a.coef + row0, polar, nk) : nk + 16);      // (explicitly wave-uniform: left as a select, the loop below was compiled as divergent and the prefetched coefficient rows went to VGPRs)
 	{
 		const double* __restrict__ tab = reinterpret_cast<const double*>(polar ? a.coef2p : a.coef2) + 2*row0;      // (a, b') of step k at tab[2 k]
-		// B operand of MFMA step-quad q: lane (j, kk) holds column j & 3 of map 4 (bb NG + g) + (j >> 2) at step q + 4 kk of the tile
-		const int jcol = lane & 15, kk4 = lane >> 4;
-		const double* bsrc[NG]; bool bok[NG];
-#pragma unroll
-		for (int g = 0; g < NG; g++) {
-			const int map = (bb*NG + g)*4 + (jcol >> 2);
-			bok[g] = map < a.nmaps;
-			bsrc[g] = a.almt + (long)(bok[g] ? map : 0)*a.almt_bs + 4*row0 + (jcol & 3) + 16*kk4;
-		}
-		auto load_b = [&](int k0, double (*b)[4]) {
-#pragma unroll
-			for (int g = 0; g < NG; g++)
-#pragma unroll
-				for (int q = 0; q < 4; q++) b[g][q] = (bok[g] && k0 + q + 4*kk4 < nk) ? bsrc[g][4L*(k0 + q)] : 0.0;
-		};
-		bool pend = __any(sc[0] < 0);
+		MmSynB<NG, false> B; B.init(a, bb, row0, lane, 0);
+		bool pend = __any(C.sc < 0);
 		const double* __restrict__ pread = pmine + 4*(lane >> 4)*MMS_PSTRIDE + (lane & 15);
 		double cf[32];      // coefficients of the 16 steps of the tile, requested a tile ahead (every tile from the wave's first one on is run)
 		double bcur[NG][4], bnxt[NG][4];
-		load_b(16*(kw >> 4), bcur);
-		if (kw < nk) {
-#pragma unroll
-			for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 32L*(kw >> 4) + i);
-		}
+		B.load(16*(kw >> 4), nk, bcur);
+		if (kw < nk) mm_load_cf(cf, tab, 16*(kw >> 4));
 		for (int t = kw >> 4; 16*t < nk; t++) {
 			const int k0 = 16*t;
 			ntile++;
-#pragma unroll
-			for (int q4 = 0; q4 < 4; q4++) {
-				const int kq = k0 + 4*q4;
-				double p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-				if (kq >= kw && kq < nk) {
-					p0 = lam2[0]; lam1[0] = fma(mm_coef(cf[8*q4 + 0], csq[0], cf[8*q4 + 1]), lam2[0], lam1[0]);
-					p1 = lam1[0]; lam2[0] = fma(mm_coef(cf[8*q4 + 2], csq[0], cf[8*q4 + 3]), lam1[0], lam2[0]);
-					p2 = lam2[0]; lam1[0] = fma(mm_coef(cf[8*q4 + 4], csq[0], cf[8*q4 + 5]), lam2[0], lam1[0]);
-					p3 = lam1[0]; lam2[0] = fma(mm_coef(cf[8*q4 + 6], csq[0], cf[8*q4 + 7]), lam1[0], lam2[0]);
-					if (pend) {      // phase B: lanes below scale 0 contribute nothing yet; rescale them every 4 steps
-						if (sc[0] < 0) { p0 = p1 = p2 = p3 = 0.0; if (fabs(lam2[0]) > SC_BIG) { lam1[0] *= SC_SMALL; lam2[0] *= SC_SMALL; sc[0]++; } }
-						pend = __any(sc[0] < 0);
-					}
-					if (kq + 1 >= nk) p1 = 0.0;
-					if (kq + 2 >= nk) p2 = 0.0;
-					if (kq + 3 >= nk) p3 = 0.0;
-				}
-				pmine[(4*q4 + 0)*MMS_PSTRIDE + lane] = p0; pmine[(4*q4 + 1)*MMS_PSTRIDE + lane] = p1;
-				pmine[(4*q4 + 2)*MMS_PSTRIDE + lane] = p2; pmine[(4*q4 + 3)*MMS_PSTRIDE + lane] = p3;
-			}
+			mm_park_tile<MMS_PSTRIDE>(C, cf, k0, kw, nk, pend, pmine, lane);
 			MM_WAVE_SYNC();
 			double av[4];
 #pragma unroll
 			for (int rb = 0; rb < 4; rb++) av[rb] = pread[16*rb];
 			MM_WAVE_SYNC();
-			if (k0 + 16 < nk) {      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
-#pragma unroll
-				for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*(k0 + 16) + i);
-				load_b(k0 + 16, bnxt);
-			}
+			if (k0 + 16 < nk) { mm_load_cf(cf, tab, k0 + 16); B.load(k0 + 16, nk, bnxt); }      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
 #pragma unroll
 			for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -583,17 +474,11 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const Le
 
 // ---- launchers ----
 void launch_leg_syn_s0(int K, dim3 grid, hipStream_t st, const LegK& a) {
-	// (ring pairs per lane the product's rules select: 4 and 2; lab builds -- PXS_K_* -- compile the others too)
-#ifdef PXS_LAB
-	if (K == 8) { hipLaunchKernelGGL(leg_syn_s0<8>, grid, dim3(64), 0, st, a); return; }
-#endif
+	// (ring pairs per lane the host's rules select: 4 and 2)
 	if (K == 2) hipLaunchKernelGGL(leg_syn_s0<2>, grid, dim3(64), 0, st, a);
 	else        hipLaunchKernelGGL(leg_syn_s0<4>, grid, dim3(64), 0, st, a);
 }
 void launch_leg_ana_s0(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a) {
-#ifdef PXS_LAB
-	if (K == 12) { hipLaunchKernelGGL(leg_ana_s0<12>, grid, dim3(64), lds, st, a); return; }
-#endif
 	if (K == 8)      hipLaunchKernelGGL(leg_ana_s0<8>, grid, dim3(64), lds, st, a);
 	else if (K == 2) hipLaunchKernelGGL(leg_ana_s0<2>, grid, dim3(64), lds, st, a);
 	else             hipLaunchKernelGGL(leg_ana_s0<4>, grid, dim3(64), lds, st, a);
@@ -602,26 +487,13 @@ void launch_leg_syn_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a) {
 	if (ng == 2) hipLaunchKernelGGL(leg_syn_s0_mm<2>, grid, dim3(64), mm_syn_lds(), st, a);
 	else         hipLaunchKernelGGL(leg_syn_s0_mm<1>, grid, dim3(64), mm_syn_lds(), st, a);
 }
-template<int NG, int W> static void mm_launch1(dim3 grid, hipStream_t st, const LegK& a) {
-	static const bool once = [] { (void)hipFuncSetAttribute((const void*)leg_ana_s0_mm<NG, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }(); (void)once;
-	hipLaunchKernelGGL((leg_ana_s0_mm<NG, W>), grid, dim3(64*W), mm_ana_lds(NG, W), st, a);
-#if defined(PXS_LAB_MMTIME) && !defined(PXS_HOST_SIM)
-	{	unsigned long long h[16]; PXS_HIP(hipStreamSynchronize(st)); PXS_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(mm_prof), sizeof(h)));
-		static const char* nm_[14] = {"init", "phaseA", "kmin_barrier", "B_final_barriers", "P_phase", "mfma+ds_add", "barrier", "flush", "B_index", "B_data_loads", "B_lds_write+barrier", "B_lds_read", "-", "-"};
-		double tot = 0; for (int i = 0; i < 14; i++) tot += (double)h[i];
-		fprintf(stderr, "[mm_prof] waves %llu, cycles per wave %.0f:", h[15], tot/std::max(1.0, (double)h[15]));
-		for (int i = 0; i < 12; i++) fprintf(stderr, " %s %.1f%%", nm_[i], 100.0*h[i]/tot);
-		fprintf(stderr, "\n"); memset(h, 0, sizeof(h)); PXS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mm_prof), h, sizeof(h))); }
-#endif
-}
-template<int W> static void mm_launch(int ng, dim3 grid, hipStream_t st, const LegK& a) { if (ng == 2) mm_launch1<2, W>(grid, st, a); else mm_launch1<1, W>(grid, st, a); }
-void launch_leg_ana_s0_mm(int ng, int W, dim3 grid, hipStream_t st, const LegK& a) {
-#ifdef PXS_LAB      /* (lab builds: other workgroup sizes, PXS_ANA_MM_W; measured at C4: 2 waves 95 ms, 4: 78, 8: 77, 16: 82 per 64 maps) */
-	if (W == 16) { mm_launch<16>(ng, grid, st, a); return; }
-	if (W == 4)  { mm_launch<4>(ng, grid, st, a); return; }
-	if (W == 2)  { mm_launch<2>(ng, grid, st, a); return; }
-#endif
-	mm_launch<MM_WAVES>(ng, grid, st, a);
+// (waves per workgroup measured at C4: 2 waves 95 ms, 4: 78, 8: 77, 16: 82 per 64 maps)
+void launch_leg_ana_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a) {
+	constexpr int W = MM_WAVES;
+	static const bool once = [] { (void)hipFuncSetAttribute((const void*)leg_ana_s0_mm<2, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
+		(void)hipFuncSetAttribute((const void*)leg_ana_s0_mm<1, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }(); (void)once;
+	if (ng == 2) hipLaunchKernelGGL((leg_ana_s0_mm<2, W>), grid, dim3(64*W), mm_ana_lds(2, W), st, a);
+	else         hipLaunchKernelGGL((leg_ana_s0_mm<1, W>), grid, dim3(64*W), mm_ana_lds(1, W), st, a);
 }
 
 } // namespace pxs

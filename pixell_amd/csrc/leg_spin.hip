@@ -160,7 +160,6 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 			}
 		// phase C: fast loop, next coefficients prefetched
 		double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1), a0 = LDC(at, j), a1 = LDC(at, j+1);
-#ifndef PXS_NO_PHASEC_UNROLL
 		while (j + 3 < nl) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
 			double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3), m0 = LDC(at, j+2), m1 = LDC(at, j+3);
 			SPIN_SYN_PAIR(f0, f1, a0, a1)
@@ -169,7 +168,6 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 			SPIN_SYN_PAIR(n0, n1, m0, m1)
 			j += 2;
 		}
-#endif
 		for (; j + 1 < nl; j += 2) {
 			const double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3), m0 = LDC(at, j+2), m1 = LDC(at, j+3);
 			SPIN_SYN_PAIR(f0, f1, a0, a1)
@@ -300,7 +298,6 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 	}
 	// phase C: next coefficients prefetched
 	double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1);
-#ifndef PXS_NO_PHASEC_UNROLL
 	while (j + 3 < nl) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
 		double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3);
 		SPIN_ANA_PAIR(f0, f1)
@@ -309,7 +306,6 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 		SPIN_ANA_PAIR(n0, n1)
 		j += 2;
 	}
-#endif
 	for (; j + 1 < nl; j += 2) {
 		const double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3);
 		SPIN_ANA_PAIR(f0, f1)
@@ -342,12 +338,23 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 // chains in every lane, two P tiles per wave, two accumulators: the LDS held two waves per SIMD and the f64 MFMA, which needs several issuing waves for
 // its rate, ran the Q/U analysis of 16 maps in 111 ms against the VALU kernel's 123.)
 // one chain of leg_ana_spin's pair of recurrences: G_{l+1} = (a x + c) G_l - G_{l-1}, c = +-b (polar waves: a +- b with x = -2 sin^2(theta / 2))
-struct SpinChain { double x, g1, g2, sgl, pa; int sc; };
+struct SpinChain {
+	double x, g1, g2, sgl, pa; int sc, half, par;      // half: 0 the G+ chain, 1 the G- chain; par: l0 + m
+	// coefficient of a step from the row (a, b): a x + (polar ? a : 0) +- b
+	__device__ __forceinline__ double coef(double ca, double cb) const { return fma(ca, x, fma(sgl, cb, pa*ca)); }
+	__device__ __forceinline__ double step(double ca, double cb) { const double p = g2, nx = fma(coef(ca, cb), g2, -g1); g1 = p; g2 = nx; return p; }
+	__device__ __forceinline__ void rescale() { if (fabs(g2) > SC_BIG) { g1 *= SC_SMALL; g2 *= SC_SMALL; sc++; } }
+	// the G- lanes park sgn_l G-: the sign of the first of the four rows from step kq on, alternating
+	__device__ __forceinline__ void park_sign(int kq, double* p) const {
+		const double se = (half && ((par + kq) & 1)) ? -1.0 : 1.0, so = half ? -se : 1.0;
+		p[0] *= se; p[1] *= so; p[2] *= se; p[3] *= so;
+	}
+};
 __device__ __forceinline__ bool spin_chain_init(const LegK& a, int p, int m, int half, bool polar, SpinChain& C) {
 	const int s_ = a.spin;
 	const bool valid = p < a.npairs;
 	const double cth = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0, shh = valid ? a.sh2[p] : 0.0;
-	C.x = polar ? -2.0*shh*shh : cth; C.sgl = half ? -1.0 : 1.0; C.pa = polar ? 1.0 : 0.0;
+	C.x = polar ? -2.0*shh*shh : cth; C.sgl = half ? -1.0 : 1.0; C.pa = polar ? 1.0 : 0.0; C.half = half; C.par = max(m, s_) + m;
 	const double t1 = a.lmax*sth + a.ofs, b = -2.0*s_*fabs(cth), c = (double)s_*s_ - t1*t1, discr = b*b - 4*c;      // (libsharp's m-limit generalised to spin, as spin_init)
 	const double mlim = discr <= 0 ? a.lmax : fmin((double)a.lmax, 0.5*(-b + sqrt(discr)));
 	const bool alive = valid && ((double)m <= mlim + 0.5);
@@ -363,8 +370,21 @@ __device__ __forceinline__ bool spin_chain_init(const LegK& a, int p, int m, int
 	}
 	return alive;
 }
-// coefficient of a step from the row (a, b): a x + (polar ? a : 0) +- b
-__device__ __forceinline__ double spin_chain_coef(const SpinChain& C, double ca, double cb) { return fma(ca, C.x, fma(C.sgl, cb, C.pa*ca)); }
+// phase A: recurrence only until the first lane of the wave is at scale 0; returns the step reached (tab: (a, b) of step k at tab[2 k])
+__device__ __forceinline__ int spin_chain_phase_a(SpinChain& C, const double* __restrict__ tab, int n) {
+	int k = 0;
+	while (k + 4 <= n) {
+		if (__any(C.sc == 0 && C.g2 != 0.0)) break;
+		double cq[8];
+#pragma unroll
+		for (int i = 0; i < 8; i++) cq[i] = LDCD(tab, 2L*k + i);
+#pragma unroll
+		for (int i = 0; i < 4; i++) C.step(cq[2*i], cq[2*i + 1]);
+		if (C.sc < 0) C.rescale();
+		k += 4;
+	}
+	return k;
+}
 
 template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_mm(const LegK a)
 {
@@ -380,7 +400,7 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_
 	if (nl <= 0) return;
 	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
 	const int pbase = wv*32*W;
-	const bool polar = [&] { const double c = a.cth[min(pbase + 32*(w + 1), a.npairs) - 1]; return c*c > PXS_POLAR_COS2; }();      // (per wave)
+	const bool polar = mm_wave_polar(a, pbase + 32*(w + 1));      // (per wave)
 	const int pmine_ = pbase + 32*w + (lane & 31);       // ring pair of this lane's chain
 	SpinChain C;
 	const bool alive = spin_chain_init(a, pmine_, m, half, polar, C);
@@ -388,23 +408,8 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_
 	if (tid == 0) *s_kmin = nl;
 	__syncthreads();
 	// phase A, per wave: recurrence only until the first lane of the wave is at scale 0
-	int k = 0;
 	const bool wave_alive = __any(alive);
-	if (wave_alive) {
-		while (k + 4 <= nl) {
-			if (__any(C.sc == 0 && C.g2 != 0.0)) break;
-			double cq[8];
-#pragma unroll
-			for (int i = 0; i < 8; i++) cq[i] = LDCD(tab, 2L*k + i);
-			C.g1 = fma(spin_chain_coef(C, cq[0], cq[1]), C.g2, -C.g1);
-			C.g2 = fma(spin_chain_coef(C, cq[2], cq[3]), C.g1, -C.g2);
-			C.g1 = fma(spin_chain_coef(C, cq[4], cq[5]), C.g2, -C.g1);
-			C.g2 = fma(spin_chain_coef(C, cq[6], cq[7]), C.g1, -C.g2);
-			if (C.sc < 0 && fabs(C.g2) > SC_BIG) { C.g1 *= SC_SMALL; C.g2 *= SC_SMALL; C.sc++; }
-			k += 4;
-		}
-	}
-	const int kw = PXS_UNIFORM_INT(wave_alive ? k : nl + 16);
+	const int kw = PXS_UNIFORM_INT(wave_alive ? spin_chain_phase_a(C, tab, nl) : nl + 16);
 	if (lane == 0) atomicMin(s_kmin, kw);
 	__syncthreads();
 	const int kmin = PXS_UNIFORM_INT(*s_kmin);
@@ -451,67 +456,21 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_
 	double cf[32];      // (a, b) of the 16 steps of a tile, requested a tile ahead
 	int cf_tile = -1;
 	long ntile = 0;
-	auto mm_flush = [&](int tf) {      // rows 4 r + lane / 16 of tile tf, column lane % 16 = 4 (map in the group) + c; c >= 2 (mu-): x sgn of the row
-		double* __restrict__ redf = red + (tf & 1)*NG*4*64;
-		for (int cidx = w; cidx < 4*NG; cidx += W) {
-			const int g = cidx >> 2, r = cidx & 3;
-			double* rp = redf + cidx*64 + lane;
-			double v = *rp; *rp = 0.0;
-			const int krow = 16*tf + 4*r + (lane >> 4), map = (bb*NG + g)*4 + ((lane & 15) >> 2), c = lane & 3;
-			if (krow < nl && map < a.nmaps) {
-				if (c >= 2 && ((l0 + krow + m) & 1)) v = -v;
-				double* dst = a.mom + (long)map*a.mom_bs + 4*(row0 + krow) + c;
-#ifdef PXS_HOST_SIM
-				atomicAdd(dst, v);
-#else
-				unsafeAtomicAdd(dst, v);
-#endif
-			}
-		}
-	};
+	auto flush = [&](int tf) { mm_flush<NG, W, true>(a, red, tf, w, lane, bb, nl, row0, l0 + m); };
 	int tlast = -1;
 	for (int t = kmin >> 4; 16*t < nl; t++) {
 		const int k0 = 16*t;
 		double* __restrict__ redt = red + (t & 1)*NG*4*64;
 		if (k0 + 16 > kw) {      // (wave-uniform) this wave has steps in the tile
 			ntile++;
-			if (cf_tile != t) {
-#pragma unroll
-				for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*k0 + i);
-			}
-#pragma unroll
-			for (int q4 = 0; q4 < 4; q4++) {
-				const int kq = k0 + 4*q4;
-				double p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-				if (kq >= kw && kq < nl) {
-					p0 = C.g2; C.g1 = fma(spin_chain_coef(C, cf[8*q4 + 0], cf[8*q4 + 1]), C.g2, -C.g1);
-					p1 = C.g1; C.g2 = fma(spin_chain_coef(C, cf[8*q4 + 2], cf[8*q4 + 3]), C.g1, -C.g2);
-					p2 = C.g2; C.g1 = fma(spin_chain_coef(C, cf[8*q4 + 4], cf[8*q4 + 5]), C.g2, -C.g1);
-					p3 = C.g1; C.g2 = fma(spin_chain_coef(C, cf[8*q4 + 6], cf[8*q4 + 7]), C.g1, -C.g2);
-					if (pend) {      // phase B: a chain below scale 0 contributes nothing yet; rescale it every 4 steps
-						if (C.sc < 0) { p0 = p1 = p2 = p3 = 0.0; if (fabs(C.g2) > SC_BIG) { C.g1 *= SC_SMALL; C.g2 *= SC_SMALL; C.sc++; } }
-						pend = __any(C.sc < 0);
-					}
-					// the G- lanes park sgn_l G-: the sign of the first row of the group, alternating
-					const double se = (half && ((l0 + kq + m) & 1)) ? -1.0 : 1.0, so = half ? -se : 1.0;
-					p0 *= se; p1 *= so; p2 *= se; p3 *= so;
-					if (kq + 1 >= nl) p1 = 0.0;
-					if (kq + 2 >= nl) p2 = 0.0;
-					if (kq + 3 >= nl) p3 = 0.0;
-				}
-				pmine[(4*q4 + 0)*MM_PSTRIDE + lane] = p0; pmine[(4*q4 + 1)*MM_PSTRIDE + lane] = p1;
-				pmine[(4*q4 + 2)*MM_PSTRIDE + lane] = p2; pmine[(4*q4 + 3)*MM_PSTRIDE + lane] = p3;
-			}
+			if (cf_tile != t) mm_load_cf(cf, tab, k0);
+			mm_park_tile<MM_PSTRIDE>(C, cf, k0, kw, nl, pend, pmine, lane);
 			MM_WAVE_SYNC();
 			double av[4];
 #pragma unroll
 			for (int q = 0; q < 4; q++) av[q] = pread[q];
 			MM_WAVE_SYNC();
-			if (k0 + 16 < nl) {
-#pragma unroll
-				for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*(k0 + 16) + i);
-				cf_tile = t + 1;
-			}
+			if (k0 + 16 < nl) { mm_load_cf(cf, tab, k0 + 16); cf_tile = t + 1; }
 			mm_acc acc[NG];
 #pragma unroll
 			for (int g = 0; g < NG; g++) { acc[g][0] = 0; acc[g][1] = 0; acc[g][2] = 0; acc[g][3] = 0; }
@@ -521,17 +480,17 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_
 #pragma unroll
 				for (int g = 0; g < NG; g++) acc[g] = mm_mfma(aq, breg[g][q], acc[g]);
 			}
-			if (tlast >= 0) { mm_flush(tlast); tlast = -1; }
+			if (tlast >= 0) { flush(tlast); tlast = -1; }
 #pragma unroll
 			for (int g = 0; g < NG; g++)
 #pragma unroll
 				for (int r = 0; r < 4; r++) mm_lds_add(redt + (g*4 + r)*64 + lane, acc[g][r]);
 		}
-		if (tlast >= 0) mm_flush(tlast);
+		if (tlast >= 0) flush(tlast);
 		tlast = t;
 		__syncthreads();
 	}
-	if (tlast >= 0) mm_flush(tlast);
+	if (tlast >= 0) flush(tlast);
 	PXS_COUNT(1, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
 }
 
@@ -550,7 +509,7 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const 
 	const int nl = a.lmax - l0 + 1;
 	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
 	const int pbase = wv*32;
-	const bool polar = [&] { const double c = a.cth[min(pbase + 32, a.npairs) - 1]; return c*c > PXS_POLAR_COS2; }();
+	const bool polar = mm_wave_polar(a, pbase + 32);
 	SpinChain C;
 	const bool alive = spin_chain_init(a, pbase + (lane & 31), m, half, polar, C);
 	mm_acc acc[NG][4];
@@ -561,87 +520,26 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const 
 	long ntile = 0;
 	const double* __restrict__ tab = reinterpret_cast<const double*>(a.coef2) + 2*row0;      // (a, b) of step k at tab[2 k]
 	// phase A: recurrence only until the first lane of the wave is at scale 0 (a wave without a live ring skips the loop below)
-	int k = 0;
 	const bool wave_alive = nl > 0 && __any(alive);
-	if (wave_alive) {
-		while (k + 4 <= nl) {
-			if (__any(C.sc == 0 && C.g2 != 0.0)) break;
-			double cq[8];
-#pragma unroll
-			for (int i = 0; i < 8; i++) cq[i] = LDCD(tab, 2L*k + i);
-			C.g1 = fma(spin_chain_coef(C, cq[0], cq[1]), C.g2, -C.g1);
-			C.g2 = fma(spin_chain_coef(C, cq[2], cq[3]), C.g1, -C.g2);
-			C.g1 = fma(spin_chain_coef(C, cq[4], cq[5]), C.g2, -C.g1);
-			C.g2 = fma(spin_chain_coef(C, cq[6], cq[7]), C.g1, -C.g2);
-			if (C.sc < 0 && fabs(C.g2) > SC_BIG) { C.g1 *= SC_SMALL; C.g2 *= SC_SMALL; C.sc++; }
-			k += 4;
-		}
-	}
-	const int kw = PXS_UNIFORM_INT(wave_alive ? k : max(nl, 0) + 16);
+	const int kw = PXS_UNIFORM_INT(wave_alive ? spin_chain_phase_a(C, tab, nl) : max(nl, 0) + 16);
 	{
-		// B operand of MFMA step-quad q: lane (j, kk) holds column j & 3 of map 4 (bb NG + g) + (j >> 2) at step q + 4 kk of the tile: (a+ re, a+ im, sgn a- re, sgn a- im)
-		const int jcol = lane & 15, kk4 = lane >> 4, cc = jcol & 3;
-		const double* bsrc[NG]; bool bok[NG];
-#pragma unroll
-		for (int g = 0; g < NG; g++) {
-			const int map = (bb*NG + g)*4 + (jcol >> 2);
-			bok[g] = map < a.nmaps;
-			bsrc[g] = a.almt + (long)(bok[g] ? map : 0)*a.almt_bs + 4*row0 + cc + 16*kk4;
-		}
-		auto load_b = [&](int k0, double (*b)[4]) {
-#pragma unroll
-			for (int g = 0; g < NG; g++)
-#pragma unroll
-				for (int q = 0; q < 4; q++) {
-					const int row = k0 + q + 4*kk4;
-					const double v = (bok[g] && row < nl) ? bsrc[g][4L*(k0 + q)] : 0.0;
-					b[g][q] = (cc >= 2 && ((l0 + row + m) & 1)) ? -v : v;
-				}
-		};
+		MmSynB<NG, true> B; B.init(a, bb, row0, lane, l0 + m);      // (a+ re, a+ im, sgn_l a- re, sgn_l a- im)
 		bool pend = __any(C.sc < 0);
 		const double* __restrict__ pread = pmine + 4*(lane >> 4)*MMS_PSTRIDE + (lane & 15);
 		double cf[32];      // (a, b) of the 16 steps of the tile, requested a tile ahead (every tile from the wave's first one on is run)
 		double bcur[NG][4], bnxt[NG][4];
-		load_b(16*(kw >> 4), bcur);
-		if (kw < nl) {
-#pragma unroll
-			for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 32L*(kw >> 4) + i);
-		}
+		B.load(16*(kw >> 4), nl, bcur);
+		if (kw < nl) mm_load_cf(cf, tab, 16*(kw >> 4));
 		for (int t = kw >> 4; 16*t < nl; t++) {
 			const int k0 = 16*t;
 			ntile++;
-#pragma unroll
-			for (int q4 = 0; q4 < 4; q4++) {
-				const int kq = k0 + 4*q4;
-				double p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-				if (kq >= kw && kq < nl) {
-					p0 = C.g2; C.g1 = fma(spin_chain_coef(C, cf[8*q4 + 0], cf[8*q4 + 1]), C.g2, -C.g1);
-					p1 = C.g1; C.g2 = fma(spin_chain_coef(C, cf[8*q4 + 2], cf[8*q4 + 3]), C.g1, -C.g2);
-					p2 = C.g2; C.g1 = fma(spin_chain_coef(C, cf[8*q4 + 4], cf[8*q4 + 5]), C.g2, -C.g1);
-					p3 = C.g1; C.g2 = fma(spin_chain_coef(C, cf[8*q4 + 6], cf[8*q4 + 7]), C.g1, -C.g2);
-					if (pend) {
-						if (C.sc < 0) { p0 = p1 = p2 = p3 = 0.0; if (fabs(C.g2) > SC_BIG) { C.g1 *= SC_SMALL; C.g2 *= SC_SMALL; C.sc++; } }
-						pend = __any(C.sc < 0);
-					}
-					const double se = (half && ((l0 + kq + m) & 1)) ? -1.0 : 1.0, so = half ? -se : 1.0;      // the G- lanes park sgn_l G-
-					p0 *= se; p1 *= so; p2 *= se; p3 *= so;
-					if (kq + 1 >= nl) p1 = 0.0;
-					if (kq + 2 >= nl) p2 = 0.0;
-					if (kq + 3 >= nl) p3 = 0.0;
-				}
-				pmine[(4*q4 + 0)*MMS_PSTRIDE + lane] = p0; pmine[(4*q4 + 1)*MMS_PSTRIDE + lane] = p1;
-				pmine[(4*q4 + 2)*MMS_PSTRIDE + lane] = p2; pmine[(4*q4 + 3)*MMS_PSTRIDE + lane] = p3;
-			}
+			mm_park_tile<MMS_PSTRIDE>(C, cf, k0, kw, nl, pend, pmine, lane);
 			MM_WAVE_SYNC();
 			double av[4];
 #pragma unroll
 			for (int rb = 0; rb < 4; rb++) av[rb] = pread[16*rb];
 			MM_WAVE_SYNC();
-			if (k0 + 16 < nl) {      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
-#pragma unroll
-				for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*(k0 + 16) + i);
-				load_b(k0 + 16, bnxt);
-			}
+			if (k0 + 16 < nl) { mm_load_cf(cf, tab, k0 + 16); B.load(k0 + 16, nl, bnxt); }      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
 #pragma unroll
 			for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -688,18 +586,11 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const 
 
 // ---- launchers ----
 void launch_leg_syn_spin(int K, dim3 grid, hipStream_t st, const LegK& a) {
-	// (ring pairs per lane the product's rules select: 3 and 2 for the synthesis, 4, 3 and 2 for the analysis; lab builds compile the others too)
-#ifdef PXS_LAB
-	if (K == 4) { hipLaunchKernelGGL(leg_syn_spin<4>, grid, dim3(64), 0, st, a); return; }
-#endif
+	// (ring pairs per lane the host's rules select: 3 and 2 for the synthesis, 4, 3 and 2 for the analysis)
 	if (K == 3) hipLaunchKernelGGL(leg_syn_spin<3>, grid, dim3(64), 0, st, a);
 	else        hipLaunchKernelGGL(leg_syn_spin<2>, grid, dim3(64), 0, st, a);
 }
 void launch_leg_ana_spin(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a) {
-#ifdef PXS_LAB
-	if (K >= 6) { hipLaunchKernelGGL(leg_ana_spin<6>, grid, dim3(64), lds, st, a); return; }
-	if (K == 5) { hipLaunchKernelGGL(leg_ana_spin<5>, grid, dim3(64), lds, st, a); return; }
-#endif
 	if (K >= 4)      hipLaunchKernelGGL(leg_ana_spin<4>, grid, dim3(64), lds, st, a);
 	else if (K == 3) hipLaunchKernelGGL(leg_ana_spin<3>, grid, dim3(64), lds, st, a);
 	else             hipLaunchKernelGGL(leg_ana_spin<2>, grid, dim3(64), lds, st, a);

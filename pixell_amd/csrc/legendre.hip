@@ -3,8 +3,9 @@
 // Replaces ducc0's alm2leg / leg2alm (inside ducc0.sht.experimental.*; not in the reference
 // tree) as reached from pixell/curvedsky.py:907-960, 1032-1084.
 //
-// Design (MI355X-first, plain FP64 FMA -- the contraction is 1-4 right-hand sides wide, too
-// narrow for the 16x16x4 f64 MFMA):
+// Design (MI355X-first).  A single map is 1-4 right-hand sides wide, too narrow for the 16x16x4 f64 MFMA: it runs on plain FP64 FMA as
+// described below.  A batch of 4 or more maps shares one recurrence per ring pair and is contracted with the f64 MFMA (leg_*_mm,
+// leg_s0.hip / leg_spin.hip; leg_batch_plan below says which maps go where).  The VALU kernels:
 //  * one wave64 per workgroup; a lane owns K ring PAIRS (theta, pi-theta) => K independent
 //    recurrence chains of ILP per lane, north/south sharing one recurrence;
 //  * spin 0: Ishioka-type two-step recurrence in x^2, p_{k+1} = (a_k x^2 + b_k) p_k + p_{k-1},
@@ -26,24 +27,14 @@
 #include "legendre_dev.hpp"
 #include <thread>
 #include <memory>
+#include <functional>
+#include <string>
 
 namespace pxs {
 
-// ring pairs per lane (K): defaults chosen by measurement on MI355X; PXS_K_SYN0/PXS_K_ANA0 (4|8) and
-// PXS_K_SYNS/PXS_K_ANAS (2|3|4) override them for tuning runs
-static int env_k(const char* name, int def, int lo, int hi) {
-	const char* v = getenv(name); if (!v) return def;
-	int k = atoi(v); return (k >= lo && k <= hi) ? k : def;
-}
-static int lab_k(const char* name, int def, int lo, int hi) {
-	const char* v = lab_getenv(name); if (!v) return def;
-	int k = atoi(v); return (k >= lo && k <= hi) ? k : def;
-}
-static int k_syn0() { static int k0 = lab_k("PXS_K_SYN0", 4, 2, 8); static int k = k0 >= 8 ? 8 : (k0 >= 4 ? 4 : 2); return k; }
-static int k_ana0() { static int k0 = lab_k("PXS_K_ANA0", 8, 2, 12); static int k = k0 >= 12 ? 12 : (k0 >= 8 ? 8 : (k0 >= 4 ? 4 : 2)); return k; }
-static int k_syns() { static int k = lab_k("PXS_K_SYNS", 3, 2, 4); return k; }
-static int k_anas() { static int k = lab_k("PXS_K_ANAS", 4, 2, 6); return k; }   // 4: 149 VGPRs = 3 waves per SIMD (6: 227 = 2 waves; measured 146.9 vs 150.5 ms at config 3)
-static int xcd_map() { static int k = lab_k("PXS_XCD_MAP", 1, 0, 1); return k; }
+// ring pairs per lane (K) of the VALU kernels: chosen by measurement on MI355X (profiles/r04_ktune_c3.txt, profiles/r05_dp_rate_and_k_waves.txt;
+// leg_ana_spin<4>: 3 waves per SIMD, K = 6 has 2: 146.9 against 150.5 ms at config 3); k_small_grid lowers them on small ring sets
+static constexpr int K_SYN0 = 4, K_ANA0 = 8, K_SYNS = 3, K_ANAS = 4;
 
 // ---------------------------------------------------------------------------------
 // alm pre / post transforms
@@ -217,9 +208,6 @@ __global__ __launch_bounds__(256) void reduce_partials(const double* __restrict_
 	}
 	mom[r0*4 + i] = s;
 }
-
-// A wave is 'polar' when all its rings have cos^2 > PXS_POLAR_COS2: it then runs the recurrences in the variable
-
 
 // compact step table: (a, b) or (a, a + b) of the rows of LegTables::coef; 32 rows of padding (a tile reads 16 steps whatever nk is)
 __global__ __launch_bounds__(256) void coef2_kernel(const double4_t* __restrict__ coef, long nrows, double2* __restrict__ c2, double2* __restrict__ c2p) {
@@ -516,27 +504,36 @@ void LegTables::build(int lmax_, int mmax_, int spin_) {
 // doubles per map of the pre-scaled alm / the moments of a batched call
 static long leg_almt_stride(const LegTables& tb) { return 4*(tb.nrows + 4); }
 static long leg_mom_stride(const LegTables& tb) { return 4*std::max<long>(tb.nrows, 1); }
-static LegK make_legk(const RingSet& rs, const LegTables& tb, LegWork& wk, double2* leg, long ld, int K, int nb = 1, long leg_bs = 0) {
+// kernel arguments of one launch: nb maps (MFMA forms: groups of maps, make_legk_mm), `pairs` ring pairs per workgroup
+static LegK make_legk(const RingSet& rs, const LegTables& tb, LegWork& wk, double2* leg, long ld, int pairs, int nb, long leg_bs) {
 	LegK a; memset(&a, 0, sizeof(a));
 	a.lmax = tb.lmax; a.mmax = tb.mmax; a.spin = tb.spin; a.nm = tb.mmax+1; a.npairs = rs.npairs; a.nring = rs.nring;
-	a.nwave = (rs.npairs + 64*K - 1)/(64*K);
+	a.nwave = (rs.npairs + pairs - 1)/pairs;
 	a.nrows = tb.nrows; a.row = tb.d_row.as<long>(); a.coef = tb.d_coef.as<double4_t>(); a.alpha = tb.d_alpha.as<double>();
 	a.ring_n = rs.d_ring_n.as<int>(); a.ring_s = rs.d_ring_s.as<int>(); a.cth = rs.d_cth.as<double>(); a.sth = rs.d_sth.as<double>();
 	a.sh2 = rs.d_sh2.as<double>(); a.ch2 = rs.d_ch2.as<double>();
 	a.almt = wk.almt.as<double>(); a.part = wk.part.as<double>(); a.mom = wk.mom.as<double>();
 	a.leg = leg; a.ld = ld > 0 ? ld : rs.nring;
 	a.ofs = std::max(100.0, 0.01*tb.lmax);
-	a.nmc = a.nm; a.xcd = xcd_map();
+	a.nmc = a.nm; a.xcd = 1;      // (the XCD-aware block order, always: see leg_block)
 	a.count = wk.count_on ? wk.count.as<double>() : nullptr;
 	a.nb = nb; a.leg_bs = leg_bs; a.almt_bs = leg_almt_stride(tb); a.mom_bs = leg_mom_stride(tb);
 	PXS_REQUIRE((long)8*((a.nm + 7)/8)*a.nwave*nb < (1L << 31), "internal: Legendre grid too large for one launch");
 	return a;
 }
+// ... of an MFMA launch: nmaps maps from `leg` on in groups of 4 ng, one group per wave (synthesis) or workgroup (analysis)
+static LegK make_legk_mm(const RingSet& rs, const LegTables& tb, LegWork& wk, double2* leg, long ld, int pairs, int nmaps, int ng, long leg_bs) {
+	LegK a = make_legk(rs, tb, wk, leg, ld, pairs, (nmaps + 4*ng - 1)/(4*ng), leg_bs);
+	a.nmaps = nmaps; a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
+	return a;
+}
 
-// maps one launch can take: all maps of a launch share one grid of 8 ceil(nm / 8) nwave blocks each (a large batch of small-ring,
-// high-lmax maps goes out as several launches instead of tripping make_legk's grid check)
-static int leg_max_batch(const RingSet& rs, const LegTables& tb, int K) {
-	const long nwave = (rs.npairs + 64L*K - 1)/(64L*K), per = 8L*((tb.mmax + 1 + 7)/8)*std::max<long>(nwave, 1);
+// maps (MFMA forms: groups) one launch can take: all of them share one grid of 8 ceil(nm / 8) nwave blocks each (a large batch of
+// small-ring, high-lmax maps goes out as several launches instead of tripping make_legk's grid check)
+// (the spin MFMA runs used to be cut at half the spin-0 synthesis limit and at the limit of 128 pairs per workgroup: lower than the grid needs; now every form is cut by its own
+// pairs per workgroup.  Out of reach at real sizes: tens of thousands of maps in one call)
+static int leg_max_batch(const RingSet& rs, const LegTables& tb, int pairs) {
+	const long nwave = (rs.npairs + (long)pairs - 1)/pairs, per = 8L*((tb.mmax + 1 + 7)/8)*std::max<long>(nwave, 1);
 	return (int)std::max<long>(1, std::min<long>(1 << 20, ((1L << 31) - 1)/per));
 }
 // seeds of (ring set, spin, direction, K): allocate on first use if the plan's budget allows; returns the mode for this launch
@@ -601,25 +598,60 @@ static void ensure_coef2(hipStream_t st, const LegTables& tb) {      // compact 
 // Rings per lane of a small ring set.  (1) A wave of 64 K ring pairs takes the polar form of the recurrences (leg_wave_polar) only if its most equatorial ring
 // stays within 71.5 degrees of the pole, so on a grid of a few hundred rings the default K leaves the rings next to the poles in the plain form (l^2 eps there):
 // where a smaller compiled K makes the first wave eligible, take it.  (2) Up to 512 ring pairs (lmax ~1000) the launch is short of waves, not of work per wave
-// -- (mmax + 1) x ceil(npairs / 64 K) waves for 1024 SIMDs -- and the smallest K is the fastest (tools/ksmall_ab.sh, profiles/r05_k_small_grids.txt: the reference's
+// -- (mmax + 1) x ceil(npairs / 64 K) waves for 1024 SIMDs -- and the smallest K is the fastest (profiles/r05_k_small_grids.txt: the reference's
 // benchmark shape 900x1800, lmax 750: 0.365 -> 0.335 ms per round trip, its T/Q/U version 1.047 -> 0.938; at lmax 1500 the defaults are level, at 2500 ahead).
 static int k_small_grid(const RingSet& rs, int kdef, std::initializer_list<int> smaller, int kmid = 0) {
 #ifdef PXS_HOST_SIM
 	const bool off = [] { const char* e = getenv("PXS_K_SMALL_OFF"); return e && atoi(e) != 0; }();      // (the host simulation runs small grids only: its tests switch the rule off to reach the default kernels)
 #else
-	static const bool off = [] { const char* e = lab_getenv("PXS_K_SMALL_OFF"); return e && atoi(e) != 0; }();
+	constexpr bool off = false;
 #endif
 	if (off || rs.npairs <= 0) return kdef;
 	if (rs.npairs <= 512) { int k = kdef; for (int c : smaller) k = std::min(k, c); return k; }
 	// (3) up to 1400 ring pairs (lmax ~2500: 2700 rings) the synthesis kernels are still 5-12 % faster with K = 2 and the scalar analysis 2-4 % with K = 4; at lmax 4000 the defaults
-	// are 20 % ahead (tools/kmid_ab.sh, tools/kbig_ab.sh, profiles/r05_k_mid_grids.txt)
+	// are 20 % ahead (profiles/r05_k_mid_grids.txt)
 	if (kmid > 0 && rs.npairs <= 1400) return kmid;
 	auto eligible = [&](int k) { const int last = std::min(64*k, rs.npairs) - 1; return last >= 0 && rs.cth[last]*rs.cth[last] > PXS_POLAR_COS2; };
 	if (eligible(kdef)) return kdef;
 	for (int k : smaller) if (k < kdef && eligible(k)) return k;
 	return kdef;
 }
-static int syn_mm_min() { static int v = [] { const char* e = getenv("PXS_SYN_MM_MIN"); const int x = e ? atoi(e) : 4; return x <= 0 ? (1 << 30) : std::max(2, x); }(); return v; }
+// ---- batch planner ----
+// A call of nb maps goes out as an ordered list of launches.  With 4 or more maps (PXS_SYN_MM_MIN / PXS_ANA_MM_MIN) the maps share one recurrence in the FP64-MFMA
+// kernels (leg_*_mm): groups of 8 maps per wave (synthesis) or workgroup (analysis); a remainder of more than 4 maps as one more 8-map group, of 4 or fewer as a
+// 4-map group, a lone left-over map through the VALU kernel (it costs more in a 4-map group).  An MFMA result equals the single-map call to rounding (1e-13), not
+// bit for bit: the sums run in another order.  Never MFMA: the ordered (bitwise repeatable) analysis, which takes every map alone, and the spin analysis of a gradient.
+// The VALU launch that records the recurrence seeds takes one map, so that only one wave writes each seed.
+enum LegForm { LEG_VALU, LEG_MM8, LEG_MM4 };
+struct LegLaunch { int b0, n; LegForm form; int ng; };      // maps [b0, b0 + n); ng: groups of 4 maps per wave / workgroup (MFMA forms)
+static int mm_min(const char* name) { const char* e = getenv(name); const int x = e ? atoi(e) : 4; return x <= 0 ? (1 << 30) : std::max(2, x); }
+static int syn_mm_min() { static const int v = mm_min("PXS_SYN_MM_MIN"); return v; }
+static int ana_mm_min() { static const int v = mm_min("PXS_ANA_MM_MIN"); return v; }
+// seeds_pending: will a VALU launch record seeds; max_valu / max_mm8: maps one launch can take (grid limit).  seeds_pending is a callable, not a bool, because asking
+// ALLOCATES the seed buffers of the VALU kernel (seeds_for): it is asked only where the parent asked, with more than one map left to the VALU kernel
+static std::vector<LegLaunch> leg_batch_plan(int nb, int spin, bool analysis, int deriv1, bool deterministic, const std::function<bool()>& seeds_pending, int max_valu, int max_mm8) {
+	const bool ordered = analysis && deterministic;
+	const bool mm = nb >= (analysis ? ana_mm_min() : syn_mm_min()) && !ordered && !(analysis && spin > 0 && deriv1);
+	std::vector<LegLaunch> plan;
+	int b = 0;
+	if (mm) {
+		const int nmm = nb - (nb % 8 == 1 ? 1 : 0), r = nmm % 8, n8 = nmm - r;
+		for (; b < n8; b += max_mm8) plan.push_back({b, std::min(max_mm8, n8 - b), LEG_MM8, 2});
+		if (r > 4) plan.push_back({n8, r, LEG_MM8, 2}); else if (r > 0) plan.push_back({n8, r, LEG_MM4, 1});
+		b = nmm;
+	}
+	if (ordered || (nb - b > 1 && seeds_pending())) for (const int e = ordered ? nb : b + 1; b < e; b++) plan.push_back({b, 1, LEG_VALU, 0});
+	for (; b < nb; b += max_valu) plan.push_back({b, std::min(max_valu, nb - b), LEG_VALU, 0});
+	return plan;
+}
+// PXS_CHAIN_VERBOSE: the launch list of the call, e.g. "[pxsht] legendre analysis spin 0, 13 maps: mm8 [0,8) mm8 [8,13)"
+static void print_batch_plan(bool analysis, int spin, int nb, const std::vector<LegLaunch>& plan) {
+	if (!getenv("PXS_CHAIN_VERBOSE")) return;
+	std::string s;
+	for (const LegLaunch& l : plan) s += std::string(l.form == LEG_VALU ? " VALU [" : l.form == LEG_MM8 ? " mm8 [" : " mm4 [") + std::to_string(l.b0) + "," + std::to_string(l.b0 + l.n) + ")";
+	fprintf(stderr, "[pxsht] legendre %s spin %d, %d maps:%s\n", analysis ? "analysis" : "synthesis", spin, nb, s.c_str());
+}
+
 void leg_synthesis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWork& wk,
                    const void* alm, int alm_dtype, long alm_cstride, const uint64_t* d_mstart, long lstride,
                    double2* leg, int deriv1, LegProfile* prof, long ld, int nb, long alm_bstride, long leg_bstride)
@@ -629,181 +661,41 @@ void leg_synthesis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWo
 	wk.almt.ensure(sizeof(double)*(size_t)leg_almt_stride(tb)*nb);
 	AlmK ak = make_almk(tb, wk, alm, alm_dtype, alm_cstride, d_mstart, lstride, deriv1, alm_bstride);
 	const int nm = tb.mmax+1;
-	const int K = tb.spin == 0 ? k_small_grid(rs, k_syn0(), {2}, 2) : k_small_grid(rs, k_syns(), {2}, 2);
+	const int K = tb.spin == 0 ? k_small_grid(rs, K_SYN0, {2}, 2) : k_small_grid(rs, K_SYNS, {2}, 2);
+	const int mm_pairs = tb.spin == 0 ? 64 : 32;      // ring pairs per wave of the MFMA form (spin s: one chain per half-wave)
 	if (tb.spin == 0) hipLaunchKernelGGL(alm_pre_s0, alm_grid(tb.lmax/2 + 1, nm, nb), dim3(256), 0, st, ak);
 	else              hipLaunchKernelGGL(alm_pre_spin, alm_grid(tb.lmax + 1, nm, nb), dim3(256), 0, st, ak);
-	// maps [b0, b0 + n) in one launch
-	auto launch = [&](int b0, int n) {
-		LegK a = make_legk(rs, tb, wk, leg + (size_t)b0*leg_bstride, ld, K, n, leg_bstride);
-		a.almt += (size_t)b0*a.almt_bs;
-		LegWork::Seeds* sb = seeds_for(wk, rs, tb, 0, K, a); seeds_wait(sb, st);
+	const std::vector<LegLaunch> plan = leg_batch_plan(nb, tb.spin, false, deriv1, wk.deterministic, [&] { return seeds_pending(wk, rs, tb, 0, K); },
+		leg_max_batch(rs, tb, 64*K), 8*leg_max_batch(rs, tb, mm_pairs));
+	print_batch_plan(false, tb.spin, nb, plan);
+	for (const LegLaunch& l : plan) {
+		double2* legl = leg + (size_t)l.b0*leg_bstride;
+		if (l.ng) ensure_coef2(st, tb);
+		LegK a = l.ng ? make_legk_mm(rs, tb, wk, legl, ld, mm_pairs, l.n, l.ng, leg_bstride) : make_legk(rs, tb, wk, legl, ld, 64*K, l.n, leg_bstride);
+		a.almt += (size_t)l.b0*a.almt_bs;
+		LegWork::Seeds* sb = nullptr;
+		if (!l.ng) { sb = seeds_for(wk, rs, tb, 0, K, a); seeds_wait(sb, st); }
 		if (prof) prof->begin(st, 0);
-		if (tb.spin == 0) launch_leg_syn_s0(K, leg_grid(a), st, a);
-		else              launch_leg_syn_spin(K, leg_grid(a), st, a);
+		if (tb.spin == 0) { if (l.ng) launch_leg_syn_s0_mm(l.ng, leg_grid(a), st, a); else launch_leg_syn_s0(K, leg_grid(a), st, a); }
+		else              { if (l.ng) launch_leg_syn_spin_mm(l.ng, leg_grid(a), st, a); else launch_leg_syn_spin(K, leg_grid(a), st, a); }
 		if (prof) prof->end(st, 0);
 		seeds_written(sb, st);
-	};
-	int b0 = 0;
-	// spin 0, 4 or more maps (PXS_SYN_MM_MIN): the FP64-MFMA form (leg_syn_s0_mm), 8 maps per wave; a remainder of <= 4 maps in 4-map waves,
-	// a single left-over map through the VALU kernel.  Each map's result equals its single-map call to rounding, not bit for bit.
-	if (tb.spin == 0 && nb >= syn_mm_min()) {
-		int nmm = nb; if (nb % 8 == 1) nmm = nb - 1;
-		ensure_coef2(st, tb);
-		auto launch_mm = [&](int m0, int nmaps, int ng) {
-			const int per = 4*ng, ngroups = (nmaps + per - 1)/per;
-			LegK a = make_legk(rs, tb, wk, leg + (size_t)m0*leg_bstride, ld, 1, ngroups, leg_bstride);
-			a.almt += (size_t)m0*a.almt_bs; a.nmaps = nmaps; a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
-			if (prof) prof->begin(st, 0);
-			launch_leg_syn_s0_mm(ng, leg_grid(a), st, a);
-			if (prof) prof->end(st, 0);
-		};
-		static const int ngmax = lab_k("PXS_SYN_MM_NG", 2, 1, 2);      // groups of 4 maps per wave (tuning)
-		const int mper = 4*ngmax, gmax = std::max(1, leg_max_batch(rs, tb, 1)), r = nmm % mper, n8 = nmm - r;
-		for (int m0 = 0; m0 < n8; m0 += mper*gmax) launch_mm(m0, std::min(mper*gmax, n8 - m0), ngmax);
-		if (r > 4) launch_mm(n8, r, 2); else if (r > 0) launch_mm(n8, r, 1);
-		b0 = nmm;
 	}
-	// spin s, 4 or more maps (Q/U pairs of a stack of maps): leg_syn_spin_mm, 8 maps per wave, a remainder of <= 4 in 4-map waves, a lone left-over map
-	// through the VALU kernel
-	if (tb.spin > 0 && nb >= syn_mm_min()) {
-		const int nmm = nb - (nb % 8 == 1 ? 1 : 0);
-		ensure_coef2(st, tb);
-		auto launch_mm = [&](int m0, int nmaps, int ng) {
-			const int per = 4*ng, ngroups = (nmaps + per - 1)/per;
-			LegK a = make_legk(rs, tb, wk, leg + (size_t)m0*leg_bstride, ld, 1, ngroups, leg_bstride);
-			a.nwave = (rs.npairs + 31)/32;      // (a wave covers 32 ring pairs: one chain per half-wave)
-			a.almt += (size_t)m0*a.almt_bs; a.nmaps = nmaps; a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
-			PXS_REQUIRE((long)8*((a.nm + 7)/8)*a.nwave*ngroups < (1L << 31), "internal: Legendre grid too large for one launch");
-			if (prof) prof->begin(st, 0);
-			launch_leg_syn_spin_mm(ng, leg_grid(a), st, a);
-			if (prof) prof->end(st, 0);
-		};
-		const int gmax = std::max(1, leg_max_batch(rs, tb, 1)/2), r = nmm % 8, n8 = nmm - r;
-		for (int m0 = 0; m0 < n8; m0 += 8*gmax) launch_mm(m0, std::min(8*gmax, n8 - m0), 2);
-		if (r > 4) launch_mm(n8, r, 2); else if (r > 0) launch_mm(n8, r, 1);
-		b0 = nmm;
-	}
-	// (the launch that records the recurrence seeds takes one map, so that only one wave writes each seed)
-	if (nb - b0 > 1 && seeds_pending(wk, rs, tb, 0, K)) { launch(b0, 1); b0 += 1; }
-	for (const int nmax = leg_max_batch(rs, tb, K); b0 < nb; b0 += nmax) launch(b0, std::min(nmax, nb - b0));
 	PXS_HIP(hipGetLastError());
 }
 
-// spin-0 analysis of nb >= PXS_ANA_MM_MIN (4) maps: the FP64-MFMA form (leg_ana_s0_mm), 8 maps per workgroup; a remainder of <= 4 maps
-// takes 4-map workgroups, a single left-over map the VALU kernel.  Summation order differs from the single-map kernel: a batched
-// call equals its single-map calls to rounding (1e-13), not bit for bit.
-static int ana_mm_min() { static int v = [] { const char* e = getenv("PXS_ANA_MM_MIN"); const int x = e ? atoi(e) : 4; return x <= 0 ? (1 << 30) : std::max(2, x); }(); return v; }
-static void leg_analysis_mm(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWork& wk,
-                  const double2* leg, void* alm, int alm_dtype, long alm_cstride, const uint64_t* d_mstart, long lstride,
-                  LegProfile* prof, long ld, int nb, long alm_bstride, long leg_bstride)
+// one VALU analysis launch: maps [0, nb) of leg into mom (pre-zeroed unless wk.deterministic).
+// Default: the waves of one m add their sums straight into mom with global_atomic_add_f64 -- the blocks of one m run back
+// to back on one XCD (leg_block), so the row they share sits in that XCD's L2 while they do.  The order of those additions
+// is not fixed: results repeat to rounding, not bit for bit.  pxs_plan_option("deterministic", 1) (or PXS_DETERMINISTIC=1 when the plan is made) selects the former scheme instead
+// (per-wave partial moments in scratch, m in chunks that keep them below part_budget, summed in wave order by reduce_partials), for callers that need bitwise repeats.
+static void leg_analysis_valu(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWork& wk, int K, const double2* leg, double* mom, LegProfile* prof, long ld, int nb, long leg_bstride)
 {
-	static const int W = [] { const int v = lab_k("PXS_ANA_MM_W", MM_WAVES, 2, 16); return v >= 16 ? 16 : (v >= 8 ? 8 : (v >= 4 ? 4 : 2)); }();      // waves per workgroup: 8 (lab builds: 2 | 4 | 8 | 16)
-	const int nm = tb.mmax+1;
-	const long n4 = leg_mom_stride(tb);
-	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16;
-	int nmm = nb;
-	if (nb % 8 == 1) nmm = nb - 1;      // (a lone map in a 4-map workgroup costs more than the VALU kernel)
-	wk.mom.ensure(sizeof(double)*(size_t)n4*nmm);
-	PXS_HIP(hipMemsetAsync(wk.mom.p, 0, sizeof(double)*(size_t)n4*nmm, st));
-	ensure_coef2(st, tb);
-	auto launch = [&](int b0, int nmaps, int ng) {      // maps [b0, b0 + nmaps) in groups of 4 ng
-		const int per = 4*ng, ngroups = (nmaps + per - 1)/per;
-		LegK a = make_legk(rs, tb, wk, const_cast<double2*>(leg) + (size_t)b0*leg_bstride, ld, W, ngroups, leg_bstride);
-		a.mom = wk.mom.as<double>() + (size_t)b0*a.mom_bs; a.part = a.mom; a.atomic = 1; a.nmaps = nmaps;
-		a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
-		if (prof) prof->begin(st, 1);
-		launch_leg_ana_s0_mm(ng, W, leg_grid(a), st, a);
-		if (prof) prof->end(st, 1);
-	};
-	const int gmax = std::max(1, leg_max_batch(rs, tb, W));      // groups one launch can take (grid limit)
-	static const int ngmax = lab_k("PXS_ANA_MM_NG", 2, 1, 2);      // groups of 4 maps per workgroup (tuning)
-	const int mper = 4*ngmax, r = nmm % mper, n8 = nmm - r;
-	for (int b0 = 0; b0 < n8; b0 += mper*gmax) launch(b0, std::min(mper*gmax, n8 - b0), ngmax);
-	if (r > 4) launch(n8, r, 2); else if (r > 0) launch(n8, r, 1);
-	AlmK ak = make_almk(tb, wk, alm, alm_dtype, alm_cstride, d_mstart, lstride, 0, alm_bstride);
-	hipLaunchKernelGGL(alm_post_s0, alm_grid(tb.lmax/2 + 1, nm, nmm), dim3(256), 0, st, ak);
-	PXS_HIP(hipGetLastError());
-	if (nmm < nb)
-		leg_analysis(st, rs, tb, wk, leg + (size_t)nmm*leg_bstride, (char*)alm + aesz*(size_t)nmm*alm_bstride, alm_dtype, alm_cstride, d_mstart, lstride, 0, prof, ld, 1, 0, 0);
-}
-
-// spin-s analysis of nb >= PXS_ANA_MM_MIN (4) maps: leg_ana_spin_mm, 8 maps (Q/U pairs) per workgroup, a remainder of <= 4 in 4-map workgroups, a lone
-// left-over map through the VALU kernel
-static void leg_analysis_spin_mm(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWork& wk,
-                  const double2* leg, void* alm, int alm_dtype, long alm_cstride, const uint64_t* d_mstart, long lstride,
-                  LegProfile* prof, long ld, int nb, long alm_bstride, long leg_bstride)
-{
-	constexpr int W = MM_WAVES;
-	const int nm = tb.mmax+1;
-	const long n4 = leg_mom_stride(tb);
-	const size_t aesz = alm_dtype == PX_C64 ? 8 : 16;
-	const int nmm = nb - (nb % 8 == 1 ? 1 : 0);      // (a lone left-over map costs more in a 4-map workgroup than in the VALU kernel)
-	wk.mom.ensure(sizeof(double)*(size_t)n4*nmm);
-	PXS_HIP(hipMemsetAsync(wk.mom.p, 0, sizeof(double)*(size_t)n4*nmm, st));
-	ensure_coef2(st, tb);
-	auto launch = [&](int b0, int nmaps, int ng) {
-		const int per = 4*ng, ngroups = (nmaps + per - 1)/per;
-		// (a workgroup covers 32 W ring pairs: nwave of the block mapping counts those)
-		LegK a = make_legk(rs, tb, wk, const_cast<double2*>(leg) + (size_t)b0*leg_bstride, ld, 1, ngroups, leg_bstride);
-		a.nwave = (rs.npairs + 32*W - 1)/(32*W);
-		a.mom = wk.mom.as<double>() + (size_t)b0*a.mom_bs; a.part = a.mom; a.atomic = 1; a.nmaps = nmaps;
-		a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
-		if (prof) prof->begin(st, 1);
-		launch_leg_ana_spin_mm(ng, leg_grid(a), st, a);
-		if (prof) prof->end(st, 1);
-	};
-	const int gmax = std::max(1, leg_max_batch(rs, tb, 2)), r = nmm % 8, n8 = nmm - r;
-	for (int b0 = 0; b0 < n8; b0 += 8*gmax) launch(b0, std::min(8*gmax, n8 - b0), 2);
-	if (r > 4) launch(n8, r, 2); else if (r > 0) launch(n8, r, 1);
-	AlmK ak = make_almk(tb, wk, alm, alm_dtype, alm_cstride, d_mstart, lstride, 0, alm_bstride);
-	hipLaunchKernelGGL(alm_post_spin, alm_grid(tb.lmax + 1, nm, nmm), dim3(256), 0, st, ak);
-	PXS_HIP(hipGetLastError());
-	if (nmm < nb)
-		leg_analysis(st, rs, tb, wk, leg + (size_t)nmm*leg_bstride, (char*)alm + aesz*(size_t)nmm*alm_bstride, alm_dtype, alm_cstride, d_mstart, lstride, 0, prof, ld, 1, 0, 0);
-}
-
-void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWork& wk,
-                  const double2* leg, void* alm, int alm_dtype, long alm_cstride, const uint64_t* d_mstart, long lstride,
-                  int deriv1, LegProfile* prof, long ld, int nb, long alm_bstride, long leg_bstride)
-{
-	PXS_REQUIRE(alm_dtype == PX_C64 || alm_dtype == PX_C128, "alm must be complex64 or complex128");
-	PXS_REQUIRE(nb >= 1, "leg_analysis: nb must be >= 1");
-	if (tb.spin > 0 && !deriv1 && nb >= ana_mm_min() && !wk.deterministic) { leg_analysis_spin_mm(st, rs, tb, wk, leg, alm, alm_dtype, alm_cstride, d_mstart, lstride, prof, ld, nb, alm_bstride, leg_bstride); return; }
-	if (tb.spin == 0 && nb >= ana_mm_min() && !wk.deterministic) { leg_analysis_mm(st, rs, tb, wk, leg, alm, alm_dtype, alm_cstride, d_mstart, lstride, prof, ld, nb, alm_bstride, leg_bstride); return; }
-	const int K = tb.spin == 0 ? k_small_grid(rs, k_ana0(), {4, 2}, 4) : k_small_grid(rs, k_anas(), {3, 2});
-	const int nm = tb.mmax+1;
-	const int nwave = (rs.npairs + 64*K - 1)/(64*K);
-	const long n4 = leg_mom_stride(tb);
-	{	// the ordered (bitwise repeatable) scheme and the launch that records the seeds take one map at a time
-		const bool one_by_one = wk.deterministic || seeds_pending(wk, rs, tb, 1, K);
-		if (nb > 1 && one_by_one) {
-			const size_t aesz = alm_dtype == PX_C64 ? 8 : 16;
-			const int first = wk.deterministic ? nb : 1;
-			for (int b = 0; b < first; b++)
-				leg_analysis(st, rs, tb, wk, leg + (size_t)b*leg_bstride, (char*)alm + aesz*(size_t)b*alm_bstride, alm_dtype, alm_cstride, d_mstart, lstride, deriv1, prof, ld, 1, 0, 0);
-			if (first < nb)
-				leg_analysis(st, rs, tb, wk, leg + (size_t)first*leg_bstride, (char*)alm + aesz*(size_t)first*alm_bstride, alm_dtype, alm_cstride, d_mstart, lstride, deriv1, prof, ld, nb - first, alm_bstride, leg_bstride);
-			return;
-		}
-	}
-	if (const int nmax = leg_max_batch(rs, tb, K); nb > nmax) {      // (grid limit of one launch)
-		const size_t aesz = alm_dtype == PX_C64 ? 8 : 16;
-		for (int b = 0; b < nb; b += nmax)
-			leg_analysis(st, rs, tb, wk, leg + (size_t)b*leg_bstride, (char*)alm + aesz*(size_t)b*alm_bstride, alm_dtype, alm_cstride, d_mstart, lstride, deriv1, prof, ld, std::min(nmax, nb - b), alm_bstride, leg_bstride);
-		return;
-	}
-	wk.mom.ensure(sizeof(double)*(size_t)n4*nb);
-	// Default: the waves of one m add their sums straight into mom with global_atomic_add_f64 -- the blocks of one m run back
-	// to back on one XCD (leg_block), so the row they share sits in that XCD's L2 while they do.  The order of those additions
-	// is not fixed: results repeat to rounding, not bit for bit.  pxs_plan_option("deterministic", 1) (or PXS_DETERMINISTIC=1 when the plan is made) selects the former scheme instead
-	// (per-wave partial moments in scratch, summed in wave order by reduce_partials), for callers that need bitwise repeats.
+	const int nm = tb.mmax+1, nwave = (rs.npairs + 64*K - 1)/(64*K);
 	const bool atomic = !wk.deterministic;
 	std::vector<int> cuts; cuts.push_back(0);
-	if (atomic) {
-		cuts.push_back(nm);
-		PXS_HIP(hipMemsetAsync(wk.mom.p, 0, sizeof(double)*(size_t)n4*nb, st));
-	} else {
-		// chunk m so that the per-wave partial moments stay below part_budget bytes
+	if (atomic) cuts.push_back(nm);
+	else {
 		const size_t budget = wk.part_budget;
 		for (int m = 0; m < nm;) {
 			int m1 = m+1;
@@ -825,10 +717,10 @@ void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWor
 		const int m0 = cuts[c], m1 = cuts[c+1];
 		const long rows = tb.row[m1]-tb.row[m0];
 		if (rows <= 0) continue;
-		LegK a = make_legk(rs, tb, wk, const_cast<double2*>(leg), ld, K, nb, leg_bstride);
-		a.m0 = m0; a.rowbase = tb.row[m0]; a.rows_chunk = rows; a.nmc = m1-m0; a.atomic = atomic ? 1 : 0;
+		LegK a = make_legk(rs, tb, wk, const_cast<double2*>(leg), ld, 64*K, nb, leg_bstride);
+		a.mom = mom; a.m0 = m0; a.rowbase = tb.row[m0]; a.rows_chunk = rows; a.nmc = m1-m0; a.atomic = atomic ? 1 : 0;
 		seeds = seeds_for(wk, rs, tb, 1, K, a); seeds_wait(seeds, st);
-		if (atomic) { a.part = (double*)wk.mom.p; a.rowbase = 0; a.rows_chunk = 0; a.first = nullptr; }
+		if (atomic) { a.part = mom; a.rowbase = 0; a.rows_chunk = 0; a.first = nullptr; }
 		else {
 			PXS_HIP(hipMemsetAsync(wk.first.p, 0, sizeof(int)*(size_t)nwave*(m1-m0), st));
 			a.first = wk.first.as<int>();
@@ -841,9 +733,38 @@ void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWor
 		if (atomic) continue;
 		const long maxrow = tb.row[m0+1] - tb.row[m0];       // rows per m shrink with m
 		hipLaunchKernelGGL(reduce_partials, dim3((unsigned)((4*maxrow+255)/256), m1-m0), dim3(256), 0, st, (const double*)wk.part.p,
-			(double*)wk.mom.p, tb.d_row.as<long>(), (const int*)wk.first.p, m0, m1-m0, tb.row[m0], rows, a.nwave);
+			mom, tb.d_row.as<long>(), (const int*)wk.first.p, m0, m1-m0, tb.row[m0], rows, a.nwave);
 	}
 	seeds_written(seeds, st);
+}
+
+void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWork& wk,
+                  const double2* leg, void* alm, int alm_dtype, long alm_cstride, const uint64_t* d_mstart, long lstride,
+                  int deriv1, LegProfile* prof, long ld, int nb, long alm_bstride, long leg_bstride)
+{
+	PXS_REQUIRE(alm_dtype == PX_C64 || alm_dtype == PX_C128, "alm must be complex64 or complex128");
+	PXS_REQUIRE(nb >= 1, "leg_analysis: nb must be >= 1");
+	const int K = tb.spin == 0 ? k_small_grid(rs, K_ANA0, {4, 2}, 4) : k_small_grid(rs, K_ANAS, {3, 2});
+	const int nm = tb.mmax+1;
+	const int mm_pairs = (tb.spin == 0 ? 64 : 32)*MM_WAVES;      // ring pairs per workgroup of the MFMA form
+	const std::vector<LegLaunch> plan = leg_batch_plan(nb, tb.spin, true, deriv1, wk.deterministic, [&] { return seeds_pending(wk, rs, tb, 1, K); },
+		leg_max_batch(rs, tb, 64*K), 8*leg_max_batch(rs, tb, mm_pairs));
+	print_batch_plan(true, tb.spin, nb, plan);
+	const size_t nmom = (size_t)leg_mom_stride(tb);
+	wk.mom.ensure(sizeof(double)*nmom*nb);
+	if (!wk.deterministic) PXS_HIP(hipMemsetAsync(wk.mom.p, 0, sizeof(double)*nmom*nb, st));      // (the ordered scheme writes every row it reads)
+	for (const LegLaunch& l : plan) {
+		const double2* legl = leg + (size_t)l.b0*leg_bstride;
+		double* mom = wk.mom.as<double>() + nmom*l.b0;
+		if (!l.ng) { leg_analysis_valu(st, rs, tb, wk, K, legl, mom, prof, ld, l.n, leg_bstride); continue; }
+		ensure_coef2(st, tb);
+		LegK a = make_legk_mm(rs, tb, wk, const_cast<double2*>(legl), ld, mm_pairs, l.n, l.ng, leg_bstride);
+		a.mom = mom; a.part = mom; a.atomic = 1;
+		if (prof) prof->begin(st, 1);
+		if (tb.spin == 0) launch_leg_ana_s0_mm(l.ng, leg_grid(a), st, a);
+		else              launch_leg_ana_spin_mm(l.ng, leg_grid(a), st, a);
+		if (prof) prof->end(st, 1);
+	}
 	AlmK ak = make_almk(tb, wk, alm, alm_dtype, alm_cstride, d_mstart, lstride, deriv1, alm_bstride);
 	if (tb.spin == 0) hipLaunchKernelGGL(alm_post_s0, alm_grid(tb.lmax/2 + 1, nm, nb), dim3(256), 0, st, ak);
 	else              hipLaunchKernelGGL(alm_post_spin, alm_grid(tb.lmax + 1, nm, nb), dim3(256), 0, st, ak);

@@ -119,7 +119,8 @@ __device__ __forceinline__ void to_scaled(double mant, int e, double& v, int& sc
 	v = ldexp(mant, e - SC_STEP*s); scale = s;
 }
 
-// coefficient adjusted accordingly (table columns c,d).  This keeps full relative precision near the
+// A wave is 'polar' when all its rings have cos^2 > PXS_POLAR_COS2: it then runs the recurrences in the variable -sin^2(theta) (spin 0) or
+// -2 sin^2(theta/2) (spin s) instead of cos^2(theta) or cos(theta), with the step coefficient adjusted accordingly (table columns c,d).  This keeps full relative precision near the
 // poles, where x = cos(theta) rounds away the information about theta: there the recurrence sits at its double root (step coefficient
 // 2 - (l theta)^2-ish) and an ABSOLUTE error eps in the coefficient grows like l^2 eps -- 4e-13 of the map rms on the rings next to the poles at
 // lmax 240, 3e-12 at lmax 600 (tests/test_grid_fuzz.py found it), against 1e-14 elsewhere.  The form is exact algebra for every ring but cancels
@@ -130,11 +131,11 @@ __device__ __forceinline__ void to_scaled(double mant, int e, double& v, int& sc
 #ifndef PXS_POLAR_COS2
 #define PXS_POLAR_COS2 0.1
 #endif
-__device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) {
-	const int last = min((wv+1)*K*64, a.npairs) - 1;   // most equatorial pair of the wave (wave-uniform; pairs are ordered pole first)
-	const double c = a.cth[last];
+__device__ __forceinline__ bool mm_wave_polar(const LegK& a, int end) {      // a wave of the ring pairs up to `end` (exclusive; wave-uniform)
+	const double c = a.cth[min(end, a.npairs) - 1];   // its most equatorial pair (pairs are ordered pole first)
 	return c*c > PXS_POLAR_COS2;
 }
+__device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { return mm_wave_polar(a, (wv+1)*K*64); }
 
 // make a VGPR copy of a wave-uniform value once, so that v_fma_f64 can take it as the addend next to
 // an SGPR multiplicand (gfx950 allows one scalar source per VALU op; without this the compiler
@@ -225,8 +226,6 @@ __device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) {
 // of the previous flush.
 #ifdef PXS_HOST_SIM
 #define PXS_WAVE_LDS_SYNC() __syncthreads()
-#elif defined(PXS_LDS_NOWAIT)
-#define PXS_WAVE_LDS_SYNC() asm volatile("" ::: "memory")
 #else
 #define PXS_WAVE_LDS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #endif
@@ -292,9 +291,6 @@ __device__ __forceinline__ double leg_flush_sum(const double* red, int lane) {
 }
 // lane j = 4 kk + r holds row r of step kk: rows are t0, t2, t1, t3
 __device__ __forceinline__ int leg_flush_col(int lane) { const int r = lane & 3; return (lane & ~3) | ((r == 1) ? 2 : (r == 2) ? 1 : r); }
-#ifdef PXS_EXP_NORED
-#define LEG_RED_PUT(kk, t0, t1, t2, t3) { asm volatile("" :: "v"(t0), "v"(t1), "v"(t2), "v"(t3)); }     // timing experiment (wrong results)
-#else
 #define LEG_RED_PUT(kk, t0, t1, t2, t3) { \
 	double a_ = t0, b_ = t1, c_ = t2, d_ = t3; \
 	leg_swap32(a_, b_); leg_swap32(c_, d_); \
@@ -302,13 +298,9 @@ __device__ __forceinline__ int leg_flush_col(int lane) { const int r = lane & 3;
 	leg_swap16(u_, v_); \
 	red[((kk)*4 + (lane >> 4))*LEG_RED_STRIDE + (lane & 15)] = u_ + v_; }
 #endif
-#endif
 // nkk steps of the tile -> dst[4 step + c] (c = 0..3: the sums t0..t3 of the step).  atomic: several waves add into the same
 // rows (dst pre-zeroed); otherwise dst belongs to this wave alone
 __device__ __forceinline__ void leg_flush(double* red, double* __restrict__ dst, int lane, int nkk, int atomic) {
-#if defined(PXS_EXP_NORED) || defined(PXS_EXP_NOFLUSH)
-	return;      // timing experiments (wrong results)
-#endif
 	PXS_WAVE_LDS_SYNC();
 	if (lane < 4*nkk) {
 		const double sum = leg_flush_sum(red, lane);
@@ -346,16 +338,92 @@ static inline void mm_lds_add(double* p, double v) { atomicAdd(p, v); }
 #else
 typedef double mm_acc __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ mm_acc mm_mfma(double av, double bv, mm_acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0); }
-#ifdef PXS_LAB_NOLDSADD
-__device__ __forceinline__ void mm_lds_add(double* p, double v) { *p = v; }      // timing experiment (wrong results)
-#else
 __device__ __forceinline__ void mm_lds_add(double* p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-#endif
 #define MM_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #endif
 // step coefficient a x^2 + b' with both a and b' wave-uniform: gfx950 takes one scalar source per VALU op, so b' is copied to a VGPR
 // right at its use (left to the compiler, the copies of all 16 steps of a tile were made early and lived in 64 VGPRs: spills)
 __device__ __forceinline__ double mm_coef(double ca, double x2, double cb) { PXS_VCOPY(vb_, cb); return fma(ca, x2, vb_); }
+// ---- what the four MFMA kernels (leg_{ana,syn}_{s0,spin}_mm) share ----
+// A chain is one recurrence of one ring pair in extended-exponent form (S0Chain, leg_s0.hip; SpinChain, leg_spin.hip): step(ca, cb) advances it by one
+// step with the table row (ca, cb) and returns the value it had, sc < 0 says that it is still below scale 0, rescale() brings it closer, park_sign()
+// gives the parked values of four steps from kq on their sign in the P tile.
+// the (a, b') of the 16 steps from k0 on: four s_load_dwordx16
+__device__ __forceinline__ void mm_load_cf(double (&cf)[32], const double* __restrict__ tab, int k0) {
+#pragma unroll
+	for (int i = 0; i < 32; i++) cf[i] = LDCD(tab, 2L*k0 + i);
+}
+// Park the 16 steps k0 ... k0 + 15 of the chain as rows of the wave's P tile (rows of STRIDE doubles, the lane's column).  kw: first step this wave contributes to
+// (a multiple of 4), n: steps of this m, pend: some chain of the wave is below scale 0 (phase B: such a chain contributes nothing yet and is rescaled every 4 steps).
+template<int STRIDE, class Chain>
+__device__ __forceinline__ void mm_park_tile(Chain& C, const double (&cf)[32], int k0, int kw, int n, bool& pend, double* __restrict__ ptile, int lane) {
+#pragma unroll
+	for (int q4 = 0; q4 < 4; q4++) {
+		const int kq = k0 + 4*q4;
+		double p[4] = {0, 0, 0, 0};
+		if (kq >= kw && kq < n) {
+#pragma unroll
+			for (int i = 0; i < 4; i++) p[i] = C.step(cf[8*q4 + 2*i], cf[8*q4 + 2*i + 1]);
+			if (pend) {
+				if (C.sc < 0) { p[0] = p[1] = p[2] = p[3] = 0.0; C.rescale(); }
+				pend = __any(C.sc < 0);
+			}
+			C.park_sign(kq, p);
+			// rows beyond the last step of this m stay out of the sums (their table rows belong to the next m)
+			if (kq + 1 >= n) p[1] = 0.0;
+			if (kq + 2 >= n) p[2] = 0.0;
+			if (kq + 3 >= n) p[3] = 0.0;
+		}
+#pragma unroll
+		for (int i = 0; i < 4; i++) ptile[(4*q4 + i)*STRIDE + lane] = p[i];
+	}
+}
+// B operands of the synthesis kernels: lane (j, kk) of MFMA step-quad q holds column j & 3 of map 4 (bb NG + g) + (j >> 2) at step q + 4 kk of the tile, read from
+// the pre-scaled alm.  SIGNED (spin s): columns 2, 3 (a-) times sgn_l = (-1)^(par + step)
+template<int NG, bool SIGNED> struct MmSynB {
+	const double* src[NG]; bool ok[NG]; int kk4, cc, par;
+	__device__ __forceinline__ void init(const LegK& a, int bb, long row0, int lane, int par_) {
+		const int jcol = lane & 15; kk4 = lane >> 4; cc = jcol & 3; par = par_;
+#pragma unroll
+		for (int g = 0; g < NG; g++) {
+			const int map = (bb*NG + g)*4 + (jcol >> 2);
+			ok[g] = map < a.nmaps;
+			src[g] = a.almt + (long)(ok[g] ? map : 0)*a.almt_bs + 4*row0 + cc + 16*kk4;
+		}
+	}
+	__device__ __forceinline__ void load(int k0, int n, double (*b)[4]) const {
+#pragma unroll
+		for (int g = 0; g < NG; g++)
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				const int row = k0 + q + 4*kk4;
+				const double v = (ok[g] && row < n) ? src[g][4L*(k0 + q)] : 0.0;
+				b[g][q] = (SIGNED && cc >= 2 && ((par + row) & 1)) ? -v : v;
+			}
+	}
+};
+// Flush of tile tf of the analysis kernels (after the barrier that ends it): the W waves share out the 4 NG rows of the reduction tile; register r of group g holds rows
+// 4 r + lane / 16 of the tile, column lane % 16 = 4 (map in the group) + c.  It is issued behind the MFMAs of the NEXT tile (the two reduction tiles alternate), off the
+// path from the barrier to that tile's recurrence.  SIGNED (spin s): c >= 2 (mu-) times sgn of the row, (-1)^(par + row)
+template<int NG, int W, bool SIGNED>
+__device__ __forceinline__ void mm_flush(const LegK& a, double* __restrict__ red, int tf, int w, int lane, int bb, int n, long row0, int par) {
+	double* __restrict__ redf = red + (tf & 1)*NG*4*64;
+	for (int cidx = w; cidx < 4*NG; cidx += W) {
+		const int g = cidx >> 2, r = cidx & 3;
+		double* rp = redf + cidx*64 + lane;
+		double v = *rp; *rp = 0.0;
+		const int krow = 16*tf + 4*r + (lane >> 4), map = (bb*NG + g)*4 + ((lane & 15) >> 2), c = lane & 3;
+		if (krow < n && map < a.nmaps) {
+			if (SIGNED && c >= 2 && ((par + krow) & 1)) v = -v;
+			double* dst = a.mom + (long)map*a.mom_bs + 4*(row0 + krow) + c;
+#ifdef PXS_HOST_SIM
+			atomicAdd(dst, v);
+#else
+			unsafeAtomicAdd(dst, v);
+#endif
+		}
+	}
+}
 // LDS: [W][16][MM_PSTRIDE] P tiles + [2][4 NG][64] reduction tiles (the staging area of the prologue, 64 W entries of MM_ESTRIDE doubles, lies over both)
 __host__ __device__ constexpr int mm_lds_doubles(int NG, int W) { return W*16*MM_PSTRIDE + 2*NG*4*64 > 64*W*MM_ESTRIDE ? W*16*MM_PSTRIDE + 2*NG*4*64 : 64*W*MM_ESTRIDE; }
 static inline size_t mm_ana_lds(int NG, int W) { return sizeof(double)*(size_t)mm_lds_doubles(NG, W) + 16; }
@@ -372,11 +440,11 @@ __device__ __forceinline__ double mms_xor2(double v) {      // value of lane ^ 2
 #define MMS_XOR2(v) mms_xor2(v)
 #endif
 
-// launchers (defined next to the kernels; K = ring pairs per lane, ng = groups of 4 maps per wave / workgroup, W = waves per workgroup)
+// launchers (defined next to the kernels; K = ring pairs per lane, ng = groups of 4 maps per wave / workgroup)
 void launch_leg_syn_s0(int K, dim3 grid, hipStream_t st, const LegK& a);
 void launch_leg_ana_s0(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a);
 void launch_leg_syn_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);
-void launch_leg_ana_s0_mm(int ng, int W, dim3 grid, hipStream_t st, const LegK& a);
+void launch_leg_ana_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);
 void launch_leg_syn_spin(int K, dim3 grid, hipStream_t st, const LegK& a);
 void launch_leg_ana_spin(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a);
 void launch_leg_syn_spin_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);

@@ -742,3 +742,63 @@ def check_baseline_analysis_forms():
 def test_baseline_analysis_forms_hostsim(): check_baseline_analysis_forms()
 @pytest.mark.gpu
 def test_baseline_analysis_forms_gpu(): check_baseline_analysis_forms()
+
+# launches of the Legendre stage for a call of nb maps at the defaults (4 or more maps: the FP64-MFMA kernels in groups of 8, a remainder of more than 4 as an 8-map
+# group, of 4 or fewer as a 4-map group, a lone left-over map through the VALU kernel)
+BATCH_PLAN = {3: "VALU [0,3)", 4: "mm4 [0,4)", 5: "mm8 [0,5)", 8: "mm8 [0,8)", 9: "mm8 [0,8) VALU [8,9)", 12: "mm8 [0,8) mm4 [8,12)",
+	13: "mm8 [0,8) mm8 [8,13)", 17: "mm8 [0,16) VALU [16,17)"}
+
+def legendre_plans(call, direction, spin, monkeypatch, capfd):
+	"""the launch lists the Legendre stage prints during call() with PXS_CHAIN_VERBOSE set (captured as tests/test_chain_static.py::planned_stage_ids does)"""
+	monkeypatch.setenv("PXS_CHAIN_VERBOSE", "1"); capfd.readouterr()
+	call()
+	monkeypatch.delenv("PXS_CHAIN_VERBOSE")
+	tag = "[pxsht] legendre %s spin %d, " % (direction, spin)
+	return [l.split(" maps: ")[1] for l in capfd.readouterr().err.splitlines() if l.startswith(tag)]
+
+def check_legendre_batch_plan(nt, nph, lmax, monkeypatch, capfd):
+	"""Which kernel serves which map of a batched call -- a routing slip would be slower, not wrong, so the launch list itself is asserted -- and maps 0, nb // 2
+	and nb - 1 of every batched call against their single-map calls: bit for bit where every map took the VALU kernel, to 1e-13 of the maximum (check_batched's
+	bound) where the FP64-MFMA kernels ran.  The rings are those of the F1 grid nt x nph, handed over as a ring set: synthesis and adjoint_synthesis then run the
+	Legendre synthesis and analysis on exactly these nt / 2 ring pairs with all maps of the call in one pass (the 2-D entry points take another ring set for the
+	analysis, and at 154 x 320 one map per pass: no theta chain for 308 points)."""
+	th = np.pi*(np.arange(nt)+0.5)/nt; nbmax = max(BATCH_PLAN)
+	for spin in (0, 2):
+		nc = 1 if spin == 0 else 2
+		kw = dict(theta=th, nphi=np.full(nt, nph, np.uint64), phi0=np.full(nt, 0.2), ringstart=np.arange(nt, dtype=np.uint64)*nph, lmax=lmax,
+			mstart=so._tri_mstart(lmax, lmax), spin=spin)
+		syn = lambda a: sht.synthesis(alm=a, map=np.zeros(a.shape[:-1]+(nt*nph,)), **kw)
+		ana = lambda m: sht.adjoint_synthesis(map=m, alm=np.zeros(m.shape[:-1]+(so.nalm(lmax),), complex), **kw)
+		def planned(direction, call, want):
+			res = []
+			plans = legendre_plans(lambda: res.append(call()), direction, spin, monkeypatch, capfd)
+			print("legendre %s spin %d: %s" % (direction, spin, plans))
+			assert plans == [want], (direction, spin, plans)
+			return res[0]
+		alm = np.stack([so.rand_alm_simple(lmax, nc, 80+i, spin=(spin,)) for i in range(nbmax)])
+		# the single-map calls, once: the maps of the single syntheses are the input of every analysis
+		maps = np.stack([syn(alm[i]) for i in range(nbmax)]); back = np.stack([ana(maps[i]) for i in range(nbmax)])
+		for nb, want in BATCH_PLAN.items():
+			for direction, res, one in (("synthesis", planned("synthesis", lambda: syn(alm[:nb]), want), maps), ("analysis", planned("analysis", lambda: ana(maps[:nb]), want), back)):
+				for i in sorted({0, nb//2, nb-1}):
+					err = np.abs(res[i]-one[i]).max()/np.abs(one[i]).max()
+					print("  %s, %d maps, map %d: %.2e" % (direction, nb, i, err))
+					if "mm" in want: assert err < 1e-13, (direction, spin, nb, i, err)
+					else: assert np.array_equal(res[i], one[i]), (direction, spin, nb, i, err)
+		# the ordered (bitwise repeatable) analysis takes every map alone through the VALU kernel; the synthesis does not look at the option
+		monkeypatch.setattr(sht, "_deterministic", True); sht.clear_plans()
+		got = planned("analysis", lambda: ana(maps[:5]), " ".join("VALU [%d,%d)" % (i, i+1) for i in range(5)))
+		for i in (0, 2, 4): assert np.array_equal(got[i], back[i])
+		planned("synthesis", lambda: syn(alm[:5]), BATCH_PLAN[5])
+		# recurrence seeds forced on at toy size: the launch that records them takes the first map alone, the next call has them
+		monkeypatch.setattr(sht, "_deterministic", None); monkeypatch.setenv("PXS_SEED_MIN_LMAX", "0"); sht.clear_plans()
+		for want in ("VALU [0,1) VALU [1,3)", "VALU [0,3)"):
+			out = planned("synthesis", lambda: syn(alm[:3]), want); got = planned("analysis", lambda: ana(maps[:3]), want)
+			for i in range(3): assert np.array_equal(out[i], maps[i]) and np.array_equal(got[i], back[i])
+		monkeypatch.delenv("PXS_SEED_MIN_LMAX"); sht.clear_plans()
+
+@pytest.mark.hostsim
+def test_legendre_batch_plan_hostsim(monkeypatch, capfd): check_legendre_batch_plan(24, 48, 20, monkeypatch, capfd)
+# 154 rings = 77 ring pairs: two waves of the spin-0 MFMA synthesis, three of the spin one, a partial last wave in each
+@pytest.mark.gpu
+def test_legendre_batch_plan_gpu(monkeypatch, capfd): check_legendre_batch_plan(154, 320, 60, monkeypatch, capfd)

@@ -1,4 +1,4 @@
-# Legendre stage times of mid-size single-map T/Q/U transforms for K sweeps (lab build)
+# Legendre stage times of mid-size single-map T/Q/U transforms for K sweeps (builds with K forced; profiles/r05_k_mid_grids.txt)
 import sys, os, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch

@@ -1,4 +1,4 @@
-# Legendre stage times of small / medium single-map transforms (hipEvent stage timers of the plan), for the K sweeps of tools/ksmall_ab.sh
+# Legendre stage times of small / medium single-map transforms (hipEvent stage timers of the plan), for K sweeps (profiles/r05_k_small_grids.txt)
 import sys, os, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch
