@@ -198,6 +198,23 @@ int pxa_lmatmul(int N, int M, int lmax, int mmax, const uint64_t* d_mstart, int6
  * allocated and freed on `stream` (stream-ordered); no host synchronisation. */
 int pxa_rotate_alm(int lmax, int ncomp, const void* alm_in, int64_t in_cstride, void* alm_out, int64_t out_cstride, int alm_dtype,
                    double psi, double theta, double phi, int device, void* stream);
+/* The filter bank of the wavelet transforms: one alm in any alm_info layout (lmax, mmax, d_mstart, lstride as for pxa_lmatmul; npre
+ * components, one every *_pitch elements) <-> nscale filtered copies.  Copy i is npre dense triangular layouts of band limit L_i
+ * (mmax = L_i, stride 1, element (l, m) at m (2 L_i + 1 - m)/2 + l), one every pitch[i] >= (L_i+1)(L_i+2)/2 elements from the DEVICE
+ * pointer outs[i] / ins[i]; it holds signal up to lmax_i <= min(lmax, L_i).
+ * pxa_bank_split: outs[i](l,m) = filt[i][l] in(l,m) for l <= lmax_i, 0 for lmax_i < l <= L_i; (l,m) the input does not hold count as 0.
+ * pxa_bank_merge: out(l,m) = (out(l,m) if accumulate, else 0) + sum_i filt[i][l] ins[i](l,m) over the scales with l <= lmax_i, added in
+ *   ascending i by one thread per element (bitwise repeatable); every (l,m) of the output layout is written.
+ * Convention for the tables: lmaxs, Ls, outs / ins and the pitches are HOST arrays of nscale entries -- they travel in the kernel
+ * arguments, 32 scales per launch (so a bank of up to 32 scales is one launch that loads each input element once); d_filt is a DEVICE
+ * table f64[nscale][nl], nl > max lmax_i.  complex64 alm use single precision arithmetic with the filter rounded to float.
+ * No host synchronisation; the scale arrays must not overlap the full alm. */
+int pxa_bank_split(int nscale, const int* lmaxs, const int* Ls, void* const* outs, const int64_t* out_pitch, int npre,
+                   int lmax, int mmax, const uint64_t* d_mstart, int64_t lstride, const void* alm_in, int64_t in_pitch, int alm_dtype,
+                   const double* d_filt, int nl, int device, void* stream);
+int pxa_bank_merge(int nscale, const int* lmaxs, const int* Ls, void* const* ins, const int64_t* in_pitch, int npre,
+                   int lmax, int mmax, const uint64_t* d_mstart, int64_t lstride, void* alm_out, int64_t out_pitch, int alm_dtype,
+                   const double* d_filt, int nl, int accumulate, int device, void* stream);
 
 /* flat-sky harmonic helpers around the 2-D map FFT (pixell/enmap.py:1358-1400 map2harm / harm2map / queb_rotmat,
  * :1959-2011 calc_ps2d, :2526-2556 lbin).  d_ly[ny], d_lx[nx]: DEVICE f64 wavenumber axes (enmap.laxes); maps [ny][nx] contiguous.

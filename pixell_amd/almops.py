@@ -189,3 +189,121 @@ def rotate_alm(alm, lmax, psi, theta, phi, inplace=False):
 	res = work.cpu().numpy().reshape(shape)
 	if inplace: alm[...] = res; return alm
 	return res
+
+# ---------------------------------------------------------------------------------------
+# the alm filter bank (include/pxsht.h pxa_bank_split / pxa_bank_merge; csrc/bank.hip)
+# ---------------------------------------------------------------------------------------
+def tri_nelem(L): return (int(L)+1)*(int(L)+2)//2
+
+def _filter_table(filters, lmaxs, nl, ctype):
+	"""f64[nscale, nl]: row i is filters[i] up to lmaxs[i] (zero beyond, or where filters[i] is shorter); rounded to float for complex64 alm"""
+	tab = np.zeros((len(lmaxs), nl))
+	for i, f in enumerate(filters):
+		f = np.asarray(f.detach().cpu().numpy() if _is_tensor(f) else f, dtype=np.float64).reshape(-1)
+		n = min(len(f), int(lmaxs[i])+1, nl)
+		tab[i, :n] = f[:n]
+	if ctype == np.dtype(np.complex64): tab = tab.astype(np.float32).astype(np.float64)
+	return tab
+
+def _bank_tables(lmaxs, Ls, ptrs, pitches):
+	n = len(lmaxs)
+	return ((ctypes.c_int*n)(*[int(v) for v in lmaxs]), (ctypes.c_int*n)(*[int(v) for v in Ls]),
+		(ctypes.c_void_p*n)(*[int(p) for p in ptrs]), (ctypes.c_int64*n)(*[int(v) for v in pitches]))
+
+def _ptr(x): return x.data_ptr() if _is_tensor(x) else x.ctypes.data
+
+def _on_device(x, ctype, tens):
+	"""contiguous array of dtype ctype the kernels can read (numpy inputs are uploaded; in the simulator they stay where they are)"""
+	if tens: return _astype(x, ctype).contiguous()
+	x = np.ascontiguousarray(x, dtype=ctype)
+	if _lib.is_hostsim(): return x
+	device_index()
+	return _torch().from_numpy(x).cuda()
+
+def _to_kind(x, tens):
+	"""the result as the caller's kind: tensors stay, device copies of numpy inputs come back"""
+	return x if (tens or not _is_tensor(x)) else x.cpu().numpy()
+
+def bank_split_groups(ainfo, alm, table, lmaxs, groups):
+	"""pxa_bank_split with the outputs laid out for batched transforms.  alm: [pre..., >= ainfo.nelem] device array (tensor; numpy in
+	the simulator), complex; table: f64[nscale, nl] (numpy); groups: [(L, [scale indices])].  Returns one uninitialised-then-filled array
+	[len(indices), pre..., tri_nelem(L)] per group: scale `indices[k]` is row k, band-limited to lmaxs[...] and zero up to L."""
+	ctype = _np_dtype(alm); pre = tuple(alm.shape[:-1]); npre = int(np.prod(pre, dtype=int))
+	if alm.shape[-1] < ainfo.nelem: raise ValueError("alm too short for this alm_info")
+	flat = _flat2(alm); csz = ctype.itemsize
+	outs = [_alloc_like(flat, (len(idx),)+pre+(tri_nelem(L),), ctype) for L, idx in groups]
+	if npre == 0: return outs
+	order = [(i, L, _ptr(o)+k*npre*tri_nelem(L)*csz) for (L, idx), o in zip(groups, outs) for k, i in enumerate(idx)]
+	tabs = _bank_tables([lmaxs[i] for i, L, p in order], [L for i, L, p in order], [p for i, L, p in order], [tri_nelem(L) for i, L, p in order])
+	bt = _Buf(np.ascontiguousarray(table[[i for i, L, p in order]])); ms = _mstart_buf(ainfo)
+	_lib.check(_lib.load().pxa_bank_split(len(order), *tabs, npre, ainfo.lmax, ainfo.mmax, ms.ptr, ainfo.stride, _ptr(flat), flat.shape[-1], _DT[ctype],
+		bt.ptr, table.shape[-1], device_index(), current_stream()))
+	return outs
+
+def bank_merge_groups(ainfo, arrays, table, lmaxs, groups, out, accumulate=False):
+	"""pxa_bank_merge, the transpose: arrays[g] is [len(indices), pre..., tri_nelem(L)] for groups[g] = (L, indices) (contiguous device arrays);
+	out [pre..., ainfo.nelem] (contiguous, same kind) receives sum_i table[i] * scale i, added to its content if `accumulate`"""
+	ctype = _np_dtype(out); pre = tuple(out.shape[:-1]); npre = int(np.prod(pre, dtype=int))
+	if out.shape[-1] < ainfo.nelem: raise ValueError("out too short for this alm_info")
+	if npre == 0: return out
+	csz = ctype.itemsize
+	order = [(i, L, _ptr(a)+k*npre*tri_nelem(L)*csz) for (L, idx), a in zip(groups, arrays) for k, i in enumerate(idx)]
+	order.sort(key=lambda t: t[0])                  # summed in ascending scale index
+	tabs = _bank_tables([lmaxs[i] for i, L, p in order], [L for i, L, p in order], [p for i, L, p in order], [tri_nelem(L) for i, L, p in order])
+	bt = _Buf(np.ascontiguousarray(table[[i for i, L, p in order]])); ms = _mstart_buf(ainfo)
+	_lib.check(_lib.load().pxa_bank_merge(len(order), *tabs, npre, ainfo.lmax, ainfo.mmax, ms.ptr, ainfo.stride, _ptr(out), out.shape[-1], _DT[ctype],
+		bt.ptr, table.shape[-1], int(bool(accumulate)), device_index(), current_stream()))
+	return out
+
+def _bank_args(ainfo, filters, lmaxs, Ls, ctype):
+	lmaxs = [int(v) for v in lmaxs]
+	Ls = list(lmaxs) if Ls is None else [int(v) for v in Ls]
+	if len(filters) != len(lmaxs) or len(Ls) != len(lmaxs): raise ValueError("filters, lmaxs and Ls must have one entry per scale")
+	if any(l < 0 or l > ainfo.lmax or L < l for l, L in zip(lmaxs, Ls)): raise ValueError("every scale needs 0 <= lmax_i <= min(ainfo.lmax, L_i)")
+	groups = [(L, [i for i, v in enumerate(Ls) if v == L]) for L in sorted(set(Ls))]
+	return lmaxs, Ls, groups, _filter_table(filters, lmaxs, ainfo.lmax+1, ctype)
+
+def bank_split(ainfo, alm, filters, lmaxs, Ls=None):
+	"""The filter bank of a wavelet analysis in one kernel launch: for every scale i a copy of alm[..., nelem] (layout ainfo) multiplied by
+	filters[i][l], truncated to lmaxs[i] and stored in the triangular layout of band limit Ls[i] >= lmaxs[i] (default lmaxs[i]; the rows
+	lmaxs[i] < l <= Ls[i] are zero).  What transfer_alm + alm_info.lmul give scale by scale, without their index arrays and with the input
+	read once.  Returns a list of arrays [..., tri_nelem(Ls[i])]; scales that share L are views of one allocation.  numpy alm are staged
+	through the device, torch CUDA tensors are used in place on the current stream and the results are tensors."""
+	tens = _is_tensor(alm)
+	if not tens: alm = np.asarray(alm)
+	ctype = np.result_type(_np_dtype(alm), np.complex64)
+	if ctype not in (np.dtype(np.complex64), np.dtype(np.complex128)): raise ValueError("bank_split requires complex64 or complex128 arrays")
+	lmaxs, Ls, groups, table = _bank_args(ainfo, filters, lmaxs, Ls, ctype)
+	outs = bank_split_groups(ainfo, _on_device(alm, ctype, tens), table, lmaxs, groups)
+	res = [None]*len(lmaxs)
+	for (L, idx), o in zip(groups, outs):
+		o = _to_kind(o, tens)
+		for k, i in enumerate(idx): res[i] = o[k]
+	return res
+
+def bank_merge(ainfo, alms, filters, lmaxs, Ls=None, out=None, accumulate=False):
+	"""The transpose of bank_split: out[..., lm] = (out[..., lm] if accumulate) + sum_i filters[i][l] alms[i][..., lm] over the scales with
+	l <= lmaxs[i], in one launch and in ascending i (bitwise repeatable).  alms[i]: [..., tri_nelem(Ls[i])]; out: [..., ainfo.nelem] in the
+	layout ainfo (allocated if None).  numpy arrays are staged, torch CUDA tensors used in place."""
+	if len(alms) == 0: raise ValueError("bank_merge needs at least one scale")
+	tens = _is_tensor(alms[0])
+	if any(_is_tensor(a) != tens for a in alms) or (out is not None and _is_tensor(out) != tens): raise ValueError("alms and out must all be numpy arrays or all torch tensors")
+	if not tens: alms = [np.asarray(a) for a in alms]
+	ctype = np.result_type(np.complex64, *[_np_dtype(a) for a in alms])
+	if ctype not in (np.dtype(np.complex64), np.dtype(np.complex128)): raise ValueError("bank_merge requires complex64 or complex128 arrays")
+	lmaxs, Ls, _, table = _bank_args(ainfo, filters, lmaxs, Ls, ctype)
+	pre = tuple(alms[0].shape[:-1])
+	for a, L in zip(alms, Ls):
+		if tuple(a.shape) != pre+(tri_nelem(L),): raise ValueError("bank_merge: scale arrays must be [pre..., (L_i+1)(L_i+2)/2] with common pre-dimensions")
+	if out is None:
+		if accumulate: raise ValueError("bank_merge: accumulate needs out")
+		out = _alloc_like(alms[0], pre+(ainfo.nelem,), ctype); _zero(out)       # (elements outside the layout, e.g. of a strided one, are defined too)
+	elif _np_dtype(out) != ctype or tuple(out.shape[:-1]) != pre: raise ValueError("bank_merge: out must have the alms' dtype and pre-dimensions")
+	direct = (tens and out.is_contiguous()) or (not tens and _lib.is_hostsim() and out.flags.c_contiguous)
+	work = out if direct else _on_device(out, ctype, tens)
+	arrays = [_on_device(a, ctype, tens)[None] for a in alms]             # every scale a group of its own: [1, pre..., nelem]
+	bank_merge_groups(ainfo, arrays, table, lmaxs, [(L, [i]) for i, L in enumerate(Ls)], work, accumulate=accumulate)
+	if work is not out:
+		if tens: out.copy_(work)
+		else: out[...] = _to_kind(work, False)
+	return out

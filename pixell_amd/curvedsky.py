@@ -79,6 +79,14 @@ class alm_info:
 		"""res[a,lm] = lmat[a,b,l]*alm[b,lm] (or the broadcasting product for lmat[...,l]) (curvedsky.py:463-466)"""
 		from . import almops
 		return almops.lmul(self, alm, lmat, out=out)
+	def bank_split(self, alm, filters, lmaxs, Ls=None):
+		"""one filtered, truncated copy of alm per scale, each in the triangular layout of Ls[i] (almops.bank_split)"""
+		from . import almops
+		return almops.bank_split(self, alm, filters, lmaxs, Ls=Ls)
+	def bank_merge(self, alms, filters, lmaxs, Ls=None, out=None, accumulate=False):
+		"""the transpose: the filtered sum of the per-scale alms in this layout (almops.bank_merge)"""
+		from . import almops
+		return almops.bank_merge(self, alms, filters, lmaxs, Ls=Ls, out=out, accumulate=accumulate)
 	def __repr__(self):
 		return "alm_info(lmax=%s,mmax=%s,mstart=%s)" % (str(self.lmax), str(self.mmax), str(self.mstart))
 

@@ -573,3 +573,57 @@ for _cls in (ndmap, dmap):
 	_cls.modlmap  = lambda self, **kw: modlmap(self.shape, self.wcs, **kw)
 	_cls.lbin     = lambda self, *a, **kw: lbin(self, *a, **kw)
 	_cls.posmap   = lambda self, **kw: posmap(self.shape, self.wcs, **kw)
+
+# ---------------------------------------------------------------------------------------
+# bounding boxes and pixel sizes of separable CAR geometries (what pixell_amd.wavelets builds its per-scale geometries from)
+# ---------------------------------------------------------------------------------------
+def _rewind(a, ref, period):
+	"""a moved by whole periods into [ref - period/2, ref + period/2)"""
+	return ref+(np.asarray(a, float)-ref+period/2.0) % period-period/2.0
+
+def _unwind_middle(a, period, ref=0.0):
+	"""the samples a[..., n] of a continuous cyclic coordinate without their period jumps: the middle sample is brought within half a period
+	of ref, and every other one is moved by the whole periods that make the sequence continuous from there outwards"""
+	a = np.array(_rewind(a, ref, period))
+	if a.ndim == 0 or a.shape[-1] < 2: return a
+	jumps = np.round((a[..., 1:]-a[..., :-1])/period)
+	mid = a.shape[-1]//2
+	a[..., mid+1:] -= np.cumsum(jumps[..., mid:], -1)*period
+	a[..., :mid] += np.cumsum(jumps[..., mid-1::-1], -1)[..., ::-1]*period
+	return a
+
+def corners(shape, wcs, npoint=10, corner=True):
+	"""[{bottom left, top right},{dec,ra}] in radians: the outer corners of the first and last pixel (corner=True) or their centres.  The
+	RA of both is on the same side of the wrapping cut: the diagonal is sampled at npoint points and followed without 2 pi jumps,
+	with the middle sample in [-pi, pi)"""
+	off = 0.5 if corner else 0.0
+	pix = np.array([np.linspace(-off, shape[-2]-1+off, num=npoint, endpoint=True), np.linspace(-off, shape[-1]-1+off, num=npoint, endpoint=True)])
+	ra, dec = wcsutils.pix2world(wcs, pix[1], pix[0])
+	return _unwind_middle(np.array([dec, ra])*degree, 2*np.pi).T[[0, -1]]
+
+def skybox2pixbox(shape, wcs, skybox, npoint=10, corner=False, include_direction=False):
+	"""pixel box [{from,to},{y,x}] (fractional) of the coordinate box [{from,to},{dec,ra}], the x pixels followed along the diagonal without
+	jumps of the sky's period; include_direction appends the sign of the pixel direction of each axis"""
+	skybox = np.asarray(skybox, float)
+	coords = np.array([np.linspace(skybox[0, 0], skybox[1, 0], num=npoint, endpoint=True), np.linspace(skybox[0, 1], skybox[1, 1], num=npoint, endpoint=True)])/degree
+	x, y = wcsutils.world2pix(wcs, coords[1], coords[0])
+	wpix = [np.array(x), np.array(y)]
+	if corner: wpix = [v+0.5 for v in wpix]
+	for i, n in enumerate(shape[-2:][::-1]):
+		wpix[i] = _unwind_middle(wpix[i], abs(360.0/wcs.wcs.cdelt[i]), ref=n/2.0+(0.5 if corner else 0.0))
+	pix = np.array(wpix[::-1])
+	res = pix[:, [0, -1]].T
+	if include_direction: res = np.concatenate([res, np.sign(pix[:, 1]-pix[:, 0])[None]], 0)
+	return res
+
+def pixshapebounds(shape, wcs, separable="auto"):
+	"""[{min,max},{height,width}] of the pixels in radians, separable cylindrical geometries only: a row's pixels are dec_hi - dec_lo high
+	and area/height = dRA (sin dec_hi - sin dec_lo)/(dec_hi - dec_lo) wide"""
+	if separable is False or not wcsutils.is_separable(wcs): raise NotImplementedError("pixshapebounds: only separable cylindrical geometries")
+	ny = shape[-2]
+	dec = np.clip(pix2sky(shape, wcs, [np.arange(ny+1)-0.5, np.zeros(ny+1)])[0], -np.pi/2, np.pi/2)
+	heights = dec[1:]-dec[:-1]
+	sdec = np.sin(dec)
+	widths = wcs.wcs.cdelt[0]*degree*(sdec[1:]-sdec[:-1])/heights
+	ps = np.abs(np.array([heights, widths]))
+	return np.array([np.min(ps, 1), np.max(ps, 1)])

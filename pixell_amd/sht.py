@@ -168,6 +168,32 @@ def memory(release=False):
 	_lib.check(_lib.load().pxs_memory(int(bool(release)), st))
 	return dict(malloc_ms=st[0], malloc_calls=int(st[1]), malloc_bytes=int(st[2]), arena_hits=int(st[3]), arena_bytes=int(st[4]), live_bytes=int(st[5]))
 
+class PlanPin:
+	"""Plans that outlive the cache: an object that transforms on a fixed set of geometries again and again (a wavelet transform: one
+	plan per scale group) owns its plans here instead of competing for the PIXELL_AMD_MAX_PLANS slots.  While a pin is active on the
+	calling thread (`with pin:`; pins nest, the innermost is used), grid_plan / ring_plan look in it first, then in the cache, and a plan
+	they have to build goes into the pin and not into the cache.  With no pin active nothing changes.  The plans (and their device
+	scratch) are released with the pin, or by clear()."""
+	def __init__(self): self.plans = {}
+	def __enter__(self):
+		if not hasattr(_tls, "pins"): _tls.pins = []
+		_tls.pins.append(self); return self
+	def __exit__(self, *exc): _tls.pins.pop(); return False
+	def clear(self): self.plans.clear()
+	def __len__(self): return len(self.plans)
+
+def _cached_plan(key, make):
+	"""the plan of `key`: from the active pin, else from the cache, else make() -- kept by the pin if there is one, by the cache otherwise"""
+	pins = getattr(_tls, "pins", None)
+	pin = pins[-1] if pins else None
+	p = pin.plans.get(key) if pin is not None else None
+	if p is None: p = _plans.get(key)
+	if p is None:
+		p = Plan(make())
+		if pin is None: _plans[key] = p
+	if pin is not None: pin.plans[key] = p
+	return p
+
 _deterministic = None
 def set_deterministic(on=True):
 	"""Bitwise repeatable transforms (pxs_plan_option "deterministic", include/pxsht.h): by default the Legendre analysis adds the
@@ -196,26 +222,24 @@ def grid_plan(geometry, ntheta, nphi, phi0, flip, lmax, mmax, mstart, lstride=1)
 	the order they were issued, whatever their streams -- include/pxsht.h)"""
 	ms = np.ascontiguousarray(np.asarray(mstart)[:mmax+1], dtype=np.uint64)
 	key = ("g", geometry, int(ntheta), int(nphi), float(phi0), bool(flip[0]), bool(flip[1]), int(lmax), int(mmax), ms.tobytes(), int(lstride), device_index())
-	p = _plans.get(key)
-	if p is None:
+	def make():
 		h = ctypes.c_void_p()
 		_lib.check(_lib.load().pxs_plan_grid2d(ctypes.byref(h), geometry.encode(), int(ntheta), int(nphi), float(phi0),
 			int(bool(flip[0])), int(bool(flip[1])), int(lmax), int(mmax), ms.ctypes.data, int(lstride), device_index()))
-		p = Plan(h); _plans[key] = p
-	return p
+		return h
+	return _cached_plan(key, make)
 
 def ring_plan(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride=1, pixstride=1):
 	th = np.ascontiguousarray(theta, dtype=np.float64); nph = np.ascontiguousarray(nphi, dtype=np.uint64)
 	p0 = np.ascontiguousarray(phi0, dtype=np.float64); rs = np.ascontiguousarray(ringstart, dtype=np.uint64)
 	ms = np.ascontiguousarray(np.asarray(mstart)[:mmax+1], dtype=np.uint64)
 	key = ("r", th.tobytes(), nph.tobytes(), p0.tobytes(), rs.tobytes(), int(pixstride), int(lmax), int(mmax), ms.tobytes(), int(lstride), device_index())
-	p = _plans.get(key)
-	if p is None:
+	def make():
 		h = ctypes.c_void_p()
 		_lib.check(_lib.load().pxs_plan_rings(ctypes.byref(h), len(th), th.ctypes.data, nph.ctypes.data, p0.ctypes.data, rs.ctypes.data,
 			int(pixstride), int(lmax), int(mmax), ms.ctypes.data, int(lstride), device_index()))
-		p = Plan(h); _plans[key] = p
-	return p
+		return h
+	return _cached_plan(key, make)
 
 def _ncomp(spin, mode):
 	if mode == "DERIV1": return 1, 2
