@@ -50,13 +50,14 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 	}
 	int k = 0;
 	if (__any(alive_any)) {
-		// phase A: nobody at scale 0 yet -> recurrence only, 4 steps per check (S0_PHASE_A)
+		// phase A: nobody live yet (LEG_LIVE) -> recurrence only, 4 steps per check (S0_PHASE_A)
 		S0_SEEDED_PHASE_A
 		k = PXS_UNIFORM_INT(k); coef = (const double4_t*)PXS_UNIFORM_LONG((long)coef);
 		PXS_COUNT(0, (long)(nk - k)*K*6 + (a.seed_mode != 2 ? (long)k*K*2 : 0L));
 		// phase B: some lanes are still below scale 0.  The steps are the plain fast steps (no per-lane gating); every
 		// 4 steps the lanes below scale 0 are rescaled.  Such a lane accumulates scaled-up garbage meanwhile; its sums are
-		// reset when it reaches scale 0 (its true terms before that are < 2^-340 of the final value).
+		// reset when it reaches scale 0 (its true terms before that are < 2^-340 of the final value).  A lane at scale 0 accumulates
+		// from the wave's start on, whatever its value.
 		while (k + 1 < nk) {
 			bool pend = false;
 #pragma unroll
@@ -264,11 +265,11 @@ __device__ __forceinline__ bool s0_chain_init(const LegK& a, int p, int m, bool 
 	if (alive) { double mt; int e; pow_scaled(sth, m, mt, e); to_scaled(mt, e, C.lam2, C.sc); }
 	return alive;
 }
-// phase A (S0_PHASE_A for one chain): recurrence only until the first lane of the wave is at scale 0; returns the step reached
+// phase A (S0_PHASE_A for one chain): recurrence only until the first lane of the wave is live (LEG_LIVE); returns the step reached
 __device__ __forceinline__ int s0_chain_phase_a(S0Chain& C, const double4_t* __restrict__ coef, bool polar, int nk) {
 	int k = 0;
 	while (k + 4 <= nk) {
-		if (__any(C.sc == 0 && C.lam2 != 0.0)) break;
+		if (__any(LEG_IS_LIVE(C.lam2, C.sc))) break;
 		const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3);
 		const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b;
 		C.lam1 = fma(fma(q0.a, C.csq, b0), C.lam2, C.lam1);
@@ -298,7 +299,7 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 	const bool alive = s0_chain_init(a, pbase + tid, m, polar, C);      // wave w owns the pairs [64 w, 64 w + 64) of the chunk
 	if (tid == 0) *s_kmin = nk;
 	__syncthreads();
-	// phase A, per wave: recurrence only until the first lane of the wave is at scale 0; kw = the first step this wave contributes to
+	// phase A, per wave: recurrence only until the first lane of the wave is live; kw = the first step this wave contributes to
 	const bool wave_alive = __any(alive);
 	const int kw = wave_alive ? PXS_UNIFORM_INT(s0_chain_phase_a(C, a.coef + row0, polar, nk)) : nk + 16;
 	if (lane == 0) atomicMin(s_kmin, kw);
@@ -412,7 +413,7 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const Le
 #pragma unroll
 		for (int rb = 0; rb < 4; rb++) { acc[g][rb][0] = 0; acc[g][rb][1] = 0; acc[g][rb][2] = 0; acc[g][rb][3] = 0; }
 	long ntile = 0;
-	// phase A: recurrence only until the first lane of the wave is at scale 0 (a wave without a live ring skips the loop below)
+	// phase A: recurrence only until the first lane of the wave is live (a wave without a live ring skips the loop below)
 	const bool wave_alive = __any(alive);
 	const int kw = PXS_UNIFORM_INT(wave_alive ? s0_chain_phase_a(C, a.coef + row0, polar, nk) : nk + 16);      // (explicitly wave-uniform: left as a select, the loop below was compiled as divergent and the prefetched coefficient rows went to VGPRs)
 	{

@@ -60,7 +60,7 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 #define SPIN_PHASE_A \
 	while (j + 4 <= nl) { \
 		bool act = false; \
-		_Pragma("unroll") for (int s = 0; s < K; s++) act |= (S.scp[s] == 0 && S.gp2[s] != 0.0) || (S.scm[s] == 0 && S.gm2[s] != 0.0); \
+		_Pragma("unroll") for (int s = 0; s < K; s++) act |= LEG_IS_LIVE(S.gp2[s], S.scp[s]) || LEG_IS_LIVE(S.gm2[s], S.scm[s]); \
 		if (__any(act)) break; \
 		const double4_t q0 = LDC(coef, j), q1 = LDC(coef, j+1), q2 = LDC(coef, j+2), q3 = LDC(coef, j+3); \
 		_Pragma("unroll") for (int s = 0; s < K; s++) { \
@@ -370,11 +370,11 @@ __device__ __forceinline__ bool spin_chain_init(const LegK& a, int p, int m, int
 	}
 	return alive;
 }
-// phase A: recurrence only until the first lane of the wave is at scale 0; returns the step reached (tab: (a, b) of step k at tab[2 k])
+// phase A: recurrence only until the first lane of the wave is live (LEG_LIVE); returns the step reached (tab: (a, b) of step k at tab[2 k])
 __device__ __forceinline__ int spin_chain_phase_a(SpinChain& C, const double* __restrict__ tab, int n) {
 	int k = 0;
 	while (k + 4 <= n) {
-		if (__any(C.sc == 0 && C.g2 != 0.0)) break;
+		if (__any(LEG_IS_LIVE(C.g2, C.sc))) break;
 		double cq[8];
 #pragma unroll
 		for (int i = 0; i < 8; i++) cq[i] = LDCD(tab, 2L*k + i);
@@ -407,7 +407,7 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_
 	const double* __restrict__ tab = reinterpret_cast<const double*>(a.coef2) + 2*row0;      // (a, b) of step k at tab[2 k]
 	if (tid == 0) *s_kmin = nl;
 	__syncthreads();
-	// phase A, per wave: recurrence only until the first lane of the wave is at scale 0
+	// phase A, per wave: recurrence only until the first lane of the wave is live
 	const bool wave_alive = __any(alive);
 	const int kw = PXS_UNIFORM_INT(wave_alive ? spin_chain_phase_a(C, tab, nl) : nl + 16);
 	if (lane == 0) atomicMin(s_kmin, kw);
@@ -519,7 +519,7 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const 
 		for (int rb = 0; rb < 4; rb++) { acc[g][rb][0] = 0; acc[g][rb][1] = 0; acc[g][rb][2] = 0; acc[g][rb][3] = 0; }
 	long ntile = 0;
 	const double* __restrict__ tab = reinterpret_cast<const double*>(a.coef2) + 2*row0;      // (a, b) of step k at tab[2 k]
-	// phase A: recurrence only until the first lane of the wave is at scale 0 (a wave without a live ring skips the loop below)
+	// phase A: recurrence only until the first lane of the wave is live (a wave without a live ring skips the loop below)
 	const bool wave_alive = nl > 0 && __any(alive);
 	const int kw = PXS_UNIFORM_INT(wave_alive ? spin_chain_phase_a(C, tab, nl) : max(nl, 0) + 16);
 	{

@@ -16,8 +16,8 @@
 //    accumulators stay in VGPRs for the whole l loop;
 //  * extended exponent: lambda_mm ~ sin^m(theta) underflows for large m, so a chain starts as
 //    (mantissa, scale) with value = mantissa * 2^(800*scale), is advanced without accumulating
-//    until some lane of the wave reaches scale 0, then advanced with gated accumulation until all
-//    lanes have, then runs the branch-free fast loop;
+//    until some lane of the wave is live (scale 0 and |value| >= LEG_LIVE = 2^-140, legendre_dev.hpp), then advanced with
+//    accumulation until all lanes are at scale 0, then runs the branch-free fast loop;
 //  * analysis needs the sum over rings (lanes) for every l: the 4 sums of a step are reduce-scattered over the lanes with
 //    v_permlane32_swap / v_permlane16_swap, one ds_write_b64 per step parks them in a tile of 16 steps; at a flush lane j owns
 //    output j, adds its 16 partial sums and the wave issues one contiguous 512-byte global_atomic_add_f64 into the moments
@@ -536,7 +536,10 @@ static int leg_max_batch(const RingSet& rs, const LegTables& tb, int pairs) {
 	const long nwave = (rs.npairs + (long)pairs - 1)/pairs, per = 8L*((tb.mmax + 1 + 7)/8)*std::max<long>(nwave, 1);
 	return (int)std::max<long>(1, std::min<long>(1 << 20, ((1L << 31) - 1)/per));
 }
-// seeds of (ring set, spin, direction, K): allocate on first use if the plan's budget allows; returns the mode for this launch
+// seeds of (ring set, spin, direction, K): allocate on first use if the plan's budget allows; returns the mode for this launch.
+// The step a seed records depends on the rule that ends phase A (LEG_LIVE).  That rule is a compile-time constant of the library, and
+// seeds live in device memory of the process that recorded them, so a seed is never loaded under another rule than it was recorded
+// under; the two directions of a plan record their own seeds (dir is part of the key) under the same constant.
 static LegWork::Seeds* seeds_for(LegWork& wk, const RingSet& rs, const LegTables& tb, int dir, int K, LegK& a) {
 	a.seed_mode = 0; a.seed_d = nullptr; a.seed_i = nullptr;
 	{ const char* e = getenv("PXS_SEED_GB"); if (e) wk.seed_budget = (size_t)atol(e) << 30; }

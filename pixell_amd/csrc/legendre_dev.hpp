@@ -11,6 +11,30 @@ namespace pxs {
 static constexpr double SC_BIG   = 0x1p+400;
 static constexpr double SC_SMALL = 0x1p-800;
 static constexpr int    SC_STEP  = 800;
+// A chain counts as LIVE -- its wave or workgroup leaves phase A and starts the full-cost accumulating steps -- when it is at scale 0
+// AND its value has reached LEG_LIVE.  (Until this constant existed, scale 0 alone did: the largest |lambda| of the wave was then about
+// 2^-400, and the steps from there to ~2^-100 of the final size ran at full cost on terms nobody can see: 3.9 % of the accumulating
+// steps of a lmax 10^4 transform.)
+// The bound.  Phase A tests once per 4 steps, so what a wave drops are the values of a chain at the test that found it below LEG_LIVE
+// and at the three steps after it (the value after the fourth step is tested again).  A chain value is the normalised lambda over
+// the step's alpha (LegTables::alpha, folded into the pre-scaled alm and the moments), so |lambda| = |value| |alpha|.
+//  * Growth.  Below its turning point lambda_lm grows monotonically and one degree multiplies it by less than x / eps_{l+1} <
+//    x sqrt(2 m / (l - m)), x = cos(theta).  A chain that starts AT scale 0 has sin^m(theta) >= 2^-400, so m x^2 / 2 <~ 400 ln 2 and
+//    2 m x^2 < 1110 whatever m is: three spin-0 steps (6 degrees) grow it by < 1110^3 / sqrt(6!) < 2^26, four by < 1110^4 / sqrt(8!)
+//    < 2^33; spin-s steps are one degree each and grow less.  (The "< 2^60 in 4 steps" of the phase-A comment below is the bound
+//    for ANY chain, x = 1 at m = 6 10^4: it guards the overflow, where chains below scale 0 count too.  The 2^30 one can read off a
+//    lmax 10^4 table next to l = m is the same thing as the 2^33 here, seen at one size.)
+//  * |alpha| <= alpha_0 = sqrt(2 m + 3) c_m ~ 0.6 m^(3/4): 2^9 at m = 10^4, < 2^12 up to m = 10^5; it falls like 1/k from there.
+//  So every dropped term has |lambda| < 2^-140 2^26 2^12 = 2^-102 < 2^-100 up to lmax 10^5.  Counted over every chain of the lmax 10^4
+//  ring set (the chains that come up from below scale 0 included; tools/leg_live_count.cpp): largest 4-step growth 2^32.3 (spin 0),
+//  2^18.6 (spin 2); largest dropped |lambda| 2^-111.8 (spin 0), 2^-126.8 (spin 2), and 2^-110.3 / 2^-126.4 at lmax 4 10^4.  2^-130 leaves
+//  2^-102.1 and 2^-100.6 at those two sizes -- no margin -- and saves 0.2 % more steps; 2^-140 it is.
+// A synthesised pixel is therefore off by less than nl 2^-100 max|a_lm| and an analysis moment by less than nring 2^-100 max|ring data|:
+// absolute errors, relative to the input's largest value, not to the pixel's or moment's own size.
+// Phase B's per-lane join is unchanged (scale 0).  The constant is compile-time: seeds, both directions and all eight kernels
+// start under the same rule within a process by construction.
+static constexpr double LEG_LIVE = 0x1p-140;
+#define LEG_IS_LIVE(v, sc) ((sc) == 0 && fabs(v) >= LEG_LIVE)
 
 struct double4_t { double a, b, c, d; };
 // Wave-uniform table rows are fetched through the constant address space: that makes them scalar loads (s_load_dwordx8)
@@ -158,7 +182,7 @@ __device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { r
 // global_load: seen when the seed stores entered the kernels -- leg_syn 101 -> 123 ms at config 3)
 #define PXS_UNIFORM_LONG(x) ((long)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)(x) >> 32)) << 32) | (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)(x))))
 #endif
-// Recurrence seeds.  Phase A (recurrence only, no accumulation, until the first lane of the wave reaches scale 0) is the same
+// Recurrence seeds.  Phase A (recurrence only, no accumulation, until the first lane of the wave is live, LEG_LIVE) is the same
 // for every transform on a plan: ~18 % of the steps of a live (wave, m) at a third of the cost of an accumulating step, i.e.
 // ~5 % of the Legendre time, plus the sin^m start values.  The first launch on a ring set records the state it ends in, later
 // launches load it: K x 20 bytes (spin 0) or K x 40 bytes (spin s) per lane.
@@ -193,14 +217,14 @@ __device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { r
 		} \
 	}
 
-// Phase A of the spin-0 kernels: no lane of the wave has reached scale 0 yet, so nothing is
+// Phase A of the spin-0 kernels: no lane of the wave is live yet (scale 0 and |value| >= LEG_LIVE), so nothing is
 // accumulated.  Four recurrence steps per iteration with the four coefficient rows fetched together;
 // the rescale / activity test runs once per 4 steps (a chain grows by < 2^60 in 4 steps, far from
-// overflow at 2^1024, and entering the accumulating phases a few steps late only drops terms < 2^-340).
+// overflow at 2^1024; what the late start drops: see LEG_LIVE).
 #define S0_PHASE_A \
 	while (k + 4 <= nk) { \
 		bool act = false; \
-		_Pragma("unroll") for (int s = 0; s < K; s++) act |= (sc[s] == 0 && lam2[s] != 0.0); \
+		_Pragma("unroll") for (int s = 0; s < K; s++) act |= LEG_IS_LIVE(lam2[s], sc[s]); \
 		if (__any(act)) break; \
 		const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3); \
 		const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b; \
