@@ -36,8 +36,8 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 	const bool polar = leg_wave_polar(a, wv, K);
 #pragma unroll
 	for (int s = 0; s < K; s++) {
-		const int p = (wv*K + s)*64 + lane;
-		const bool valid = p < a.npairs;
+		const int p = leg_pair_u(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
 		rn[s] = valid ? a.ring_n[p] : -1; rs[s] = valid ? a.ring_s[p] : -1;
 		x[s] = valid ? a.cth[p] : 0.0;
 		const double sth = valid ? a.sth[p] : 0.0;
@@ -105,8 +105,8 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 	double2* __restrict__ out = a.leg + (long)bb*a.leg_bs + (long)m*a.ld;
 #pragma unroll
 	for (int s = 0; s < K; s++) {      // ring indices and cos(theta) are re-read here rather than kept in registers through the loops
-		const int p = (wv*K + s)*64 + lane;
-		const bool valid = p < a.npairs;
+		const int p = leg_pair_u(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
 		const int rn_ = valid ? a.ring_n[p] : -1, rs_ = valid ? a.ring_s[p] : -1;
 		const double x_ = valid ? a.cth[p] : 0.0;
 		if (rn_ >= 0) out[rn_] = make_double2(p1r[s] + x_*p2r[s], p1i[s] + x_*p2i[s]);
@@ -149,8 +149,8 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 	const bool polar = leg_wave_polar(a, wv, K);
 	// ring data of slot s: sum and (difference x cos theta) of the north and south ring
 	auto load_data = [&](int s) {
-		const int p = (wv*K + s)*64 + lane;
-		const bool valid = p < a.npairs;
+		const int p = leg_pair(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
 		const int rn = valid ? a.ring_n[p] : -1, rs = valid ? a.ring_s[p] : -1;
 		const double x = valid ? a.cth[p] : 0.0;
 		const double2 vn = rn >= 0 ? in[rn] : make_double2(0, 0);
@@ -160,8 +160,8 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 	};
 #pragma unroll
 	for (int s = 0; s < K; s++) {
-		const int p = (wv*K + s)*64 + lane;
-		const bool valid = p < a.npairs;
+		const int p = leg_pair(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
 		const double x = valid ? a.cth[p] : 0.0;
 		const double sth = valid ? a.sth[p] : 0.0;
 		csq[s] = polar ? -sth*sth : x*x;

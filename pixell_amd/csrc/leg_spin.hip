@@ -20,8 +20,8 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 	bool alive_any = false;
 #pragma unroll
 	for (int s = 0; s < K; s++) {
-		const int p = (wv*K + s)*64 + lane;
-		const bool valid = p < a.npairs;
+		const int p = leg_pair(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
 		rn[s] = valid ? a.ring_n[p] : -1; rs[s] = valid ? a.ring_s[p] : -1;
 		const double cth = valid ? a.cth[p] : 0.0;
 		const double sth = valid ? a.sth[p] : 0.0;
@@ -187,8 +187,9 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 	// Q = (P+M)/2, U = -i (P-M)/2.  The ring indices are re-read here rather than kept in registers through the loops.
 #pragma unroll
 	for (int s = 0; s < K; s++) {
-		const int p = (wv*K + s)*64 + lane;
-		const int rn_ = p < a.npairs ? a.ring_n[p] : -1, rs_ = p < a.npairs ? a.ring_s[p] : -1;
+		const int p = leg_pair(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
+		const int rn_ = valid ? a.ring_n[p] : -1, rs_ = valid ? a.ring_s[p] : -1;
 		if (rn_ >= 0) {
 			outq[rn_] = make_double2(0.5*(pnr[s] + mnr[s]), 0.5*(pni[s] + mni[s]));
 			outu[rn_] = make_double2(0.5*(pni[s] - mni[s]), -0.5*(pnr[s] - mnr[s]));
@@ -259,8 +260,9 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 	double tpnr[K], tpni[K], tmnr[K], tmni[K], tpsr[K], tpsi[K], tmsr[K], tmsi[K];
 	auto load_data = [&](int s) {
 		// ring indices are re-read here rather than kept in registers through the loops (the kernel sits at the 256-VGPR line)
-		const int p = (wv*K + s)*64 + lane;
-		const int rn_ = p < a.npairs ? a.ring_n[p] : -1, rs_ = p < a.npairs ? a.ring_s[p] : -1;
+		const int p = leg_pair(a, wv, K, s, lane);
+		const bool valid = leg_pair_valid(a, p);
+		const int rn_ = valid ? a.ring_n[p] : -1, rs_ = valid ? a.ring_s[p] : -1;
 		double2 q = rn_ >= 0 ? inq[rn_] : make_double2(0, 0), u = rn_ >= 0 ? inu[rn_] : make_double2(0, 0);
 		tpnr[s] = q.x - u.y; tpni[s] = q.y + u.x; tmnr[s] = q.x + u.y; tmni[s] = q.y - u.x;
 		q = rs_ >= 0 ? inq[rs_] : make_double2(0, 0); u = rs_ >= 0 ? inu[rs_] : make_double2(0, 0);

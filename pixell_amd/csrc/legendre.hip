@@ -17,7 +17,8 @@
 //  * extended exponent: lambda_mm ~ sin^m(theta) underflows for large m, so a chain starts as
 //    (mantissa, scale) with value = mantissa * 2^(800*scale), is advanced without accumulating
 //    until some lane of the wave is live (scale 0 and |value| >= LEG_LIVE = 2^-140, legendre_dev.hpp), then advanced with
-//    accumulation until all lanes are at scale 0, then runs the branch-free fast loop;
+//    accumulation until all lanes are at scale 0, then runs the branch-free fast loop; a wave's 64 K pairs are consecutive, pole first, with the
+//    padding in wave 0 (leg_pair_of);
 //  * analysis needs the sum over rings (lanes) for every l: the 4 sums of a step are reduce-scattered over the lanes with
 //    v_permlane32_swap / v_permlane16_swap, one ds_write_b64 per step parks them in a tile of 16 steps; at a flush lane j owns
 //    output j, adds its 16 partial sums and the wave issues one contiguous 512-byte global_atomic_add_f64 into the moments
@@ -614,7 +615,8 @@ static int k_small_grid(const RingSet& rs, int kdef, std::initializer_list<int> 
 	// (3) up to 1400 ring pairs (lmax ~2500: 2700 rings) the synthesis kernels are still 5-12 % faster with K = 2 and the scalar analysis 2-4 % with K = 4; at lmax 4000 the defaults
 	// are 20 % ahead (profiles/r05_k_mid_grids.txt)
 	if (kmid > 0 && rs.npairs <= 1400) return kmid;
-	auto eligible = [&](int k) { const int last = std::min(64*k, rs.npairs) - 1; return last >= 0 && rs.cth[last]*rs.cth[last] > PXS_POLAR_COS2; };
+	// (the first wave's most equatorial pair under the kernels' pair map, leg_pair_of: the first wave is the one that holds the padding)
+	auto eligible = [&](int k) { const int last = leg_wave_last_pair(rs.npairs, k, 0); return last >= 0 && rs.cth[last]*rs.cth[last] > PXS_POLAR_COS2; };
 	if (eligible(kdef)) return kdef;
 	for (int k : smaller) if (k < kdef && eligible(k)) return k;
 	return kdef;

@@ -159,7 +159,20 @@ __device__ __forceinline__ bool mm_wave_polar(const LegK& a, int end) {      // 
 	const double c = a.cth[min(end, a.npairs) - 1];   // its most equatorial pair (pairs are ordered pole first)
 	return c*c > PXS_POLAR_COS2;
 }
-__device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { return mm_wave_polar(a, (wv+1)*K*64); }
+// Ring pair -> (wave, block s, lane) of the VALU kernels, the one definition of it.  A wave holds 64 K consecutive ring pairs, pole first, in K blocks of 64;
+// the nwave K 64 - npairs slots without a pair sit in front of pair 0, in wave 0, the polar wave, which is dead or late for almost every m.  (They used to sit behind
+// the last pair, in the most equatorial wave, which is live from the smallest l on for every m: its empty lanes ran every step.)  Every wave's most equatorial pair
+// -- the one that decides when the wave leaves phase A -- lies `pad` pairs polewards of where it lay, so no wave starts earlier than before.
+// (the MFMA kernels keep their own partition: wave w of workgroup wv holds the pairs from 64 (W wv + w) on)
+__host__ __device__ constexpr int leg_pair_of(int npairs, int nwave, int K, int wv, int s, int lane) { return (wv*K + s)*64 + lane - (nwave*K*64 - npairs); }
+__host__ __device__ constexpr int leg_wave_last_pair(int npairs, int K, int wv) { return leg_pair_of(npairs, (npairs + 64*K - 1)/(64*K), K, wv, K - 1, 63); }      // the wave's most equatorial pair; >= 0 whenever npairs > 0 (the wave count is the launch's: make_legk)
+// (1451 pairs = 7 192 + 107 = 5 256 + 171 = 2 512 + 427: wave 0 holds 107, 171, 427 pairs for K = 3, 4, 8, the last wave ends at the last pair, a full set has no padding)
+static_assert(leg_wave_last_pair(1451, 3, 0) == 106 && leg_wave_last_pair(1451, 4, 0) == 170 && leg_wave_last_pair(1451, 8, 0) == 426, "pair map: first wave");
+static_assert(leg_wave_last_pair(1451, 3, 7) == 1450 && leg_wave_last_pair(1451, 4, 5) == 1450 && leg_wave_last_pair(1451, 8, 2) == 1450, "pair map: last wave");
+static_assert(leg_pair_of(1451, 8, 3, 0, 0, 0) == -85 && leg_pair_of(1451, 8, 3, 0, 1, 21) == 0 && leg_pair_of(512, 2, 4, 0, 0, 0) == 0 && leg_wave_last_pair(30, 4, 0) == 29, "pair map: padding");
+__device__ __forceinline__ int leg_pair(const LegK& a, int wv, int K, int s, int lane) { return leg_pair_of(a.npairs, a.nwave, K, wv, s, lane); }
+__device__ __forceinline__ bool leg_pair_valid(const LegK& a, int p) { return (unsigned)p < (unsigned)a.npairs; }
+__device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { return mm_wave_polar(a, leg_wave_last_pair(a.npairs, K, wv) + 1); }
 
 // make a VGPR copy of a wave-uniform value once, so that v_fma_f64 can take it as the addend next to
 // an SGPR multiplicand (gfx950 allows one scalar source per VALU op; without this the compiler
@@ -182,6 +195,9 @@ __device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { r
 // global_load: seen when the seed stores entered the kernels -- leg_syn 101 -> 123 ms at config 3)
 #define PXS_UNIFORM_LONG(x) ((long)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)(x) >> 32)) << 32) | (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)(x))))
 #endif
+// leg_pair with the block's first pair taken through v_readfirstlane: for leg_syn_s0, which is held to 72 VGPRs and spills 52 bytes with it against 68 without (44 before
+// the padding moved; profiles/leg_kernel_resources.txt).  Not for the analysis kernels: leg_ana_s0<8> 159 -> 168, leg_ana_spin<4> 152 -> 156 VGPRs.
+__device__ __forceinline__ int leg_pair_u(const LegK& a, int wv, int K, int s, int lane) { return PXS_UNIFORM_INT(leg_pair(a, wv, K, s, 0)) + lane; }
 // Recurrence seeds.  Phase A (recurrence only, no accumulation, until the first lane of the wave is live, LEG_LIVE) is the same
 // for every transform on a plan: ~18 % of the steps of a live (wave, m) at a third of the cost of an accumulating step, i.e.
 // ~5 % of the Legendre time, plus the sin^m start values.  The first launch on a ring set records the state it ends in, later

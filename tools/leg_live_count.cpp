@@ -6,11 +6,17 @@
 // Prints, per kernel and threshold, sum over (m, wave) of (steps - start step) x K x FMAs per step (what PXS_COUNT adds up in a
 // seeded launch) and its ratio to the scale-0 rule, then log2 of the largest |lambda| (chain value x alpha) any chain has at a step
 // before it is live itself -- an upper bound of what its wave drops, since a wave starts no later than any of its lanes.
+// Then, at LEG_LIVE = 2^-140, three ways of dealing ring pairs to waves and blocks: (a) 64 K consecutive pairs per wave with the padding behind the last pair
+// (the partition until leg_pair_of existed), (b) the padding in front of pair 0, in wave 0 (leg_pair_of: what the kernels do and PXS_COUNT adds up), (c) = (b) and
+// a block of 64 pairs accumulates only from the first 4-step test at which one of its chains, or of a more polar block of the wave, is live: the recurrence FMAs
+// (2 of 6, 4 of 12) from the wave's start, the accumulation FMAs from the block's.  (c) is modelled, not built: no kernel does it.
+// Runtime on 16 cores: lmax 10^4 at stride 1 about 10 minutes, at stride 7 a minute and a half (the ratios agree to four digits); lmax 4000 (C2: Ncc 8064) at stride 1 a minute.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
+#include <climits>
 typedef long double LDb;
 static const double SC_BIG = 0x1p+400, SC_SMALL = 0x1p-800;
 static const int SC_STEP = 800;
@@ -32,8 +38,8 @@ static const char* THRN[NT] = {"scale 0", "2^-340", "2^-200", "2^-160", "2^-140"
 static bool live(double v, int sc, int t) { return sc == 0 && (t == 0 ? v != 0.0 : fabs(v) >= THR[t]); }
 static double lg(double v, int sc, double alpha) { return (v == 0.0 || alpha == 0.0) ? -1e9 : log2(fabs(v)) + 800.0*sc + log2(fabs(alpha)); }
 
-int main(int argc, char** argv) {
-	const int lmax = argc > 1 ? atoi(argv[1]) : 10000; const long Ncc = argc > 2 ? atol(argv[2]) : 20160; const int mstride = argc > 3 ? atoi(argv[3]) : 1;
+static const int TLIVE = 4;      // index of LEG_LIVE = 2^-140 in THR
+static void run(const int lmax, const long Ncc, const int mstride) {
 	const LDb PIl = 3.141592653589793238462643383279502884L;
 	const int ncc = (int)(Ncc/2 + 1), npairs = (ncc + 1)/2;
 	std::vector<double> cth(npairs), sth(npairs), sh2(npairs), ch2(npairs);
@@ -41,7 +47,7 @@ int main(int argc, char** argv) {
 	const double ofs = std::max(100.0, 0.01*lmax);
 	const int KS[2][2] = {{4, 8}, {3, 4}};      // [spin 0 / spin 2][synthesis / analysis]
 	const char* KN[2][2] = {{"leg_syn_s0<4>", "leg_ana_s0<8>"}, {"leg_syn_spin<3>", "leg_ana_spin<4>"}};
-	double fma_sum[2][2][NT] = {}, steps_sum[2][2][NT] = {}; double dropmax[2][NT]; double grow4[2] = {0, 0};
+	double fma_sum[2][2][NT] = {}, steps_sum[2][2][NT] = {}, part_sum[2][2][3] = {}; double dropmax[2][NT]; double grow4[2] = {0, 0};
 	for (int i = 0; i < 2; i++) for (int t = 0; t < NT; t++) dropmax[i][t] = -1e9;
 	// sectoral normalisations (build_host)
 	std::vector<LDb> cms(lmax + 1), nrm(lmax + 1);
@@ -81,7 +87,7 @@ int main(int argc, char** argv) {
 				}
 			}
 			const int kend = 4*(n/4);      // where phase A stops whatever the chains do
-			std::vector<int> klive(NT*(size_t)npairs); std::vector<char> alive(npairs);
+			std::vector<int> klive(NT*(size_t)npairs), ktrue(npairs, INT_MAX); std::vector<char> alive(npairs);      // ktrue: the test at which the chain IS live at LEG_LIVE (klive: or phase A ran out of steps)
 			double dm[NT]; for (int t = 0; t < NT; t++) dm[t] = -1e9; double g4 = 0;
 			for (int p = 0; p < npairs; p++) {
 				// nc chains: spin 0 one (v2 current, v1 previous), spin 2 two
@@ -105,7 +111,7 @@ int main(int argc, char** argv) {
 				int k = 0, found = 0;
 				if (!alive[p]) { for (int t = 0; t < NT; t++) kl[t] = kend; continue; }
 				while (true) {
-					for (int t = 0; t < NT; t++) if (kl[t] < 0) { bool lv = false; for (int h = 0; h < nc; h++) lv |= live(v2[h], sc[h], t); if (lv || k + 4 > n) { kl[t] = k; found++; } }
+					for (int t = 0; t < NT; t++) if (kl[t] < 0) { bool lv = false; for (int h = 0; h < nc; h++) lv |= live(v2[h], sc[h], t); if (lv || k + 4 > n) { kl[t] = k; found++; if (lv && t == TLIVE) ktrue[p] = k; } }
 					if (found == NT) break;
 					double before = 0; for (int h = 0; h < nc; h++) if (sc[h] == 0) before = fmax(before, fabs(v2[h]));
 					// four steps; the values of these steps are dropped by every threshold not yet reached
@@ -136,8 +142,35 @@ int main(int argc, char** argv) {
 					for (int t = 0; t < NT; t++) { ss[d][t] += n - ks[t]; fs[d][t] += (double)(n - ks[t])*K*(sp ? 12 : 6); }
 				}
 			}
+			// the partitions at LEG_LIVE: pt = 0 padding behind the last pair, 1 in front of pair 0, 2 the same and blocks from their own step
+			double ps[2][3] = {};
+			for (int d = 0; d < 2; d++) {
+				const int K = KS[sp][d], per = 64*K, nwave = (npairs + per - 1)/per, frec = sp ? 4 : 2, facc = sp ? 8 : 4;
+				for (int pt = 0; pt < 3; pt++) {
+					const int pad = pt ? nwave*per - npairs : 0;
+					for (int w = 0; w < nwave; w++) {
+						bool any = false; int k0 = kend; int bs[8];
+						for (int b = 0; b < K; b++) {
+							bs[b] = INT_MAX;
+							for (int p = std::max(0, w*per + 64*b - pad); p < std::min(npairs, w*per + 64*b + 64 - pad); p++)
+								if (alive[p]) { any = true; bs[b] = std::min(bs[b], ktrue[p]); }
+							k0 = std::min(k0, bs[b]);
+						}
+						if (!any) continue;
+						if (pt < 2) { ps[d][pt] += (double)(n - k0)*K*(frec + facc); continue; }
+						double f = (double)(n - k0)*K*frec; int eff = INT_MAX;
+						for (int b = 0; b < K; b++) {
+							eff = std::min(eff, bs[b]);
+							const int start = b == K - 1 ? k0 : eff;      // (the last block starts with the wave)
+							if (start < n) f += (double)(n - start)*facc;
+						}
+						ps[d][pt] += f;
+					}
+				}
+			}
 #pragma omp critical
 			{
+				for (int d = 0; d < 2; d++) for (int pt = 0; pt < 3; pt++) part_sum[sp][d][pt] += ps[d][pt];
 				for (int d = 0; d < 2; d++) for (int t = 0; t < NT; t++) { fma_sum[sp][d][t] += fs[d][t]; steps_sum[sp][d][t] += ss[d][t]; }
 				for (int t = 0; t < NT; t++) dropmax[sp][t] = fmax(dropmax[sp][t], dm[t]);
 				grow4[sp] = fmax(grow4[sp], g4);
@@ -154,10 +187,19 @@ int main(int argc, char** argv) {
 		for (int t = 0; t < NT; t++) { const double a = fma_sum[0][dir][t] + fma_sum[1][dir][t], b = fma_sum[0][dir][0] + fma_sum[1][dir][0];
 			printf("  live at %-8s flops %.4e  ratio %.4f\n", THRN[t], a*128*mstride, a/b); }
 	}
+	printf("at LEG_LIVE = %s, FP64 flops (FMA per lane x 128): padding behind the last pair | in wave 0 | in wave 0 and blocks from their own step (ratios to the first)\n", THRN[TLIVE]);
+	for (int sp = 0; sp < 2; sp++) for (int d = 0; d < 2; d++) { const double* q = part_sum[sp][d];
+		printf("  %-16s %.5e | %.5e | %.5e   (%.4f, %.4f)\n", KN[sp][d], q[0]*128*mstride, q[1]*128*mstride, q[2]*128*mstride, q[1]/q[0], q[2]/q[0]); }
+	for (int d = 0; d < 2; d++) { double q[3]; for (int pt = 0; pt < 3; pt++) q[pt] = part_sum[0][d][pt] + part_sum[1][d][pt];
+		printf("  %-16s %.5e | %.5e | %.5e   (%.4f, %.4f)\n", d ? "analysis, both" : "synthesis, both", q[0]*128*mstride, q[1]*128*mstride, q[2]*128*mstride, q[1]/q[0], q[2]/q[0]); }
 	for (int sp = 0; sp < 2; sp++) {
 		printf("spin %d: largest 4-step growth of a scale-0 chain below 2^-90: 2^%.1f; log2 of the largest |lambda| before a chain is live:", sp ? 2 : 0, log2(grow4[sp]));
 		for (int t = 0; t < NT; t++) printf("  %s: %.1f", THRN[t], dropmax[sp][t]);
 		printf("\n");
 	}
+}
+
+int main(int argc, char** argv) {
+	run(argc > 1 ? atoi(argv[1]) : 10000, argc > 2 ? atol(argv[2]) : 20160, argc > 3 ? atoi(argv[3]) : 1);
 	return 0;
 }
