@@ -251,6 +251,30 @@ int pxm_deflect(int64_t npts, int ny, int nx, double dec0, double ddec, double r
                 const void* d_grad, int grad_dtype, int64_t grad_cstride, int geodesic, double* d_loc, double* d_psi, int device, void* stream);
 int pxm_rotate_pol(int64_t npts, int npair, void* a, void* b, int64_t pair_stride, int dtype, const double* d_psi, int spin, int device, void* stream);
 
+/* radially symmetric objects painted into a map, and radial sums read back out around a catalogue (pixell/pointsrcs.py:35-210 sim_objects /
+ * radial_sum; cython/srcsim_core.c).  The map is [ncomp][ny][nx] on the separable CAR grid dec0 + y ddec, ra0 + x dra (radians, as in
+ * the deflection call above; nx |dra| = 2 pi: the columns wrap), f32 | f64, components map_cstride elements apart.  Pixel and object
+ * coordinates are taken as float32; the distance is r = 2 asin sqrt(sin^2(ddec/2) + cos dec cos dec' sin^2(dra/2)).  All arrays DEVICE.
+ * pxm_sim_objects: d_obj_dec, d_obj_ra: f32 [nobj]; d_amps: f32 [ncomp][nobj], components amp_cstride apart; d_prof_ids: int32 [nobj] or
+ *   NULL (profile 0).  The nprof profiles are laid end to end (nsamp samples in all): profile q is d_prof_rs / d_prof_vs
+ *   [d_prof_off[q] .. d_prof_off[q+1]) (d_prof_off: int32 [nprof+1]), rs ascending; d_prof_vmax[k] = max |vs[j]| over the samples j >= k of
+ *   the same profile; prof_equi != 0: every profile has rs[k] = k rs[1].  P(r): linear interpolation, vs[0] below rs[0], 0 from the last
+ *   sample on.  Object i reaches to rcut_i = rs[min(k+1, n-1)], k the last sample with |vs[k]| >= vmin / max_c |amps[c][i]| (0 if none), capped
+ *   by rmax when rmax > 0.  transpose = 0: map[c][p] = op(map[c][p], amps[c][i] P_i(r)) for every object with r <= rcut_i; op: 0 add (in
+ *   ascending i), 1 max, 2 min.  The result is the same bit for bit from run to run.  The call waits once for the stream (it reads the total
+ *   length of the per-tile object lists back to size them).  transpose != 0 (op 0): d_amps[c][i] += sum_{p: r <= rcut_i} map[c][p] P_i(r),
+ *   rcut from the incoming amplitudes; no wait.
+ * pxm_radial_sum: d_oprofs[i][c][k] += sum of map[c][p] over the pixels with d_bins[k] <= r < d_bins[k+1] (d_bins: f32 [nbin+1], ascending;
+ *   rlast: the value of d_bins[nbin]; equi != 0: d_bins[k] = k d_bins[1]); d_oprofs: f32 [nobj][ncomp][nbin], ncomp nbin <= 12288.  Each pixel
+ *   counts once however wide the bins reach. */
+int pxm_sim_objects(int ny, int nx, double dec0, double ddec, double ra0, double dra, void* d_map, int map_dtype, int ncomp, int64_t map_cstride,
+                    int64_t nobj, const float* d_obj_dec, const float* d_obj_ra, float* d_amps, int64_t amp_cstride, const int32_t* d_prof_ids,
+                    int nprof, const int32_t* d_prof_off, int64_t nsamp, const float* d_prof_rs, const float* d_prof_vs, const float* d_prof_vmax,
+                    int prof_equi, double vmin, double rmax, int op, int transpose, int device, void* stream);
+int pxm_radial_sum(int ny, int nx, double dec0, double ddec, double ra0, double dra, const void* d_map, int map_dtype, int ncomp, int64_t map_cstride,
+                   int64_t nobj, const float* d_obj_dec, const float* d_obj_ra, int nbin, const float* d_bins, double rlast, int equi, float* d_oprofs,
+                   int device, void* stream);
+
 /* 1 if the engine can transform this length (2,3,5-smooth or prime factors small enough) */
 int pxf_fft_supported(int64_t n);
 int64_t pxf_fft_good_size(int64_t n);

@@ -175,6 +175,10 @@ static inline double atomicAdd(double* p, double v) {   // lanes are OS threads 
 	uint64_t* q = reinterpret_cast<uint64_t*>(p); uint64_t old = __atomic_load_n(q, __ATOMIC_RELAXED), nw; double o;
 	do { std::memcpy(&o, &old, 8); double n = o + v; std::memcpy(&nw, &n, 8); } while (!__atomic_compare_exchange_n(q, &old, nw, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED));
 	return o; }
+static inline float atomicAdd(float* p, float v) {
+	uint32_t* q = reinterpret_cast<uint32_t*>(p); uint32_t old = __atomic_load_n(q, __ATOMIC_RELAXED), nw; float o;
+	do { std::memcpy(&o, &old, 4); float n = o + v; std::memcpy(&nw, &n, 4); } while (!__atomic_compare_exchange_n(q, &old, nw, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED));
+	return o; }
 static inline int atomicMin(int* p, int v) { int old = __atomic_load_n(p, __ATOMIC_RELAXED); while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {} return old; }
 static inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 static inline float __fmul_rn(float a, float b) { volatile float r = a*b; return r; }

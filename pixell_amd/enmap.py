@@ -627,3 +627,60 @@ def pixshapebounds(shape, wcs, separable="auto"):
 	widths = wcs.wcs.cdelt[0]*degree*(sdec[1:]-sdec[:-1])/heights
 	ps = np.abs(np.array([heights, widths]))
 	return np.array([np.min(ps, 1), np.max(ps, 1)])
+
+# ---------------------------------------------------------------------------------------
+# what pointsrcs.sim_objects needs: object positions in pixels, and the pixel window
+# ---------------------------------------------------------------------------------------
+def sky2pix(shape, wcs, coords, safe=True, corner=False):
+	"""[{dec,ra},...] in radians -> [{y,x},...] (fractional, 0-based; enmap.sky2pix, enmap.py:496-529) for the linear CAR relation of
+	wcs.py.  The x of a geometry whose columns go round the sky is not brought into [0, nx): callers that need that wrap themselves."""
+	coords = np.asarray(coords, float)
+	x, y = wcsutils.world2pix(wcs, coords[1]/degree, coords[0]/degree)
+	res = np.array([y, x])
+	return res+0.5 if corner else res
+
+def pixwin_1d(f, order=0):
+	"""the pixel window along one axis at the dimensionless frequency f (pixel pitch 1): nearest-neighbour (order 0) or linear (order 1)
+	map-making (utils.pixwin_1d, utils.py:856-869)"""
+	f = np.asarray(f, float)
+	if order is None or order == "none": return f*0+1
+	if order == 0 or order == "nn": return np.sinc(f)
+	if order == 1 or order == "lin": return np.sinc(f)**2/(1/3*(2+np.cos(2*np.pi*f)))
+	raise ValueError("Unsupported pixel window order '%s'" % str(order))
+
+def calc_window(shape, order=0, scale=1):
+	"""(wy[ny], wx[nx]): the separable Fourier-space pixel window, window = wy[:,None]*wx[None,:] (enmap.calc_window, enmap.py:1472-1483)"""
+	return pixwin_1d(np.fft.fftfreq(shape[-2], scale), order=order), pixwin_1d(np.fft.fftfreq(shape[-1], scale), order=order)
+
+def apply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
+	"""A copy of emap with the pixel window to the power pow applied (enmap.apply_window, enmap.py:1485-1496): FFT, one multiplication
+	per axis on the device (pxm_mul_axis), inverse FFT.  nofft: emap is a Fourier-space map already.  Host maps, dmaps and CUDA tensors."""
+	from . import sht
+	wy, wx = calc_window(emap.shape, order=order, scale=scale)
+	like = emap if isinstance(emap, (dmap, ndmap)) else None
+	dev, was_host = _to_device(emap if like is not None else dmap(emap, None) if hasattr(emap, "data_ptr") else ndmap(np.asarray(emap), None))
+	d = _data(dev)
+	rdt = sht._np_dtype(d)
+	ct = np.result_type(rdt, np.complex64)
+	if hasattr(d, "data_ptr"): work = d.to(getattr(_torch(), np.dtype(ct).name), copy=True).contiguous()
+	else: work = np.array(d, dtype=ct, order="C")
+	wmap = _wrap(work, dev)
+	if not nofft: wmap = fft(wmap, normalize=False)
+	data = _data(wmap)
+	enfft._mul_axis(data, data.ndim-2, wy**pow)
+	enfft._mul_axis(data, data.ndim-1, wx**pow)
+	if not nofft:
+		wmap = ifft(wmap, normalize=False)
+		data = _data(wmap)
+		data = data.real*(1.0/(data.shape[-2]*data.shape[-1]))
+		if rdt.kind != "c": data = data.to(getattr(_torch(), rdt.name)) if hasattr(data, "data_ptr") else data.astype(rdt)
+		data = data.contiguous() if hasattr(data, "contiguous") else np.ascontiguousarray(data)
+	elif rdt.kind != "c": raise ValueError("apply_window(nofft=True) needs a complex Fourier-space map")
+	res = _wrap(data, dev)
+	if was_host: res = _to_host(res)
+	if like is None: return _data(res)
+	return res
+
+def unapply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
+	"""the inverse of apply_window (enmap.py:1498-1500)"""
+	return apply_window(emap, pow=-pow, order=order, scale=scale, nofft=nofft)
