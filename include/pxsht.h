@@ -275,6 +275,27 @@ int pxm_radial_sum(int ny, int nx, double dec0, double ddec, double ra0, double 
                    int64_t nobj, const float* d_obj_dec, const float* d_obj_ra, int nbin, const float* d_bins, double rlast, int equi, float* d_oprofs,
                    int device, void* stream);
 
+/* distance transforms (pixell/enmap.py:2127-2215 distance_from / distance_transform / labeled_distance_transform; cython/distances_core.c),
+ * on the separable CAR grid dec0 + y ddec, ra0 + x dra of the calls above, FP64 coordinates and arithmetic.  All arrays DEVICE.
+ * pxm_find_edges: the edge pixels of d_map [ny][nx] as ascending flat indices.  labeled = 0: d_map is uint8, an edge pixel has value 0
+ *   and lies on the border of the array or has a non-zero 4-neighbour; labeled != 0: d_map is int32, an edge pixel is non-zero and lies on
+ *   the border or has a 4-neighbour of another value.  d_edges = NULL: only counts; *count (HOST, may be NULL when d_edges is given)
+ *   receives the number of edge pixels, and the call waits for the stream to read it.  d_edges: DEVICE int64 [cap], receives the first cap
+ *   indices; with count = NULL the call does not wait.  (Count, allocate, fill: two calls, one wait.)
+ * pxm_distance_from: d_omap[p] = min_i r(p, i) over the npoint points, r the great-circle distance, exact; d_domains (int32 [ny][nx] or
+ *   NULL) the winning i: the comparison is on h = sin^2(ddec/2) + cos dec cos dec' sin^2(dra/2), the lowest i among equal h, and the
+ *   winner's distance is evaluated in Vincenty's atan2 form (good on [0, pi]).  Points: d_pt_pix != NULL: int64 [npoint] flat pixel
+ *   indices of this grid (the pixel centres); otherwise d_pt_dec, d_pt_ra: f64 [npoint] radians, anywhere on the sphere, RA modulo 2 pi,
+ *   duplicates allowed.  rmax > 0: pixels with a distance above rmax get rmax and domain -1 (rmax <= 0: no limit).  npoint = 0: rmax
+ *   (infinity without one) and -1 everywhere.  d_skip (uint8 [ny][nx] or NULL): pixels where it is 0 get distance 0 and domain -1 without a
+ *   search.  d_omap: f32 | f64 [ny][nx].  d_visits (int32 [ceil(ny/16)][ceil(nx/16)] or NULL): how many points each 16 x 16 pixel tile
+ *   looked at (the measure of the pruning: npoint for a brute-force search).  The result is the same bit for bit from run to run; the call
+ *   does not wait for the stream. */
+int pxm_find_edges(int ny, int nx, const void* d_map, int labeled, int64_t* d_edges, int64_t cap, int64_t* count, int device, void* stream);
+int pxm_distance_from(int ny, int nx, double dec0, double ddec, double ra0, double dra, int64_t npoint, const double* d_pt_dec, const double* d_pt_ra,
+                      const int64_t* d_pt_pix, double rmax, const uint8_t* d_skip, void* d_omap, int map_dtype, int32_t* d_domains, int32_t* d_visits,
+                      int device, void* stream);
+
 /* 1 if the engine can transform this length (2,3,5-smooth or prime factors small enough) */
 int pxf_fft_supported(int64_t n);
 int64_t pxf_fft_good_size(int64_t n);

@@ -4,6 +4,8 @@
   pixell_amd.sht        ducc0.sht.experimental-shaped functions (synthesis_2d, analysis_2d, ...)
   pixell_amd.fft        fft / ifft / rfft / irfft + the `hip` engine object for pixell.fft.engines
   pixell_amd.enmap      the few enmap pieces the path needs (ndmap, fullsky_geometry, fft, ifft)
+  pixell_amd.pointsrcs  sim_objects / radial_sum / radial_bin: painting catalogues, radial profiles
+  pixell_amd.distances  find_edges / distance_from_points behind enmap.distance_from, distance_transform, apod_mask
 All arithmetic runs in hand-written HIP kernels (pixell_amd/csrc) behind include/pxsht.h.
 """
 __version__ = "0.1.0"

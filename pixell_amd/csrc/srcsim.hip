@@ -18,6 +18,7 @@
 // total list length, to size the lists).  The transpose and the radial sum run one workgroup per object over the object's own box.
 #include "../../include/pxsht.h"
 #include "common.hpp"
+#include "scan_dev.hpp"
 #include <map>
 #include <mutex>
 
@@ -29,11 +30,9 @@ static constexpr int NCH = 64;            // objects staged in LDS per step
 static constexpr int NCC = 4;             // map components carried in registers per pass over a tile's list
 static constexpr int PROF_LDS = 4096;     // profile samples (of all profiles together) up to which the tables are kept in LDS
 static constexpr int SRC_MAXBLK = 2048;   // workgroups of the kernels that loop over the listed tiles
-static constexpr int SCAN_PER = 4;        // tiles per lane of the scan
 
 struct Geo { int ny, nx; double dec0, ddec, ra0, dra; int wrap; };      // wrap: the columns cover the whole circle
 struct Box { int y1, nyb, x1, nxb; };     // rows y1 .. y1 + nyb - 1, columns (x1 + j) mod nx for j < nxb <= nx; nyb = 0: the disc misses the map
-struct TileRec { long long off; int tile, n; };      // a tile with objects: its list is entries off .. off + n - 1
 struct ObjRec { int idx; float dec, ra, cd, rc, hm; int po, pn; };      // a list entry: the object's index, position, cos dec, cut radius, a bound on h beyond which r > rc for certain, its profile (first sample, samples)
 struct Prof { int nprof; const int* off; const float* rs; const float* vs; const float* vmax; int equi; };      // profile q: samples off[q] .. off[q+1]-1; vmax[k] = max_{j >= k} |vs[j]|
 
@@ -153,64 +152,6 @@ __global__ __launch_bounds__(256) void tile_fill_kernel(Geo g, int ntx, long nob
 	r.hm = s*s*1.0001f + 1e-30f;
 	r.po = pr.off[q]; r.pn = pr.off[q+1] - r.po;
 	for_each_tile(g, b, ntx, [&](int t) { raw[off[t] + atomicAdd(&cur[t], 1)] = r; });
-}
-
-// exclusive sums over the 256 lanes of a workgroup of a 64-bit and a 32-bit number at once; sc[256], sa[256]: LDS
-__device__ inline void block_scan2(long long lc, int la, long long* sc, int* sa, long long& ex_c, int& ex_a, long long& tot_c, int& tot_a) {
-	const int t = threadIdx.x;
-	sc[t] = lc; sa[t] = la;
-	__syncthreads();
-	for (int d = 1; d < 256; d <<= 1) {
-		const long long a = t >= d ? sc[t-d] : 0; const int b = t >= d ? sa[t-d] : 0;
-		__syncthreads();
-		sc[t] += a; sa[t] += b;
-		__syncthreads();
-	}
-	ex_c = sc[t] - lc; ex_a = sa[t] - la; tot_c = sc[255]; tot_a = sa[255];
-	__syncthreads();
-}
-
-// the scan of the tile counts in three steps: sums per workgroup of 256*SCAN_PER tiles; their exclusive sums and the totals (one workgroup);
-// off[tile] and the list `act` of the tiles with a count.  tot[0]: pairs of (tile, object), tot[1]: tiles with objects
-__global__ __launch_bounds__(256) void scan_part_kernel(int ntiles, const int* __restrict__ cnt, long long* __restrict__ bs_c, int* __restrict__ bs_a)
-{
-	PXS_SHARED(long long, ssh); long long* sc = ssh; int* sa = (int*)(ssh + 256);
-	const long base = ((long)blockIdx.x*256 + threadIdx.x)*SCAN_PER;
-	long long lc = 0; int la = 0;
-	for (int k = 0; k < SCAN_PER; k++) if (base + k < ntiles) { const int v = cnt[base + k]; lc += v; la += v > 0; }
-	long long ec, tc; int ea, ta;
-	block_scan2(lc, la, sc, sa, ec, ea, tc, ta);
-	if (threadIdx.x == 0) { bs_c[blockIdx.x] = tc; bs_a[blockIdx.x] = ta; }
-}
-__global__ __launch_bounds__(256) void scan_top_kernel(int nblk, long long* __restrict__ bs_c, int* __restrict__ bs_a, long long* __restrict__ tot)
-{
-	PXS_SHARED(long long, ssh); long long* sc = ssh; int* sa = (int*)(ssh + 256);
-	long long run_c = 0; int run_a = 0;
-	for (int b0 = 0; b0 < nblk; b0 += 256) {
-		const int b = b0 + threadIdx.x;
-		const long long lc = b < nblk ? bs_c[b] : 0; const int la = b < nblk ? bs_a[b] : 0;
-		long long ec, tc; int ea, ta;
-		block_scan2(lc, la, sc, sa, ec, ea, tc, ta);
-		if (b < nblk) { bs_c[b] = run_c + ec; bs_a[b] = run_a + ea; }
-		run_c += tc; run_a += ta;
-	}
-	if (threadIdx.x == 0) { tot[0] = run_c; tot[1] = run_a; }
-}
-__global__ __launch_bounds__(256) void scan_apply_kernel(int ntiles, const int* __restrict__ cnt, const long long* __restrict__ bs_c, const int* __restrict__ bs_a,
-		long long* __restrict__ off, TileRec* __restrict__ act)
-{
-	PXS_SHARED(long long, ssh); long long* sc = ssh; int* sa = (int*)(ssh + 256);
-	const long base = ((long)blockIdx.x*256 + threadIdx.x)*SCAN_PER;
-	int v[SCAN_PER]; long long lc = 0; int la = 0;
-	for (int k = 0; k < SCAN_PER; k++) { v[k] = base + k < ntiles ? cnt[base + k] : 0; lc += v[k]; la += v[k] > 0; }
-	long long ec, tc; int ea, ta;
-	block_scan2(lc, la, sc, sa, ec, ea, tc, ta);
-	ec += bs_c[blockIdx.x]; ea += bs_a[blockIdx.x];
-	for (int k = 0; k < SCAN_PER; k++) if (base + k < ntiles) {
-		off[base + k] = ec;
-		if (v[k] > 0) { TileRec t; t.off = ec; t.tile = (int)(base + k); t.n = v[k]; act[ea++] = t; }
-		ec += v[k];
-	}
 }
 
 // list[off .. off + n) = raw[off .. off + n) in ascending order, tile by tile.  An object is in a tile's list once, so an entry's place is

@@ -40,8 +40,7 @@ class dmap:
 	def ndim(self): return self.tensor.ndim
 	@property
 	def dtype(self):
-		from .sht import _np_dtype
-		return _np_dtype(self.tensor)
+		return np.dtype(str(self.tensor.dtype).replace("torch.", ""))      # (any dtype: domains and masks are maps too)
 	def __getitem__(self, sel):
 		res = _sliced(self, self.tensor[sel], sel)
 		if not isinstance(res, dmap): raise IndexError("indexing a pixel axis of a dmap leaves no map geometry: slice the tensor itself")
@@ -684,3 +683,162 @@ def apply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
 def unapply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
 	"""the inverse of apply_window (enmap.py:1498-1500)"""
 	return apply_window(emap, pow=-pow, order=order, scale=scale, nofft=nofft)
+
+# ---------------------------------------------------------------------------------------
+# distance transforms and apodisation (enmap.py:2127-2286, 2440-2490); the kernels are behind pixell_amd.distances
+# ---------------------------------------------------------------------------------------
+_DIST_METHODS = ("cellgrid", "bubble", "simple")
+def _check_method(method):
+	if method not in _DIST_METHODS: raise ValueError("Unknown method '%s'" % str(method))
+def _is_t(x): return hasattr(x, "data_ptr")
+def _np_any(x):
+	"""the numpy dtype of an array or tensor of any kind"""
+	return np.dtype(str(x.dtype).replace("torch.", "")) if _is_t(x) else np.dtype(x.dtype)
+def _astype(x, dtype):
+	"""x (array or tensor) as the numpy dtype `dtype`"""
+	return x.to(getattr(_torch(), np.dtype(dtype).name)) if _is_t(x) else np.asarray(x).astype(dtype, copy=False)
+def _like_zeros(like, shape, dtype):
+	if _is_t(like): return _torch().zeros(tuple(shape), dtype=getattr(_torch(), np.dtype(dtype).name), device=like.device)
+	return np.zeros(shape, dtype)
+
+def distance_from(shape, wcs, points, omap=None, odomains=None, domains=False, method="cellgrid", rmax=None, step=1024):
+	"""The distance of each pixel of the geometry from the nearest of points [{dec,ra}, npoint], [ny, nx]; with domains=True also the index
+	of that point (enmap.distance_from, enmap.py:2160-2215).  rmax: beyond it the distance is rmax and the domain -1.  Every method
+	("cellgrid", "bubble", "simple") runs the same exact search on the device; step is accepted and not used."""
+	from . import distances
+	_check_method(method)
+	return distances.distance_from_points(shape, wcs, points=points, rmax=rmax, omap=omap, odomains=odomains, domains=domains)
+
+def _planes(m, what):
+	"""(the data of map m as [npre, ny, nx], its leading shape)"""
+	if not hasattr(m, "wcs"): raise ValueError("%s needs a map with a geometry (ndmap or dmap)" % what)
+	d = _data(m)
+	if d.ndim < 2: raise ValueError("%s needs at least two axes" % what)
+	return d.reshape((-1,)+tuple(d.shape[-2:])), tuple(d.shape[:-2])
+
+def distance_transform(mask, omap=None, rmax=None, method="cellgrid"):
+	"""The distance of each pixel from the closest zero pixel of mask [..., ny, nx]; zero inside the zero regions (enmap.distance_transform,
+	enmap.py:2127-2138).  The edges of the zero regions are found on the device, searched from as pixel indices, and the mask itself says
+	where no search is needed.  A mask without zeros gives rmax (infinity without one)."""
+	from . import distances
+	_check_method(method)
+	md, pre = _planes(mask, "distance_transform")
+	if omap is None: od = _like_zeros(md, md.shape, np.float64)
+	else:
+		od = _data(omap)
+		if tuple(od.shape) != pre+tuple(md.shape[-2:]): raise ValueError("omap must have the shape of the mask")
+		od = od.reshape(md.shape)
+	for i in range(md.shape[0]):
+		m8 = _astype(md[i] != 0, np.uint8)
+		edges = distances.find_edges(m8, flat=True)
+		if _is_t(od) or not _is_t(m8): distances.distance_from_points(mask.shape, mask.wcs, pix=edges, rmax=rmax, omap=od[i], skip=m8)
+		else: od[i] = _to_host(distances.distance_from_points(mask.shape, mask.wcs, pix=edges, rmax=rmax, skip=m8))      # (a device mask and a host omap)
+	if omap is not None: return omap
+	return _wrap(od.reshape(pre+tuple(md.shape[-2:])), mask)
+
+def labeled_distance_transform(labels, omap=None, odomains=None, rmax=None, method="cellgrid"):
+	"""The distance of each pixel from the closest non-zero pixel of labels [..., ny, nx], and the label of that pixel: (omap, odomains)
+	(enmap.labeled_distance_transform, enmap.py:2140-2158).  The distance is zero inside the labelled regions; odomains keeps what it held
+	where no labelled pixel is within rmax."""
+	from . import distances
+	_check_method(method)
+	ld, pre = _planes(labels, "labeled_distance_transform")
+	ld = _astype(ld, np.int32)
+	full = pre+tuple(ld.shape[-2:])
+	od = _like_zeros(ld, ld.shape, np.float64) if omap is None else _data(omap).reshape(ld.shape)
+	dd = _like_zeros(ld, ld.shape, np.int32) if odomains is None else _data(odomains).reshape(ld.shape)
+	if _is_t(ld) != _is_t(od) or _is_t(ld) != _is_t(dd): raise ValueError("labels, omap and odomains must all live on the host or all on the device")
+	for i in range(ld.shape[0]):
+		lab = ld[i].contiguous() if _is_t(ld) else np.ascontiguousarray(ld[i])
+		edges = distances.find_edges_labeled(lab, flat=True)
+		_, dom = distances.distance_from_points(labels.shape, labels.wcs, pix=edges, rmax=rmax, omap=od[i], domains=True)
+		dom = _data(dom)
+		good = dom >= 0
+		if int(edges.shape[0]) > 0:
+			mapping = lab.reshape(-1)[edges]
+			dd[i][good] = _astype(mapping[_astype(dom[good], np.int64)], _np_any(dd))
+		od[i][lab != 0] = 0
+	oo = omap if omap is not None else _wrap(od.reshape(full), labels)
+	do = odomains if odomains is not None else _wrap(dd.reshape(full), labels)
+	return oo, do
+
+def _mask_not(mask): return _wrap(_data(mask) == 0, mask)
+
+def grow_mask(mask, r):
+	"""Grow the true part of the boolean mask by a distance of r radians (enmap.grow_mask, enmap.py:2280-2282)"""
+	d = distance_transform(_mask_not(mask), rmax=r)
+	return _wrap(_data(d) < r, mask)
+
+def shrink_mask(mask, r):
+	"""Shrink the true part of the boolean mask by a distance of r radians (enmap.shrink_mask, enmap.py:2284-2286)"""
+	d = distance_transform(mask, rmax=r)
+	return _wrap(_data(d) >= r, mask)
+
+def apod_profile_lin(x): return x
+def apod_profile_cos(x):
+	"""0.5 (1 - cos(pi x)), of a numpy array or a torch tensor"""
+	if isinstance(x, dmap): return dmap(apod_profile_cos(x.tensor), x.wcs)
+	return 0.5*(1-(_torch().cos(np.pi*x) if _is_t(x) else np.cos(np.pi*x)))
+
+def apod_mask(mask, width=1*degree, edge=True, profile=apod_profile_cos):
+	"""Given a mask that is 0 in bad regions and 1 in good regions, an apodisation map that is still 0 in the bad regions and goes to 1 over
+	`width` radians inside the good ones, as profile(distance/width) (enmap.apod_mask, enmap.py:2479-2490).  edge: what lies outside the
+	image counts as bad."""
+	if edge:
+		md = _data(mask)
+		md = md.clone() if _is_t(md) else np.array(md)
+		md[..., 0, :] = 0; md[..., :, 0] = 0
+		md[..., -1, :] = 0; md[..., :, -1] = 0
+		mask = _wrap(md, mask)
+	r = distance_transform(mask, rmax=width)
+	return _wrap(profile(_data(r)/width), mask)
+
+def _median2(d):
+	"""the median over the last two axes, as numpy.median takes it (the mean of the two middle values of an even count)"""
+	if not _is_t(d): return np.median(d, (-2, -1))
+	s = d.reshape(tuple(d.shape[:-2])+(-1,)).sort(-1).values
+	n = s.shape[-1]
+	return 0.5*(s[..., (n-1)//2]+s[..., n//2])
+
+def apod(map, width, profile="cos", fill="zero", inplace=False):
+	"""Apodise the outermost width [{y,x}] (or one number: both) pixels of each edge of the map (enmap.apod, enmap.py:2440-2474).  fill:
+	"zero": towards 0; "mean", "median": towards the mean or median of each [ny, nx] map; "crossfade": towards the opposite edge.
+	Slicing only, on the host or on the device wherever the map lives."""
+	if fill not in ("zero", "mean", "median", "crossfade"): raise ValueError("Unknown fill '%s'" % str(fill))
+	if profile not in ("lin", "cos"): raise ValueError("Unknown apodization profile '%s'" % str(profile))
+	width = (np.zeros(2, int)+width).astype(int)
+	d = _data(map)
+	if not inplace: d = d.clone() if _is_t(d) else np.array(d)
+	if fill == "mean": offset = d.mean((-2, -1))[..., None, None]
+	elif fill == "median": offset = _median2(d)[..., None, None]
+	if fill in ("mean", "median"): d -= offset
+	for i, w in enumerate(width):
+		w = int(w)
+		if w <= 0: continue
+		x = np.arange(1, w+1, dtype=float)/((2*w+1) if fill == "crossfade" else (w+1))
+		prof = apod_profile_lin(x) if profile == "lin" else apod_profile_cos(x)
+		if _is_t(d): prof = _torch().as_tensor(prof, dtype=d.dtype, device=d.device)
+		else: prof = prof.astype(d.dtype, copy=False)
+		rev = prof.flip(0) if _is_t(d) else prof[::-1]
+		slice1 = (Ellipsis,)+(slice(None),)*i+(slice(0, w),)+(slice(None),)*(1-i)
+		slice2 = (Ellipsis,)+(slice(None),)*i+(slice(-w, None),)+(slice(None),)*(1-i)
+		broad = (None,)*i+(slice(None),)+(None,)*(1-i)
+		if fill == "crossfade":
+			m1 = d[slice1].clone() if _is_t(d) else d[slice1].copy()
+			m2 = d[slice2].clone() if _is_t(d) else d[slice2].copy()
+			d[slice1] = m1*(1-prof).flip(0)[broad]+m2*rev[broad] if _is_t(d) else m1*(1-prof)[::-1][broad]+m2*rev[broad]
+			d[slice2] = m2*(1-prof)[broad]+m1*prof[broad]
+		else:
+			d[slice1] *= prof[broad]
+			d[slice2] *= rev[broad]
+	if fill in ("mean", "median"): d += offset
+	return map if inplace else _wrap(d, map)
+
+for _cls in (ndmap, dmap):
+	_cls.distance_transform = lambda self, **kw: distance_transform(self, **kw)
+	_cls.labeled_distance_transform = lambda self, **kw: labeled_distance_transform(self, **kw)
+	_cls.distance_from = lambda self, points, **kw: distance_from(self.shape, self.wcs, points, **kw)
+	_cls.grow_mask    = lambda self, r: grow_mask(self, r)
+	_cls.shrink_mask  = lambda self, r: shrink_mask(self, r)
+	_cls.apod_mask    = lambda self, **kw: apod_mask(self, **kw)
+	_cls.apod         = lambda self, width, **kw: apod(self, width, **kw)
