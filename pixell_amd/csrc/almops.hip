@@ -5,8 +5,6 @@
 // along l so that loads of one m-column are contiguous (lstride 1).
 #include "../../include/pxsht.h"
 #include "common.hpp"
-#include <map>
-#include <mutex>
 
 namespace pxs {
 const char* get_last_error();
@@ -137,9 +135,6 @@ __global__ __launch_bounds__(256) void lmatmul_kernel(int N, int M, int lmax, in
 } // namespace pxs
 
 using namespace pxs;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 
@@ -158,12 +153,10 @@ int pxa_alm2cl(int lmax, int mmax, const uint64_t* d_mstart, int64_t lstride, co
 		hipLaunchKernelGGL(alm2cl_kernel, dim3((lmax+256)/256), dim3(256), 0, (hipStream_t)stream, lmax, mmax, d_mstart, (long)lstride,
 			alm1, alm2, alm_dtype, cl, cl_dtype, acc_f32 ? 1 : 0);
 	} else {
-		// partial sums per m chunk: scratch per (device, stream), like the FFT scratch (api_fft.hip) -- calls on two streams must not share it,
-		// and calls on one stream are ordered by the stream.  (A torch process has at most a few dozen streams; entries are 8 (lmax + 1) nch bytes.)
-		static std::mutex mu; static std::map<std::pair<int, void*>, DevBuf> scratch;
+		// partial sums per m chunk, in the stream's scratch (common.hpp stream_scratch; entries are 8 (lmax + 1) nch bytes)
 		const int nch = mmax/ALM2CL_MCH + 1;
-		double* part;
-		{ std::lock_guard<std::mutex> g(mu); DevBuf& b = scratch[std::make_pair(device, stream)]; b.ensure(sizeof(double)*(size_t)nch*(lmax+1)); part = b.as<double>(); }
+		DevBuf& scratch = stream_scratch(SCR_ALM2CL, device, stream); scratch.ensure(sizeof(double)*(size_t)nch*(lmax+1));
+		double* part = scratch.as<double>();
 		hipLaunchKernelGGL(alm2cl_part_kernel, dim3((lmax+256)/256, nch), dim3(256), 0, (hipStream_t)stream, lmax, mmax, d_mstart, (long)lstride,
 			alm1, alm2, alm_dtype, part);
 		hipLaunchKernelGGL(alm2cl_sum_kernel, dim3((lmax+256)/256), dim3(256), 0, (hipStream_t)stream, lmax, mmax, (const double*)part, cl, cl_dtype);

@@ -65,7 +65,6 @@ static const BluePlan& blue_plan(FftContext& fc, int device, hipStream_t st, lon
 static void fft_axis(FftContext& fc, hipStream_t st, long n, bool forward, std::vector<AxisDim> dims, long is_e, long os_e,
                      FftLoad ld, FftStore stf);
 
-static std::mutex g_blue_mu; static std::map<std::pair<int, hipStream_t>, std::unique_ptr<DevBuf>> g_blue_scratch;
 // chain engine (and its scratch) of the 2-D real -> complex fast path, per stream like the other scratch
 // (each entry owns the transposed intermediate of its last transform -- 15 GB for a complex 21600 x 43200 map -- so the table is
 // bounded: beyond PXF_F2_MAX_STREAMS (4) the entry used longest ago is dropped.  Its kernels may still be queued on its stream: its
@@ -97,13 +96,10 @@ static std::shared_ptr<FftChain> f2_chain(int device, hipStream_t st, FftContext
 	it->second.stamp = ++g_f2_clock;
 	return it->second.ch;
 }
-// scratch of the multi-axis c2r transforms, per stream like the other scratch (grows only; no synchronisation in the call path)
-static std::mutex g_c2r_mu; static std::map<std::pair<int, hipStream_t>, std::unique_ptr<DevBuf>> g_c2r_scratch;
 // a stream is about to be destroyed: free the scratch keyed by it (a recycled handle must not inherit a stale buffer)
 void fft_release_stream(int device, hipStream_t st) {
-	{ std::lock_guard<std::mutex> g(g_blue_mu); g_blue_scratch.erase(std::make_pair(device, st)); }
+	stream_scratch_release(device, st);
 	{ std::lock_guard<std::mutex> g(g_f2_mu); g_f2.erase(std::make_pair(device, st)); }
-	{ std::lock_guard<std::mutex> g(g_c2r_mu); g_c2r_scratch.erase(std::make_pair(device, st)); }
 	fft_context(device).release_stream(st);
 }
 
@@ -117,12 +113,9 @@ static void bluestein_axis(FftContext& fc, int device, hipStream_t st, long n, b
 	std::vector<AxisDim> d1 = dims, d2 = dims;
 	long lines = 1;
 	for (size_t k = dims.size(); k-- > 0;) { d1[k].os = lines*M; d2[k].is = lines*M; lines *= dims[k].n; }
-	// scratch per stream, grown on demand and kept (growing gives the old block to the arena, which synchronises the device before the
-	// block is used again, or to hipFree, which waits for the device: the stream's earlier transforms may still read it); owners of private
-	// streams give it back with fft_release_stream before they destroy the stream
-	DevBuf* sp;
-	{ std::lock_guard<std::mutex> g(g_blue_mu); auto& u = g_blue_scratch[std::make_pair(device, st)]; if (!u) u.reset(new DevBuf()); sp = u.get(); }
-	DevBuf& scratch = *sp; scratch.ensure(sizeof(double2)*(size_t)lines*M);
+	// scratch per stream, grown on demand and kept (common.hpp stream_scratch); owners of private streams give it back with
+	// fft_release_stream before they destroy the stream
+	DevBuf& scratch = stream_scratch(SCR_BLUESTEIN, device, st); scratch.ensure(sizeof(double2)*(size_t)lines*M);
 	{	// y = FFT_M(x w, zero padded)
 		FftLoad l1 = ld; l1.mul = bp.w.as<double2>();
 		if (c2r) l1.herm_n = n;                                   // Hermitian extension of n points (times the chirp), zero padded to M
@@ -246,9 +239,6 @@ const R2RPlan& r2r_plan(int device, int kind, long n) {
 
 using namespace pxs;
 
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 
@@ -362,10 +352,8 @@ int pxf_fft_nd(int ndim, const int64_t* shape, const int64_t* istride, const int
 		const void* src = in; int src_dtype = in_dtype; std::vector<int64_t> sstride(istride, istride+ndim);
 		if (naxes > 1) {
 			size_t tot = 1; for (int k = 0; k < ndim; k++) tot *= cshape[k];
-			DevBuf* sp;
-			{ std::lock_guard<std::mutex> g(g_c2r_mu); auto& u = g_c2r_scratch[std::make_pair(device, st)]; if (!u) u.reset(new DevBuf()); sp = u.get(); }
-			sp->ensure(tot*sizeof(double2));
-			DevBuf& scratch = *sp;
+			DevBuf& scratch = stream_scratch(SCR_C2R, device, st);      // (grows only; no synchronisation in the call path)
+			scratch.ensure(tot*sizeof(double2));
 			std::vector<int64_t> cs(ndim); long acc = 1;
 			for (int k = ndim-1; k >= 0; k--) { cs[k] = acc; acc *= cshape[k]; }
 			for (int t = 0; t < naxes-1; t++) {

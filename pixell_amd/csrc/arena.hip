@@ -2,8 +2,10 @@
 // know about a slow first call (round 5: first alm2map of a fresh process 162 ms on one box, 1248 ms on another, same code).
 #include "common.hpp"
 #include <chrono>
+#include <climits>
 #include <map>
 #include <mutex>
+#include <tuple>
 #include <unordered_map>
 
 namespace pxs {
@@ -94,6 +96,21 @@ void dev_free(void* p, size_t n) {      // no runtime call unless the block goes
 		return;
 	}
 	(void)hipFree(p);      // (hipFree waits for the device)
+}
+
+namespace {
+struct Scratch { std::mutex mu; std::map<std::tuple<int, void*, int>, DevBuf> tab; };      // (device, stream, slot): std::map nodes do not move
+Scratch& scratch() { static Scratch* s = new Scratch; return *s; }      // (never destroyed, like the arena its buffers go back to)
+}
+DevBuf& stream_scratch(ScratchSlot slot, int device, void* stream) {
+	Scratch& s = scratch();
+	std::lock_guard<std::mutex> g(s.mu);
+	return s.tab[std::make_tuple(device, stream, (int)slot)];
+}
+void stream_scratch_release(int device, void* stream) {
+	Scratch& s = scratch();
+	std::lock_guard<std::mutex> g(s.mu);
+	s.tab.erase(s.tab.lower_bound(std::make_tuple(device, stream, 0)), s.tab.upper_bound(std::make_tuple(device, stream, INT_MAX)));
 }
 } // namespace pxs
 

@@ -135,9 +135,6 @@ static void check_bank(const char* who, int nscale, const int* lmaxs, const int*
 } // namespace pxs
 
 using namespace pxs;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 

@@ -23,6 +23,12 @@ void set_last_error(const std::string& msg);
 #define PXS_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
 	throw pxs::Error(pxs::PXS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 #define PXS_REQUIRE(cond, msg) do { if (!(cond)) throw pxs::Error(pxs::PXS_ERR_ARG, std::string(msg)); } while (0)
+// the body of every extern "C" entry point: an exception becomes the last error and its code, anything else returns 0
+#define PXS_TRY try {
+#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
+	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
+
+static constexpr double PXS_PI = 3.14159265358979323846;
 
 // Device memory of the library goes through one per-process arena (arena.hip): blocks of 32 MB and more that a plan releases are
 // kept (up to PXS_ARENA_GB, default 48) and handed to the next plan that asks for a similar size instead of going back to the driver
@@ -49,6 +55,20 @@ struct DevBuf {
 	}
 	void release() { if (p) { dev_free(p, bytes); p = nullptr; bytes = 0; } }
 	template<class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// Scratch that a library call keeps between calls, one buffer per (slot, device, stream): calls on two streams must not share it, calls
+// on one stream are ordered by the stream.  The reference is found under the registry's lock and stays valid until the stream is
+// released (entries never move); the caller grows it with ensure() and launches outside the lock.  Growing hands the old block to the
+// arena, which synchronises the device before the block serves anybody else: the stream's earlier kernels may still read it.
+enum ScratchSlot : int { SCR_BLUESTEIN, SCR_C2R, SCR_ALM2CL, SCR_SRC_FIXED, SCR_SRC_PAIRS, SCR_DISTANCE };
+DevBuf& stream_scratch(ScratchSlot slot, int device, void* stream);
+void stream_scratch_release(int device, void* stream);      // a stream is about to be destroyed: a recycled handle must not inherit a stale buffer
+
+inline unsigned blocks_of(long n) { return (unsigned)((n + 255)/256); }      // workgroups of 256 lanes for n items
+struct Carve {      // consecutive 16-byte aligned pieces of one buffer
+	size_t at = 0;
+	size_t take(size_t bytes) { const size_t o = at; at += (bytes + 15)/16*16; return o; }
 };
 
 template<class T> inline DevBuf upload(const std::vector<T>& v) {

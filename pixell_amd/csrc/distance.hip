@@ -22,24 +22,20 @@
 #include "../../include/pxsht.h"
 #include "common.hpp"
 #include "scan_dev.hpp"
-#include <map>
-#include <mutex>
+#include "pixgeo.hpp"
 #include <limits>
 
 namespace pxs {
 namespace dst {
 
-static constexpr double DPI = 3.14159265358979323846;
 static constexpr int TILE = 16;           // a tile is TILE x TILE pixels: one lane of a 256-lane workgroup per pixel; the cells points are binned into are the tiles
 static constexpr int NCH = 64;            // points staged in LDS per step
 static constexpr int EDGE_PER = 4;        // pixels per lane of the edge finder
 
-struct DGeo { int ny, nx; double dec0, ddec, ra0, dra; int ncy, ncx; double period; };      // ncy x ncx cells; period: the pixels that 2 pi of RA are
+struct DGeo : PixGeo { int ncy, ncx; };      // the geometry and its ncy x ncx cells
 struct Pts { long n; const double* dec; const double* ra; const long long* pix; };          // pix != null: point i is the centre of flat pixel pix[i]
 struct Win { int ty1, nrow, nr, a0[3], w[3], W; };      // cell rows ty1 .. ty1 + nrow - 1, columns a0[j] .. a0[j] + w[j] - 1 for j < nr; W = sum w
 
-__device__ __forceinline__ double pix_dec(const DGeo& g, int y) { return g.dec0 + (double)y*g.ddec; }
-__device__ __forceinline__ double pix_ra(const DGeo& g, int x) { return g.ra0 + (double)x*g.dra; }
 __device__ __forceinline__ void pt_pos(const DGeo& g, const Pts& p, long i, double& dec, double& ra) {
 	if (p.pix) {
 		long long q = p.pix[i]; const long long npix = (long long)g.ny*g.nx;
@@ -96,14 +92,14 @@ __global__ __launch_bounds__(256) void pt_fill_kernel(DGeo g, Pts pts, const lon
 	const int c = cell_of(g, dec, ra);
 	plist[off[c] + atomicAdd(&cur[c], 1)] = (int)i;
 	double cd, cr; cell_centre(g, c, cd, cr);
-	const double r = finite_pos(dec, ra) ? vincenty(cd, cr, dec, ra) : DPI;
-	atomicMax(&rad[c], to_bits(r >= 0 ? r : DPI));
+	const double r = finite_pos(dec, ra) ? vincenty(cd, cr, dec, ra) : PXS_PI;
+	atomicMax(&rad[c], to_bits(r >= 0 ? r : PXS_PI));
 	atomicMax(&seed[c], (int)i + 1);
 }
 
 // one jump-flooding pass: every cell takes, among its own seed and those of the 8 cells `step` away (x wraps when the map does), the
 // point nearest to its centre.  seed: point index + 1, 0: none yet
-__global__ __launch_bounds__(256) void flood_kernel(DGeo g, Pts pts, int wrap, int step, const int* __restrict__ in, int* __restrict__ out)
+__global__ __launch_bounds__(256) void flood_kernel(DGeo g, Pts pts, int step, const int* __restrict__ in, int* __restrict__ out)
 {
 	const long c = (long)blockIdx.x*blockDim.x + threadIdx.x;
 	if (c >= (long)g.ncy*g.ncx) return;
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(256) void flood_kernel(DGeo g, Pts pts, int wrap, i
 	for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) {
 		const int yy = cy + dy*step; int xx = cx + dx*step;
 		if (yy < 0 || yy >= g.ncy) continue;
-		if (xx < 0 || xx >= g.ncx) { if (!wrap) continue; xx %= g.ncx; if (xx < 0) xx += g.ncx; }
+		if (xx < 0 || xx >= g.ncx) { if (!g.wrap) continue; xx %= g.ncx; if (xx < 0) xx += g.ncx; }
 		const int s = in[(long)yy*g.ncx + xx];
 		if (s <= 0 || s == best) continue;
 		double pd, pr; pt_pos(g, pts, s - 1, pd, pr);
@@ -151,13 +147,13 @@ __device__ inline void block_scan_incl(int v, int* s) {
 // the points' cells are; all columns where the disc holds a pole
 __device__ inline Win make_window(const DGeo& g, double cdec, double cra, double rad) {
 	Win w; w.nr = 1; w.a0[0] = 0; w.w[0] = g.ncx; w.W = g.ncx; w.ty1 = 0; w.nrow = g.ncy;
-	if (!(rad < DPI)) return w;
+	if (!(rad < PXS_PI)) return w;
 	double ya = (cdec - rad - g.dec0)/g.ddec, yb = (cdec + rad - g.dec0)/g.ddec;
 	if (ya > yb) { const double t = ya; ya = yb; yb = t; }
 	ya = fmax(floor(ya) - 1, 0.0); yb = fmin(ceil(yb) + 1, (double)(g.ny - 1));
 	if (!(yb >= ya)) { w.nrow = 0; return w; }
 	w.ty1 = (int)ya/TILE; w.nrow = (int)yb/TILE - w.ty1 + 1;
-	if (!(fabs(cdec) + rad < 0.5*DPI)) return w;
+	if (!(fabs(cdec) + rad < 0.5*PXS_PI)) return w;
 	const double hw = (asin(fmin(1.0, sin(rad)/cos(cdec))) + 1e-9)/fabs(g.dra) + 1;
 	if (!(2*hw + 2 < g.period)) return w;
 	const double xc = (cra - g.ra0)/g.dra, lo = 0.5*g.nx - 0.5*g.period, hi = lo + g.period;
@@ -240,7 +236,7 @@ template<class T> __global__ __launch_bounds__(256) void gather_kernel(DGeo g, P
 	// how far a winner can still be from its pixel: the largest distance found so far, a little more than that, and no further than rmax
 	auto bound = [&]() {
 		const double hm = block_max(active ? bh : 0.0, red);
-		double u = hm >= 1.0 ? DPI : 2.0*asin(sqrt(hm));
+		double u = hm >= 1.0 ? PXS_PI : 2.0*asin(sqrt(hm));
 		u = u*(1 + 1e-9) + 1e-12;
 		if (rmax > 0) u = fmin(u, rmax*(1 + 1e-9) + 1e-12);
 		return u;
@@ -342,28 +338,6 @@ template<class V, int LAB> __global__ __launch_bounds__(256) void edge_fill_kern
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 namespace {
-struct DistScratch { DevBuf fixed; };
-// scratch per (device, stream), like srcsim.hip's: calls on two streams must not share it, calls on one are ordered by it
-DistScratch& dist_scratch(int device, void* stream) {
-	static std::mutex mu; static std::map<std::pair<int, void*>, DistScratch> tab;
-	std::lock_guard<std::mutex> g(mu);
-	return tab[std::make_pair(device, stream)];
-}
-struct Carve {      // consecutive 16-byte aligned pieces of one buffer
-	size_t at = 0;
-	size_t take(size_t bytes) { const size_t o = at; at += (bytes + 15)/16*16; return o; }
-};
-unsigned blocks_of(long n) { return (unsigned)((n + 255)/256); }
-const size_t SCAN_LDS = 256*sizeof(long long) + 256*sizeof(int);
-
-// cnt[n] -> off[n], act, tot (scan_dev.hpp)
-void scan_counts(hipStream_t st, int n, const int* cnt, long long* bsc, int* bsa, long long* tot, long long* off, TileRec* act) {
-	const int nblk = (n + 256*SCAN_PER - 1)/(256*SCAN_PER);
-	hipLaunchKernelGGL(scan_part_kernel, dim3(nblk), dim3(256), SCAN_LDS, st, n, cnt, bsc, bsa);
-	hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), SCAN_LDS, st, nblk, bsc, bsa, tot);
-	hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk), dim3(256), SCAN_LDS, st, n, cnt, (const long long*)bsc, (const int*)bsa, off, act);
-}
-
 template<class V, int LAB> void run_edges(hipStream_t st, int ny, int nx, const void* map, int nblk, int* bcnt, long long* bsc, int* bsa, long long* tot,
 		long long* off, TileRec* act, long long* out, long long cap)
 {
@@ -378,9 +352,6 @@ template<class V, int LAB> void run_edges(hipStream_t st, int ny, int nx, const 
 
 using namespace pxs;
 using namespace pxs::dst;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 
@@ -396,12 +367,12 @@ int pxm_find_edges(int ny, int nx, const void* d_map, int labeled, int64_t* d_ed
 	const int nblk = (int)nblk_l, nsb = (nblk + 256*SCAN_PER - 1)/(256*SCAN_PER);
 	PXS_HIP(hipSetDevice(device));
 	hipStream_t st = (hipStream_t)stream;
-	DistScratch& sc = dist_scratch(device, stream);
+	DevBuf& fixed = stream_scratch(SCR_DISTANCE, device, stream);
 	Carve cv;
 	const size_t o_cnt = cv.take(4*(size_t)nblk), o_off = cv.take(8*(size_t)nblk), o_act = cv.take(sizeof(TileRec)*(size_t)nblk);
 	const size_t o_bsc = cv.take(8*(size_t)nsb), o_bsa = cv.take(4*(size_t)nsb), o_tot = cv.take(16);
-	sc.fixed.ensure(cv.at);
-	char* base = sc.fixed.as<char>();
+	fixed.ensure(cv.at);
+	char* base = fixed.as<char>();
 	int* bcnt = (int*)(base + o_cnt); long long* off = (long long*)(base + o_off); TileRec* act = (TileRec*)(base + o_act);
 	long long* bsc = (long long*)(base + o_bsc); int* bsa = (int*)(base + o_bsa); long long* tot = (long long*)(base + o_tot);
 	if (labeled) run_edges<int32_t, 1>(st, ny, nx, d_map, nblk, bcnt, bsc, bsa, tot, off, act, (long long*)d_edges, (long long)cap);
@@ -422,7 +393,7 @@ int pxm_distance_from(int ny, int nx, double dec0, double ddec, double ra0, doub
 {
 	PXS_TRY
 	PXS_REQUIRE(ny >= 1 && nx >= 1 && npoint >= 0 && npoint < (int64_t(1) << 31) - 1, "pxm_distance_from: bad sizes");
-	PXS_REQUIRE(ddec != 0 && dra != 0 && (double)nx*std::fabs(dra) <= 2*DPI + 1e-6, "pxm_distance_from: bad geometry (the columns may cover the circle at most once)");
+	const PixGeo pg = make_pixgeo("pxm_distance_from", ny, nx, dec0, ddec, ra0, dra);
 	PXS_REQUIRE(map_dtype == PX_F32 || map_dtype == PX_F64, "pxm_distance_from: the map must be float32 or float64");
 	PXS_REQUIRE(d_omap, "pxm_distance_from: null map");
 	PXS_REQUIRE(npoint == 0 || d_pt_pix || (d_pt_dec && d_pt_ra), "pxm_distance_from: points need coordinates or pixel indices");
@@ -439,17 +410,16 @@ int pxm_distance_from(int ny, int nx, double dec0, double ddec, double ra0, doub
 		PXS_HIP(hipGetLastError());
 		return 0;
 	}
-	DGeo g; g.ny = ny; g.nx = nx; g.dec0 = dec0; g.ddec = ddec; g.ra0 = ra0; g.dra = dra; g.ncy = (int)ncy; g.ncx = (int)ncx; g.period = 2*DPI/std::fabs(dra);
-	const int wrap = std::fabs((double)nx*std::fabs(dra) - 2*DPI) < 1e-6 ? 1 : 0;
+	const DGeo g = {pg, (int)ncy, (int)ncx};
 	const Pts pts = {(long)npoint, d_pt_dec, d_pt_ra, (const long long*)d_pt_pix};
 	const int nsb = (int)((ncell + 256*SCAN_PER - 1)/(256*SCAN_PER));
-	DistScratch& sc = dist_scratch(device, stream);
+	DevBuf& fixed = stream_scratch(SCR_DISTANCE, device, stream);
 	Carve cv;
 	const size_t o_cnt = cv.take(4*(size_t)ncell), o_cur = cv.take(4*(size_t)ncell), o_rad = cv.take(8*(size_t)ncell), o_sda = cv.take(4*(size_t)ncell);
 	const size_t o_sdb = cv.take(4*(size_t)ncell), o_off = cv.take(8*(size_t)ncell), o_act = cv.take(sizeof(TileRec)*(size_t)ncell);
 	const size_t o_bsc = cv.take(8*(size_t)nsb), o_bsa = cv.take(4*(size_t)nsb), o_tot = cv.take(16), o_pl = cv.take(4*(size_t)npoint);
-	sc.fixed.ensure(cv.at);
-	char* base = sc.fixed.as<char>();
+	fixed.ensure(cv.at);
+	char* base = fixed.as<char>();
 	int* cnt = (int*)(base + o_cnt); int* cur = (int*)(base + o_cur); unsigned long long* rad = (unsigned long long*)(base + o_rad);
 	int* sda = (int*)(base + o_sda); int* sdb = (int*)(base + o_sdb); long long* off = (long long*)(base + o_off); TileRec* act = (TileRec*)(base + o_act);
 	long long* bsc = (long long*)(base + o_bsc); int* bsa = (int*)(base + o_bsa); long long* tot = (long long*)(base + o_tot); int* plist = (int*)(base + o_pl);
@@ -460,7 +430,7 @@ int pxm_distance_from(int ny, int nx, double dec0, double ddec, double ra0, doub
 	int s0 = 1;
 	while (2*s0 < (ncx > ncy ? ncx : ncy)) s0 *= 2;
 	for (int s = s0; s >= 1; s /= 2) {
-		hipLaunchKernelGGL(flood_kernel, dim3(blocks_of(ncell)), dim3(256), 0, st, g, pts, wrap, s, (const int*)sda, sdb);
+		hipLaunchKernelGGL(flood_kernel, dim3(blocks_of(ncell)), dim3(256), 0, st, g, pts, s, (const int*)sda, sdb);
 		int* t = sda; sda = sdb; sdb = t;
 	}
 	const size_t shmem = sizeof(double)*(2*NCH*TILE + 4*TILE + 5*NCH + 256) + sizeof(int)*(NCH + 3*256);

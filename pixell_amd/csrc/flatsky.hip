@@ -176,9 +176,6 @@ __global__ __launch_bounds__(256) void mul_axis_kernel(long total, long n, long 
 } // namespace pxs
 
 using namespace pxs;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 

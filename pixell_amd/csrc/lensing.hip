@@ -16,7 +16,6 @@
 namespace pxs {
 
 static constexpr int DEFLECT_MAXBLK = 2048;      // 256 CUs x 8 blocks of 256 threads: the rest of the pixels by the grid-stride loop
-static constexpr double LENS_PI = 3.14159265358979323846;
 
 __device__ __forceinline__ double ld_real(const void* p, int dtype, long i) {
 	return dtype == PX_F32 ? (double)((const float*)p)[i] : ((const double*)p)[i];
@@ -24,7 +23,7 @@ __device__ __forceinline__ double ld_real(const void* p, int dtype, long i) {
 
 // ra into [0, 2 pi) (the form pxs_plan_points documents; it accepts any finite value, so the rounding case 2 pi is harmless)
 __device__ __forceinline__ double wrap_2pi(double a) {
-	if (a < 0 || a >= 2*LENS_PI) a -= 2*LENS_PI*floor(a/(2*LENS_PI));
+	if (a < 0 || a >= 2*PXS_PI) a -= 2*PXS_PI*floor(a/(2*PXS_PI));
 	return a;
 }
 
@@ -57,14 +56,14 @@ __global__ __launch_bounds__(256) void deflect_kernel(long npts, int nx, double 
 					const double x2 = (qx*cp + qy*sp)*nz_ - qz*r, y2 = qy*cp - qx*sp;                    // t' in (e_theta', e_phi')
 					rot = p0 - 2.0*atan2(y2*ut - x2*up, x2*ut + y2*up);
 				}
-			} else { theta = 0.5*LENS_PI - dec; phi = ra; rot = p0; }
+			} else { theta = 0.5*PXS_PI - dec; phi = ra; rot = p0; }
 		} else {
 			double d2 = dec + g0; phi = ra + g1/cos(dec);
-			if (d2 > 0.5*LENS_PI) { d2 = LENS_PI - d2; phi += LENS_PI; }
-			else if (d2 < -0.5*LENS_PI) { d2 = -LENS_PI - d2; phi += LENS_PI; }
-			theta = 0.5*LENS_PI - d2; rot = 0.0;
+			if (d2 > 0.5*PXS_PI) { d2 = PXS_PI - d2; phi += PXS_PI; }
+			else if (d2 < -0.5*PXS_PI) { d2 = -PXS_PI - d2; phi += PXS_PI; }
+			theta = 0.5*PXS_PI - d2; rot = 0.0;
 		}
-		theta = fmin(fmax(theta, 0.0), LENS_PI);      // (rounding of pi/2 - dec at the poles; NaN passes through and is refused by the point plan)
+		theta = fmin(fmax(theta, 0.0), PXS_PI);      // (rounding of pi/2 - dec at the poles; NaN passes through and is refused by the point plan)
 		loc[i] = make_double2(theta, wrap_2pi(phi));
 		if (psi) psi[i] = rot;
 	}
@@ -121,9 +120,6 @@ template<class T, class T2> static void launch_rotate(long npts, int npair, void
 } // namespace pxs
 
 using namespace pxs;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 

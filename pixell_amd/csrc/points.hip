@@ -31,7 +31,6 @@ static const int PT_WMAX = 16;               // largest kernel width
 static const int RS_IPB = 1024, RS_THR = 256;   // radix sort: items and threads per block
 enum { PT_ST_CC = 0, PT_ST_FFT = 1, PT_ST_GRID = 2, PT_ST_INTERP = 3, PT_ST_SPREAD = 4, PT_NSTAGE = 5 };
 static const char* const PT_STAGE_NAMES[PT_NSTAGE] = {"cc_sht", "fft", "grid", "interp", "spread"};
-static const double PT_PI = 3.141592653589793238462643383279502884;
 
 __device__ __forceinline__ double es_kernel(double z, double beta) {
 	const double t = 1.0 - z*z;
@@ -64,9 +63,9 @@ __global__ void pt_bin(long npts, const double* loc, long n1, long n2, int W, in
 	const long i = (long)blockIdx.x*blockDim.x + threadIdx.x;
 	if (i >= npts) return;
 	double th = loc[2*i], ph = loc[2*i+1];
-	if (!(th >= 0.0 && th <= PT_PI) || !(ph == ph) || fabs(ph) > 1e300) { *bad = 1; th = 0.0; ph = 0.0; }
-	double u = ph*(0.5/PT_PI); u -= floor(u);
-	const double x1 = th*(0.5/PT_PI)*(double)n1, x2 = u*(double)n2;
+	if (!(th >= 0.0 && th <= PXS_PI) || !(ph == ph) || fabs(ph) > 1e300) { *bad = 1; th = 0.0; ph = 0.0; }
+	double u = ph*(0.5/PXS_PI); u -= floor(u);
+	const double x1 = th*(0.5/PXS_PI)*(double)n1, x2 = u*(double)n2;
 	double s;
 	const long i0 = pt_first(x1, n1, W, &s), j0 = pt_first(x2, n2, W, &s);
 	xu[i] = make_double2(x1, x2);

@@ -256,9 +256,6 @@ static void rot_group(RotK p, double2* coef, bool make_coef, double2* x1, double
 } // namespace pxs
 
 using namespace pxs;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" int pxa_rotate_alm(int lmax, int ncomp, const void* alm_in, int64_t in_cstride, void* alm_out, int64_t out_cstride, int alm_dtype,
                               double psi, double theta, double phi, int device, void* stream)

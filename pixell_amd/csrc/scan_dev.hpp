@@ -67,4 +67,14 @@ static __global__ __launch_bounds__(256) void scan_apply_kernel(int ntiles, cons
 	}
 }
 
+
+// cnt[n] -> off[n], act, tot; bsc, bsa: one entry per workgroup of the scan, (n + 256*SCAN_PER - 1)/(256*SCAN_PER) of them
+static const size_t SCAN_LDS = 256*sizeof(long long) + 256*sizeof(int);
+static inline void scan_counts(hipStream_t st, int n, const int* cnt, long long* bsc, int* bsa, long long* tot, long long* off, TileRec* act) {
+	const int nblk = (n + 256*SCAN_PER - 1)/(256*SCAN_PER);
+	hipLaunchKernelGGL(scan_part_kernel, dim3(nblk), dim3(256), SCAN_LDS, st, n, cnt, bsc, bsa);
+	hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), SCAN_LDS, st, nblk, bsc, bsa, tot);
+	hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk), dim3(256), SCAN_LDS, st, n, cnt, (const long long*)bsc, (const int*)bsa, off, act);
+}
+
 } // namespace pxs

@@ -913,9 +913,6 @@ void resample_from_cc(pxs_plan* p, hipStream_t st, const double2* leg_cc, double
 
 } // namespace
 
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 

@@ -19,25 +19,23 @@
 #include "../../include/pxsht.h"
 #include "common.hpp"
 #include "scan_dev.hpp"
-#include <map>
-#include <mutex>
+#include "pixgeo.hpp"
 
 namespace pxs {
 
-static constexpr double SRC_PI = 3.14159265358979323846;
 static constexpr int TILE = 16;           // a tile is TILE x TILE pixels: one lane of a 256-lane workgroup per pixel
 static constexpr int NCH = 64;            // objects staged in LDS per step
 static constexpr int NCC = 4;             // map components carried in registers per pass over a tile's list
 static constexpr int PROF_LDS = 4096;     // profile samples (of all profiles together) up to which the tables are kept in LDS
 static constexpr int SRC_MAXBLK = 2048;   // workgroups of the kernels that loop over the listed tiles
 
-struct Geo { int ny, nx; double dec0, ddec, ra0, dra; int wrap; };      // wrap: the columns cover the whole circle
 struct Box { int y1, nyb, x1, nxb; };     // rows y1 .. y1 + nyb - 1, columns (x1 + j) mod nx for j < nxb <= nx; nyb = 0: the disc misses the map
 struct ObjRec { int idx; float dec, ra, cd, rc, hm; int po, pn; };      // a list entry: the object's index, position, cos dec, cut radius, a bound on h beyond which r > rc for certain, its profile (first sample, samples)
 struct Prof { int nprof; const int* off; const float* rs; const float* vs; const float* vmax; int equi; };      // profile q: samples off[q] .. off[q+1]-1; vmax[k] = max_{j >= k} |vs[j]|
 
-__device__ __forceinline__ float pix_dec(const Geo& g, int y) { return (float)(g.dec0 + (double)y*g.ddec); }
-__device__ __forceinline__ float pix_ra(const Geo& g, int x) { return (float)(g.ra0 + (double)x*g.dra); }
+// the pixel coordinates rounded to float: the reference's float32 axes, bit for bit
+__device__ __forceinline__ float pix_decf(const PixGeo& g, int y) { return (float)pix_dec(g, y); }
+__device__ __forceinline__ float pix_raf(const PixGeo& g, int x) { return (float)pix_ra(g, x); }
 __device__ __forceinline__ int prof_id(const Prof& pr, const int* pid, long i) { const int q = pid ? pid[i] : 0; return q < 0 ? 0 : (q >= pr.nprof ? pr.nprof - 1 : q); }
 
 __device__ __forceinline__ float pair_dist(float pdec, float pra, float cp, float odec, float ora, float co) {
@@ -62,7 +60,7 @@ __device__ __forceinline__ float prof_eval(const float* rs, const float* vs, int
 
 // every pixel whose centre can lie within rc of the object, and then some: the radius is widened by 1e-6 (relative and in radians, which
 // covers the float rounding of the coordinates) and the box by up to a pixel on each side
-__device__ inline Box bounding_box(const Geo& g, float odec, float ora, float rcf) {
+__device__ inline Box bounding_box(const PixGeo& g, float odec, float ora, float rcf) {
 	Box b = {0, 0, 0, 0};
 	const double dec = odec, rc = (double)rcf*(1 + 1e-6) + 1e-6;
 	if (!(rc >= 0) || !(fabs(dec) <= 4.0) || !(fabs((double)ora) <= 1e6)) return b;
@@ -70,8 +68,8 @@ __device__ inline Box bounding_box(const Geo& g, float odec, float ora, float rc
 	if (ya > yb) { const double t = ya; ya = yb; yb = t; }
 	ya = fmax(floor(ya), 0.0); yb = fmin(ceil(yb), (double)(g.ny - 1));
 	if (!(yb >= ya)) return b;
-	const double adra = fabs(g.dra), period = 2*SRC_PI/adra;
-	const bool full = !(fabs(dec) + rc < 0.5*SRC_PI);      // the disc holds a pole: every column
+	const double adra = fabs(g.dra), period = 2*PXS_PI/adra;
+	const bool full = !(fabs(dec) + rc < 0.5*PXS_PI);      // the disc holds a pole: every column
 	const double w = full ? period : (asin(fmin(1.0, sin(rc)/cos(dec))) + 1e-6)/adra;      // the half width of a small circle in RA: sin(dRA) = sin(rc)/cos(dec)
 	double xc = ((double)ora - g.ra0)/g.dra;
 	if (g.wrap) {
@@ -93,7 +91,7 @@ __device__ inline Box bounding_box(const Geo& g, float odec, float ora, float rc
 }
 
 // f(tile) once for every tile the box touches
-template<class F> __device__ inline void for_each_tile(const Geo& g, const Box& b, int ntx, F f) {
+template<class F> __device__ inline void for_each_tile(const PixGeo& g, const Box& b, int ntx, F f) {
 	if (b.nyb <= 0) return;
 	const int ty1 = b.y1/TILE, ty2 = (b.y1 + b.nyb - 1)/TILE;
 	const int xe = b.x1 + b.nxb - 1;
@@ -107,7 +105,7 @@ template<class F> __device__ inline void for_each_tile(const Geo& g, const Box& 
 }
 
 // fixed_rcut >= 0: every object has that cut radius (radial sums); otherwise it follows from the amplitudes and the profile
-__global__ __launch_bounds__(256) void obj_prep_kernel(Geo g, long nobj, const float* __restrict__ odec, const float* __restrict__ ora,
+__global__ __launch_bounds__(256) void obj_prep_kernel(PixGeo g, long nobj, const float* __restrict__ odec, const float* __restrict__ ora,
 		const float* __restrict__ amps, int ncomp, long astride, const int* __restrict__ pid, Prof pr, float vmin, float rmax, float fixed_rcut,
 		float* __restrict__ rcut, Box* __restrict__ box)
 {
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(256) void obj_prep_kernel(Geo g, long nobj, const f
 	box[i] = bounding_box(g, odec[i], ora[i], rc);
 }
 
-__global__ __launch_bounds__(256) void tile_count_kernel(Geo g, int ntx, long nobj, const Box* __restrict__ box, int* __restrict__ cnt)
+__global__ __launch_bounds__(256) void tile_count_kernel(PixGeo g, int ntx, long nobj, const Box* __restrict__ box, int* __restrict__ cnt)
 {
 	const long i = (long)blockIdx.x*blockDim.x + threadIdx.x;
 	if (i >= nobj) return;
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(256) void tile_count_kernel(Geo g, int ntx, long no
 }
 
 // the object's record into the list of every tile its box touches, in the order the lanes arrive (tile_sort_kernel orders the lists)
-__global__ __launch_bounds__(256) void tile_fill_kernel(Geo g, int ntx, long nobj, const Box* __restrict__ box, const float* __restrict__ odec,
+__global__ __launch_bounds__(256) void tile_fill_kernel(PixGeo g, int ntx, long nobj, const Box* __restrict__ box, const float* __restrict__ odec,
 		const float* __restrict__ ora, const int* __restrict__ pid, Prof pr, const float* __restrict__ rcut, const long long* __restrict__ off,
 		int* __restrict__ cur, ObjRec* __restrict__ raw)
 {
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(256) void tile_fill_kernel(Geo g, int ntx, long nob
 	const int q = prof_id(pr, pid, i);
 	ObjRec r;
 	r.idx = (int)i; r.dec = odec[i]; r.ra = ora[i]; r.cd = (float)cos((double)r.dec); r.rc = rcut[i];
-	const float s = sinf(0.5f*fminf(r.rc, (float)SRC_PI));
+	const float s = sinf(0.5f*fminf(r.rc, (float)PXS_PI));
 	r.hm = s*s*1.0001f + 1e-30f;
 	r.po = pr.off[q]; r.pn = pr.off[q+1] - r.po;
 	for_each_tile(g, b, ntx, [&](int t) { raw[off[t] + atomicAdd(&cur[t], 1)] = r; });
@@ -189,7 +187,7 @@ __global__ __launch_bounds__(256) void tile_sort_kernel(const TileRec* __restric
 }
 
 // OP: 0 add, 1 max, 2 min.  nprofl: the profile samples staged in LDS (all of them, or 0: read from global memory)
-template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(Geo g, int ntx, T* __restrict__ map, int ncomp, long cstride,
+template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(PixGeo g, int ntx, T* __restrict__ map, int ncomp, long cstride,
 		const float* __restrict__ amps, long astride, Prof pr, int nprofl, const TileRec* __restrict__ act, const long long* __restrict__ tot,
 		const ObjRec* __restrict__ list)
 {
@@ -211,7 +209,7 @@ template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(Ge
 		const int y = ty*TILE + py, x = tx*TILE + px;
 		const bool inside = y < g.ny && x < g.nx;
 		const long p = (long)y*g.nx + x;
-		const float cp = cosf(pix_dec(g, y));
+		const float cp = cosf(pix_decf(g, y));
 		const long long o0 = tr.off;
 		const int n = tr.n;
 		for (int c0 = 0; c0 < ncomp; c0 += NCC) {
@@ -228,8 +226,8 @@ template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(Ge
 				for (int t = tid; t < m*2*TILE; t += 256) {
 					const int o = t/(2*TILE), k = t%(2*TILE);
 					const ObjRec* r = list + (o0 + j0 + o);
-					if (k < TILE) { const double s = sin(0.5*((double)pix_dec(g, ty*TILE + k) - (double)r->dec)); sy[o*TILE + k] = (float)(s*s); }
-					else { const double s = sin(0.5*((double)pix_ra(g, tx*TILE + k - TILE) - (double)r->ra)); sx[o*TILE + k - TILE] = (float)((double)r->cd*s*s); }
+					if (k < TILE) { const double s = sin(0.5*((double)pix_decf(g, ty*TILE + k) - (double)r->dec)); sy[o*TILE + k] = (float)(s*s); }
+					else { const double s = sin(0.5*((double)pix_raf(g, tx*TILE + k - TILE) - (double)r->ra)); sx[o*TILE + k - TILE] = (float)((double)r->cd*s*s); }
 				}
 				__syncthreads();
 				if (inside) for (int o = 0; o < m; o++) {
@@ -251,7 +249,7 @@ template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(Ge
 }
 
 // one workgroup per object over the pixels of its box; the 256 partial sums are added up as a tree in LDS (a fixed order)
-template<class T> __global__ __launch_bounds__(256) void transpose_kernel(Geo g, const T* __restrict__ map, int ncomp, long cstride,
+template<class T> __global__ __launch_bounds__(256) void transpose_kernel(PixGeo g, const T* __restrict__ map, int ncomp, long cstride,
 		const float* __restrict__ odec, const float* __restrict__ ora, float* __restrict__ amps, long astride, const int* __restrict__ pid,
 		Prof pr, const float* __restrict__ rcut, const Box* __restrict__ box)
 {
@@ -270,8 +268,8 @@ template<class T> __global__ __launch_bounds__(256) void transpose_kernel(Geo g,
 		for (long j = tid; j < npx; j += 256) {
 			const int jy = (int)(j/b.nxb), y = b.y1 + jy;
 			int x = b.x1 + (int)(j - (long)jy*b.nxb); if (x >= g.nx) x -= g.nx;
-			const float pd = pix_dec(g, y);
-			const float r = pair_dist(pd, pix_ra(g, x), cosf(pd), od, orr, co);
+			const float pd = pix_decf(g, y);
+			const float r = pair_dist(pd, pix_raf(g, x), cosf(pd), od, orr, co);
 			if (!(r <= rc)) continue;
 			const float P = prof_eval(pr.rs + po, pr.vs + po, pn, pr.equi, r);
 			for (int c = 0; c < NCC; c++) if (c < nc) acc[c] += (float)map[(c0 + c)*cstride + (long)y*g.nx + x]*P;
@@ -287,7 +285,7 @@ template<class T> __global__ __launch_bounds__(256) void transpose_kernel(Geo g,
 }
 
 // one workgroup per object; the bins of all components are summed in LDS
-template<class T> __global__ __launch_bounds__(256) void radial_sum_kernel(Geo g, const T* __restrict__ map, int ncomp, long cstride,
+template<class T> __global__ __launch_bounds__(256) void radial_sum_kernel(PixGeo g, const T* __restrict__ map, int ncomp, long cstride,
 		const float* __restrict__ odec, const float* __restrict__ ora, int nbin, const float* __restrict__ bins, int equi,
 		const Box* __restrict__ box, float* __restrict__ oprofs)
 {
@@ -303,8 +301,8 @@ template<class T> __global__ __launch_bounds__(256) void radial_sum_kernel(Geo g
 	for (long j = tid; j < npx; j += 256) {
 		const int jy = (int)(j/b.nxb), y = b.y1 + jy;
 		int x = b.x1 + (int)(j - (long)jy*b.nxb); if (x >= g.nx) x -= g.nx;
-		const float pd = pix_dec(g, y);
-		const float r = pair_dist(pd, pix_ra(g, x), cosf(pd), od, orr, co);
+		const float pd = pix_decf(g, y);
+		const float r = pair_dist(pd, pix_raf(g, x), cosf(pd), od, orr, co);
 		if (!(r >= r0 && r < r1)) continue;
 		int k;
 		if (equi) {      // a guess, put right against the edges themselves
@@ -324,25 +322,7 @@ template<class T> __global__ __launch_bounds__(256) void radial_sum_kernel(Geo g
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
-struct SrcScratch { DevBuf fixed, pairs; };
-// scratch per (device, stream), like the alm2cl scratch (almops.hip): calls on two streams must not share it, calls on one are ordered by it
-SrcScratch& src_scratch(int device, void* stream) {
-	static std::mutex mu; static std::map<std::pair<int, void*>, SrcScratch> tab;
-	std::lock_guard<std::mutex> g(mu);
-	return tab[std::make_pair(device, stream)];
-}
-struct Carve {      // consecutive 16-byte aligned pieces of one buffer
-	size_t at = 0;
-	size_t take(size_t bytes) { const size_t o = at; at += (bytes + 15)/16*16; return o; }
-};
-Geo make_geo(int ny, int nx, double dec0, double ddec, double ra0, double dra) {
-	Geo g; g.ny = ny; g.nx = nx; g.dec0 = dec0; g.ddec = ddec; g.ra0 = ra0; g.dra = dra;
-	g.wrap = std::fabs((double)nx*std::fabs(dra) - 2*SRC_PI) < 1e-6 ? 1 : 0;
-	return g;
-}
-unsigned blocks_of(long n) { return (unsigned)((n + 255)/256); }
-
-template<class T> void launch_paint(int op, dim3 grid, size_t shmem, hipStream_t st, Geo g, int ntx, void* map, int ncomp, long cstride,
+template<class T> void launch_paint(int op, dim3 grid, size_t shmem, hipStream_t st, PixGeo g, int ntx, void* map, int ncomp, long cstride,
 		const float* amps, long astride, Prof pr, int nprofl, const TileRec* act, const long long* tot, const ObjRec* list)
 {
 	if (op == 0) hipLaunchKernelGGL((paint_kernel<T, 0>), grid, dim3(256), shmem, st, g, ntx, (T*)map, ncomp, cstride, amps, astride, pr, nprofl, act, tot, list);
@@ -354,9 +334,6 @@ template<class T> void launch_paint(int op, dim3 grid, size_t shmem, hipStream_t
 } // namespace pxs
 
 using namespace pxs;
-#define PXS_TRY try {
-#define PXS_CATCH } catch (const pxs::Error& e) { pxs::set_last_error(e.what()); return e.code; } \
-	catch (const std::exception& e) { pxs::set_last_error(e.what()); return pxs::PXS_ERR_ARG; } return 0;
 
 extern "C" {
 
@@ -367,7 +344,7 @@ int pxm_sim_objects(int ny, int nx, double dec0, double ddec, double ra0, double
 {
 	PXS_TRY
 	PXS_REQUIRE(ny >= 1 && nx >= 1 && ncomp >= 0 && nobj >= 0 && nobj < (int64_t(1) << 31), "pxm_sim_objects: bad sizes");
-	PXS_REQUIRE(ddec != 0 && dra != 0 && (double)nx*std::fabs(dra) <= 2*SRC_PI + 1e-6, "pxm_sim_objects: bad geometry (the columns may cover the circle at most once)");
+	const PixGeo g = make_pixgeo("pxm_sim_objects", ny, nx, dec0, ddec, ra0, dra);
 	PXS_REQUIRE(map_dtype == PX_F32 || map_dtype == PX_F64, "pxm_sim_objects: the map must be float32 or float64");
 	PXS_REQUIRE(op >= 0 && op <= 2, "pxm_sim_objects: op must be 0 (add), 1 (max) or 2 (min)");
 	PXS_REQUIRE(!(transpose && op != 0), "pxm_sim_objects: the transpose is that of op = add");
@@ -380,16 +357,15 @@ int pxm_sim_objects(int ny, int nx, double dec0, double ddec, double ra0, double
 	PXS_REQUIRE(ntiles < (1l << 31), "pxm_sim_objects: the map has too many tiles");
 	PXS_HIP(hipSetDevice(device));
 	hipStream_t st = (hipStream_t)stream;
-	const Geo g = make_geo(ny, nx, dec0, ddec, ra0, dra);
 	const Prof pr = {nprof, d_prof_off, d_prof_rs, d_prof_vs, d_prof_vmax, prof_equi ? 1 : 0};
 	const int nblk = (int)((ntiles + 256*SCAN_PER - 1)/(256*SCAN_PER));
-	SrcScratch& sc = src_scratch(device, stream);
+	DevBuf& fixed = stream_scratch(SCR_SRC_FIXED, device, stream);
 	Carve cv;
 	const size_t o_rcut = cv.take(4*(size_t)nobj), o_box = cv.take(sizeof(Box)*(size_t)nobj);
 	const size_t o_cnt = cv.take(4*(size_t)ntiles), o_cur = cv.take(4*(size_t)ntiles), o_off = cv.take(8*(size_t)ntiles), o_act = cv.take(sizeof(TileRec)*(size_t)ntiles);
 	const size_t o_bsc = cv.take(8*(size_t)nblk), o_bsa = cv.take(4*(size_t)nblk), o_tot = cv.take(16);
-	sc.fixed.ensure(cv.at);
-	char* base = sc.fixed.as<char>();
+	fixed.ensure(cv.at);
+	char* base = fixed.as<char>();
 	float* rcut = (float*)(base + o_rcut); Box* box = (Box*)(base + o_box);
 	hipLaunchKernelGGL(obj_prep_kernel, dim3(blocks_of(nobj)), dim3(256), 0, st, g, (long)nobj, d_obj_dec, d_obj_ra, (const float*)d_amps, ncomp, (long)amp_cstride,
 		d_prof_ids, pr, (float)vmin, (float)rmax, -1.0f, rcut, box);
@@ -402,18 +378,15 @@ int pxm_sim_objects(int ny, int nx, double dec0, double ddec, double ra0, double
 	int* cnt = (int*)(base + o_cnt); int* cur = (int*)(base + o_cur); long long* off = (long long*)(base + o_off); TileRec* act = (TileRec*)(base + o_act);
 	long long* bsc = (long long*)(base + o_bsc); int* bsa = (int*)(base + o_bsa); long long* tot = (long long*)(base + o_tot);
 	PXS_HIP(hipMemsetAsync(cnt, 0, o_off - o_cnt, st));      // (the counts and the fill cursors)
-	const size_t scan_lds = 256*sizeof(long long) + 256*sizeof(int);
 	hipLaunchKernelGGL(tile_count_kernel, dim3(blocks_of(nobj)), dim3(256), 0, st, g, (int)ntx, (long)nobj, (const Box*)box, cnt);
-	hipLaunchKernelGGL(scan_part_kernel, dim3(nblk), dim3(256), scan_lds, st, (int)ntiles, (const int*)cnt, bsc, bsa);
-	hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), scan_lds, st, nblk, bsc, bsa, tot);
-	hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk), dim3(256), scan_lds, st, (int)ntiles, (const int*)cnt, (const long long*)bsc, (const int*)bsa, off, act);
+	scan_counts(st, (int)ntiles, cnt, bsc, bsa, tot, off, act);
 	PXS_HIP(hipGetLastError());
 	long long htot[2] = {0, 0};      // the one number the host needs: how long the lists are together
 	PXS_HIP(hipMemcpyAsync(htot, tot, sizeof(htot), hipMemcpyDeviceToHost, st));
 	PXS_HIP(hipStreamSynchronize(st));
 	if (htot[0] <= 0) return 0;
-	sc.pairs.ensure(2*sizeof(ObjRec)*(size_t)htot[0]);
-	ObjRec* raw = sc.pairs.as<ObjRec>(); ObjRec* list = raw + htot[0];
+	DevBuf& pairs = stream_scratch(SCR_SRC_PAIRS, device, stream); pairs.ensure(2*sizeof(ObjRec)*(size_t)htot[0]);
+	ObjRec* raw = pairs.as<ObjRec>(); ObjRec* list = raw + htot[0];
 	const unsigned nwg = (unsigned)(htot[1] < SRC_MAXBLK ? htot[1] : SRC_MAXBLK);
 	hipLaunchKernelGGL(tile_fill_kernel, dim3(blocks_of(nobj)), dim3(256), 0, st, g, (int)ntx, (long)nobj, (const Box*)box, d_obj_dec, d_obj_ra, d_prof_ids, pr, (const float*)rcut, (const long long*)off, cur, raw);
 	hipLaunchKernelGGL(tile_sort_kernel, dim3(nwg), dim3(256), 256*sizeof(int), st, (const TileRec*)act, (const long long*)tot, (const ObjRec*)raw, list);
@@ -431,7 +404,7 @@ int pxm_radial_sum(int ny, int nx, double dec0, double ddec, double ra0, double 
 {
 	PXS_TRY
 	PXS_REQUIRE(ny >= 1 && nx >= 1 && ncomp >= 0 && nobj >= 0 && nobj < (int64_t(1) << 31) && nbin >= 0, "pxm_radial_sum: bad sizes");
-	PXS_REQUIRE(ddec != 0 && dra != 0 && (double)nx*std::fabs(dra) <= 2*SRC_PI + 1e-6, "pxm_radial_sum: bad geometry (the columns may cover the circle at most once)");
+	const PixGeo g = make_pixgeo("pxm_radial_sum", ny, nx, dec0, ddec, ra0, dra);
 	PXS_REQUIRE(map_dtype == PX_F32 || map_dtype == PX_F64, "pxm_radial_sum: the map must be float32 or float64");
 	if (nobj == 0 || ncomp == 0 || nbin == 0) return 0;
 	PXS_REQUIRE(d_map && d_obj_dec && d_obj_ra && d_bins && d_oprofs && rlast >= 0, "pxm_radial_sum: bad arguments");
@@ -439,12 +412,11 @@ int pxm_radial_sum(int ny, int nx, double dec0, double ddec, double ra0, double 
 	PXS_REQUIRE((size_t)ncomp*nbin*sizeof(float) <= 48*1024, "pxm_radial_sum: components x bins must not exceed 12288");
 	PXS_HIP(hipSetDevice(device));
 	hipStream_t st = (hipStream_t)stream;
-	const Geo g = make_geo(ny, nx, dec0, ddec, ra0, dra);
-	SrcScratch& sc = src_scratch(device, stream);
+	DevBuf& fixed = stream_scratch(SCR_SRC_FIXED, device, stream);
 	Carve cv;
 	const size_t o_rcut = cv.take(4*(size_t)nobj), o_box = cv.take(sizeof(Box)*(size_t)nobj);
-	sc.fixed.ensure(cv.at);
-	char* base = sc.fixed.as<char>();
+	fixed.ensure(cv.at);
+	char* base = fixed.as<char>();
 	float* rcut = (float*)(base + o_rcut); Box* box = (Box*)(base + o_box);
 	const Prof none = {0, nullptr, nullptr, nullptr, nullptr, 0};
 	hipLaunchKernelGGL(obj_prep_kernel, dim3(blocks_of(nobj)), dim3(256), 0, st, g, (long)nobj, d_obj_dec, d_obj_ra, (const float*)nullptr, 0, 0l,

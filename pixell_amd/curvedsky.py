@@ -15,8 +15,7 @@ Differences that matter for speed, not for results:
 """
 import os
 import numpy as np
-from . import enmap, sht, wcs as wcsutils
-from .sht import _is_tensor, _np_dtype, _torch
+from . import enmap, sht, _lib, _arrays as A, wcs as wcsutils
 
 from .geometry import Bunch, degree
 
@@ -111,13 +110,7 @@ def quad_weights(shape, wcs, pix_tol=1e-6, row_order="reference"):
 # ---------------------------------------------------------------------------------------
 def _mdata(map):
 	if isinstance(map, enmap.dmap): return map.tensor
-	return map if _is_tensor(map) else np.asarray(map)      # (a bare device tensor stays where it is: alm2map_pos makes one for a tensor alm)
-
-def _zeros_like_kind(shape, dtype, like):
-	if _is_tensor(like):
-		torch = _torch()
-		return torch.zeros(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
-	return np.zeros(shape, dtype)
+	return map if A.is_tensor(map) else np.asarray(map)      # (a bare device tensor stays where it is: alm2map_pos makes one for a tensor alm)
 
 def prepare_alm(alm=None, ainfo=None, lmax=None, pre=(), dtype=np.float64, convert=False, like=None):
 	"""(alm, ainfo) ready for a transform of maps of real type `dtype` (the contract of curvedsky.prepare_alm, curvedsky.py:1413-1427):
@@ -127,12 +120,12 @@ def prepare_alm(alm=None, ainfo=None, lmax=None, pre=(), dtype=np.float64, conve
 	if alm is None:
 		if ainfo is None and lmax is None: raise ValueError("prepare_alm needs either alm, ainfo or lmax to be specified")
 		ainfo = ainfo if ainfo is not None else alm_info(lmax)
-		return _zeros_like_kind(tuple(pre)+(ainfo.nelem,), want, like), ainfo
+		return A.zeros(tuple(pre)+(ainfo.nelem,), want, like), ainfo
 	ainfo = ainfo if ainfo is not None else alm_info(nalm=alm.shape[-1])
-	have = _np_dtype(alm)
+	have = A.np_dtype(alm)
 	if have != want:
 		if not convert: raise ValueError("alm had dtype '%s', but expected '%s'" % (str(have), str(want)))
-		alm = alm.to(getattr(_torch(), np.dtype(want).name)) if _is_tensor(alm) else alm.astype(want)
+		alm = A.astype(alm, want)
 	return alm, ainfo
 
 def _atleast(x, n):
@@ -140,7 +133,7 @@ def _atleast(x, n):
 	return x
 
 def _contig(x):
-	if _is_tensor(x): return x if x.is_contiguous() else x.contiguous()
+	if A.is_tensor(x): return x if x.is_contiguous() else x.contiguous()
 	return x
 
 def _batched_jobs(spin, alm_full, map_full):
@@ -161,7 +154,7 @@ def _batched_jobs(spin, alm_full, map_full):
 def _as_view(x, shape):
 	"""x reshaped WITHOUT copying (results are written through these views), or None"""
 	try:
-		if _is_tensor(x): return x.view(shape)
+		if A.is_tensor(x): return x.view(shape)
 		v = x.view(); v.shape = tuple(int(np.prod(x.shape[:x.ndim-len(shape)+1], dtype=int)) if n == -1 else n for n in shape); return v
 	except (RuntimeError, AttributeError): return None
 
@@ -234,7 +227,7 @@ def _padded_like(map, pads, fill):
 	mdata = _mdata(map)
 	shape = tuple(map.shape[:-2])+(map.shape[-2]+y0+y1, map.shape[-1]+x0+x1)
 	w = map.wcs.deepcopy(); w.wcs.crpix[0] += x0; w.wcs.crpix[1] += y0
-	buf = _zeros_like_kind(shape, _np_dtype(mdata), mdata)
+	buf = A.zeros(shape, A.np_dtype(mdata), mdata)
 	if fill: buf[..., y0:y0+map.shape[-2], x0:x0+map.shape[-1]] = mdata
 	return (enmap.dmap(buf, w) if isinstance(map, enmap.dmap) else enmap.ndmap(buf, w))
 
@@ -245,11 +238,11 @@ def _crop_into(map, pmap, pads):
 def alm2map_2d(alm, map, ainfo=None, minfo=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, pix_tol=1e-6):
 	"""curvedsky.alm2map_2d + alm2map_raw_2d (curvedsky.py:756-774, 900-926)"""
 	if copy:
-		if adjoint and alm is not None: alm = alm.clone() if _is_tensor(alm) else alm.copy()
+		if adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
 		elif not adjoint: map = map.copy()
 	mdata = _mdata(map)
-	if adjoint: alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=_np_dtype(mdata), convert=False, like=mdata)
-	else:       alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=_np_dtype(mdata), convert=True, like=mdata)
+	if adjoint: alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=False, like=mdata)
+	else:       alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=True, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	pads = _native_pads(minfo, use_y=True)
 	if pads != ((0, 0), (0, 0)):
@@ -285,9 +278,9 @@ def map2alm_2d(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], de
 	if adjoint:
 		if copy and map is not None: map = map.copy()
 	else:
-		if copy and alm is not None: alm = alm.clone() if _is_tensor(alm) else alm.copy()
+		if copy and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
 	mdata = _mdata(map)
-	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=map.shape[:-2], dtype=_np_dtype(mdata), convert=adjoint, like=mdata)
+	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=adjoint, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	if deriv:
 		raise NotImplementedError("ducc does not support derivatives for map2alm operations. Can be worked around if necessary.")
@@ -332,10 +325,10 @@ def _flat(m):
 def alm2map_cyl(alm, map, ainfo=None, minfo=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, pix_tol=1e-6):
 	"""curvedsky.alm2map_cyl + alm2map_raw_cyl (curvedsky.py:776-794, 928-962)"""
 	if copy:
-		if adjoint and alm is not None: alm = alm.clone() if _is_tensor(alm) else alm.copy()
+		if adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
 		elif not adjoint: map = map.copy()
 	mdata = _mdata(map)
-	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=_np_dtype(mdata), convert=not adjoint, like=mdata)
+	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=not adjoint, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	pads = _native_pads(minfo, use_y=False)
 	if pads != ((0, 0), (0, 0)):
@@ -379,10 +372,10 @@ def map2alm_cyl(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], w
 	if adjoint:
 		if copy and map is not None: map = map.copy()
 	else:
-		if copy and alm is not None: alm = alm.clone() if _is_tensor(alm) else alm.copy()
+		if copy and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
 	mdata = _mdata(map)
 	# (with deriv the alm has no component axis; the reference allocates [2,nelem] here and then fails its shape check)
-	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=map.shape[:-3] if deriv else map.shape[:-2], dtype=_np_dtype(mdata), convert=adjoint, like=mdata)
+	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=map.shape[:-3] if deriv else map.shape[:-2], dtype=A.np_dtype(mdata), convert=adjoint, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	# Row weights.  The reference applies `weights` to the rows of its flipped buffer (north first: map2buffer, curvedsky.py:866-868),
 	# here the rings are the map's rows as stored.  weights_order="reference" (default) reproduces the reference result for result:
@@ -403,9 +396,9 @@ def map2alm_cyl(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], w
 			weights = np.abs(np.sin(dec[1:])-np.sin(dec[:-1]))*abs(map.wcs.wcs.cdelt[0])*degree
 			if ref_order and not minfo.flip[0]: weights = weights[::-1]
 	else:
-		weights = np.asarray(weights.cpu() if _is_tensor(weights) else weights)
+		weights = np.asarray(weights.cpu() if A.is_tensor(weights) else weights)
 		if ref_order and minfo.flip[0]: weights = weights[::-1]
-	weights = np.ascontiguousarray(weights, dtype=_np_dtype(mdata))
+	weights = np.ascontiguousarray(weights, dtype=A.np_dtype(mdata))
 	pads = _native_pads(minfo, use_y=False)
 	if pads != ((0, 0), (0, 0)):
 		# partial-width map: zero-extend the rings to the full circle (curvedsky.py:866-871); weights are per row
@@ -418,12 +411,12 @@ def map2alm_cyl(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], w
 	alm_full = _atleast(alm, 2 if deriv else 3)
 	map_full = _atleast(mdata, 4)
 	_check_shapes(alm_full, map_full, deriv)
-	if _is_tensor(mdata): w = _torch().as_tensor(weights, device=mdata.device)[:, None]
+	if A.is_tensor(mdata): w = A.torch().as_tensor(weights, device=mdata.device)[:, None]
 	else: w = weights[:, None]
 	def wmul(m): return m*w
 	if deriv:
 		# gradient maps [ddec, dra] <-> alm through the DERIV1 transforms (curvedsky.py:1067-1076)
-		decflip = (_torch().as_tensor([-1.0, 1.0], device=mdata.device, dtype=mdata.dtype) if _is_tensor(mdata) else np.array([-1.0, 1.0], _np_dtype(mdata)))[:, None, None]
+		decflip = (A.torch().as_tensor([-1.0, 1.0], device=mdata.device, dtype=mdata.dtype) if A.is_tensor(mdata) else np.array([-1.0, 1.0], A.np_dtype(mdata)))[:, None, None]
 		for I in nditer(map_full.shape[:-3]):
 			shp = map_full[I].shape
 			def Y(a):   return sht.synthesis(alm=_contig(a), spin=1, mode="DERIV1", **kwargs).reshape(shp)
@@ -484,7 +477,7 @@ def prepare_raw(alm, map, ainfo=None, lmax=None, deriv=False, verbose=False, nth
 	"""(alm_full, map_full, ainfo, nthread): alm [..., ncomp, nelem] and map [..., ncomp, pixels] with agreeing leading dimensions
 	(deriv: alm [..., nelem], map [..., 2, pixels]); AssertionError otherwise (curvedsky.py:1429-1446)"""
 	mdata = _mdata(map)
-	alm, ainfo = prepare_alm(alm, ainfo, lmax=lmax, pre=map.shape[:-pixdims], dtype=_np_dtype(mdata), convert=convert_alm, like=mdata)
+	alm, ainfo = prepare_alm(alm, ainfo, lmax=lmax, pre=map.shape[:-pixdims], dtype=A.np_dtype(mdata), convert=convert_alm, like=mdata)
 	alm_full = _atleast(alm, 2 if deriv else 3); map_full = _atleast(mdata, pixdims+2)
 	if deriv:
 		assert map_full.shape[-pixdims-1] == 2, "map must have shape [...,2,%s] when deriv is True" % ("nloc" if pixdims == 1 else "ny,nx")
@@ -538,7 +531,7 @@ def get_ring_info_radial(r): return _geo.radial_rings(r)
 def apply_minfo_theta_lim(minfo, theta_min=None, theta_max=None): return _geo.theta_window(minfo, theta_min, theta_max)
 def prepare_healmap(healmap, nside=None, pre=(), dtype=np.float64, like=None):
 	if healmap is not None: return healmap
-	return _zeros_like_kind(tuple(pre)+(12*int(nside)**2,), dtype, like)
+	return A.zeros(tuple(pre)+(12*int(nside)**2,), dtype, like)
 
 def _healpix_kwargs(npix, ainfo, theta_min, theta_max):
 	rinfo = apply_minfo_theta_lim(get_ring_info_healpix(npix2nside(npix)), theta_min, theta_max)
@@ -549,9 +542,9 @@ def alm2map_healpix(alm, healmap=None, spin=[0, 2], deriv=False, adjoint=False, 
 	"""alm[..., ncomp, nelem] -> healpix map[..., ncomp, 12 nside^2] in RING order (curvedsky.alm2map_healpix, curvedsky.py:312-351);
 	adjoint: the transpose, map -> alm.  With deriv the map is [..., 2, npix] = (d/ddec, d/dra / cos dec)."""
 	if copy:
-		if adjoint and alm is not None: alm = alm.clone() if _is_tensor(alm) else alm.copy()
-		elif not adjoint and healmap is not None: healmap = healmap.clone() if _is_tensor(healmap) else healmap.copy()
-	rdt = real_dtype(_np_dtype(alm))
+		if adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
+		elif not adjoint and healmap is not None: healmap = healmap.clone() if A.is_tensor(healmap) else healmap.copy()
+	rdt = real_dtype(A.np_dtype(alm))
 	alm, ainfo = prepare_alm(alm, ainfo, dtype=rdt, convert=not adjoint, like=alm)
 	healmap = prepare_healmap(healmap, nside, alm.shape[:-2]+(2,) if deriv else alm.shape[:-1], rdt, like=alm)
 	alm_full = _atleast(alm, 2 if deriv else 3); map_full = _atleast(healmap, 3)
@@ -580,19 +573,19 @@ def map2alm_healpix(healmap, alm=None, ainfo=None, lmax=None, spin=[0, 2], weigh
 	"""healpix map -> alm with pixel-area weights 4 pi / npix (or `weights`) and `niter` Jacobi refinements
 	(curvedsky.map2alm_healpix, curvedsky.py:353-403; like healpy.map2alm).  adjoint: the transpose of that operator, alm -> map."""
 	if copy:
-		if adjoint and healmap is not None: healmap = healmap.clone() if _is_tensor(healmap) else healmap.copy()
-		elif not adjoint and alm is not None: alm = alm.clone() if _is_tensor(alm) else alm.copy()
+		if adjoint and healmap is not None: healmap = healmap.clone() if A.is_tensor(healmap) else healmap.copy()
+		elif not adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
 	if deriv: raise NotImplementedError("map2alm_healpix with deriv=True is broken")          # (as in the reference, curvedsky.py:378)
-	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=healmap.shape[:-1], dtype=_np_dtype(healmap), convert=adjoint, like=healmap)
+	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=healmap.shape[:-1], dtype=A.np_dtype(healmap), convert=adjoint, like=healmap)
 	alm_full = _atleast(alm, 3); map_full = _atleast(healmap, 3)
 	rinfo, kwargs = _healpix_kwargs(map_full.shape[-1], ainfo, theta_min, theta_max)
 	if weights is None: weights = 4*np.pi/rinfo.npix
-	if _is_tensor(healmap) and not np.isscalar(weights): weights = _torch().as_tensor(np.asarray(weights), device=healmap.device)
+	if A.is_tensor(healmap) and not np.isscalar(weights): weights = A.torch().as_tensor(np.asarray(weights), device=healmap.device)
 	for I in nditer(map_full.shape[:-2]):
 		for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
 			Ij = I+(slice(j1, j2),)
 			like = map_full[Ij]
-			def Y(a):   return sht.synthesis(alm=_contig(a), map=_zeros_like_kind(tuple(like.shape), _np_dtype(like), like), spin=int(s), **kwargs)
+			def Y(a):   return sht.synthesis(alm=_contig(a), map=A.zeros(tuple(like.shape), A.np_dtype(like), like), spin=int(s), **kwargs)
 			def YT(m):  return sht.adjoint_synthesis(map=_contig(m), spin=int(s), **kwargs)
 			def YTW(m): return YT(m*weights)
 			def WY(a):  return Y(a)*weights
@@ -603,14 +596,14 @@ def map2alm_healpix(healmap, alm=None, ainfo=None, lmax=None, spin=[0, 2], weigh
 # ---------------------------------------------------------------------------------------
 # arbitrary positions: the point transforms of sht.synthesis_general (curvedsky.py:174-207, 993-1016, 1088-1120)
 # ---------------------------------------------------------------------------------------
-def _copy(x): return None if x is None else (x.clone() if _is_tensor(x) else x.copy())
+def _copy(x): return None if x is None else (x.clone() if A.is_tensor(x) else x.copy())
 
 def _loc_from_pos(pos):
 	"""pos [{dec,ra}, ...] -> loc [..., {codec, ra}] with ra made positive (curvedsky.py:185-193)"""
-	if _is_tensor(pos):
-		loc = pos.movedim(0, -1).to(_torch().float64).clone()
+	if A.is_tensor(pos):
+		loc = pos.movedim(0, -1).to(A.torch().float64).clone()
 		loc[..., 0] = np.pi/2 - loc[..., 0]
-		loc[..., 1] = _torch().where(loc[..., 1] < 0, loc[..., 1]+2*np.pi, loc[..., 1])
+		loc[..., 1] = A.torch().where(loc[..., 1] < 0, loc[..., 1]+2*np.pi, loc[..., 1])
 		return loc
 	loc = np.moveaxis(np.asarray(pos, np.float64), 0, -1).copy(order="C")
 	loc[..., 0] *= -1; loc[..., 0] += np.pi/2
@@ -632,7 +625,7 @@ def alm2map_pos(alm, pos=None, loc=None, ainfo=None, map=None, spin=[0, 2], deri
 	npts = int(loc.shape[0])
 	if map is None:
 		oshape = tuple(alm.shape[:-1])+((2, npts) if deriv else (npts,))
-		mflat = _zeros_like_kind(oshape, real_dtype(_np_dtype(alm)), alm)
+		mflat = A.zeros(oshape, real_dtype(A.np_dtype(alm)), alm)
 	else: mflat = map.reshape(tuple(map.shape[:map.ndim-len(lpre)])+(npts,))
 	res = alm2map_raw_general(alm, mflat, loc, ainfo=ainfo, spin=spin, deriv=deriv, nthread=nthread, verbose=verbose, epsilon=epsilon, adjoint=adjoint)
 	if adjoint: return res
@@ -645,7 +638,7 @@ def alm2map_raw_general(alm, map, loc, ainfo=None, spin=[0, 2], deriv=False, cop
 		if adjoint: alm = _copy(alm)
 		else: map = _copy(map)
 	alm_full, map_full, ainfo, nthread = prepare_raw(alm, map, ainfo=ainfo, deriv=deriv, nthread=nthread, pixdims=1, convert_alm=not adjoint)
-	if epsilon is None: epsilon = 1e-10 if _np_dtype(map_full) == np.float64 else 1e-6
+	if epsilon is None: epsilon = 1e-10 if A.np_dtype(map_full) == np.float64 else 1e-6
 	kw = dict(loc=loc, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride, epsilon=epsilon)
 	kw["plan"] = sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon)     # one binning of the points for every spin group
 	func = sht.adjoint_synthesis_general if adjoint else sht.synthesis_general
@@ -668,7 +661,7 @@ def alm2map_raw_general(alm, map, loc, ainfo=None, spin=[0, 2], deriv=False, cop
 
 def _dec_flip(like):
 	f = np.array([-1.0, 1.0])[:, None]
-	return _torch().as_tensor(f, dtype=like.dtype, device=like.device) if _is_tensor(like) else f.astype(like.dtype)
+	return A.torch().as_tensor(f, dtype=like.dtype, device=like.device) if A.is_tensor(like) else f.astype(like.dtype)
 
 def map2alm_raw_general(map, loc, alm=None, ainfo=None, lmax=None, spin=[0, 2], weights=None, deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, niter=0, epsilon=None):
 	"""values at loc [npts, 2] -> alm: weighted adjoint synthesis (pixel weights `weights`, default 1) with `niter` Jacobi refinements
@@ -677,12 +670,12 @@ def map2alm_raw_general(map, loc, alm=None, ainfo=None, lmax=None, spin=[0, 2], 
 		if copy and map is not None: map = _copy(map)
 	else:
 		if copy and alm is not None: alm = _copy(alm)
-	if epsilon is None: epsilon = 1e-10 if _np_dtype(_mdata(map)) == np.float64 else 1e-6
+	if epsilon is None: epsilon = 1e-10 if A.np_dtype(_mdata(map)) == np.float64 else 1e-6
 	alm_full, map_full, ainfo, nthread = prepare_raw(alm, map, ainfo=ainfo, lmax=lmax, deriv=deriv, nthread=nthread, pixdims=1, convert_alm=adjoint)
 	kw = dict(loc=loc, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride, epsilon=epsilon)
 	kw["plan"] = sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon)     # shared by the spin groups and the Jacobi steps
 	if weights is None: weights = 1.0
-	if _is_tensor(map_full) and not np.isscalar(weights): weights = _torch().as_tensor(np.asarray(weights), device=map_full.device)
+	if A.is_tensor(map_full) and not np.isscalar(weights): weights = A.torch().as_tensor(np.asarray(weights), device=map_full.device)
 	for I in nditer(map_full.shape[:-2]):
 		if deriv:
 			def Y(a):   return sht.synthesis_general(alm=_contig(a), mode="DERIV1", spin=1, **kw)
@@ -772,7 +765,7 @@ def prof2alm(profile, dir=[0, np.pi/2], spin=0, geometry="CC", nthread=None, nor
 # ---------------------------------------------------------------------------------------
 def almxfl(alm, lfilter=None, ainfo=None, out=None):
 	"""a_lm * lfilter(l); lfilter is an array starting at l=0 or a function of l (curvedsky.py:630-652)"""
-	if not _is_tensor(alm): alm = np.asarray(alm)
+	if not A.is_tensor(alm): alm = np.asarray(alm)
 	ainfo = alm_info(nalm=alm.shape[-1]) if ainfo is None else ainfo
 	if callable(lfilter):
 		l = np.arange(ainfo.lmax+1.0)
@@ -781,7 +774,7 @@ def almxfl(alm, lfilter=None, ainfo=None, out=None):
 
 def alm2cl(alm, alm2=None, ainfo=None, dtype=None):
 	"""(cross) power spectrum of alm (and alm2, which must broadcast) (curvedsky.py:674-712)"""
-	if not _is_tensor(alm): alm = np.asarray(alm)
+	if not A.is_tensor(alm): alm = np.asarray(alm)
 	ainfo = alm_info(nalm=alm.shape[-1]) if ainfo is None else ainfo
 	return ainfo.alm2cl(alm, alm2=alm2, dtype=dtype)
 
@@ -840,7 +833,7 @@ def _transpose_index(ainfo, device=None):
 		arange, repeat, cumsum, cat, minimum = np.arange, np.repeat, np.cumsum, np.concatenate, np.minimum
 		ms = ainfo.mstart.astype(np.int64); zero = np.zeros(1, np.int64)
 	else:
-		torch = _torch()
+		torch = A.torch()
 		arange = lambda n: torch.arange(n, device=device, dtype=torch.int64)
 		repeat, cumsum, cat = torch.repeat_interleave, (lambda x: torch.cumsum(x, 0)), torch.cat
 		minimum = lambda a, b: torch.clamp(a, max=b)
@@ -856,7 +849,7 @@ def _transpose_index(ainfo, device=None):
 def transpose_alm(ainfo, alm, out=None):
 	"""alm_info.transpose_alm (curvedsky.py:443-451): reorder numbers generated in l-major order into
 	the m-major layout.  alm is out is allowed."""
-	if _is_tensor(alm):
+	if A.is_tensor(alm):
 		src, dst = _transpose_index(ainfo, alm.device)
 		if out is None: out = alm.clone()
 	else:
@@ -875,7 +868,7 @@ def rand_alm_white(ainfo, pre=None, alm=None, seed=None, dtype=np.complex128, m_
 	are drawn on the GPU (torch's Philox generator seeded with `seed`) straight into the m-major layout and stay there (a CUDA
 	tensor is returned) -- same distribution, NOT the reference's numbers for a seed."""
 	if rng == "device":
-		torch = _torch()
+		torch = A.torch()
 		if alm is not None: raise ValueError("rng='device' allocates its own (device) alm")
 		g = torch.Generator(device="cuda")
 		if seed is not None: g.manual_seed(int(seed))
@@ -888,10 +881,8 @@ def rand_alm_white(ainfo, pre=None, alm=None, seed=None, dtype=np.complex128, m_
 	if alm is None: alm = np.empty((tuple(pre) if pre is not None else ())+(ainfo.nelem,), dtype)
 	fill_gauss(alm)
 	if not m_major: return alm
-	from . import _lib
 	if not _lib.is_hostsim() and alm.nbytes >= (1 << 24):     # large alm: the reordering as one gather on the GPU (0.6 s of host indexing at lmax 10^4)
-		torch = _torch()
-		alm[...] = ainfo.transpose_alm(torch.from_numpy(alm).cuda()).cpu().numpy()
+		alm[...] = A.host(ainfo.transpose_alm(A.to_gpu(alm)))
 		return alm
 	return ainfo.transpose_alm(alm, alm)
 
@@ -905,7 +896,7 @@ def rand_alm(ps, ainfo=None, lmax=None, seed=None, dtype=np.complex128, m_major=
 	white = rand_alm_white(ainfo, pre=[wps.shape[0]], seed=seed, dtype=dtype, m_major=m_major, rng=rng)
 	colour = (_multi_sqrt(wps)/np.sqrt(2.0)).astype(real_dtype(dtype), copy=False)
 	alm = ainfo.lmul(white, colour)
-	if _is_tensor(alm):
+	if A.is_tensor(alm):
 		alm[:, :ainfo.lmax+1] = (alm[:, :ainfo.lmax+1].real*np.sqrt(2.0)).to(alm.dtype)
 	else:
 		m0 = alm[:, :ainfo.lmax+1]                        # the m = 0 column comes first in the m-major layout
@@ -924,7 +915,7 @@ def rotate_alm(alm, psi, theta, phi, lmax=None, method="auto", nthread=None, inp
 	nthread is accepted and ignored.  inplace: alm is overwritten and returned; otherwise it is left as it is."""
 	if method is None: raise ValueError("No rotate_alm implementations found")
 	if method not in ("auto", "ducc0", "healpy"): raise ValueError("Unrecognized rotate_alm implementation '%s'" % str(method))
-	if not _is_tensor(alm): alm = np.asarray(alm)
+	if not A.is_tensor(alm): alm = np.asarray(alm)
 	nalm = alm.shape[-1] if alm.ndim else 0
 	if lmax is None:
 		lmax = nalm2lmax(nalm)
@@ -935,9 +926,9 @@ def rotate_alm(alm, psi, theta, phi, lmax=None, method="auto", nthread=None, inp
 def transfer_alm(iainfo, ialm, oainfo, oalm=None, op=lambda a, b: b):
 	"""Copy alm between layouts / band limits (curvedsky.py:744-750 -> cmisc.pyx:131-151): for every (l,m) both
 	layouts hold, oalm = op(oalm, ialm).  Works on numpy arrays and on torch CUDA tensors (one gather/scatter)."""
-	tens = _is_tensor(ialm)
+	tens = A.is_tensor(ialm)
 	if oalm is None:
-		oalm = _zeros_like_kind(tuple(ialm.shape[:-1])+(oainfo.nelem,), _np_dtype(ialm), ialm)
+		oalm = A.zeros(tuple(ialm.shape[:-1])+(oainfo.nelem,), A.np_dtype(ialm), ialm)
 	if tuple(ialm.shape[:-1]) != tuple(oalm.shape[:-1]):
 		raise ValueError("ialm and oalm must agree on pre-dimensions")
 	lmax = min(iainfo.lmax, oainfo.lmax); mmax = min(iainfo.mmax, oainfo.mmax)
@@ -947,7 +938,7 @@ def transfer_alm(iainfo, ialm, oainfo, oalm=None, op=lambda a, b: b):
 	src = iainfo.mstart.astype(np.int64)[m]+l*iainfo.stride
 	dst = oainfo.mstart.astype(np.int64)[m]+l*oainfo.stride
 	if tens:
-		torch = _torch()
+		torch = A.torch()
 		src = torch.as_tensor(src, device=ialm.device); dst = torch.as_tensor(dst, device=oalm.device)
 	oalm[..., dst] = op(oalm[..., dst], ialm[..., src])
 	return oalm
@@ -973,5 +964,5 @@ def filter(imap, lfilter, ainfo=None, lmax=None):
 	"""alm2map(almxfl(map2alm(imap), lfilter)): isotropic filtering of a map (curvedsky.filter, curvedsky.py:654-671)"""
 	alm = map2alm(imap, ainfo=ainfo, lmax=lmax, spin=0)
 	alm = almxfl(alm, lfilter=lfilter, ainfo=ainfo)
-	out = enmap.dmap(_torch().empty_like(imap.tensor), imap.wcs) if isinstance(imap, enmap.dmap) else enmap.empty(imap.shape, imap.wcs, dtype=imap.dtype)
+	out = enmap.dmap(A.torch().empty_like(imap.tensor), imap.wcs) if isinstance(imap, enmap.dmap) else enmap.empty(imap.shape, imap.wcs, dtype=imap.dtype)
 	return alm2map(alm, out, spin=0, ainfo=ainfo)

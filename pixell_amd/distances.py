@@ -11,33 +11,29 @@ Where this differs from the reference on purpose: the distanc
 "cellgrid" propagates a front from pixel to pixel and is not), edges come in ascending order and each once, and points may lie anywhere."""
 import ctypes
 import numpy as np
-from . import enmap, sht
-from .sht import _is_tensor, _np_dtype
-from .pointsrcs import _geometry, _device_of, _put, _host, _ptr
+from . import enmap, _lib, _arrays as A, wcs as wcsutils
 
 TILE = 16      # the kernel's tile: return_stats counts visits per TILE x TILE pixels
+_MASK = (np.dtype(np.uint8), np.dtype(bool))
 
-def _new(shape, dtype, device):
-	"""an uninitialised array where the library writes: numpy in the simulator when nothing came as a tensor, a tensor otherwise"""
-	if device is None and sht._lib.is_hostsim(): return np.empty(shape, dtype)
-	torch = sht._torch()
-	if device is None: sht.device_index()
-	return torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=device if device is not None else "cuda")
+def _mask8(x, device):
+	"""a mask of any dtype as the uint8 array the kernels read: non-zero is set"""
+	return A.put(x if A.np_dtype(x) in _MASK else (x != 0), np.uint8, device)
 
 def _edges(arr, labeled, flat):
-	if isinstance(arr, enmap.dmap): arr = arr.tensor
-	if not _is_tensor(arr): arr = np.asarray(arr)
+	arr = A.unwrap(arr)
+	if not A.is_tensor(arr): arr = np.asarray(arr)
 	if arr.ndim != 2: raise ValueError("find_edges needs a 2-D array")
-	device = _device_of(arr)
+	device = A.device_of(arr)
 	ny, nx = int(arr.shape[0]), int(arr.shape[1])
-	if labeled: d = _put(arr, np.int32, device)
-	else: d = _put(arr if enmap._np_any(arr) in (np.dtype(np.uint8), np.dtype(bool)) else (arr != 0), np.uint8, device)
-	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
+	if labeled: d = A.put(arr, np.int32, device)
+	else: d = _mask8(arr, device)
+	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
 	n = ctypes.c_int64(0)
-	sht._lib.check(lib.pxm_find_edges(ny, nx, _ptr(d), int(labeled), None, 0, ctypes.byref(n), dev, st))
-	out = _new((n.value,), np.int64, device)
-	if n.value > 0: sht._lib.check(lib.pxm_find_edges(ny, nx, _ptr(d), int(labeled), _ptr(out), n.value, None, dev, st))
-	if device is None: out = _host(out)
+	_lib.check(lib.pxm_find_edges(ny, nx, A.ptr(d), int(labeled), None, 0, ctypes.byref(n), dev, st))
+	out = A.empty((n.value,), np.int64, device=device)
+	if n.value > 0: _lib.check(lib.pxm_find_edges(ny, nx, A.ptr(d), int(labeled), A.ptr(out), n.value, None, dev, st))
+	if device is None: out = A.host(out)
 	if flat: return out
 	return (out//nx, out % nx)
 
@@ -60,47 +56,37 @@ def distance_from_points(shape, wcs, points=None, pix=None, rmax=None, omap=None
 	lowest among equals).  skip: a [ny, nx] map; pixels where it is 0 get distance 0 and domain -1 without a search.  return_stats: also
 	return int32 [ceil(ny/16), ceil(nx/16)]: the number of points each 16 x 16 pixel tile looked at.
 	Returns omap[, odomains][, stats]."""
-	ny, nx, dec0, ddec, ra0, dra = _geometry(shape, wcs, "auto")
+	ny, nx, dec0, ddec, ra0, dra = wcsutils.separable_geometry(shape, wcs)
 	if (points is None) == (pix is None): raise ValueError("distance_from_points needs either points or pix")
-	if isinstance(points, enmap.dmap): points = points.tensor
-	if isinstance(skip, enmap.dmap): skip = skip.tensor
-	device = _device_of(omap, odomains, points, pix, skip)
+	points, skip = A.unwrap(points), A.unwrap(skip)
+	device = A.device_of(omap, odomains, points, pix, skip)
 	d_dec = d_ra = d_pix = None
 	if pix is not None:
-		if not _is_tensor(pix): pix = np.asarray(pix)
-		d_pix = _put(pix.reshape(-1), np.int64, device); npoint = int(d_pix.shape[0])
+		if not A.is_tensor(pix): pix = np.asarray(pix)
+		d_pix = A.put(pix.reshape(-1), np.int64, device); npoint = int(d_pix.shape[0])
 	else:
-		if not _is_tensor(points): points = np.asarray(points, float)
+		if not A.is_tensor(points): points = np.asarray(points, float)
 		if points.ndim == 1: points = points[:, None]
 		if points.ndim != 2 or points.shape[0] != 2: raise ValueError("points must be [{dec,ra},npoint]")
-		d_dec, d_ra = _put(points[0], np.float64, device), _put(points[1], np.float64, device); npoint = int(points.shape[1])
+		d_dec, d_ra = A.put(points[0], np.float64, device), A.put(points[1], np.float64, device); npoint = int(points.shape[1])
 	d_skip = None
 	if skip is not None:
 		if tuple(skip.shape) != (ny, nx): raise ValueError("skip must be [ny,nx]")
-		d_skip = _put(skip if enmap._np_any(skip) in (np.dtype(np.uint8), np.dtype(bool)) else (skip != 0), np.uint8, device)
-	def out_array(given, dtypes, default, name):
-		"""(the array the kernel writes, the caller's array or None)"""
-		if given is None: return _new((ny, nx), default, device), None
-		data = given.tensor if isinstance(given, enmap.dmap) else given
-		dt = enmap._np_any(data)
-		if dt not in dtypes: raise ValueError("%s must be %s" % (name, " or ".join(np.dtype(t).name for t in dtypes)))
-		if tuple(data.shape) != (ny, nx): raise ValueError("%s must be [ny,nx], as the geometry" % name)
-		if not (data.is_contiguous() if _is_tensor(data) else data.flags["C_CONTIGUOUS"]): raise ValueError("%s must be C-contiguous" % name)
-		return (data if _is_tensor(data) else _put(data, dt, device)), given
-	work, given_map = out_array(omap, (np.dtype(np.float32), np.dtype(np.float64)), np.float64, "omap")
-	want_dom = domains or odomains is not None
-	dom, given_dom = out_array(odomains, (np.dtype(np.int32),), np.int32, "odomains") if want_dom else (None, None)
-	stats = _new(((ny+TILE-1)//TILE, (nx+TILE-1)//TILE), np.int32, device) if return_stats else None
-	sht._lib.check(sht._lib.load().pxm_distance_from(ny, nx, dec0, ddec, ra0, dra, npoint, _ptr(d_dec), _ptr(d_ra), _ptr(d_pix),
-		0.0 if rmax is None else float(rmax), _ptr(d_skip), _ptr(work), sht._DT[_np_dtype(work)], _ptr(dom), _ptr(stats), sht.device_index(), sht.current_stream()))
+		d_skip = _mask8(skip, device)
+	def out_array(given, dtypes, name):
+		"""the array the kernel writes: the caller's (or a staged copy of it), else a new one of the last of dtypes"""
+		if given is None: return A.empty((ny, nx), dtypes[-1], device=device)
+		return A.out_array(given, (ny, nx), dtypes, device, name, "[ny,nx], as the geometry")
+	work = out_array(omap, (np.dtype(np.float32), np.dtype(np.float64)), "omap")
+	dom = out_array(odomains, (np.dtype(np.int32),), "odomains") if domains or odomains is not None else None
+	stats = A.empty(((ny+TILE-1)//TILE, (nx+TILE-1)//TILE), np.int32, device=device) if return_stats else None
+	_lib.check(_lib.load().pxm_distance_from(ny, nx, dec0, ddec, ra0, dra, npoint, A.ptr(d_dec), A.ptr(d_ra), A.ptr(d_pix),
+		0.0 if rmax is None else float(rmax), A.ptr(d_skip), A.ptr(work), A.DT[A.np_dtype(work)], A.ptr(dom), A.ptr(stats), A.device_index(), A.current_stream()))
 	def result(arr, given):
-		if given is not None:
-			gdata = given.tensor if isinstance(given, enmap.dmap) else given
-			if not _is_tensor(gdata) and _ptr(arr) != _ptr(gdata): gdata[...] = _host(arr)
-			return given
-		return enmap.dmap(arr, wcs) if device is not None else enmap.ndmap(_host(arr), wcs)
-	res = (result(work, given_map),)
-	if domains: res += (result(dom, given_dom),)
-	elif given_dom is not None: result(dom, given_dom)
-	if return_stats: res += (stats if device is not None else _host(stats),)
+		if given is not None: return A.result(arr, given)
+		return enmap.dmap(arr, wcs) if device is not None else enmap.ndmap(A.host(arr), wcs)
+	res = (result(work, omap),)
+	if domains: res += (result(dom, odomains),)
+	elif odomains is not None: A.result(dom, odomains)
+	if return_stats: res += (stats if device is not None else A.host(stats),)
 	return res if len(res) > 1 else res[0]

@@ -6,7 +6,7 @@ Mirrors: ndmap (enmap.py:33-163), fullsky_geometry (enmap.py:1713-1740), spin_he
 (enmap.py:1307-1337)."""
 import threading
 import numpy as np
-from . import wcs as wcsutils, fft as enfft
+from . import wcs as wcsutils, fft as enfft, _lib, _arrays as A
 from .wcs import CarWCS
 
 degree = np.pi/180
@@ -53,7 +53,7 @@ def _sliced(parent, res, sel):
 	nd = parent.ndim
 	if isinstance(parent, ndmap) and not isinstance(res, np.ndarray): return res     # every axis indexed: a numpy scalar stays one
 	sel = sel if isinstance(sel, tuple) else (sel,)
-	if any(isinstance(x, (list, np.ndarray)) or hasattr(x, "data_ptr") for x in sel):
+	if any(isinstance(x, (list, np.ndarray)) or A.is_tensor(x) for x in sel):
 		return np.asarray(res) if isinstance(parent, ndmap) else res          # fancy indexing: no geometry
 	nreal = sum(1 for x in sel if x is not None and x is not Ellipsis)
 	full = []
@@ -168,7 +168,7 @@ def ifft_adjoint(emap, omap=None, nthread=0, normalize=True): return fft(emap, o
 def _data(m):
 	if m is None: return None
 	if isinstance(m, dmap): return m.tensor
-	if hasattr(m, "data_ptr"): return m          # a bare torch tensor
+	if A.is_tensor(m): return m          # a bare torch tensor
 	return np.asarray(m)
 def _wrap(res, like):
 	if isinstance(like, dmap): return dmap(res, like.wcs)
@@ -231,22 +231,13 @@ def queb_rotmat(lmap, inverse=False, iau=False, spin=2, wcs=None):
 	c, s_ = np.cos(ang), np.sin(ang)
 	return samewcs(np.array([[c, -s_], [s_, c]]), lmap)
 
-def _torch():
-	import torch
-	return torch
 def _to_device(emap, dtype=None):
 	"""(dmap on the GPU, True if the input was a host array)"""
-	from . import sht
 	if isinstance(emap, dmap): return emap, False
-	if sht._lib.is_hostsim(): return ndmap(np.ascontiguousarray(emap, dtype=dtype), getattr(emap, "wcs", None)), False
-	sht.device_index()
-	t = _torch().from_numpy(np.ascontiguousarray(emap, dtype=dtype)).cuda()
-	return dmap(t, getattr(emap, "wcs", None)), True
+	t = A.put(emap, dtype); staged = A.is_tensor(t)
+	return (dmap if staged else ndmap)(t, getattr(emap, "wcs", None)), staged
 def _to_host(m):
-	return ndmap(m.tensor.cpu().numpy(), m.wcs) if isinstance(m, dmap) else m
-def _ptr(x):
-	x = _data(x)
-	return x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data
+	return ndmap(A.host(m), m.wcs) if isinstance(m, dmap) else m
 def _geo_key(shape, wcs):
 	"""what the l axes of a map depend on: its pixel shape and the WCS numbers (None: no usable key, do not cache)"""
 	try: return (tuple(int(v) for v in shape[-2:]), tuple(np.asarray(wcs.wcs.cdelt, float)), tuple(np.asarray(wcs.wcs.crval, float)), tuple(np.asarray(wcs.wcs.crpix, float)), tuple(wcs.wcs.ctype))
@@ -256,8 +247,7 @@ _cache_lock = threading.Lock()      # (the geometry caches below are shared betw
 def _dev_axes(shape, wcs, like):
 	"""ly, lx as device f64 arrays living next to `like` (kept per geometry and device: a Monte-Carlo loop calls lbin / map2harm on the
 	same geometry every realisation, and the upload from pageable memory is a host synchronisation each time)"""
-	from . import sht
-	if sht._lib.is_hostsim():
+	if _lib.is_hostsim():
 		ly, lx = laxes(shape, wcs)
 		return np.ascontiguousarray(ly), np.ascontiguousarray(lx)
 	key = _geo_key(shape, wcs)
@@ -265,10 +255,8 @@ def _dev_axes(shape, wcs, like):
 	with _cache_lock:      # lookup, fill and eviction as one step; the cached tensors are shared and must not be modified by callers
 		hit = _axes_cache.get(key) if key is not None else None
 		if hit is None:
-			torch = _torch()
-			ly, lx = laxes(shape, wcs)
-			hit = (torch.from_numpy(np.ascontiguousarray(ly)).to(like.device), torch.from_numpy(np.ascontiguousarray(lx)).to(like.device))
-			torch.cuda.current_stream().synchronize()      # (complete before another thread's stream may read them)
+			hit = tuple(A.put(l, None, like.device) for l in laxes(shape, wcs))
+			A.torch().cuda.current_stream().synchronize()      # (complete before another thread's stream may read them)
 			if key is not None:
 				if len(_axes_cache) >= 8: _axes_cache.pop(next(iter(_axes_cache)))
 				_axes_cache[key] = hit
@@ -276,21 +264,20 @@ def _dev_axes(shape, wcs, like):
 
 def _rotate_pairs(hmap, spin, iau, inverse):
 	"""rotate every spin-s pair of a contiguous complex harmonic map [...,ncomp,ny,nx] in place"""
-	from . import sht
 	data = _data(hmap)
 	if data.ndim <= 2: return
 	ny, nx = data.shape[-2:]; nc = data.shape[-3]
-	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
-	dt = sht._DT[sht._np_dtype(data)]; esz = sht._np_dtype(data).itemsize
+	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
+	dt = A.DT[A.np_dtype(data)]; esz = A.np_dtype(data).itemsize
 	ly, lx = _dev_axes(hmap.shape, hmap.wcs, data)
 	npre = int(np.prod(data.shape[:-3], dtype=int))
-	base = _ptr(data)
+	base = A.ptr(data)
 	for s, i1, i2 in spin_helper(spin, nc):
 		if s == 0: continue
 		sign = (-1 if iau else 1)*(-1 if inverse else 1)
 		for p in range(npre):
 			a = int(base+((p*nc+int(i1))*ny*nx)*esz); b = int(a+ny*nx*esz)
-			sht._lib.check(lib.pxm_rotate_queb(ny, nx, _ptr(ly), _ptr(lx), int(s), 1 if sign < 0 else 0, a, b, dt, dev, st))
+			_lib.check(lib.pxm_rotate_queb(ny, nx, A.ptr(ly), A.ptr(lx), int(s), 1 if sign < 0 else 0, a, b, dt, dev, st))
 
 def map2harm(emap, nthread=0, normalize=True, iau=False, spin=[0, 2], adjoint_harm2map=False):
 	"""2-D FFT + Q/U -> E/B rotation (enmap.map2harm, enmap.py:1358-1375); the rotation runs in place on the GPU"""
@@ -319,40 +306,33 @@ def harm2map_adjoint(emap, nthread=0, normalize=True, iau=False, spin=[0, 2]):
 def calc_ps2d(harm, harm2=None):
 	"""2-D (cross) power spectrum Re(harm conj(harm2)) with numpy broadcasting of the leading axes
 	(enmap.calc_ps2d, enmap.py:1959-2011); each distinct pair of 2-D maps is computed once."""
-	from . import sht
 	same = harm2 is None or harm2 is harm
 	h1, host1 = _to_device(harm); h2, host2 = (h1, host1) if same else _to_device(harm2)
 	d1, d2 = _data(h1), _data(h2)
-	ct = np.result_type(sht._np_dtype(d1), sht._np_dtype(d2))
+	ct = np.result_type(A.np_dtype(d1), A.np_dtype(d2))
 	if ct not in (np.dtype(np.complex64), np.dtype(np.complex128)): raise ValueError("calc_ps2d needs complex harmonic maps")
-	def cast(d):
-		if sht._np_dtype(d) == ct: return d if not hasattr(d, "contiguous") else d.contiguous()
-		return d.to(getattr(_torch(), np.dtype(ct).name)) if hasattr(d, "data_ptr") else d.astype(ct)
-	d1 = cast(d1); d2 = d1 if same else cast(d2)
-	if not hasattr(d1, "data_ptr"): d1 = np.ascontiguousarray(d1); d2 = d1 if same else np.ascontiguousarray(d2)
+	d1 = A.put(d1, ct); d2 = d1 if same else A.put(d2, ct)
 	ny, nx = d1.shape[-2:]
 	pshape = np.broadcast_shapes(tuple(d1.shape[:-2]), tuple(d2.shape[:-2]))
 	i1 = np.broadcast_to(np.arange(int(np.prod(d1.shape[:-2], dtype=int))).reshape(d1.shape[:-2]), pshape).reshape(-1)
 	i2 = np.broadcast_to(np.arange(int(np.prod(d2.shape[:-2], dtype=int))).reshape(d2.shape[:-2]), pshape).reshape(-1)
 	rt = np.dtype(np.float32) if ct == np.dtype(np.complex64) else np.dtype(np.float64)
-	if hasattr(d1, "data_ptr"): out = _torch().empty(tuple(pshape)+(ny, nx), dtype=getattr(_torch(), rt.name), device=d1.device)
-	else: out = np.empty(tuple(pshape)+(ny, nx), rt)
-	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
+	out = A.empty(tuple(pshape)+(ny, nx), rt, like=d1)
+	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
 	n = ny*nx; done = {}
 	flat = out.reshape(-1, ny, nx)
 	for i in range(len(i1)):
 		key = tuple(sorted((int(i1[i]), int(i2[i])))) if same else (int(i1[i]), int(i2[i]))
 		if key in done: flat[i] = flat[done[key]]; continue
 		done[key] = i
-		sht._lib.check(lib.pxm_ps2d(n, _ptr(d1)+int(i1[i])*n*ct.itemsize, _ptr(d2)+int(i2[i])*n*ct.itemsize, sht._DT[ct],
-			_ptr(out)+i*n*rt.itemsize, sht._DT[rt], dev, st))
+		_lib.check(lib.pxm_ps2d(n, A.ptr(d1)+int(i1[i])*n*ct.itemsize, A.ptr(d2)+int(i2[i])*n*ct.itemsize, A.DT[ct],
+			A.ptr(out)+i*n*rt.itemsize, A.DT[rt], dev, st))
 	res = _wrap(out, h1)
 	return _to_host(res) if host1 else res
 
 _lbin_cache = {}
 def lbin(map, bsize=None, brel=1.0, return_nhit=False, return_bins=False, lop=None):
 	"""radial binning of a real fourier-space map in |l| (enmap.lbin / _bin_helper, enmap.py:2526-2556): returns b(l), l"""
-	from . import sht
 	if lop is not None:
 		# a transform of |l| (e.g. a logarithm): the bin of a pixel is no longer floor(|l| / bsize) of the kernel above but a table of the geometry,
 		# made here as the reference makes it (the default bin width comes from the TRANSFORMED |l|, enmap.py:2528-2530)
@@ -374,23 +354,20 @@ def lbin(map, bsize=None, brel=1.0, return_nhit=False, return_bins=False, lop=No
 	bsize, n = geo["bsize"], geo["n"]
 	dev_map, was_host = _to_device(map)
 	d = _data(dev_map)
-	if sht._np_dtype(d) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("lbin needs a real map")
+	if A.np_dtype(d) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("lbin needs a real map")
 	if hasattr(d, "contiguous"): d = d.contiguous()
 	ny, nx = d.shape[-2:]; npre = int(np.prod(d.shape[:-2], dtype=int))
 	dly, dlx = _dev_axes(map.shape, map.wcs, d)
-	if hasattr(d, "data_ptr"):
-		torch = _torch()
-		acc = torch.zeros((npre+2, max(n, 1)), dtype=torch.float64, device=d.device)
-	else: acc = np.zeros((npre+2, max(n, 1)))
-	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
-	esz = sht._np_dtype(d).itemsize
+	acc = A.zeros((npre+2, max(n, 1)), np.float64, like=d)
+	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
+	esz = A.np_dtype(d).itemsize
 	# the sums of |l| and the pixel counts per bin depend on the geometry alone: taken with the first map of the first call on a geometry
 	# and kept (two of the kernel's three atomic adds per pixel)
 	for i in range(npre):
 		first = i == 0 and geo["nhit"] is None
-		sht._lib.check(lib.pxm_lbin(ny, nx, _ptr(dly), _ptr(dlx), bsize, n, _ptr(d)+i*ny*nx*esz, sht._DT[sht._np_dtype(d)],
-			_ptr(acc)+i*max(n, 1)*8, (_ptr(acc)+npre*max(n, 1)*8) if first else None, (_ptr(acc)+(npre+1)*max(n, 1)*8) if first else None, dev, st))
-	acc = acc.cpu().numpy() if hasattr(acc, "data_ptr") else acc
+		_lib.check(lib.pxm_lbin(ny, nx, A.ptr(dly), A.ptr(dlx), bsize, n, A.ptr(d)+i*ny*nx*esz, A.DT[A.np_dtype(d)],
+			A.ptr(acc)+i*max(n, 1)*8, (A.ptr(acc)+npre*max(n, 1)*8) if first else None, (A.ptr(acc)+(npre+1)*max(n, 1)*8) if first else None, dev, st))
+	acc = A.host(acc)
 	if geo["nhit"] is None and npre > 0:
 		with _cache_lock: geo["lsum"], geo["nhit"] = acc[npre, :n].copy(), acc[npre+1, :n].copy()      # (the geometry-only sums: set once, under the lock)
 	nhit = geo["nhit"] if geo["nhit"] is not None else acc[npre+1, :n]
@@ -407,7 +384,6 @@ def lbin(map, bsize=None, brel=1.0, return_nhit=False, return_bins=False, lop=No
 def _bin_helper(map, r, bsize, return_nhit=False, return_bins=False):
 	"""means of the map over the bins floor(r / bsize) of a per-pixel coordinate r[ny,nx] (enmap._bin_helper, enmap.py:2533-2556): the bin table,
 	the pixel counts and the mean coordinate of every bin are functions of the geometry (host); the sums over the map run on the GPU (pxm_bin_index)"""
-	from . import sht
 	r = np.asarray(r, float)
 	n = int(np.max(r/bsize))
 	rinds = np.floor(r/bsize).reshape(-1).astype(np.int64)
@@ -415,20 +391,17 @@ def _bin_helper(map, r, bsize, return_nhit=False, return_bins=False):
 	with np.errstate(invalid="ignore", divide="ignore"): orads = np.bincount(rinds, weights=r.reshape(-1), minlength=n)[:n]/nhit
 	dev_map, was_host = _to_device(map)
 	d = _data(dev_map)
-	if sht._np_dtype(d) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("binning needs a real map")
+	if A.np_dtype(d) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("binning needs a real map")
 	if hasattr(d, "contiguous"): d = d.contiguous()
 	ny, nx = d.shape[-2:]; npre = int(np.prod(d.shape[:-2], dtype=int))
 	if rinds.size != ny*nx: raise ValueError("binning: the coordinate map does not have the map's pixel shape")
 	tab = np.where((rinds >= 0) & (rinds < n), rinds, -1).astype(np.int32)
-	if hasattr(d, "data_ptr"):
-		torch = _torch()
-		dtab = torch.as_tensor(tab, device=d.device); acc = torch.zeros((npre, max(n, 1)), dtype=torch.float64, device=d.device)
-	else: dtab = tab; acc = np.zeros((npre, max(n, 1)))
-	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
-	esz = sht._np_dtype(d).itemsize
+	dtab = A.put(tab, None, A.device_of(d)); acc = A.zeros((npre, max(n, 1)), np.float64, like=d)
+	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
+	esz = A.np_dtype(d).itemsize
 	for i in range(npre):
-		sht._lib.check(lib.pxm_bin_index(ny*nx, _ptr(dtab), n, _ptr(d)+i*ny*nx*esz, sht._DT[sht._np_dtype(d)], _ptr(acc)+i*max(n, 1)*8, dev, st))
-	acc = acc.cpu().numpy() if hasattr(acc, "data_ptr") else acc
+		_lib.check(lib.pxm_bin_index(ny*nx, A.ptr(dtab), n, A.ptr(d)+i*ny*nx*esz, A.DT[A.np_dtype(d)], A.ptr(acc)+i*max(n, 1)*8, dev, st))
+	acc = A.host(acc)
 	with np.errstate(invalid="ignore", divide="ignore"): mout = (acc[:, :n]/nhit).reshape(tuple(d.shape[:-2])+(n,))
 	if return_bins:
 		edges = np.arange(len(orads)+1)*bsize
@@ -454,8 +427,8 @@ def posmap(shape, wcs, safe=True, corner=False, separable="auto", dtype=np.float
 		w = wcs.wcs; dec = dec-0.5*w.cdelt[1]*degree; ra = ra-0.5*w.cdelt[0]*degree
 	ny, nx = int(shape[-2]), int(shape[-1])
 	if device is not None:
-		torch = _torch()
-		res = torch.empty((2, ny, nx), dtype=getattr(torch, np.dtype(dtype).name), device=device)
+		torch = A.torch()
+		res = A.empty((2, ny, nx), dtype, device=device)
 		res[0] = torch.as_tensor(dec, device=device)[:, None]; res[1] = torch.as_tensor(ra, device=device)[None, :]
 		return dmap(res, wcs)
 	res = np.empty((2, ny, nx), dtype)
@@ -465,56 +438,50 @@ def posmap(shape, wcs, safe=True, corner=False, separable="auto", dtype=np.float
 def _rotate_pairs_by(data, psi, c0, c1, spin):
 	"""in place: components (c0, c1) of the contiguous real array data [npre, ncomp, npix...] (numpy in the simulator, a tensor next to
 	psi otherwise) rotated by spin*psi, psi f64 [npix...] contiguous -- every pre-dimension entry in one pxm_rotate_pol call"""
-	from . import sht
 	npre, nc = int(data.shape[0]), int(data.shape[1])
 	npix = int(np.prod(data.shape[2:], dtype=np.int64))
-	dt = sht._np_dtype(data)
-	lib = sht._lib.load(); dev = sht.device_index(); st = sht.current_stream()
-	base = _ptr(data)
-	sht._lib.check(lib.pxm_rotate_pol(npix, npre, base+int(c0)*npix*dt.itemsize, base+int(c1)*npix*dt.itemsize, nc*npix, sht._DT[dt], _ptr(psi), int(spin), dev, st))
+	dt = A.np_dtype(data)
+	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
+	base = A.ptr(data)
+	_lib.check(lib.pxm_rotate_pol(npix, npre, base+int(c0)*npix*dt.itemsize, base+int(c1)*npix*dt.itemsize, nc*npix, A.DT[dt], A.ptr(psi), int(spin), dev, st))
 
 def rotate_pol(emap, angle, comps=[-2, -1], spin=2, axis=-3):
 	"""A copy of emap with the components `comps` of `axis` rotated by spin*angle (radians): (a, b) -> (c a - s b, s a + c b),
 	c + i s = exp(i spin angle) (enmap.rotate_pol, enmap.py:1402-1416).  angle: a scalar or an array (host or device) that broadcasts
 	against emap with `axis` removed.  Host arrays, dmaps and CUDA tensors; the rotation runs on the GPU (pxm_rotate_pol), all leading
 	entries in one call when the angle does not depend on them."""
-	from . import sht
 	if spin == 0: return emap
 	data = _data(emap)
-	tens = hasattr(data, "data_ptr")
-	rdt = sht._np_dtype(data)
+	tens = A.is_tensor(data)
+	rdt = A.np_dtype(data)
 	if rdt not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("rotate_pol needs a real float32 or float64 map")
 	axis %= data.ndim
 	nc = int(data.shape[axis]); c0, c1 = int(comps[0]) % nc, int(comps[1]) % nc
 	if c0 == c1: raise ValueError("rotate_pol: the two components must differ")
 	pre, post = tuple(data.shape[:axis]), tuple(data.shape[axis+1:])
-	sim = sht._lib.is_hostsim()
 	if tens:
-		torch = _torch()
-		work = data.clone(memory_format=torch.contiguous_format)
-		if not sim and not work.is_cuda: raise ValueError("torch tensors passed to pixell_amd must live on the GPU")
+		torch = A.torch()
+		work = A.require_gpu(data).clone(memory_format=torch.contiguous_format)
 		ang = _data(angle)
-		ang = ang.to(device=work.device, dtype=torch.float64) if hasattr(ang, "data_ptr") else torch.as_tensor(np.asarray(ang, np.float64), device=work.device)
+		ang = ang.to(device=work.device, dtype=torch.float64) if A.is_tensor(ang) else torch.as_tensor(np.asarray(ang, np.float64), device=work.device)
 		full = torch.broadcast_shapes(tuple(ang.shape), pre+post)
 	else:
-		if sim: work = np.array(data, dtype=rdt, order="C")
-		else:
-			sht.device_index(); torch = _torch()
-			work = torch.from_numpy(np.ascontiguousarray(data)).cuda()
-		ang = np.asarray(_to_host(angle) if isinstance(angle, dmap) else (angle.cpu().numpy() if hasattr(angle, "data_ptr") else angle), np.float64)
+		work = A.put(data)
+		if not A.is_tensor(work): work = np.array(work, order="C")      # (in the simulator what put() returns may be the caller's own array, and the rotation is in place)
+		ang = np.asarray(A.host(angle), np.float64)
 		full = np.broadcast_shapes(ang.shape, pre+post)
-		if not sim: ang = torch.from_numpy(np.ascontiguousarray(ang)).cuda()
+		ang = A.put(ang)
 	if tuple(full) != pre+post: raise ValueError("rotate_pol: angle of shape %s does not broadcast against the map" % (tuple(ang.shape),))
 	lead = tuple(ang.shape)[:max(ang.ndim-len(post), 0)]
 	w3 = work.reshape((int(np.prod(pre, dtype=np.int64)), nc)+post)
-	if hasattr(ang, "data_ptr"): spread = lambda a, sh: a.broadcast_to(sh).contiguous()
+	if A.is_tensor(ang): spread = lambda a, sh: a.broadcast_to(sh).contiguous()
 	else: spread = lambda a, sh: np.ascontiguousarray(np.broadcast_to(a, sh))
 	if all(n == 1 for n in lead):
 		_rotate_pairs_by(w3, spread(ang.reshape(tuple(ang.shape)[len(lead):]), post), c0, c1, spin)
 	else:
 		afull = spread(ang, pre+post).reshape((w3.shape[0],)+post)
 		for p in range(w3.shape[0]): _rotate_pairs_by(w3[p:p+1], afull[p], c0, c1, spin)
-	if not tens and not sim: work = work.cpu().numpy()
+	if not tens: work = A.host(work)
 	if isinstance(emap, dmap): return dmap(work, emap.wcs)
 	if tens: return work
 	return ndmap(work, emap.wcs) if isinstance(emap, ndmap) else work
@@ -543,7 +510,7 @@ def shift(map, off, inplace=False, keepwcs=False):
 	off = np.atleast_1d(off).astype(int)
 	axes = tuple(range(-len(off), 0))
 	if isinstance(map, dmap):
-		t = _torch().roll(map.tensor, tuple(int(o) for o in off), axes)
+		t = A.torch().roll(map.tensor, tuple(int(o) for o in off), axes)
 		if inplace: map.tensor.copy_(t); res = map
 		else: res = dmap(t, map.wcs)
 	else:
@@ -654,14 +621,13 @@ def calc_window(shape, order=0, scale=1):
 def apply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
 	"""A copy of emap with the pixel window to the power pow applied (enmap.apply_window, enmap.py:1485-1496): FFT, one multiplication
 	per axis on the device (pxm_mul_axis), inverse FFT.  nofft: emap is a Fourier-space map already.  Host maps, dmaps and CUDA tensors."""
-	from . import sht
 	wy, wx = calc_window(emap.shape, order=order, scale=scale)
 	like = emap if isinstance(emap, (dmap, ndmap)) else None
-	dev, was_host = _to_device(emap if like is not None else dmap(emap, None) if hasattr(emap, "data_ptr") else ndmap(np.asarray(emap), None))
+	dev, was_host = _to_device(emap if like is not None else dmap(emap, None) if A.is_tensor(emap) else ndmap(np.asarray(emap), None))
 	d = _data(dev)
-	rdt = sht._np_dtype(d)
+	rdt = A.np_dtype(d)
 	ct = np.result_type(rdt, np.complex64)
-	if hasattr(d, "data_ptr"): work = d.to(getattr(_torch(), np.dtype(ct).name), copy=True).contiguous()
+	if A.is_tensor(d): work = d.to(A.tdtype(ct), copy=True).contiguous()
 	else: work = np.array(d, dtype=ct, order="C")
 	wmap = _wrap(work, dev)
 	if not nofft: wmap = fft(wmap, normalize=False)
@@ -672,8 +638,7 @@ def apply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
 		wmap = ifft(wmap, normalize=False)
 		data = _data(wmap)
 		data = data.real*(1.0/(data.shape[-2]*data.shape[-1]))
-		if rdt.kind != "c": data = data.to(getattr(_torch(), rdt.name)) if hasattr(data, "data_ptr") else data.astype(rdt)
-		data = data.contiguous() if hasattr(data, "contiguous") else np.ascontiguousarray(data)
+		data = A.put(data if rdt.kind == "c" else A.astype(data, rdt))
 	elif rdt.kind != "c": raise ValueError("apply_window(nofft=True) needs a complex Fourier-space map")
 	res = _wrap(data, dev)
 	if was_host: res = _to_host(res)
@@ -690,16 +655,6 @@ def unapply_window(emap, pow=1.0, order=0, scale=1, nofft=False):
 _DIST_METHODS = ("cellgrid", "bubble", "simple")
 def _check_method(method):
 	if method not in _DIST_METHODS: raise ValueError("Unknown method '%s'" % str(method))
-def _is_t(x): return hasattr(x, "data_ptr")
-def _np_any(x):
-	"""the numpy dtype of an array or tensor of any kind"""
-	return np.dtype(str(x.dtype).replace("torch.", "")) if _is_t(x) else np.dtype(x.dtype)
-def _astype(x, dtype):
-	"""x (array or tensor) as the numpy dtype `dtype`"""
-	return x.to(getattr(_torch(), np.dtype(dtype).name)) if _is_t(x) else np.asarray(x).astype(dtype, copy=False)
-def _like_zeros(like, shape, dtype):
-	if _is_t(like): return _torch().zeros(tuple(shape), dtype=getattr(_torch(), np.dtype(dtype).name), device=like.device)
-	return np.zeros(shape, dtype)
 
 def distance_from(shape, wcs, points, omap=None, odomains=None, domains=False, method="cellgrid", rmax=None, step=1024):
 	"""The distance of each pixel of the geometry from the nearest of points [{dec,ra}, npoint], [ny, nx]; with domains=True also the index
@@ -723,15 +678,15 @@ def distance_transform(mask, omap=None, rmax=None, method="cellgrid"):
 	from . import distances
 	_check_method(method)
 	md, pre = _planes(mask, "distance_transform")
-	if omap is None: od = _like_zeros(md, md.shape, np.float64)
+	if omap is None: od = A.zeros(md.shape, np.float64, like=md)
 	else:
 		od = _data(omap)
 		if tuple(od.shape) != pre+tuple(md.shape[-2:]): raise ValueError("omap must have the shape of the mask")
 		od = od.reshape(md.shape)
 	for i in range(md.shape[0]):
-		m8 = _astype(md[i] != 0, np.uint8)
+		m8 = A.astype(md[i] != 0, np.uint8)
 		edges = distances.find_edges(m8, flat=True)
-		if _is_t(od) or not _is_t(m8): distances.distance_from_points(mask.shape, mask.wcs, pix=edges, rmax=rmax, omap=od[i], skip=m8)
+		if A.is_tensor(od) or not A.is_tensor(m8): distances.distance_from_points(mask.shape, mask.wcs, pix=edges, rmax=rmax, omap=od[i], skip=m8)
 		else: od[i] = _to_host(distances.distance_from_points(mask.shape, mask.wcs, pix=edges, rmax=rmax, skip=m8))      # (a device mask and a host omap)
 	if omap is not None: return omap
 	return _wrap(od.reshape(pre+tuple(md.shape[-2:])), mask)
@@ -743,20 +698,20 @@ def labeled_distance_transform(labels, omap=None, odomains=None, rmax=None, meth
 	from . import distances
 	_check_method(method)
 	ld, pre = _planes(labels, "labeled_distance_transform")
-	ld = _astype(ld, np.int32)
+	ld = A.astype(ld, np.int32)
 	full = pre+tuple(ld.shape[-2:])
-	od = _like_zeros(ld, ld.shape, np.float64) if omap is None else _data(omap).reshape(ld.shape)
-	dd = _like_zeros(ld, ld.shape, np.int32) if odomains is None else _data(odomains).reshape(ld.shape)
-	if _is_t(ld) != _is_t(od) or _is_t(ld) != _is_t(dd): raise ValueError("labels, omap and odomains must all live on the host or all on the device")
+	od = A.zeros(ld.shape, np.float64, like=ld) if omap is None else _data(omap).reshape(ld.shape)
+	dd = A.zeros(ld.shape, np.int32, like=ld) if odomains is None else _data(odomains).reshape(ld.shape)
+	if A.is_tensor(ld) != A.is_tensor(od) or A.is_tensor(ld) != A.is_tensor(dd): raise ValueError("labels, omap and odomains must all live on the host or all on the device")
 	for i in range(ld.shape[0]):
-		lab = ld[i].contiguous() if _is_t(ld) else np.ascontiguousarray(ld[i])
+		lab = ld[i].contiguous() if A.is_tensor(ld) else np.ascontiguousarray(ld[i])
 		edges = distances.find_edges_labeled(lab, flat=True)
 		_, dom = distances.distance_from_points(labels.shape, labels.wcs, pix=edges, rmax=rmax, omap=od[i], domains=True)
 		dom = _data(dom)
 		good = dom >= 0
 		if int(edges.shape[0]) > 0:
 			mapping = lab.reshape(-1)[edges]
-			dd[i][good] = _astype(mapping[_astype(dom[good], np.int64)], _np_any(dd))
+			dd[i][good] = A.astype(mapping[A.astype(dom[good], np.int64)], A.np_dtype(dd))
 		od[i][lab != 0] = 0
 	oo = omap if omap is not None else _wrap(od.reshape(full), labels)
 	do = odomains if odomains is not None else _wrap(dd.reshape(full), labels)
@@ -778,7 +733,7 @@ def apod_profile_lin(x): return x
 def apod_profile_cos(x):
 	"""0.5 (1 - cos(pi x)), of a numpy array or a torch tensor"""
 	if isinstance(x, dmap): return dmap(apod_profile_cos(x.tensor), x.wcs)
-	return 0.5*(1-(_torch().cos(np.pi*x) if _is_t(x) else np.cos(np.pi*x)))
+	return 0.5*(1-(A.torch().cos(np.pi*x) if A.is_tensor(x) else np.cos(np.pi*x)))
 
 def apod_mask(mask, width=1*degree, edge=True, profile=apod_profile_cos):
 	"""Given a mask that is 0 in bad regions and 1 in good regions, an apodisation map that is still 0 in the bad regions and goes to 1 over
@@ -786,7 +741,7 @@ def apod_mask(mask, width=1*degree, edge=True, profile=apod_profile_cos):
 	image counts as bad."""
 	if edge:
 		md = _data(mask)
-		md = md.clone() if _is_t(md) else np.array(md)
+		md = md.clone() if A.is_tensor(md) else np.array(md)
 		md[..., 0, :] = 0; md[..., :, 0] = 0
 		md[..., -1, :] = 0; md[..., :, -1] = 0
 		mask = _wrap(md, mask)
@@ -795,7 +750,7 @@ def apod_mask(mask, width=1*degree, edge=True, profile=apod_profile_cos):
 
 def _median2(d):
 	"""the median over the last two axes, as numpy.median takes it (the mean of the two middle values of an even count)"""
-	if not _is_t(d): return np.median(d, (-2, -1))
+	if not A.is_tensor(d): return np.median(d, (-2, -1))
 	s = d.reshape(tuple(d.shape[:-2])+(-1,)).sort(-1).values
 	n = s.shape[-1]
 	return 0.5*(s[..., (n-1)//2]+s[..., n//2])
@@ -808,7 +763,7 @@ def apod(map, width, profile="cos", fill="zero", inplace=False):
 	if profile not in ("lin", "cos"): raise ValueError("Unknown apodization profile '%s'" % str(profile))
 	width = (np.zeros(2, int)+width).astype(int)
 	d = _data(map)
-	if not inplace: d = d.clone() if _is_t(d) else np.array(d)
+	if not inplace: d = d.clone() if A.is_tensor(d) else np.array(d)
 	if fill == "mean": offset = d.mean((-2, -1))[..., None, None]
 	elif fill == "median": offset = _median2(d)[..., None, None]
 	if fill in ("mean", "median"): d -= offset
@@ -817,16 +772,16 @@ def apod(map, width, profile="cos", fill="zero", inplace=False):
 		if w <= 0: continue
 		x = np.arange(1, w+1, dtype=float)/((2*w+1) if fill == "crossfade" else (w+1))
 		prof = apod_profile_lin(x) if profile == "lin" else apod_profile_cos(x)
-		if _is_t(d): prof = _torch().as_tensor(prof, dtype=d.dtype, device=d.device)
+		if A.is_tensor(d): prof = A.torch().as_tensor(prof, dtype=d.dtype, device=d.device)
 		else: prof = prof.astype(d.dtype, copy=False)
-		rev = prof.flip(0) if _is_t(d) else prof[::-1]
+		rev = prof.flip(0) if A.is_tensor(d) else prof[::-1]
 		slice1 = (Ellipsis,)+(slice(None),)*i+(slice(0, w),)+(slice(None),)*(1-i)
 		slice2 = (Ellipsis,)+(slice(None),)*i+(slice(-w, None),)+(slice(None),)*(1-i)
 		broad = (None,)*i+(slice(None),)+(None,)*(1-i)
 		if fill == "crossfade":
-			m1 = d[slice1].clone() if _is_t(d) else d[slice1].copy()
-			m2 = d[slice2].clone() if _is_t(d) else d[slice2].copy()
-			d[slice1] = m1*(1-prof).flip(0)[broad]+m2*rev[broad] if _is_t(d) else m1*(1-prof)[::-1][broad]+m2*rev[broad]
+			m1 = d[slice1].clone() if A.is_tensor(d) else d[slice1].copy()
+			m2 = d[slice2].clone() if A.is_tensor(d) else d[slice2].copy()
+			d[slice1] = m1*(1-prof).flip(0)[broad]+m2*rev[broad] if A.is_tensor(d) else m1*(1-prof)[::-1][broad]+m2*rev[broad]
 			d[slice2] = m2*(1-prof)[broad]+m1*prof[broad]
 		else:
 			d[slice1] *= prof[broad]

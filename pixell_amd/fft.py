@@ -8,26 +8,21 @@ dtypes of input and output exactly as the reference's numpy engine does.  Arrays
 `register()` installs the engine into an imported `pixell.fft` as engines["hip"]."""
 import ctypes
 import numpy as np
-from . import _lib
-from .sht import _Buf, _np_dtype, _is_tensor, _torch, _DT, current_stream, device_index
+from . import _lib, _arrays as A
+from ._arrays import current_stream, device_index
+from .sht import _Buf
 
 def astuple(x):
 	try: return tuple(x)
 	except TypeError: return (x,)
 
-def _empty_like(shape, dtype, like):
-	if _is_tensor(like):
-		torch = _torch()
-		return torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
-	return np.empty(shape, dtype)
-
 def _strides(x):
-	if _is_tensor(x): return list(x.stride())
+	if A.is_tensor(x): return list(x.stride())
 	return [s//x.itemsize for s in x.strides]
 
 def _exec(a, b, axes, forward, scale, r2r=0):
 	"""a -> b along axes; kind from shapes/dtypes (fft.py:14-31)"""
-	ad, bd = _np_dtype(a), _np_dtype(b)
+	ad, bd = A.np_dtype(a), A.np_dtype(b)
 	nd = a.ndim
 	axes = [ax % nd for ax in astuple(axes)]
 	ashape, bshape = tuple(a.shape), tuple(b.shape)
@@ -44,8 +39,8 @@ def _exec(a, b, axes, forward, scale, r2r=0):
 		if ad.kind != "c" or ashape != half(bshape): raise ValueError("c2r: input shape %s does not match output %s" % (str(ashape), str(bshape)))
 		kind, shape = 2, bshape
 	# numpy inputs are staged contiguously; tensors are used with their own strides
-	ab = _Buf(a) if not _is_tensor(a) else None
-	bb = _Buf(b, writeback=True) if not _is_tensor(b) else None
+	ab = _Buf(a) if not A.is_tensor(a) else None
+	bb = _Buf(b, writeback=True) if not A.is_tensor(b) else None
 	def cstr(shp):
 		st = [1]*len(shp)
 		for i in range(len(shp)-2, -1, -1): st[i] = st[i+1]*shp[i+1]
@@ -57,7 +52,7 @@ def _exec(a, b, axes, forward, scale, r2r=0):
 	I64 = ctypes.c_int64
 	sh = (I64*nd)(*shape); isa = (I64*nd)(*ist); osa = (I64*nd)(*ost); ax = (ctypes.c_int*len(axes))(*axes)
 	_lib.check(_lib.load().pxf_fft_nd(nd, sh, isa, osa, len(axes), ax, kind, int(bool(forward)), float(scale),
-		_DT[ad], _DT[bd], aptr, bptr, device_index(), current_stream()))
+		A.DT[ad], A.DT[bd], aptr, bptr, device_index(), current_stream()))
 	if bb is not None: bb.finish()
 	return b
 
@@ -66,14 +61,14 @@ def fft(tod, ft=None, nthread=0, axes=[-1], flags=None, _direction="FFTW_FORWARD
 	axes = astuple(-1 if axes is None else axes)
 	if int(np.prod(tod.shape)) == 0: return
 	if ft is None:
-		ft = _empty_like(tod.shape, np.result_type(_np_dtype(tod), 0j), tod)
+		ft = A.empty(tod.shape, np.result_type(A.np_dtype(tod), 0j), like=tod)
 	return _exec(tod, ft, axes, _direction == "FFTW_FORWARD", _scale)
 
 def ifft(ft, tod=None, nthread=0, normalize=False, axes=[-1], flags=None, engine="auto", _scale=1.0):
 	"""pixell.fft.ifft: unnormalised backward transform unless normalize=True"""
 	axes = astuple(-1 if axes is None else axes)
 	if int(np.prod(ft.shape)) == 0: return
-	if tod is None: tod = _empty_like(ft.shape, _np_dtype(ft), ft)
+	if tod is None: tod = A.empty(ft.shape, A.np_dtype(ft), like=ft)
 	scale = _scale
 	if normalize: scale = scale/np.prod([tod.shape[i] for i in axes])
 	return _exec(ft, tod, axes, False, scale)
@@ -88,12 +83,12 @@ def irfft_shape(shape, axes=[-1], n=None):
 
 def rfft(tod, ft=None, nthread=0, axes=[-1], flags=None, engine="auto"):
 	axes = astuple(-1 if axes is None else axes)
-	if ft is None: ft = _empty_like(rfft_shape(tod.shape, axes), np.result_type(_np_dtype(tod), 0j), tod)
+	if ft is None: ft = A.empty(rfft_shape(tod.shape, axes), np.result_type(A.np_dtype(tod), 0j), like=tod)
 	return fft(tod, ft, nthread, axes, flags=flags)
 
 def irfft(ft, tod=None, n=None, nthread=0, normalize=False, axes=[-1], flags=None, engine="auto"):
 	axes = astuple(-1 if axes is None else axes)
-	if tod is None: tod = _empty_like(irfft_shape(ft.shape, axes, n), np.zeros([], _np_dtype(ft)).real.dtype, ft)
+	if tod is None: tod = A.empty(irfft_shape(ft.shape, axes, n), np.zeros([], A.np_dtype(ft)).real.dtype, like=ft)
 	return ifft(ft, tod, nthread, normalize, axes, flags=flags)
 
 # names, inverses and normalisation offsets as in pixell/fft.py:269-290
@@ -109,7 +104,7 @@ def _dct_type(type):
 	if type not in _dct_names: raise ValueError("unknown DCT/DST type %s" % str(type))
 	return _dct_names[type]
 def _asreal(a):
-	if _is_tensor(a): return a
+	if A.is_tensor(a): return a
 	a = np.asarray(a)
 	return a if a.dtype.kind == "f" else a.astype(np.result_type(a.dtype, 0.0))
 
@@ -118,7 +113,7 @@ def dct(tod, dt=None, nthread=0, normalize=False, axes=[-1], flags=None, type="D
 	t = _dct_type(type)
 	axes = astuple(-1 if axes is None else axes)
 	tod = _asreal(tod)
-	if dt is None: dt = _empty_like(tod.shape, _np_dtype(tod), tod)
+	if dt is None: dt = A.empty(tod.shape, A.np_dtype(tod), like=tod)
 	return _exec(tod, dt, axes, True, _scale, r2r=_r2r_kind[t])
 
 def idct(dt, tod=None, nthread=0, normalize=False, axes=[-1], flags=None, type="DCT-I", engine="auto", _scale=1.0):
@@ -128,7 +123,7 @@ def idct(dt, tod=None, nthread=0, normalize=False, axes=[-1], flags=None, type="
 	off = _dct_sizes[t]
 	axes = astuple(-1 if axes is None else axes)
 	dt = _asreal(dt)
-	if tod is None: tod = _empty_like(dt.shape, _np_dtype(dt), dt)
+	if tod is None: tod = A.empty(dt.shape, A.np_dtype(dt), like=dt)
 	scale = _scale
 	if normalize: scale = scale/float(np.prod([2*(dt.shape[i]+off) for i in axes]))
 	return _exec(dt, tod, axes, True, scale, r2r=_r2r_kind[t])
@@ -170,7 +165,7 @@ class HipFFTW:
 		fwd = self.direction == "FFTW_FORWARD"
 		scale = 1.0
 		if not fwd and normalise_idft:
-			shp = self.a.shape if tuple(self.a.shape) == tuple(self.b.shape) or _np_dtype(self.b).kind == "c" else self.b.shape
+			shp = self.a.shape if tuple(self.a.shape) == tuple(self.b.shape) or A.np_dtype(self.b).kind == "c" else self.b.shape
 			scale = 1.0/np.prod([shp[i] for i in self.axes])
 		_exec(self.a, self.b, self.axes, fwd, scale)
 		return self.b
@@ -195,38 +190,23 @@ def register(pixell_fft_module, make_default=True):
 def fftfreq(n, d=1.0, dtype=np.float64): return np.fft.fftfreq(n, d=d).astype(dtype, copy=False)
 def rfftfreq(n, d=1.0, dtype=np.float64): return np.arange(n//2+1, dtype=dtype)/(n*d)
 
-def _to_dev(a):
-	"""contiguous device copy of a numpy array (tensors pass through); second value: was it a host array"""
-	if _is_tensor(a): return a, False
-	a = np.ascontiguousarray(a)
-	if _lib.is_hostsim(): return a, False
-	device_index()
-	import torch
-	return torch.from_numpy(a).cuda(), True
-def _to_host(a, was_host): return a.cpu().numpy() if was_host else a
-
 def _mul_axis(ca, ax, vec):
 	"""ca *= vec along axis ax (ca: contiguous complex array on the device / in the simulator)"""
 	n = ca.shape[ax]; inner = int(np.prod(ca.shape[ax+1:], dtype=np.int64)); total = int(np.prod(ca.shape, dtype=np.int64))
 	v = _Buf(np.ascontiguousarray(vec, dtype=np.complex128))
-	ptr = ca.data_ptr() if _is_tensor(ca) else ca.ctypes.data
-	_lib.check(_lib.load().pxm_mul_axis(total, n, inner, ptr, _DT[_np_dtype(ca)], v.ptr, device_index(), current_stream()))
+	_lib.check(_lib.load().pxm_mul_axis(total, n, inner, A.ptr(ca), A.DT[A.np_dtype(ca)], v.ptr, device_index(), current_stream()))
 
 def shift(a, shift, axes=None, nofft=False, deriv=None, engine="auto"):
 	"""pixell.fft.shift (fft.py:347-368): shift a by a (fractional) number of samples along the given axes through phase
 	ramps in Fourier space; deriv = i differentiates along the i-th listed axis as well"""
-	host_in = not _is_tensor(a)
+	host_in = not A.is_tensor(a)
 	if host_in: a = np.asanyarray(a)
-	iscomplex = _np_dtype(a).kind == "c"
-	ctype = np.result_type(_np_dtype(a), np.complex64)
+	iscomplex = A.np_dtype(a).kind == "c"
+	ctype = np.result_type(A.np_dtype(a), np.complex64)
 	shift_ = np.atleast_1d(shift)
 	if axes is None: axes = range(-len(shift_), 0)
 	axes = astuple(axes)
-	if host_in: ca = np.ascontiguousarray(a, dtype=ctype)+0
-	else:
-		import torch
-		ca = a.to(getattr(torch, np.dtype(ctype).name)).contiguous().clone()
-	ca, was_host = _to_dev(ca)
+	ca = A.put(np.ascontiguousarray(a, dtype=ctype)+0) if host_in else a.to(A.tdtype(ctype)).contiguous().clone()
 	fa = fft(ca, axes=axes) if not nofft else ca
 	for i, ax in enumerate(axes):
 		ax %= fa.ndim
@@ -235,7 +215,7 @@ def shift(a, shift, axes=None, nofft=False, deriv=None, engine="auto"):
 		if deriv == i: phase = phase*(-2j*np.pi*freqs)
 		_mul_axis(fa, ax, phase)
 	res = ifft(fa, axes=axes, normalize=True) if not nofft else fa
-	res = _to_host(res, was_host)
+	if host_in: res = A.host(res)
 	return res if iscomplex else res.real
 
 def resample_fft(fa, n, out=None, axes=-1, norm=1, op=lambda a, b: b):
@@ -246,7 +226,7 @@ def resample_fft(fa, n, out=None, axes=-1, norm=1, op=lambda a, b: b):
 	oshape = list(fa.shape)
 	for i, ax in enumerate(axes): oshape[ax] = int(n[i])
 	oshape = tuple(oshape)
-	if out is None: out = _empty_like(oshape, _np_dtype(fa), fa); out[...] = 0
+	if out is None: out = A.empty(oshape, A.np_dtype(fa), like=fa); out[...] = 0
 	elif tuple(out.shape) != oshape:
 		raise ValueError("out argument has wrong shape in resample. Expected %s but got %s" % (str(oshape), str(tuple(out.shape))))
 	for I in np.ndindex(*([2]*len(axes))):
@@ -261,19 +241,18 @@ def resample_fft(fa, n, out=None, axes=-1, norm=1, op=lambda a, b: b):
 
 def resample(a, n, axes=None, nthread=0, engine="auto"):
 	"""pixell.fft.resample (fft.py:370-387): Fourier-resize the given axes of a to length n"""
-	host_in = not _is_tensor(a)
+	host_in = not A.is_tensor(a)
 	if host_in: a = np.asarray(a)
 	n = astuple(n)
 	if axes is None: axes = [-len(n)+i for i in range(len(n))]
 	axes = astuple(axes)
 	if len(n) != len(axes): raise ValueError("Resize size n = %s does not match axes = %s" % (str(n), str(axes)))
-	iscomplex = _np_dtype(a).kind == "c"
-	da, was_host = _to_dev(a)
-	fa = fft(da, axes=axes)
+	iscomplex = A.np_dtype(a).kind == "c"
+	fa = fft(A.put(a) if host_in else a, axes=axes)
 	norm = 1/np.prod([a.shape[ax] for ax in axes])
 	fa = resample_fft(fa, n, axes=axes, norm=norm)
 	out = ifft(fa, axes=axes, normalize=False)
-	out = _to_host(out, was_host)
+	if host_in: out = A.host(out)
 	return out if iscomplex else out.real
 
 # ---- the registry face of pixell.fft (fft.py:78-131, 313-338): on this backend there is one engine ---------------------------

@@ -9,8 +9,7 @@ one in-place rotation (pxm_rotate_pol).  No position map is made and nothing lea
 Not here: the flat-sky lens_map, lens_map_flat, displace_map, delens_map and delens_grad interpolate maps with splines, which this
 package does not have; method="lenspyx" needs the lenspyx package."""
 import numpy as np
-from . import enmap, curvedsky, sht, wcs as wcsutils
-from .sht import _is_tensor, _np_dtype
+from . import enmap, curvedsky, _lib, _arrays as A, wcs as wcsutils
 
 degree = np.pi/180
 
@@ -28,8 +27,8 @@ def kappa_to_phi(kappa_alm, kappa_ainfo=None):
 
 def pole_wrap(pos):
 	"""pos [{dec,ra},...] with points that went over a pole reflected back: dec -> +-pi - dec, ra -> ra + pi"""
-	if _is_tensor(pos):
-		torch = sht._torch()
+	if A.is_tensor(pos):
+		torch = A.torch()
 		a = pos.clone()
 		north, south = a[0] > np.pi/2, a[0] < -np.pi/2
 		a[0] = torch.where(north, np.pi-a[0], torch.where(south, -np.pi-a[0], a[0]))
@@ -42,48 +41,35 @@ def pole_wrap(pos):
 	return a
 
 # ---- deflection ------------------------------------------------------------------------------------------------------------
-def _ptr(x): return x.data_ptr() if _is_tensor(x) else x.ctypes.data
-
 def _device_array(x, dtype=None):
-	"""x where the library reads it: numpy arrays go to the GPU (they stay numpy in the simulator), tensors must be there already"""
-	if _is_tensor(x):
-		if not x.is_cuda and not sht._lib.is_hostsim(): raise ValueError("torch tensors passed to pixell_amd must live on the GPU")
-		return x if dtype is None else x.to(getattr(sht._torch(), np.dtype(dtype).name))
-	x = np.asarray(x) if dtype is None else np.asarray(x, dtype)
-	if sht._lib.is_hostsim(): return x
-	sht.device_index()
-	return sht._torch().from_numpy(np.ascontiguousarray(x)).cuda()
-
-def _empty_like_kind(shape, like):
-	if _is_tensor(like): return sht._torch().empty(tuple(shape), dtype=sht._torch().float64, device=like.device)
-	return np.empty(tuple(shape), np.float64)
+	"""x where the library reads it: numpy arrays go to the GPU (they stay numpy in the simulator), tensors must be there already and
+	keep their strides"""
+	if A.is_tensor(x): return A.require_gpu(x) if dtype is None else A.require_gpu(x).to(A.tdtype(dtype))
+	return A.put(x, dtype)
 
 def _deflect(grad, geodesic, want_psi, pos=None, geometry=None):
 	"""pxm_deflect: grad [2, ...] (device array, f32 | f64, pixels contiguous) at the positions pos [{dec,ra}(,psi0), ...] (device array, f64,
 	contiguous) or at the pixel centres of geometry = (shape, wcs) -> loc [npts, 2] = (colatitude, ra in [0, 2 pi)), psi [npts] | None"""
 	npts = int(np.prod(grad.shape[1:], dtype=np.int64))
-	if _np_dtype(grad) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("the gradient must be float32 or float64")
-	if _is_tensor(grad):
+	if A.np_dtype(grad) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("the gradient must be float32 or float64")
+	if A.is_tensor(grad):
 		inner = grad[0]
 		if not inner.is_contiguous(): grad = grad.contiguous()
 		gstride = grad.stride(0) if grad.shape[0] > 1 else npts
 	else:
 		grad = np.ascontiguousarray(grad); gstride = npts
 	if grad.shape[0] != 2: raise ValueError("the gradient must have shape [2, ...]")
-	loc = _empty_like_kind((npts, 2), grad)
-	psi = _empty_like_kind((npts,), grad) if want_psi else None
+	loc = A.empty((npts, 2), np.float64, like=grad)
+	psi = A.empty((npts,), np.float64, like=grad) if want_psi else None
 	if pos is not None:
 		if tuple(pos.shape[1:]) != tuple(grad.shape[1:]) or pos.shape[0] not in (2, 3): raise ValueError("positions [{dec,ra}(,psi0), ...] and gradient [2, ...] disagree on their shapes")
-		geo = (0, 0, 0.0, 0.0, 0.0, 0.0, _ptr(pos), int(pos.shape[0]))
+		geo = (0, 0, 0.0, 0.0, 0.0, 0.0, A.ptr(pos), int(pos.shape[0]))
 	else:
 		shape, wcs = geometry
-		if not wcsutils.is_separable(wcs): raise NotImplementedError("only separable cylindrical geometries")
+		geo = wcsutils.separable_geometry(shape, wcs)+(None, 0)
 		if tuple(shape[-2:]) != tuple(grad.shape[1:]): raise ValueError("geometry and gradient disagree on the pixel shape")
-		w = wcs.wcs
-		geo = (int(shape[-2]), int(shape[-1]), float(w.crval[1]+(1-w.crpix[1])*w.cdelt[1])*degree, float(w.cdelt[1])*degree,
-			float(w.crval[0]+(1-w.crpix[0])*w.cdelt[0])*degree, float(w.cdelt[0])*degree, None, 0)
-	sht._lib.check(sht._lib.load().pxm_deflect(npts, *geo, _ptr(grad), sht._DT[_np_dtype(grad)], int(gstride), int(bool(geodesic)),
-		_ptr(loc), _ptr(psi) if psi is not None else None, sht.device_index(), sht.current_stream()))
+	_lib.check(_lib.load().pxm_deflect(npts, *geo, A.ptr(grad), A.DT[A.np_dtype(grad)], int(gstride), int(bool(geodesic)),
+		A.ptr(loc), A.ptr(psi), A.device_index(), A.current_stream()))
 	return loc, psi
 
 def offset_by_grad(ipos, grad, geodesic=True, pol=None, _loc=False, _geometry=None):
@@ -95,34 +81,25 @@ def offset_by_grad(ipos, grad, geodesic=True, pol=None, _loc=False, _geometry=No
 	Device arrays in, device arrays out; numpy in, numpy out.
 	Internal: _loc=True returns (loc [npts, 2] = (colatitude, ra), psi [npts] | None) as the kernel wrote them, on the device;
 	_geometry=(shape, wcs) takes the pixel centres of that geometry as ipos (ipos=None) without making them."""
-	if isinstance(grad, enmap.dmap): grad = grad.tensor
-	if isinstance(ipos, enmap.dmap): ipos = ipos.tensor
-	on_host = not _is_tensor(grad) and not (ipos is not None and _is_tensor(ipos))
+	grad, ipos = A.unwrap(grad), A.unwrap(ipos)
+	like = getattr(ipos, "wcs", None)
+	on_host = not A.is_tensor(grad) and not (ipos is not None and A.is_tensor(ipos))
 	nin = 2 if ipos is None else int(ipos.shape[0])
 	ncomp = 2 if pol is False or (pol is None and nin <= 2) else 3
-	like = getattr(ipos, "wcs", None)
 	dgrad = _device_array(grad)
 	dpos = None
 	if ipos is not None:
-		dpos = _device_array(ipos, np.float64)
-		dpos = dpos.contiguous() if _is_tensor(dpos) else np.ascontiguousarray(dpos)
-		if _is_tensor(dpos) and _is_tensor(dgrad) and dpos.device != dgrad.device: dgrad = dgrad.to(dpos.device)
+		dpos = A.put(ipos, np.float64)
+		if A.is_tensor(dpos) and A.is_tensor(dgrad) and dpos.device != dgrad.device: dgrad = dgrad.to(dpos.device)
 	loc, psi = _deflect(dgrad, geodesic, ncomp > 2, pos=dpos, geometry=_geometry)
 	if _loc: return loc, psi
 	pixshape = tuple(grad.shape[1:])
-	if _is_tensor(loc):
-		torch = sht._torch()
-		out = torch.empty((ncomp,)+pixshape, dtype=torch.float64, device=loc.device)
-		o2 = out.reshape(ncomp, -1)
-		o2[0] = np.pi/2-loc[:, 0]; o2[1] = loc[:, 1]
-		if ncomp > 2: o2[2] = psi
-		if on_host: out = out.cpu().numpy()
-	else:
-		out = np.empty((ncomp,)+pixshape)
-		o2 = out.reshape(ncomp, -1)
-		o2[0] = np.pi/2-loc[:, 0]; o2[1] = loc[:, 1]
-		if ncomp > 2: o2[2] = psi
-	if not _is_tensor(out) and like is not None: out = enmap.ndmap(out, like)
+	out = A.empty((ncomp,)+pixshape, np.float64, like=loc)
+	o2 = out.reshape(ncomp, -1)
+	o2[0] = np.pi/2-loc[:, 0]; o2[1] = loc[:, 1]
+	if ncomp > 2: o2[2] = psi
+	if on_host: out = A.host(out)
+	if not A.is_tensor(out) and like is not None: out = enmap.ndmap(out, like)
 	return out
 
 # ---- simulation ------------------------------------------------------------------------------------------------------------
@@ -168,10 +145,10 @@ def _rotate_band(obs, psi):
 	"""in place: the last two components of the band obs [ncomp, rows, nx] rotated by 2 psi.  The band may be rows of a larger device map:
 	its components are then a whole map apart, each one's rows still contiguous"""
 	npix = int(obs.shape[-2])*int(obs.shape[-1]); ncomp = int(obs.shape[0])
-	cstride = obs.stride(0) if _is_tensor(obs) else npix
-	esz = _np_dtype(obs).itemsize
-	sht._lib.check(sht._lib.load().pxm_rotate_pol(npix, 1, _ptr(obs)+(ncomp-2)*cstride*esz, _ptr(obs)+(ncomp-1)*cstride*esz, 0,
-		sht._DT[_np_dtype(obs)], _ptr(psi), 2, sht.device_index(), sht.current_stream()))
+	cstride = obs.stride(0) if A.is_tensor(obs) else npix
+	esz = A.np_dtype(obs).itemsize
+	_lib.check(_lib.load().pxm_rotate_pol(npix, 1, A.ptr(obs)+(ncomp-2)*cstride*esz, A.ptr(obs)+(ncomp-1)*cstride*esz, 0,
+		A.DT[A.np_dtype(obs)], A.ptr(psi), 2, A.device_index(), A.current_stream()))
 
 def lens_map_curved(shape, wcs, phi_alm, cmb_alm, phi_ainfo=None, dtype=np.float64, spin=[0, 2], output="l", method="pixell",
 		geodesic=True, delta_theta=None, epsilon=None, nthreads=0, verbose=False):
@@ -191,24 +168,23 @@ def lens_map_curved(shape, wcs, phi_alm, cmb_alm, phi_ainfo=None, dtype=np.float
 	oshape = tuple(shape[-3:])
 	shape = ((1,)+oshape) if len(oshape) == 2 else oshape
 	ncomp, ny, nx = shape
-	on_device = _is_tensor(phi_alm) or _is_tensor(cmb_alm)
+	on_device = A.is_tensor(phi_alm) or A.is_tensor(cmb_alm)
 	ctype = np.result_type(dtype, 0j)
 	def prep(alm):
 		alm = _device_array(alm)
-		return alm if _np_dtype(alm) == ctype else _device_array(alm, ctype)
+		return alm if A.np_dtype(alm) == ctype else _device_array(alm, ctype)
 	phi_d, cmb_d = prep(phi_alm), prep(cmb_alm)
 	if cmb_d.ndim == 1: cmb_d = cmb_d[None]
 	if cmb_d.shape[0] != ncomp: raise ValueError("cmb_alm has %d components, the map %d" % (cmb_d.shape[0], ncomp))
-	tens = _is_tensor(phi_d)
+	tens = A.is_tensor(phi_d)
 	def new_map(pre, band=None):
 		"""an output map (on the device when the alm came from there), or, with band = (lshape, lwcs), a work map of one band on the device"""
 		shp, w = (tuple(pre)+(ny, nx), wcs) if band is None else (tuple(pre)+tuple(band[0][-2:]), band[1])
 		if tens and (on_device or band is not None):
-			torch = sht._torch()
-			return enmap.dmap(torch.empty(shp, dtype=getattr(torch, np.dtype(dtype).name), device=phi_d.device), w)
+			return enmap.dmap(A.empty(shp, dtype, like=phi_d), w)
 		return enmap.empty(shp, w, dtype=dtype)
 	def rows(m, i1, i2): return m[..., i1:i2, :]
-	host_alm = lambda a: a if on_device or not tens else a.cpu().numpy()       # (maps on the host take host alm through the package's own staging)
+	host_alm = lambda a: a if on_device or not tens else A.host(a)       # (maps on the host take host alm through the package's own staging)
 	bsize = _band_size(ny, wcs, delta_theta)
 	maps = {}
 	if "p" in output: maps["p"] = new_map(())
@@ -230,7 +206,7 @@ def lens_map_curved(shape, wcs, phi_alm, cmb_alm, phi_ainfo=None, dtype=np.float
 		elif "a" in output or "l" in output:
 			grad = new_map((2,), band)
 			curvedsky.alm2map(phi_d, grad, deriv=True, ainfo=phi_ainfo)
-			if "a" in output: rows(maps["a"], i1, i2)[...] = grad.tensor.cpu().numpy()
+			if "a" in output: rows(maps["a"], i1, i2)[...] = A.host(grad)
 		if "u" in output: curvedsky.alm2map(host_alm(cmb_d), rows(maps["u"], i1, i2), spin=spin)
 		if "l" not in output: continue
 		rotate = geodesic and ncomp > 1
@@ -240,11 +216,11 @@ def lens_map_curved(shape, wcs, phi_alm, cmb_alm, phi_ainfo=None, dtype=np.float
 		in_place = isinstance(dest, enmap.dmap)
 		obs = dest.tensor if in_place else (new_map((ncomp,), band).tensor if tens else np.empty((ncomp, i2-i1, nx), dtype))
 		got = curvedsky.alm2map_pos(cmb_d, loc=loc.reshape(i2-i1, nx, 2), map=obs, spin=spin, epsilon=epsilon)
-		if _ptr(got) != _ptr(obs): obs[...] = got
+		if A.ptr(got) != A.ptr(obs): obs[...] = got
 		del loc, got
 		if rotate: _rotate_band(obs, psi)
 		del psi
-		if not in_place: dest[...] = obs.cpu().numpy() if tens else obs
+		if not in_place: dest[...] = A.host(obs)
 	res = []
 	for c in output:
 		m = maps[c]

@@ -6,8 +6,7 @@ ndmaps is the numpy container; dmaps is its device counterpart around a torch CU
 leaves HBM until `.to_host()`.  The per-map reductions (mean, var, std, min, max) return host arrays [nmap, pre...] for both.
 I/O, the position / l tables and the FFT wrappers of the reference's module are not here."""
 import numpy as np
-from . import enmap
-from .sht import _is_tensor, _np_dtype, _torch
+from . import enmap, _arrays as A
 
 class Geometry:
 	"""(shape, wcs) of one map; unpacks like the pair it stands for"""
@@ -65,7 +64,7 @@ class dmaps(_Common):
 	@property
 	def ndim(self): return self.tensor.ndim
 	@property
-	def dtype(self): return _np_dtype(self.tensor)
+	def dtype(self): return A.np_dtype(self.tensor)
 	def copy(self): return dmaps(self.tensor.clone(), self.geometries)
 	def contig(self): return dmaps(self.tensor.contiguous(), self.geometries)
 	def to_host(self): return ndmaps(self.tensor.cpu().numpy(), self.geometries)
@@ -92,8 +91,8 @@ class dmaps(_Common):
 def _operand(x, like):
 	"""the other side of an operator as something torch can combine with the tensor `like`"""
 	if isinstance(x, dmaps) or isinstance(x, enmap.dmap): return x.tensor
-	if _is_tensor(x) or isinstance(x, (int, float, complex, bool, np.number)): return x
-	if isinstance(x, (np.ndarray, list, tuple)): return _torch().as_tensor(np.ascontiguousarray(x), device=like.device)
+	if A.is_tensor(x) or isinstance(x, (int, float, complex, bool, np.number)): return x
+	if isinstance(x, (np.ndarray, list, tuple)): return A.torch().as_tensor(np.ascontiguousarray(x), device=like.device)
 	return NotImplemented
 
 import operator as _op
@@ -133,7 +132,7 @@ class _map_view:
 		if isinstance(self.mmap, dmaps):
 			m.tensor[rest if rest else Ellipsis] = _operand(val, m.tensor)
 		else:
-			if _is_tensor(val): val = val.cpu().numpy()
+			if A.is_tensor(val): val = val.cpu().numpy()
 			np.asarray(m)[rest if rest else Ellipsis] = val
 
 def _geo_helper(geometries):
@@ -148,9 +147,8 @@ def _new(geometries, dtype, device, make):
 	geometries, ntot = _geo_helper(geometries)
 	shape = (geometries[0].shape[:-2] if geometries else ())+(ntot,)
 	if device is None or device is False: return ndmaps(getattr(np, make)(shape, dtype), geometries)
-	torch = _torch()
 	dev = "cuda" if device is True else device
-	return dmaps(getattr(torch, make)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev), geometries)
+	return dmaps(getattr(A.torch(), make)(shape, dtype=A.tdtype(dtype), device=dev), geometries)
 
 def zeros(geometries, dtype=np.float64, device=None):
 	"""zero-initialised multimap of the given geometries [(shape, wcs), ...] (the shapes may carry common leading dimensions);
@@ -178,14 +176,14 @@ def multimap(maps):
 			raise ValueError("Map %d in multimaps constructor has pre-shape %s, incompatible with map 0 with %s" % (i, str(m.shape[:-2]), str(maps[0].shape[:-2])))
 	geos = [(m.shape, m.wcs) for m in maps]
 	if isinstance(maps[0], enmap.dmap):
-		return dmaps(_torch().cat([m.tensor.reshape(m.shape[:-2]+(-1,)) for m in maps], -1), geos)
+		return dmaps(A.torch().cat([m.tensor.reshape(m.shape[:-2]+(-1,)) for m in maps], -1), geos)
 	return ndmaps(np.concatenate([np.asarray(m).reshape(m.shape[:-2]+(-1,)) for m in maps], -1), geos)
 
 def samegeos(arr, *args):
 	"""arr with the geometries of the first multimap among args (sharing arr's memory where possible); arr itself if there is none"""
 	for m in args:
 		geos = getattr(m, "geometries", None)
-		if geos is not None: return dmaps(arr, geos) if _is_tensor(arr) else ndmaps(arr, geos)
+		if geos is not None: return dmaps(arr, geos) if A.is_tensor(arr) else ndmaps(arr, geos)
 	return arr
 
 def _reduce(mmap, host_fn, dev_fn):

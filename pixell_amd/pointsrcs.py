@@ -12,49 +12,15 @@ bin is complete, the last one included; `op` is honoured; maps may be float64.
 Not here: sim_srcs(method="python"), sim_srcs_dist_transform, the catalogue readers and crossmatch."""
 import time
 import numpy as np
-from . import enmap, sht, wcs as wcsutils
-from .sht import _is_tensor, _np_dtype
+from . import enmap, _lib, _arrays as A, wcs as wcsutils
 
 degree = np.pi/180
 _OPS = {"add": 0, "max": 1, "min": 2}
-
-def _ptr(x): return None if x is None else (x.data_ptr() if _is_tensor(x) else x.ctypes.data)
-
-def _geometry(shape, wcs, separable):
-	"""(ny, nx, dec0, ddec, ra0, dra) in radians of a separable cylindrical geometry"""
-	if separable == "auto": separable = wcsutils.is_separable(wcs)
-	if not separable or not wcsutils.is_separable(wcs): raise NotImplementedError("pointsrcs: only separable cylindrical geometries")
-	w = wcs.wcs
-	return (int(shape[-2]), int(shape[-1]), float(w.crval[1]+(1-w.crpix[1])*w.cdelt[1])*degree, float(w.cdelt[1])*degree,
-		float(w.crval[0]+(1-w.crpix[0])*w.cdelt[0])*degree, float(w.cdelt[0])*degree)
-
-def _device_of(*arrs):
-	"""the torch device of the first CUDA tensor / dmap among arrs (None: everything lives on the host)"""
-	for a in arrs:
-		if isinstance(a, enmap.dmap): a = a.tensor
-		if a is not None and _is_tensor(a):
-			if not a.is_cuda and not sht._lib.is_hostsim(): raise ValueError("torch tensors passed to pixell_amd must live on the GPU")
-			return a.device
-	return None
-
-def _put(x, dtype, device):
-	"""x as a contiguous array of dtype where the library reads it: a tensor on `device` (a numpy array in the simulator when nothing came as a tensor)"""
-	if _is_tensor(x):
-		torch = sht._torch()
-		return x.to(device=device if device is not None else x.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
-	x = np.ascontiguousarray(x, dtype=dtype)
-	if device is None and sht._lib.is_hostsim(): return x
-	torch = sht._torch()
-	if device is None: sht.device_index(); return torch.from_numpy(x).cuda()
-	return torch.from_numpy(x).to(device)
-
-def _host(x):
-	if isinstance(x, enmap.dmap): x = x.tensor
-	return x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+_REAL = (np.dtype(np.float32), np.dtype(np.float64))
 
 def is_equi(r):
 	"""whether r[:] = arange(n)*delta, which allows index arithmetic instead of a search (pointsrcs.is_equi, pointsrcs.py:124-128)"""
-	r = _host(r)
+	r = A.host(r)
 	return bool(len(r) > 1 and r[0] == 0 and np.allclose(r[-1], (len(r)-1)*r[1]))
 
 def _profile_tables(profile):
@@ -62,7 +28,7 @@ def _profile_tables(profile):
 	vmax[k] = max |vs[j]| over the samples j >= k of the same profile"""
 	try: profile[0][0][0]
 	except (TypeError, IndexError): profile = [profile]
-	profs = [np.ascontiguousarray(_host(p), dtype=np.float32) for p in profile]
+	profs = [np.ascontiguousarray(A.host(p), dtype=np.float32) for p in profile]
 	for p in profs:
 		if p.ndim != 2 or p.shape[0] != 2 or p.shape[1] < 1: raise ValueError("a profile must be [{r,b(r)}, nsamp]")
 		if np.any(np.diff(p[0]) <= 0): raise ValueError("the radii of a profile must increase")
@@ -85,64 +51,45 @@ def sim_objects(shape, wcs, poss, amps, profile, prof_ids=None, omap=None, vmin=
 	C-contiguous array or tensor; vmin must be given, since rcut follows from the incoming amps); returns omap.
 	cache is accepted and not used (no position map is made).  return_times: also return [seconds spent in the call]."""
 	t0 = time.time()
-	ny, nx, dec0, ddec, ra0, dra = _geometry(shape, wcs, separable)
+	ny, nx, dec0, ddec, ra0, dra = wcsutils.separable_geometry(shape, wcs, separable)
 	if op not in _OPS: raise ValueError("op must be one of 'add', 'max', 'min', not %s" % repr(op))
-	if isinstance(amps, enmap.dmap): amps = amps.tensor
+	amps = A.unwrap(amps)
 	if transpose:
-		if not ((_is_tensor(amps) and amps.is_contiguous()) or (isinstance(amps, np.ndarray) and amps.flags["C_CONTIGUOUS"])) or _np_dtype(amps) != np.dtype(np.float32):
-			raise ValueError("transpose=True adds into amps in place: it must be a float32 C-contiguous array or tensor")
+		if not (A.is_tensor(amps) or isinstance(amps, np.ndarray)): raise ValueError("transpose=True adds into amps in place: it must be an array or tensor")
 		if vmin is None: raise ValueError("transpose=True needs vmin: the cut radii follow from the amplitudes that come in")
 		if op != "add": raise ValueError("transpose=True is the transpose of op='add'")
 		if omap is None: raise ValueError("transpose=True reads omap")
-	device = _device_of(omap, amps, poss)
-	sim = sht._lib.is_hostsim()
-	pre = tuple(amps.shape[:-1]) if _is_tensor(amps) else np.shape(amps)[:-1]
-	nobj = int(amps.shape[-1]) if _is_tensor(amps) else int(np.shape(amps)[-1])
+	device = A.device_of(omap, amps, poss)
+	pre = tuple(amps.shape[:-1]) if A.is_tensor(amps) else np.shape(amps)[:-1]
+	nobj = int(amps.shape[-1]) if A.is_tensor(amps) else int(np.shape(amps)[-1])
 	ncomp = int(np.prod(pre, dtype=np.int64))
-	d_amps = _put(amps, np.float32, device).reshape(ncomp, nobj)
-	if isinstance(poss, enmap.dmap): poss = poss.tensor
-	if not _is_tensor(poss): poss = np.asarray(poss)
+	d_amps = (A.out_array(amps, amps.shape, _REAL[:1], device, "amps", "") if transpose else A.put(amps, np.float32, device)).reshape(ncomp, nobj)
+	poss = A.unwrap(poss)
+	if not A.is_tensor(poss): poss = np.asarray(poss)
 	if tuple(poss.shape) != (2, nobj): raise ValueError("poss must be [{dec,ra},nobj]")
-	d_dec, d_ra = _put(poss[0], np.float32, device), _put(poss[1], np.float32, device)
+	d_dec, d_ra = A.put(poss[0], np.float32, device), A.put(poss[1], np.float32, device)
 	profs, off, rs, vs, vmax = _profile_tables(profile)
-	if prof_ids is not None and not _is_tensor(prof_ids) and nobj > 0:
+	if prof_ids is not None and not A.is_tensor(prof_ids) and nobj > 0:
 		ids = np.asarray(prof_ids)
 		if ids.shape != (nobj,) or ids.min() < 0 or ids.max() >= len(profs): raise ValueError("prof_ids must be [nobj] indices into the profile list")
-	d_ids = None if prof_ids is None else _put(prof_ids, np.int32, device)
+	d_ids = None if prof_ids is None else A.put(prof_ids, np.int32, device)
 	if prof_equi == "auto": prof_equi = all(is_equi(p[0]) for p in profs)
 	if vmin is None:
 		vmin = 0.0 if nobj == 0 or ncomp == 0 else float(abs(d_amps).min())*1e-3
 	if rmax is None: rmax = 0
 	# the map the kernel works on
 	pixshape = (ny, nx)
-	if omap is None:
-		if device is None and sim: work = np.zeros((ncomp,)+pixshape, np.float32)
-		else:
-			torch = sht._torch()
-			if device is None: sht.device_index()
-			work = torch.zeros((ncomp,)+pixshape, dtype=torch.float32, device=device if device is not None else "cuda")
-	else:
-		odata = omap.tensor if isinstance(omap, enmap.dmap) else omap
-		if _np_dtype(odata) not in (np.dtype(np.float32), np.dtype(np.float64)): raise ValueError("omap must be float32 or float64")
-		if tuple(odata.shape) != tuple(pre)+pixshape: raise ValueError("omap must be [...,ny,nx], where [ny,nx] agrees with shape, and ... agrees with amps")
-		if not (odata.is_contiguous() if _is_tensor(odata) else odata.flags["C_CONTIGUOUS"]): raise ValueError("omap must be C-contiguous")
-		work = (odata if _is_tensor(odata) else _put(odata, _np_dtype(odata), device)).reshape((ncomp,)+pixshape)
-	tabs = [_put(t, t.dtype, device) for t in (off, rs, vs, vmax)]
-	sht._lib.check(sht._lib.load().pxm_sim_objects(ny, nx, dec0, ddec, ra0, dra, _ptr(work), sht._DT[_np_dtype(work)], ncomp, ny*nx,
-		nobj, _ptr(d_dec), _ptr(d_ra), _ptr(d_amps), nobj, _ptr(d_ids), len(profs), _ptr(tabs[0]), len(rs), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]),
-		int(bool(prof_equi)), float(vmin), float(rmax), _OPS[op], int(bool(transpose)), sht.device_index(), sht.current_stream()))
-	if transpose:
-		if _ptr(d_amps) != _ptr(amps):      # amps came from the host: back into the caller's array
-			amps[...] = _host(d_amps).reshape(amps.shape)
-		res = omap
-	elif omap is not None:
-		odata = omap.tensor if isinstance(omap, enmap.dmap) else omap
-		if not _is_tensor(odata) and _ptr(work) != _ptr(odata): odata[...] = _host(work).reshape(odata.shape)
-		res = omap
+	if omap is None: work = A.zeros((ncomp,)+pixshape, np.float32, device=device)
+	else: work = A.out_array(omap, tuple(pre)+pixshape, _REAL, device, "omap", "[...,ny,nx], where [ny,nx] agrees with shape, and ... agrees with amps").reshape((ncomp,)+pixshape)
+	tabs = [A.put(t, t.dtype, device) for t in (off, rs, vs, vmax)]
+	_lib.check(_lib.load().pxm_sim_objects(ny, nx, dec0, ddec, ra0, dra, A.ptr(work), A.DT[A.np_dtype(work)], ncomp, ny*nx,
+		nobj, A.ptr(d_dec), A.ptr(d_ra), A.ptr(d_amps), nobj, A.ptr(d_ids), len(profs), A.ptr(tabs[0]), len(rs), A.ptr(tabs[1]), A.ptr(tabs[2]), A.ptr(tabs[3]),
+		int(bool(prof_equi)), float(vmin), float(rmax), _OPS[op], int(bool(transpose)), A.device_index(), A.current_stream()))
+	if transpose: A.result(d_amps, amps); res = omap
+	elif omap is not None: res = A.result(work, omap)
 	else:
 		full = work.reshape(tuple(pre)+pixshape)
-		if device is not None: res = enmap.dmap(full, wcs)
-		else: res = enmap.ndmap(_host(full), wcs)
+		res = enmap.dmap(full, wcs) if device is not None else enmap.ndmap(A.host(full), wcs)
 	# NB! Since we're not padding, this fourier operation will have problems at the edges (the reference's remark)
 	if pixwin and not transpose: res = enmap.apply_window(res, order=pixwin_order)
 	return (res, np.array([time.time()-t0])) if return_times else res
@@ -153,35 +100,28 @@ def radial_sum(map, poss, bins, oprofs=None, separable="auto", prof_equi="auto",
 	C-contiguous array instead.  Every bin is complete, the last one too."""
 	t0 = time.time()
 	if not hasattr(map, "wcs"): raise ValueError("radial_sum needs a map with a geometry (ndmap or dmap)")
-	ny, nx, dec0, ddec, ra0, dra = _geometry(map.shape, map.wcs, separable)
+	ny, nx, dec0, ddec, ra0, dra = wcsutils.separable_geometry(map.shape, map.wcs, separable)
 	mdata = map.tensor if isinstance(map, enmap.dmap) else np.asarray(map)
-	if isinstance(poss, enmap.dmap): poss = poss.tensor
-	device = _device_of(mdata, poss, oprofs)
-	if _np_dtype(mdata) not in (np.dtype(np.float32), np.dtype(np.float64)):
-		mdata = mdata.to(sht._torch().float64) if _is_tensor(mdata) else mdata.astype(np.float64)
+	poss = A.unwrap(poss)
+	device = A.device_of(mdata, poss, oprofs)
+	if A.np_dtype(mdata) not in _REAL: mdata = A.astype(mdata, np.float64)
 	pre = tuple(mdata.shape[:-2]); ncomp = int(np.prod(pre, dtype=np.int64))
 	nobj = int(poss.shape[1])
-	hbins = np.ascontiguousarray(_host(bins), dtype=np.float32)
+	hbins = np.ascontiguousarray(A.host(bins), dtype=np.float32)
 	nbin = len(hbins)-1
 	if nbin < 1 or np.any(np.diff(hbins) < 0): raise ValueError("bins must be at least two ascending edges")
 	if prof_equi == "auto": prof_equi = is_equi(hbins)
-	d_map = _put(mdata, _np_dtype(mdata), device).reshape((ncomp, ny, nx))
-	d_dec, d_ra = _put(poss[0], np.float32, device), _put(poss[1], np.float32, device)
-	d_bins = _put(hbins, np.float32, device)
-	if oprofs is None:
-		acc = _put(np.zeros((nobj, ncomp, nbin), np.float32), np.float32, device)
-	else:
-		if _np_dtype(oprofs) != np.dtype(np.float32) or tuple(oprofs.shape) != (nobj,)+pre+(nbin,): raise ValueError("oprofs must be float32 [nobj,...,nbin]")
-		if not (oprofs.is_contiguous() if _is_tensor(oprofs) else oprofs.flags["C_CONTIGUOUS"]): raise ValueError("oprofs must be C-contiguous")
-		acc = _put(oprofs, np.float32, device)
-	sht._lib.check(sht._lib.load().pxm_radial_sum(ny, nx, dec0, ddec, ra0, dra, _ptr(d_map), sht._DT[_np_dtype(d_map)], ncomp, ny*nx,
-		nobj, _ptr(d_dec), _ptr(d_ra), nbin, _ptr(d_bins), float(hbins[-1]), int(bool(prof_equi)), _ptr(acc), sht.device_index(), sht.current_stream()))
-	if oprofs is not None:
-		if _ptr(acc) != _ptr(oprofs): oprofs[...] = (_host(acc) if not _is_tensor(oprofs) else acc).reshape(oprofs.shape)
-		res = oprofs
+	d_map = A.put(mdata, None, device).reshape((ncomp, ny, nx))
+	d_dec, d_ra = A.put(poss[0], np.float32, device), A.put(poss[1], np.float32, device)
+	d_bins = A.put(hbins, np.float32, device)
+	if oprofs is None: acc = A.zeros((nobj, ncomp, nbin), np.float32, device=device)
+	else: acc = A.out_array(oprofs, (nobj,)+pre+(nbin,), _REAL[:1], device, "oprofs", "[nobj,...,nbin]")
+	_lib.check(_lib.load().pxm_radial_sum(ny, nx, dec0, ddec, ra0, dra, A.ptr(d_map), A.DT[A.np_dtype(d_map)], ncomp, ny*nx,
+		nobj, A.ptr(d_dec), A.ptr(d_ra), nbin, A.ptr(d_bins), float(hbins[-1]), int(bool(prof_equi)), A.ptr(acc), A.device_index(), A.current_stream()))
+	if oprofs is not None: res = A.result(acc, oprofs)
 	else:
 		res = acc.reshape((nobj,)+pre+(nbin,))
-		if device is None: res = _host(res)
+		if device is None: res = A.host(res)
 	return (res, np.array([time.time()-t0])) if return_times else res
 
 def radial_bin(map, poss, bins, weights=None, separable="auto", prof_equi="auto", cache=None, return_times=False):
@@ -190,17 +130,17 @@ def radial_bin(map, poss, bins, weights=None, separable="auto", prof_equi="auto"
 	mdata = map.tensor if isinstance(map, enmap.dmap) else np.asarray(map)
 	if weights is not None:
 		wdata = weights.tensor if isinstance(weights, enmap.dmap) else weights
-		if _is_tensor(mdata) and not _is_tensor(wdata): wdata = sht._torch().as_tensor(np.asarray(wdata), device=mdata.device)
+		if A.is_tensor(mdata) and not A.is_tensor(wdata): wdata = A.torch().as_tensor(np.asarray(wdata), device=mdata.device)
 		prod = mdata*wdata
-		map = enmap.dmap(prod, map.wcs) if _is_tensor(prod) else enmap.ndmap(prod, map.wcs)
-		wmap = enmap.dmap(wdata, map.wcs) if _is_tensor(wdata) else enmap.ndmap(np.asarray(wdata), map.wcs)
-	elif _is_tensor(mdata): wmap = enmap.dmap(sht._torch().ones(tuple(mdata.shape[-2:]), dtype=mdata.dtype, device=mdata.device), map.wcs)
+		map = enmap.dmap(prod, map.wcs) if A.is_tensor(prod) else enmap.ndmap(prod, map.wcs)
+		wmap = enmap.dmap(wdata, map.wcs) if A.is_tensor(wdata) else enmap.ndmap(np.asarray(wdata), map.wcs)
+	elif A.is_tensor(mdata): wmap = enmap.dmap(A.torch().ones(tuple(mdata.shape[-2:]), dtype=mdata.dtype, device=mdata.device), map.wcs)
 	else: wmap = enmap.ones(mdata.shape[-2:], map.wcs, mdata.dtype)
 	profs, times1 = radial_sum(map, poss, bins, separable=separable, prof_equi=prof_equi, return_times=True)
 	div, times2 = radial_sum(wmap, poss, bins, separable=separable, prof_equi=prof_equi, return_times=True)
 	# leading axes of the weights broadcast against those of the map
 	div = div.reshape(tuple(profs.shape[:1])+(1,)*(profs.ndim-div.ndim)+tuple(profs.shape[-1:])) if div.ndim < profs.ndim else div
-	if _is_tensor(profs): profs /= div
+	if A.is_tensor(profs): profs /= div
 	else:
 		with np.errstate(invalid="ignore", divide="ignore"): profs /= div
 	return (profs, np.concatenate([times1, times2])) if return_times else profs
@@ -220,7 +160,7 @@ def sim_srcs(shape, wcs, srcs, beam, omap=None, dtype=None, nsigma=5, rmax=None,
 	elif op is np.min or op is np.minimum or op == "min": op_ = "min"
 	else: raise ValueError("method 'c' only supports op add, max or min")
 	if return_padded: raise ValueError("method 'c' does not support return_padded")
-	srcs = _host(srcs)
+	srcs = A.host(srcs)
 	ncomp = int(np.prod(shape[:-2], dtype=int))
 	nobj = len(srcs)
 	poss = srcs.T[:2]
@@ -232,7 +172,7 @@ def sim_srcs(shape, wcs, srcs, beam, omap=None, dtype=None, nsigma=5, rmax=None,
 
 def expand_beam(beam, nsigma=5, rmax=None, nper=400):
 	"""a Gaussian sigma -> the profile [{r,b(r)}, nsigma*nper] out to rmax (default nsigma sigma); a profile passes through (pointsrcs.py:375-385)"""
-	beam = np.asarray(_host(beam))
+	beam = np.asarray(A.host(beam))
 	if beam.ndim == 0:
 		sigma = beam.reshape(-1)[0]
 		if rmax is None: rmax = sigma*nsigma

@@ -9,39 +9,8 @@ addressing; phi0 is still that of the flipped map (analyse_geometry().phi0).
 """
 import ctypes, os, contextlib, threading
 import numpy as np
-from . import _lib
-
-_DT = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
-
-def _torch():
-	import torch
-	return torch
-
-def _is_tensor(x):
-	return type(x).__module__.startswith("torch")
-
-def _np_dtype(x):
-	if _is_tensor(x):
-		torch = _torch()
-		return np.dtype({torch.float32: np.float32, torch.float64: np.float64, torch.complex64: np.complex64, torch.complex128: np.complex128}[x.dtype])
-	return np.dtype(x.dtype)
-
-_cuda_ready = False
-def device_index():
-	if _lib.is_hostsim(): return 0
-	torch = _torch()
-	if not torch.cuda.is_available():
-		raise RuntimeError("pixell_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
-	global _cuda_ready
-	if not _cuda_ready:
-		# make torch create its HIP context before libpxsht.so makes its first runtime call: a process whose first HIP
-		# call came from the library (numpy-only callers) got "no ROCm-capable device" from hipSetDevice on the GPU box
-		torch.cuda.init(); torch.zeros(1, device="cuda"); _cuda_ready = True
-	return torch.cuda.current_device()
-
-def current_stream():
-	if _lib.is_hostsim(): return None
-	return ctypes.c_void_p(_torch().cuda.current_stream().cuda_stream)
+from . import _lib, _arrays as A
+from ._arrays import device_index, current_stream      # (tests and tools call them under these names)
 
 # host-array route (pixell_amd/hostio.py): the Pipeline of the API call in progress ON THIS THREAD, if any.  Per thread: a call on
 # another thread must neither see this one's pipeline (its write-backs would complete on a queue this call may already have closed)
@@ -65,8 +34,8 @@ class _Buf:
 	element (an output whose old content need not travel to the device)"""
 	def __init__(self, arr, writeback=False, overwrite=False):
 		self.arr = arr; self.writeback = writeback; self.tmp = None; self.keep = None; self.slab = False
-		if _is_tensor(arr):
-			if not arr.is_cuda and not _lib.is_hostsim(): raise ValueError("torch tensors passed to pixell_amd must live on the GPU")
+		if A.is_tensor(arr):
+			A.require_gpu(arr)
 			if not arr.is_contiguous():
 				if writeback: raise ValueError("output tensors must be contiguous")
 				arr = arr.contiguous()
@@ -77,7 +46,7 @@ class _Buf:
 				else: self.keep = np.ascontiguousarray(arr); self.tmp = self.keep
 				self.ptr = self.keep.ctypes.data
 			else:
-				torch = _torch()
+				torch = A.torch()
 				from . import hostio
 				pipe = _pipe(); got = pipe.take(arr) if pipe is not None else None
 				self.slab = hostio.eligible(arr)
@@ -85,21 +54,21 @@ class _Buf:
 					self.tmp, ev = got; torch.cuda.current_stream().wait_event(ev)
 					self.tmp.record_stream(torch.cuda.current_stream())      # (allocated by the background thread: tell the allocator which stream consumes it)
 				elif self.slab and writeback and overwrite:
-					self.tmp = torch.empty(arr.shape, dtype=getattr(torch, arr.dtype.name), device="cuda")
+					self.tmp = A.empty(arr.shape, arr.dtype)
 				elif self.slab:
 					self.tmp, ev = hostio.upload(arr); torch.cuda.current_stream().wait_event(ev)
-				else: self.tmp = torch.from_numpy(np.ascontiguousarray(arr)).cuda()
+				else: self.tmp = A.put(arr)
 				self.ptr = self.tmp.data_ptr()
 	def finish(self):
 		if not self.writeback or self.tmp is None: return
 		if _lib.is_hostsim(): self.arr[...] = self.tmp
 		elif self.slab:
 			from . import hostio
-			ev = _torch().cuda.Event(); ev.record()
+			ev = A.torch().cuda.Event(); ev.record()
 			pipe = _pipe()
 			if pipe is not None: pipe.writeback(self.tmp, self.arr, ev)      # complete when the host_pipeline block (of this thread) exits
 			else: hostio.download(self.tmp, self.arr, after=ev)
-		else: self.arr[...] = self.tmp.cpu().numpy()
+		else: self.arr[...] = A.host(self.tmp)
 
 class Plan:
 	"""RAII wrapper of pxs_plan"""
@@ -253,7 +222,7 @@ def _check_pair(alm, map, spin, mode, pixdims):
 		alm, map = alm[0], map[0]
 	if alm.ndim != 2 or alm.shape[0] != nca: raise ValueError("alm must have shape [%d,nelem] for spin %d mode %s" % (nca, spin, mode))
 	if map.ndim != 1+pixdims or map.shape[0] != ncm: raise ValueError("map must have %d components" % ncm)
-	ad, md = _np_dtype(alm), _np_dtype(map)
+	ad, md = A.np_dtype(alm), A.np_dtype(map)
 	if ad not in (np.complex64, np.complex128) or md not in (np.float32, np.float64): raise TypeError("alm must be complex, map real")
 	return ad, md
 
@@ -263,7 +232,7 @@ class _View:
 	many maps); numpy arrays and other tensors are staged contiguously (and written back for outputs)."""
 	def __init__(self, arr, inner_ndim, batched, writeback, overwrite=False):
 		self.buf = None
-		if _is_tensor(arr) and (arr.is_cuda or _lib.is_hostsim()):
+		if A.is_tensor(arr) and (arr.is_cuda or _lib.is_hostsim()):
 			st = list(arr.stride()); sh = list(arr.shape)
 			inner_ok = all(st[-k] == int(np.prod(sh[len(sh)-k+1:], dtype=np.int64)) for k in range(1, inner_ndim+1))
 			if inner_ok:
@@ -278,14 +247,14 @@ class _View:
 
 def _run_syn(plan, alm, map, spin, mode, adjoint, map_overwrite=False):
 	"""alm [nca, nelem], map [ncm, ...] -- or a batch of independent maps alm [nb, nca, nelem], map [nb, ncm, ...] in ONE library call"""
-	ad, md = _np_dtype(alm), _np_dtype(map)
+	ad, md = A.np_dtype(alm), A.np_dtype(map)
 	batched = alm.ndim == 3
 	nb = alm.shape[0] if batched else 1
 	av = _View(alm, 1, batched, bool(adjoint)); mv = _View(map, map.ndim-(2 if batched else 1), batched, not adjoint, overwrite=map_overwrite and not adjoint)
 	with plan.lock:      # (the adjoint synthesis runs the Legendre analysis: the deterministic option and the call as one step)
 		_apply_mode(plan)
 		_lib.check(_lib.load().pxs_synthesis(plan.handle, int(spin), 1 if mode == "DERIV1" else 0, int(bool(adjoint)), int(nb),
-			av.ptr, _DT[ad], av.cstride, av.bstride, mv.ptr, _DT[md], mv.cstride, mv.bstride, current_stream()))
+			av.ptr, A.DT[ad], av.cstride, av.bstride, mv.ptr, A.DT[md], mv.cstride, mv.bstride, current_stream()))
 	av.finish(); mv.finish()
 
 ANALYSIS_MODES = {"ducc0": 2, "interpolant": 0, "weights": 1}
@@ -305,15 +274,15 @@ def analysis_form(geometry, ntheta, nphi, lmax, mmax=None, mstart=None, phi0=0.0
 	return dict(form={0: "interpolant", 1: "weights", 2: "ducc0"}[plan.query("analysis_form")], ncc_circle=plan.query("ncc_circle"), ducc_ncc_circle=plan.query("ducc_ncc_circle"))
 
 def _run_ana(plan, map, alm, spin, adjoint, analysis=None, alm_dense=False):
-	ad, md = _np_dtype(alm), _np_dtype(map)
+	ad, md = A.np_dtype(alm), A.np_dtype(map)
 	batched = alm.ndim == 3
 	nb = alm.shape[0] if batched else 1
 	av = _View(alm, 1, batched, not adjoint, overwrite=alm_dense and not adjoint); mv = _View(map, map.ndim-(2 if batched else 1), batched, bool(adjoint), overwrite=bool(adjoint))      # (a grid plan writes every pixel)
 	with plan.lock:      # the options and the call they apply to, as one step: plans are cached and shared between threads
 		_apply_mode(plan)
 		plan.set_option("analysis", _analysis_mode(analysis))
-		_lib.check(_lib.load().pxs_analysis(plan.handle, int(spin), int(bool(adjoint)), int(nb), mv.ptr, _DT[md], mv.cstride, mv.bstride,
-			av.ptr, _DT[ad], av.cstride, av.bstride, current_stream()))
+		_lib.check(_lib.load().pxs_analysis(plan.handle, int(spin), int(bool(adjoint)), int(nb), mv.ptr, A.DT[md], mv.cstride, mv.bstride,
+			av.ptr, A.DT[ad], av.cstride, av.bstride, current_stream()))
 	av.finish(); mv.finish()
 
 def _grid_args(alm, map, spin, lmax, mmax, mstart, geometry, phi0, lstride, mode, flip):
@@ -364,8 +333,8 @@ def synthesis(*, alm, theta, nphi, phi0, ringstart, lmax, mmax=None, mstart=None
 	if map is None:
 		rs_ = np.asarray(ringstart).astype(np.int64); last_ = rs_+(np.asarray(nphi).astype(np.int64)-1)*pixstride
 		npix = int(max(rs_.max(), last_.max())+1)
-		rdt = np.float32 if _np_dtype(alm) == np.complex64 else np.float64
-		map = _torch().zeros((ncm, npix), dtype=getattr(_torch(), np.dtype(rdt).name), device=alm.device) if _is_tensor(alm) else np.zeros((ncm, npix), rdt)
+		rdt = np.float32 if A.np_dtype(alm) == np.complex64 else np.float64
+		map = A.zeros((ncm, npix), rdt, like=alm)
 	_check_pair(alm, map, spin, mode, 1)
 	_run_syn(plan, alm, map, spin, mode, False)
 	synthesis.last_plan = plan
@@ -377,8 +346,8 @@ def adjoint_synthesis(*, map, theta, nphi, phi0, ringstart, lmax, mmax=None, mst
 	nca, ncm = _ncomp(spin, mode)
 	if alm is None:
 		nelem = int(np.max(np.asarray(mstart).astype(np.int64))+lmax*lstride+1)
-		cdt = np.complex64 if _np_dtype(map) == np.float32 else np.complex128
-		alm = _torch().zeros((nca, nelem), dtype=getattr(_torch(), np.dtype(cdt).name), device=map.device) if _is_tensor(map) else np.zeros((nca, nelem), cdt)
+		cdt = np.complex64 if A.np_dtype(map) == np.float32 else np.complex128
+		alm = A.zeros((nca, nelem), cdt, like=map)
 	_check_pair(alm, map, spin, mode, 1)
 	_run_syn(plan, alm, map, spin, mode, True)
 	adjoint_synthesis.last_plan = plan
@@ -396,20 +365,13 @@ def points_grid_shape(lmax, mmax):
 
 def _loc_device(loc):
 	"""loc [npts, 2] f64 -> (device array the library reads, npts); ValueError for theta outside [0, pi] or a non-finite phi"""
-	if _is_tensor(loc):
-		torch = _torch()
-		if loc.ndim != 2 or loc.shape[1] != 2: raise ValueError("loc must have shape [npts, 2]")
-		loc = loc.to(torch.float64).contiguous()
-		if loc.shape[0] and not bool(((loc[:, 0] >= 0) & (loc[:, 0] <= np.pi) & torch.isfinite(loc[:, 1])).all()):
-			raise ValueError("loc: theta must lie in [0, pi] and phi be finite")
-		if _lib.is_hostsim(): return loc, loc.shape[0]
-		return (loc if loc.is_cuda else loc.cuda()), loc.shape[0]
-	loc = np.ascontiguousarray(loc, dtype=np.float64)
+	tens = A.is_tensor(loc); xp = A.torch() if tens else np
+	loc = loc.to(xp.float64).contiguous() if tens else np.ascontiguousarray(loc, dtype=np.float64)
 	if loc.ndim != 2 or loc.shape[1] != 2: raise ValueError("loc must have shape [npts, 2]")
-	if loc.shape[0] and not (np.all((loc[:, 0] >= 0) & (loc[:, 0] <= np.pi)) and np.all(np.isfinite(loc[:, 1]))):
+	if loc.shape[0] and not bool(((loc[:, 0] >= 0) & (loc[:, 0] <= np.pi) & xp.isfinite(loc[:, 1])).all()):
 		raise ValueError("loc: theta must lie in [0, pi] and phi be finite")
-	if _lib.is_hostsim(): return loc, loc.shape[0]
-	return _torch().from_numpy(loc).cuda(), loc.shape[0]
+	if _lib.is_hostsim() or (tens and loc.is_cuda): return loc, loc.shape[0]
+	return A.to_gpu(loc), loc.shape[0]
 
 def points_plan(loc, lmax, mmax=None, mstart=None, lstride=1, epsilon=1e-10):
 	"""a pxs_plan of the points loc [npts, 2] (theta, phi) on the cached CC grid plan of (lmax, mmax, layout); not cached itself"""
@@ -420,9 +382,8 @@ def points_plan(loc, lmax, mmax=None, mstart=None, lstride=1, epsilon=1e-10):
 	nt, nph = points_grid_shape(lmax, mmax)
 	grid = grid_plan("CC", nt, nph, 0.0, (False, False), lmax, mmax, mstart, lstride)
 	dloc, npts = _loc_device(loc)
-	ptr = dloc.data_ptr() if _is_tensor(dloc) else dloc.ctypes.data
 	h = ctypes.c_void_p()
-	_lib.check(_lib.load().pxs_plan_points(ctypes.byref(h), grid.handle, int(npts), ptr if npts else None, epsilon, device_index(), current_stream()))
+	_lib.check(_lib.load().pxs_plan_points(ctypes.byref(h), grid.handle, int(npts), A.ptr(dloc) if npts else None, epsilon, device_index(), current_stream()))
 	p = Plan(h); p.grid = grid; p.npts = int(npts)
 	return p
 
@@ -463,12 +424,12 @@ def synthesis_general(*, alm, loc, spin, lmax, mmax=None, mstart=None, lstride=1
 	if mode not in ("STANDARD", "DERIV1"): raise ValueError("unknown mode '%s'" % str(mode))
 	npts = int(loc.shape[0])
 	if map is None:
-		rdt = np.float32 if _np_dtype(alm) == np.complex64 else np.float64
+		rdt = np.float32 if A.np_dtype(alm) == np.complex64 else np.float64
 		shape = tuple(alm.shape[:-2])+(ncm, npts)
-		map = _torch().zeros(shape, dtype=getattr(_torch(), np.dtype(rdt).name), device=alm.device) if _is_tensor(alm) else np.zeros(shape, rdt)
+		map = A.zeros(shape, rdt, like=alm)
 	_check_pair(alm, map, spin, mode, 1)
 	if map.shape[-1] != npts: raise ValueError("map has %d points, loc %d" % (map.shape[-1], npts))
-	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, _np_dtype(map))
+	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, A.np_dtype(map))
 	if npts == 0: return map
 	_run_points(plan, alm, map, spin, mode, False)
 	return map
@@ -483,12 +444,12 @@ def adjoint_synthesis_general(*, map, loc, spin, lmax, mmax=None, mstart=None, l
 	npts = int(loc.shape[0])
 	if alm is None:
 		nelem = int(np.max(np.asarray(mstart).astype(np.int64))+lmax*lstride+1)
-		cdt = np.complex64 if _np_dtype(map) == np.float32 else np.complex128
+		cdt = np.complex64 if A.np_dtype(map) == np.float32 else np.complex128
 		shape = tuple(map.shape[:-2])+(nca, nelem)
-		alm = _torch().zeros(shape, dtype=getattr(_torch(), np.dtype(cdt).name), device=map.device) if _is_tensor(map) else np.zeros(shape, cdt)
+		alm = A.zeros(shape, cdt, like=map)
 	_check_pair(alm, map, spin, mode, 1)
 	if map.shape[-1] != npts: raise ValueError("map has %d points, loc %d" % (map.shape[-1], npts))
-	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, _np_dtype(map))
+	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, A.np_dtype(map))
 	if npts == 0:      # (no map to read: the transpose of an empty synthesis is zero)
 		alm[...] = 0
 		return alm

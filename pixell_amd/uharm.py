@@ -10,8 +10,7 @@ Maps may be numpy ndmaps (staged) or enmap.dmap (device resident, nothing leaves
 The stock pixell.uharm.UHT itself also runs on this backend unchanged through the integration routes of INTEGRATION.md
 (pixell.curvedsky over pixell_amd.sht, pixell.fft.engines["hip"]); this class is for callers that keep their data on the GPU."""
 import numpy as np
-from . import enmap, curvedsky
-from .sht import _is_tensor, _torch
+from . import enmap, curvedsky, _arrays as A
 
 def res2lmax(res):
 	"""band limit that resolves the angular scale res (radians)"""
@@ -50,8 +49,8 @@ class UHT:
 	def _zeros_map(self, harm):
 		"""a real map for every alm of harm[..., nelem], next to it"""
 		pre = tuple(harm.shape[:-1])
-		if _is_tensor(harm):
-			torch = _torch()
+		if A.is_tensor(harm):
+			torch = A.torch()
 			rt = torch.float32 if harm.dtype == torch.complex64 else torch.float64
 			return enmap.dmap(torch.zeros(pre+self.shape, dtype=rt, device=harm.device), self.wcs)
 		return enmap.zeros(pre+self.shape, self.wcs, np.zeros(1, harm.dtype).real.dtype)
@@ -95,15 +94,15 @@ class UHT:
 		"""hprof * harm -> harm.  flat: hprof [ny,nx], [ncomp,ny,nx] (elementwise) or [ncomp,ncomp,ny,nx] (matrix product over the
 		component axis); curved: [nl], [ncomp,nl] or [ncomp,ncomp,nl] through alm_info.lmul on the GPU"""
 		if self.mode == "curved":
-			if not _is_tensor(harm):
+			if not A.is_tensor(harm):
 				harm = np.asanyarray(harm); harm = harm.astype(np.result_type(harm, 0j), copy=False)
 			return self.ainfo.lmul(harm, hprof, out=harm if inplace else None)
 		dev = isinstance(harm, enmap.dmap)
 		h = harm.tensor if dev else np.asanyarray(harm)
 		p = np.asarray(hprof) if not isinstance(hprof, enmap.dmap) else hprof.tensor
-		if dev and not _is_tensor(p): p = _torch().as_tensor(np.ascontiguousarray(p), device=h.device)
+		if dev and not A.is_tensor(p): p = A.torch().as_tensor(np.ascontiguousarray(p), device=h.device)
 		if p.ndim <= 3: res = p*h
-		else: res = (_torch() if dev else np).einsum("...abyx,...byx->...ayx", p.to(h.dtype) if dev else p, h)
+		else: res = (A.torch() if dev else np).einsum("...abyx,...byx->...ayx", p.to(h.dtype) if dev else p, h)
 		if inplace: h[...] = res; return harm
 		return enmap.dmap(res, harm.wcs) if dev else enmap.ndmap(res, getattr(harm, "wcs", self.wcs))
 	def hrand(self, hprof):
@@ -117,7 +116,7 @@ class UHT:
 		ps = curvedsky.alm2cl(harm, harm2)
 		return ps/self.fsky if patch else ps
 	def sum_hprof(self, hprof):
-		hprof = hprof.cpu().numpy() if _is_tensor(hprof) else np.asanyarray(hprof.tensor.cpu().numpy() if isinstance(hprof, enmap.dmap) else hprof)
+		hprof = hprof.cpu().numpy() if A.is_tensor(hprof) else np.asanyarray(hprof.tensor.cpu().numpy() if isinstance(hprof, enmap.dmap) else hprof)
 		return np.sum(hprof*self.nper, (-2, -1) if self.mode == "flat" else -1)
 	def mean_hprof(self, hprof): return self.sum_hprof(hprof)/self.ntot
 	def rprof2hprof(self, br, r):

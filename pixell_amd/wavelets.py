@@ -22,8 +22,7 @@ the size of the process-wide plan cache.
 
 Flat-sky mode, the variance transform and the Haar / digital / scale-discrete bases of the reference are not here."""
 import numpy as np
-from . import enmap, curvedsky, multimap, almops, sht, wcs as wcsutils
-from .sht import _is_tensor, _np_dtype, _torch
+from . import enmap, curvedsky, multimap, almops, sht, _arrays as A, wcs as wcsutils
 
 degree = np.pi/180
 
@@ -132,11 +131,9 @@ def _consecutive(idx): return all(b == a+1 for a, b in zip(idx[:-1], idx[1:]))
 
 def _split_last(x, n, npix):
 	"""x[..., n*npix] -> x[..., n, npix] without a copy"""
-	if _is_tensor(x): return x.unflatten(-1, (n, npix))
+	if A.is_tensor(x): return x.unflatten(-1, (n, npix))
 	v = x.view(); v.shape = x.shape[:-1]+(n, npix); return v
 
-def _empty_like_kind(shape, dtype, like):
-	return almops._alloc_like(like, shape, dtype)
 
 class WaveletTransform:
 	"""map2wave / wave2map between a map on uht's geometry and its wavelet coefficients (a multimap).
@@ -201,7 +198,7 @@ class WaveletTransform:
 	def _check_pre(self, pre):
 		if len(pre) > 0: list(enmap.spin_helper([0, 2], pre[-1]))          # T or T,Q,U ...: a cut pair raises as in the transforms themselves
 	def _wave_data(self, wave): return wave.tensor if isinstance(wave, multimap.dmaps) else np.asarray(wave)
-	def _as_map(self, data, wcs): return enmap.dmap(data, wcs) if _is_tensor(data) else enmap.ndmap(data, wcs)
+	def _as_map(self, data, wcs): return enmap.dmap(data, wcs) if A.is_tensor(data) else enmap.ndmap(data, wcs)
 	# ---- transforms
 	def map2wave(self, map, owave=None, fl=None, scales=None, fill_value=None):
 		"""wavelet coefficients of map[..., ny, nx] (leading dimensions: T, or T,Q,U with the transforms' default spin [0, 2]) as a multimap:
@@ -211,12 +208,12 @@ class WaveletTransform:
 		pre = tuple(map.shape[:-2]); self._check_pre(pre)
 		want = sorted(set(range(self.nlevel) if scales is None else [int(i) for i in scales]))
 		dm, staged = enmap._to_device(map)
-		mdata = curvedsky._mdata(dm); rdt = _np_dtype(mdata)
+		mdata = curvedsky._mdata(dm); rdt = A.np_dtype(mdata)
 		geos = [(pre+shape, wcs) for shape, wcs in self.geometries]
 		offs = multimap._offsets(multimap.nopre(geos))
-		fresh = owave is None or _is_tensor(self._wave_data(owave)) != _is_tensor(mdata) or owave.dtype != rdt
+		fresh = owave is None or A.is_tensor(self._wave_data(owave)) != A.is_tensor(mdata) or owave.dtype != rdt
 		if owave is not None and (tuple(owave.npixs) != tuple(offs[1:]-offs[:-1]) or tuple(owave.pre) != pre): raise ValueError("map2wave: owave does not have this transform's geometries and the map's leading dimensions")
-		work = multimap.zeros(geos, rdt, device=mdata.device if _is_tensor(mdata) else None) if fresh else owave
+		work = multimap.zeros(geos, rdt, device=mdata.device if A.is_tensor(mdata) else None) if fresh else owave
 		wdata = self._wave_data(work)
 		with self.pin:
 			alm = curvedsky.map2alm(dm, ainfo=self.ainfo)
@@ -227,7 +224,7 @@ class WaveletTransform:
 			if fl is not None:
 				flp = np.zeros(self.ainfo.lmax+1); flp[:min(len(fl), len(flp))] = fl[:len(flp)]
 				filters = [f*flp for f in filters]
-			table = almops._filter_table(filters, self.basis.lmaxs, self.ainfo.lmax+1, _np_dtype(alm))
+			table = almops._filter_table(filters, self.basis.lmaxs, self.ainfo.lmax+1, A.np_dtype(alm))
 			groups = self._groups(want)
 			apre = pre if pre else (1,)
 			salms = almops.bank_split_groups(self.ainfo, alm.reshape(apre+(alm.shape[-1],)), table, self.basis.lmaxs, [(L, idx) for L, idx, geo in groups])
@@ -236,11 +233,11 @@ class WaveletTransform:
 				block = wdata[..., offs[idx[0]]:offs[idx[-1]+1]] if _consecutive(idx) else None
 				tgt = curvedsky._as_view(block, (ng, 1)+shape) if block is not None and pre == () else None       # scalar maps, side by side: written in place
 				direct = tgt is not None
-				if not direct: tgt = _empty_like_kind((ng,)+apre+shape, rdt, mdata)
+				if not direct: tgt = A.empty((ng,)+apre+shape, rdt, like=mdata)
 				curvedsky.alm2map(salm, self._as_map(tgt, wcs), ainfo=self._small(L))
 				if direct: continue
 				src = tgt.reshape((ng,)+pre+(npix,))
-				if block is not None: _split_last(block, ng, npix)[...] = src.movedim(0, -2) if _is_tensor(src) else np.moveaxis(src, 0, -2)
+				if block is not None: _split_last(block, ng, npix)[...] = src.movedim(0, -2) if A.is_tensor(src) else np.moveaxis(src, 0, -2)
 				else:
 					for k, i in enumerate(idx): wdata[..., offs[i]:offs[i+1]] = src[k]
 		for i in range(self.nlevel):
@@ -248,7 +245,7 @@ class WaveletTransform:
 		if owave is None: return work.to_host() if staged else work
 		if work is not owave:
 			host = work.to_host() if isinstance(work, multimap.dmaps) else work
-			if isinstance(owave, multimap.dmaps): owave.tensor.copy_(_torch().as_tensor(np.asarray(host), device=owave.tensor.device))
+			if isinstance(owave, multimap.dmaps): owave.tensor.copy_(A.torch().as_tensor(np.asarray(host), device=owave.tensor.device))
 			else: owave[...] = host
 		return owave
 	def wave2map(self, wave, omap=None):
@@ -257,10 +254,9 @@ class WaveletTransform:
 		the scales that share its grid; what lies above its own lmaxs[i] is dropped when the scales are summed."""
 		pre = tuple(wave.pre); self._check_pre(pre)
 		if tuple(wave.npixs) != tuple(s[0]*s[1] for s, w in self.geometries): raise ValueError("wave2map: the multimap does not have this transform's geometries")
-		wdata = self._wave_data(wave); staged = False
-		if not _is_tensor(wdata) and not sht._lib.is_hostsim():
-			sht.device_index(); wdata = _torch().from_numpy(np.ascontiguousarray(wdata)).cuda(); staged = True
-		rdt = _np_dtype(wdata); cdt = np.result_type(rdt, 0j)
+		wdata = self._wave_data(wave); staged = not A.is_tensor(wdata)
+		if staged: wdata = A.put(wdata); staged = A.is_tensor(wdata)
+		rdt = A.np_dtype(wdata); cdt = np.result_type(rdt, 0j)
 		offs = multimap._offsets(wave.geometries)
 		apre = pre if pre else (1,)
 		table = almops._filter_table([self.filters[i]*self.norms[i] for i in range(self.nlevel)], self.basis.lmaxs, self.ainfo.lmax+1, cdt)
@@ -272,22 +268,21 @@ class WaveletTransform:
 				block = wdata[..., offs[idx[0]]:offs[idx[-1]+1]] if _consecutive(idx) else None
 				src = curvedsky._as_view(block, (ng, 1)+shape) if block is not None and pre == () else None
 				if src is None:
-					src = _empty_like_kind((ng,)+apre+shape, rdt, wdata); flat = src.reshape((ng,)+pre+(npix,))
-					if block is not None: flat[...] = _split_last(block, ng, npix).movedim(-2, 0) if _is_tensor(block) else np.moveaxis(_split_last(block, ng, npix), -2, 0)
+					src = A.empty((ng,)+apre+shape, rdt, like=wdata); flat = src.reshape((ng,)+pre+(npix,))
+					if block is not None: flat[...] = _split_last(block, ng, npix).movedim(-2, 0) if A.is_tensor(block) else np.moveaxis(_split_last(block, ng, npix), -2, 0)
 					else:
 						for k, i in enumerate(idx): flat[k] = wdata[..., offs[i]:offs[i+1]]
 				salms.append(curvedsky.map2alm(self._as_map(src, wcs), ainfo=self._small(L)))
-			oalm = _empty_like_kind(apre+(self.ainfo.nelem,), cdt, wdata)
+			oalm = A.empty(apre+(self.ainfo.nelem,), cdt, like=wdata)
 			almops.bank_merge_groups(self.ainfo, salms, table, self.basis.lmaxs, [(L, idx) for L, idx, geo in groups], oalm)
-			kind_ok = omap is not None and isinstance(omap, enmap.dmap) == _is_tensor(wdata) and omap.dtype == rdt and tuple(omap.shape) == pre+tuple(self.shape)
+			kind_ok = omap is not None and isinstance(omap, enmap.dmap) == A.is_tensor(wdata) and omap.dtype == rdt and tuple(omap.shape) == pre+tuple(self.shape)
 			if kind_ok: work = omap
 			else:
-				z = _torch().zeros(pre+tuple(self.shape), dtype=wdata.dtype, device=wdata.device) if _is_tensor(wdata) else np.zeros(pre+tuple(self.shape), rdt)
-				work = self._as_map(z, self.wcs)
+				work = self._as_map(A.zeros(pre+tuple(self.shape), rdt, like=wdata), self.wcs)
 			curvedsky.alm2map(oalm.reshape(pre+(self.ainfo.nelem,)), work, ainfo=self.ainfo)
 		if omap is None: return enmap._to_host(work) if staged else work
 		if work is not omap:
 			host = enmap._to_host(work)
-			if isinstance(omap, enmap.dmap): omap.tensor.copy_(_torch().as_tensor(np.asarray(host), device=omap.tensor.device))
+			if isinstance(omap, enmap.dmap): omap.tensor.copy_(A.torch().as_tensor(np.asarray(host), device=omap.tensor.device))
 			else: omap[...] = host
 		return omap

@@ -41,6 +41,14 @@ def is_separable(wcs):
 	"""wcsutils.is_separable (wcsutils.py:174-175)"""
 	return is_cyl(wcs) and wcs.wcs.crval[1] == 0
 def is_car(wcs): return get_proj(wcs) == "car"
+def separable_geometry(shape, wcs, separable="auto"):
+	"""(ny, nx, dec0, ddec, ra0, dra) in radians of a separable cylindrical geometry: what the pixel-operator kernels take instead of a
+	position map (pixel (y, x) lies at dec0 + y ddec, ra0 + x dra)"""
+	if separable == "auto": separable = is_separable(wcs)
+	if not separable or not is_separable(wcs): raise NotImplementedError("only separable cylindrical geometries")
+	w = wcs.wcs; degree = np.pi/180
+	return (int(shape[-2]), int(shape[-1]), float(w.crval[1]+(1-w.crpix[1])*w.cdelt[1])*degree, float(w.cdelt[1])*degree,
+		float(w.crval[0]+(1-w.crpix[0])*w.cdelt[0])*degree, float(w.cdelt[0])*degree)
 
 def pix2world(wcs, x, y):
 	"""0-based pixel -> (ra, dec) in degrees (linear CAR)"""
