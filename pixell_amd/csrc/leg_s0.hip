@@ -5,6 +5,42 @@
 
 namespace pxs {
 
+// ---- the VALU kernels ----
+// Phase A of the spin-0 kernels: no lane of the wave is live yet (scale 0 and |value| >= LEG_LIVE), so nothing is
+// accumulated.  Four recurrence steps per iteration with the four coefficient rows fetched together;
+// the rescale / activity test runs once per 4 steps (a chain grows by < 2^60 in 4 steps, far from
+// overflow at 2^1024; what the late start drops: see LEG_LIVE).
+#define S0_PHASE_A \
+	while (k + 4 <= nk) { \
+		bool act = false; \
+		_Pragma("unroll") for (int s = 0; s < K; s++) act |= LEG_IS_LIVE(lam2[s], sc[s]); \
+		if (__any(act)) break; \
+		const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3); \
+		const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b; \
+		_Pragma("unroll") for (int s = 0; s < K; s++) { \
+			lam1[s] = fma(fma(q0.a, csq[s], b0), lam2[s], lam1[s]); \
+			lam2[s] = fma(fma(q1.a, csq[s], b1), lam1[s], lam2[s]); \
+			lam1[s] = fma(fma(q2.a, csq[s], b2), lam2[s], lam1[s]); \
+			lam2[s] = fma(fma(q3.a, csq[s], b3), lam1[s], lam2[s]); \
+			if (sc[s] < 0 && fabs(lam2[s]) > SC_BIG) { lam1[s] *= SC_SMALL; lam2[s] *= SC_SMALL; sc[s]++; } \
+		} \
+		k += 4; \
+	}
+// phase A with the recurrence seeds (legendre_dev.hpp, "Recurrence seeds"): mode 2 loads the state and the step reached, mode 1 records them
+#define S0_SEEDED_PHASE_A \
+	if (a.seed_mode == 2) { \
+		const double* sd = a.seed_d + ((long)m*a.nwave + wv)*(2*K*64); const int* si = a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64); \
+		k = PXS_UNIFORM_INT(si[K*64]); \
+		_Pragma("unroll") for (int s = 0; s < K; s++) { lam1[s] = sd[s*64 + lane]; lam2[s] = sd[(K+s)*64 + lane]; sc[s] = si[s*64 + lane]; } \
+	} else { \
+		S0_PHASE_A \
+		if (a.seed_mode == 1) { \
+			double* sd = a.seed_d + ((long)m*a.nwave + wv)*(2*K*64); int* si = a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64); \
+			_Pragma("unroll") for (int s = 0; s < K; s++) { sd[s*64 + lane] = lam1[s]; sd[(K+s)*64 + lane] = lam2[s]; si[s*64 + lane] = sc[s]; } \
+			if (lane == 0) si[K*64] = k; \
+		} \
+	}
+
 // two fast steps of the spin-0 synthesis (lam1/lam2 swap roles)
 #define S0_SYN_PAIR(c0, c1, a0, a1) { \
 	PXS_VCOPY(vb0, polar ? c0.c : c0.b); \
@@ -255,134 +291,85 @@ struct S0Chain {
 	__device__ __forceinline__ void rescale() { if (fabs(lam2) > SC_BIG) { lam1 *= SC_SMALL; lam2 *= SC_SMALL; sc++; } }
 	__device__ __forceinline__ void park_sign(int, double*) const {}
 };
-// start value of ring pair p at m; returns whether the pair carries signal at this m
-__device__ __forceinline__ bool s0_chain_init(const LegK& a, int p, int m, bool polar, S0Chain& C) {
-	const bool valid = p < a.npairs;
-	const double x = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0;
-	C.csq = polar ? -sth*sth : x*x;
-	const bool alive = valid && ((double)m <= a.lmax*sth + a.ofs);
-	C.lam1 = 0; C.lam2 = 0; C.sc = 0;
-	if (alive) { double mt; int e; pow_scaled(sth, m, mt, e); to_scaled(mt, e, C.lam2, C.sc); }
-	return alive;
-}
-// phase A (S0_PHASE_A for one chain): recurrence only until the first lane of the wave is live (LEG_LIVE); returns the step reached
-__device__ __forceinline__ int s0_chain_phase_a(S0Chain& C, const double4_t* __restrict__ coef, bool polar, int nk) {
-	int k = 0;
-	while (k + 4 <= nk) {
-		if (__any(LEG_IS_LIVE(C.lam2, C.sc))) break;
-		const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3);
-		const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b;
-		C.lam1 = fma(fma(q0.a, C.csq, b0), C.lam2, C.lam1);
-		C.lam2 = fma(fma(q1.a, C.csq, b1), C.lam1, C.lam2);
-		C.lam1 = fma(fma(q2.a, C.csq, b2), C.lam2, C.lam1);
-		C.lam2 = fma(fma(q3.a, C.csq, b3), C.lam1, C.lam2);
-		if (C.sc < 0) C.rescale();
-		k += 4;
+// the spin-0 side of leg_ana_mm / leg_syn_mm (legendre_dev.hpp): one chain per lane, 64 ring pairs per wave
+struct S0Mm {
+	typedef S0Chain Chain;
+	static constexpr int SLOTS = 64;
+	static constexpr bool SIGNED = false;
+	static constexpr bool BREG_SYNC = true;      // (the spin analysis has none: kept as it was, kernel by kernel)
+	static __device__ __forceinline__ int steps(const LegK& a, int m, int& par) { par = 0; return (a.lmax - m)/2 + 1; }
+	// start value of ring pair p at m; returns whether the pair carries signal at this m
+	static __device__ __forceinline__ bool init(const LegK& a, int p, int m, int, bool polar, S0Chain& C) {
+		const bool valid = p < a.npairs;
+		const double x = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0;
+		C.csq = polar ? -sth*sth : x*x;
+		const bool alive = valid && ((double)m <= a.lmax*sth + a.ofs);
+		C.lam1 = 0; C.lam2 = 0; C.sc = 0;
+		if (alive) { double mt; int e; pow_scaled(sth, m, mt, e); to_scaled(mt, e, C.lam2, C.sc); }
+		return alive;
 	}
-	return k;
-}
-
-template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm(const LegK a)
-{
-	PXS_SHARED(double, sh);
-	double* __restrict__ ptile = sh;                              // [W][16][MM_PSTRIDE]
-	double* __restrict__ red = sh + W*16*MM_PSTRIDE;              // [2][4 NG][64]: the accumulators of a tile summed over the waves
-	int* __restrict__ s_kmin = reinterpret_cast<int*>(sh + mm_lds_doubles(NG, W));
-	const int tid = threadIdx.x, lane = tid & 63, w = PXS_UNIFORM_INT(tid >> 6);
-	int wv, m, bb;
-	if (!leg_block(a, wv, m, bb)) return;
-	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
-	const int nk = (a.lmax - m)/2 + 1;
-	const int pbase = wv*64*W;
-	const bool polar = mm_wave_polar(a, pbase + 64*(w + 1));      // (per wave: its own 64 pairs, its own coefficient stream)
-	S0Chain C;
-	const bool alive = s0_chain_init(a, pbase + tid, m, polar, C);      // wave w owns the pairs [64 w, 64 w + 64) of the chunk
-	if (tid == 0) *s_kmin = nk;
-	__syncthreads();
-	// phase A, per wave: recurrence only until the first lane of the wave is live; kw = the first step this wave contributes to
-	const bool wave_alive = __any(alive);
-	const int kw = wave_alive ? PXS_UNIFORM_INT(s0_chain_phase_a(C, a.coef + row0, polar, nk)) : nk + 16;
-	if (lane == 0) atomicMin(s_kmin, kw);
-	__syncthreads();
-	const int kmin = PXS_UNIFORM_INT(*s_kmin);
-	if (kmin >= nk) return;      // (workgroup-uniform) no ring of this chunk carries signal at this m
-	// B operands through the LDS: thread = ring pair, 4 maps per round
-	double breg[NG][16];
-	{
-		const int p = pbase + tid;
-		const bool ok = p < a.npairs;
-		const int rn = ok ? a.ring_n[p] : -1, rs = ok ? a.ring_s[p] : -1;
-		const double x = ok ? a.cth[p] : 0.0;
-		double* __restrict__ ent = sh + tid*MM_ESTRIDE;
-		const double* __restrict__ rd = sh + (64*w + 16*(lane >> 4))*MM_ESTRIDE + (lane & 15);
+	// polar waves take the table (a, a + b)
+	static __device__ __forceinline__ const double* table(const LegK& a, bool polar, long row0) { return reinterpret_cast<const double*>(polar ? a.coef2p : a.coef2) + 2*row0; }
+	// phase A (S0_PHASE_A for one chain, on the 32-byte rows of the VALU kernels): recurrence only until the first lane of the wave is live (LEG_LIVE); returns the step reached
+	static __device__ __forceinline__ int phase_a(const LegK& a, S0Chain& C, long row0, bool polar, int nk) {
+		const double4_t* __restrict__ coef = a.coef + row0;
+		int k = 0;
+		while (k + 4 <= nk) {
+			if (__any(LEG_IS_LIVE(C.lam2, C.sc))) break;
+			const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3);
+			const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b;
+			C.lam1 = fma(fma(q0.a, C.csq, b0), C.lam2, C.lam1);
+			C.lam2 = fma(fma(q1.a, C.csq, b1), C.lam1, C.lam2);
+			C.lam1 = fma(fma(q2.a, C.csq, b2), C.lam2, C.lam1);
+			C.lam2 = fma(fma(q3.a, C.csq, b3), C.lam1, C.lam2);
+			if (C.sc < 0) C.rescale();
+			k += 4;
+		}
+		return k;
+	}
+	// analysis prologue: the north and south ring values of the slot's pair in the 4 maps from map0 on, parked as (sum re, im, difference x cos theta re, im) per map
+	struct Data { double2 vn[4], vs[4]; };
+	static __device__ __forceinline__ void load(const LegK& a, int m, int map0, int rn, int rs, Data& d) {
+#pragma unroll
+		for (int mm = 0; mm < 4; mm++) {
+			const int map = map0 + mm;
+			const double2* __restrict__ in = a.leg + (long)map*a.leg_bs + (long)m*a.ld;
+			const bool okm = map < a.nmaps;
+			d.vn[mm] = (okm && rn >= 0) ? in[rn] : make_double2(0, 0); d.vs[mm] = (okm && rs >= 0) ? in[rs] : make_double2(0, 0);
+		}
+	}
+	static __device__ __forceinline__ void park(const Data& d, double x, int, double* __restrict__ ent) {
+#pragma unroll
+		for (int mm = 0; mm < 4; mm++) {
+			ent[4*mm + 0] = d.vn[mm].x + d.vs[mm].x; ent[4*mm + 1] = d.vn[mm].y + d.vs[mm].y;
+			ent[4*mm + 2] = (d.vn[mm].x - d.vs[mm].x)*x; ent[4*mm + 3] = (d.vn[mm].y - d.vs[mm].y)*x;
+		}
+	}
+	// synthesis epilogue.  Register r of acc[g][rb] at lane (i4 = lane / 16, j = lane % 16): ring pair 16 rb + 4 r + i4, column j = 4 (map in the group) + c: a lane holds
+	// one column of one ring pair, and the quad (even re, even im, odd re, odd im) is combined across lanes into the north and south ring values
+	template<int NG> static __device__ __forceinline__ void store(const LegK& a, int m, int bb, int pbase, int lane, mm_acc (&acc)[NG][4]) {
+		const int c = lane & 3;
 #pragma unroll
 		for (int g = 0; g < NG; g++) {
-			double2 vn[4], vs[4];
+			const int map = (bb*NG + g)*4 + ((lane & 15) >> 2);
+			double* __restrict__ out = reinterpret_cast<double*>(a.leg + (long)(map < a.nmaps ? map : 0)*a.leg_bs + (long)m*a.ld) + (c & 1);
 #pragma unroll
-			for (int mm = 0; mm < 4; mm++) {
-				const int map = (bb*NG + g)*4 + mm;
-				const double2* __restrict__ in = a.leg + (long)map*a.leg_bs + (long)m*a.ld;
-				const bool okm = map < a.nmaps;
-				vn[mm] = (okm && rn >= 0) ? in[rn] : make_double2(0, 0); vs[mm] = (okm && rs >= 0) ? in[rs] : make_double2(0, 0);
-			}
-			if (g > 0) __syncthreads();      // the reads of the previous round
+			for (int rb = 0; rb < 4; rb++)
 #pragma unroll
-			for (int mm = 0; mm < 4; mm++) {
-				ent[4*mm + 0] = vn[mm].x + vs[mm].x; ent[4*mm + 1] = vn[mm].y + vs[mm].y;
-				ent[4*mm + 2] = (vn[mm].x - vs[mm].x)*x; ent[4*mm + 3] = (vn[mm].y - vs[mm].y)*x;
-			}
-			__syncthreads();
-#pragma unroll
-			for (int q = 0; q < 16; q++) breg[g][q] = rd[q*MM_ESTRIDE];
-			MM_WAVE_SYNC();
+				for (int r = 0; r < 4; r++) {
+					const int p = pbase + 16*rb + 4*r + (lane >> 4);
+					const bool valid = p < a.npairs && map < a.nmaps;
+					const double v = acc[g][rb][r], o = MMS_XOR2(v);
+					const double x = valid ? a.cth[p] : 0.0;
+					// c = 0, 1: north ring, even + x odd; c = 2, 3: south ring, even - x odd (this lane holds the odd part)
+					const double val = c < 2 ? fma(x, o, v) : fma(-x, v, o);
+					const int ring = valid ? (c < 2 ? a.ring_n[p] : a.ring_s[p]) : -1;
+					if (ring >= 0) out[2*ring] = val;
+				}
 		}
-		__syncthreads();
-		for (int i = tid; i < 2*NG*4*64; i += 64*W) red[i] = 0.0;
-		__syncthreads();
 	}
-	const double* __restrict__ tab = reinterpret_cast<const double*>(polar ? a.coef2p : a.coef2) + 2*row0;      // (a, b') of step k at tab[2 k]
-	bool pend = __any(C.sc < 0);
-	double* __restrict__ pmine = ptile + w*16*MM_PSTRIDE;
-	const double* __restrict__ pread = pmine + (lane & 15)*MM_PSTRIDE + 16*(lane >> 4);
-	double cf[32]; int cf_tile = -1;      // coefficients of the 16 steps of tile cf_tile, requested a tile ahead
-	long ntile = 0;
-	auto flush = [&](int tf) { mm_flush<NG, W, false>(a, red, tf, w, lane, bb, nk, row0, 0); };
-	int tlast = -1;
-	for (int t = kmin >> 4; 16*t < nk; t++) {
-		const int k0 = 16*t;
-		double* __restrict__ redt = red + (t & 1)*NG*4*64;
-		if (k0 + 16 > kw) {      // (wave-uniform) this wave has steps in the tile
-			ntile++;
-			if (cf_tile != t) mm_load_cf(cf, tab, k0);
-			mm_park_tile<MM_PSTRIDE>(C, cf, k0, kw, nk, pend, pmine, lane);
-			MM_WAVE_SYNC();
-			double av[4];
-#pragma unroll
-			for (int q = 0; q < 4; q++) av[q] = pread[q];
-			MM_WAVE_SYNC();
-			if (k0 + 16 < nk) { mm_load_cf(cf, tab, k0 + 16); cf_tile = t + 1; }      // the rows of the next tile, on their way during the MFMAs (requested after the first A operands have landed)
-			mm_acc acc[NG];
-#pragma unroll
-			for (int g = 0; g < NG; g++) { acc[g][0] = 0; acc[g][1] = 0; acc[g][2] = 0; acc[g][3] = 0; }
-#pragma unroll
-			for (int q = 0; q < 16; q++) {
-				const double aq = q < 4 ? av[q] : pread[q];
-#pragma unroll
-				for (int g = 0; g < NG; g++) acc[g] = mm_mfma(aq, breg[g][q], acc[g]);
-			}
-			if (tlast >= 0) { flush(tlast); tlast = -1; }
-#pragma unroll
-			for (int g = 0; g < NG; g++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) mm_lds_add(redt + (g*4 + r)*64 + lane, acc[g][r]);
-		}
-		if (tlast >= 0) flush(tlast);
-		tlast = t;
-		__syncthreads();
-	}
-	if (tlast >= 0) flush(tlast);
-	PXS_COUNT(1, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
-}
+};
+template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm(const LegK a) { leg_ana_mm<S0Mm, NG, W>(a); }
 
 
 // ---- batched spin-0 synthesis as an FP64-MFMA GEMM (round 5) ----------------------------------------------------------------------
@@ -395,106 +382,14 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_s0_mm
 // loaded a tile ahead (the 32 bytes per step and map the VALU kernel takes through the scalar cache).  At the end a lane holds one
 // column of one ring pair: the quad (even re, even im, odd re, odd im) is combined across lanes into the north and south ring values.
 
-template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const LegK a)
-{
-	PXS_SHARED(double, pmine);      // [16][MMS_PSTRIDE]
-	const int lane = threadIdx.x;
-	int wv, m, bb;
-	if (!leg_block(a, wv, m, bb)) return;
-	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
-	const int nk = (a.lmax - m)/2 + 1;
-	const int pbase = wv*64;
-	const bool polar = mm_wave_polar(a, pbase + 64);
-	S0Chain C;
-	const bool alive = s0_chain_init(a, pbase + lane, m, polar, C);
-	mm_acc acc[NG][4];
-#pragma unroll
-	for (int g = 0; g < NG; g++)
-#pragma unroll
-		for (int rb = 0; rb < 4; rb++) { acc[g][rb][0] = 0; acc[g][rb][1] = 0; acc[g][rb][2] = 0; acc[g][rb][3] = 0; }
-	long ntile = 0;
-	// phase A: recurrence only until the first lane of the wave is live (a wave without a live ring skips the loop below)
-	const bool wave_alive = __any(alive);
-	const int kw = PXS_UNIFORM_INT(wave_alive ? s0_chain_phase_a(C, a.coef + row0, polar, nk) : nk + 16);      // (explicitly wave-uniform: left as a select, the loop below was compiled as divergent and the prefetched coefficient rows went to VGPRs)
-	{
-		const double* __restrict__ tab = reinterpret_cast<const double*>(polar ? a.coef2p : a.coef2) + 2*row0;      // (a, b') of step k at tab[2 k]
-		MmSynB<NG, false> B; B.init(a, bb, row0, lane, 0);
-		bool pend = __any(C.sc < 0);
-		const double* __restrict__ pread = pmine + 4*(lane >> 4)*MMS_PSTRIDE + (lane & 15);
-		double cf[32];      // coefficients of the 16 steps of the tile, requested a tile ahead (every tile from the wave's first one on is run)
-		double bcur[NG][4], bnxt[NG][4];
-		B.load(16*(kw >> 4), nk, bcur);
-		if (kw < nk) mm_load_cf(cf, tab, 16*(kw >> 4));
-		for (int t = kw >> 4; 16*t < nk; t++) {
-			const int k0 = 16*t;
-			ntile++;
-			mm_park_tile<MMS_PSTRIDE>(C, cf, k0, kw, nk, pend, pmine, lane);
-			MM_WAVE_SYNC();
-			double av[4];
-#pragma unroll
-			for (int rb = 0; rb < 4; rb++) av[rb] = pread[16*rb];
-			MM_WAVE_SYNC();
-			if (k0 + 16 < nk) { mm_load_cf(cf, tab, k0 + 16); B.load(k0 + 16, nk, bnxt); }      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
-#pragma unroll
-			for (int q = 0; q < 4; q++)
-#pragma unroll
-				for (int rb = 0; rb < 4; rb++) {
-					const double aq = q == 0 ? av[rb] : pread[q*MMS_PSTRIDE + 16*rb];
-#pragma unroll
-					for (int g = 0; g < NG; g++) acc[g][rb] = mm_mfma(aq, bcur[g][q], acc[g][rb]);
-				}
-			MM_WAVE_SYNC();      // the A operands are out of the tile before the next one is written
-#pragma unroll
-			for (int g = 0; g < NG; g++)
-#pragma unroll
-				for (int q = 0; q < 4; q++) bcur[g][q] = bnxt[g][q];
-		}
-	}
-	// register r of acc[g][rb] at lane (i4 = lane / 16, j = lane % 16): ring pair 16 rb + 4 r + i4, column j = 4 (map in the group) + c
-	const int c = lane & 3;
-#pragma unroll
-	for (int g = 0; g < NG; g++) {
-		const int map = (bb*NG + g)*4 + ((lane & 15) >> 2);
-		double* __restrict__ out = reinterpret_cast<double*>(a.leg + (long)(map < a.nmaps ? map : 0)*a.leg_bs + (long)m*a.ld) + (c & 1);
-#pragma unroll
-		for (int rb = 0; rb < 4; rb++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				const int p = pbase + 16*rb + 4*r + (lane >> 4);
-				const bool valid = p < a.npairs && map < a.nmaps;
-				const double v = acc[g][rb][r], o = MMS_XOR2(v);
-				const double x = valid ? a.cth[p] : 0.0;
-				// c = 0, 1: north ring, even + x odd; c = 2, 3: south ring, even - x odd (this lane holds the odd part)
-				const double val = c < 2 ? fma(x, o, v) : fma(-x, v, o);
-				const int ring = valid ? (c < 2 ? a.ring_n[p] : a.ring_s[p]) : -1;
-				if (ring >= 0) out[2*ring] = val;
-			}
-	}
-	PXS_COUNT(0, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
-}
+template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const LegK a) { leg_syn_mm<S0Mm, NG>(a); }
 
-// ---- launchers ----
-void launch_leg_syn_s0(int K, dim3 grid, hipStream_t st, const LegK& a) {
-	// (ring pairs per lane the host's rules select: 4 and 2)
-	if (K == 2) hipLaunchKernelGGL(leg_syn_s0<2>, grid, dim3(64), 0, st, a);
-	else        hipLaunchKernelGGL(leg_syn_s0<4>, grid, dim3(64), 0, st, a);
-}
-void launch_leg_ana_s0(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a) {
-	if (K == 8)      hipLaunchKernelGGL(leg_ana_s0<8>, grid, dim3(64), lds, st, a);
-	else if (K == 2) hipLaunchKernelGGL(leg_ana_s0<2>, grid, dim3(64), lds, st, a);
-	else             hipLaunchKernelGGL(leg_ana_s0<4>, grid, dim3(64), lds, st, a);
-}
-void launch_leg_syn_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a) {
-	if (ng == 2) hipLaunchKernelGGL(leg_syn_s0_mm<2>, grid, dim3(64), mm_syn_lds(), st, a);
-	else         hipLaunchKernelGGL(leg_syn_s0_mm<1>, grid, dim3(64), mm_syn_lds(), st, a);
-}
-// (waves per workgroup measured at C4: 2 waves 95 ms, 4: 78, 8: 77, 16: 82 per 64 maps)
-void launch_leg_ana_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a) {
-	constexpr int W = MM_WAVES;
-	static const bool once = [] { (void)hipFuncSetAttribute((const void*)leg_ana_s0_mm<2, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-		(void)hipFuncSetAttribute((const void*)leg_ana_s0_mm<1, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }(); (void)once;
-	if (ng == 2) hipLaunchKernelGGL((leg_ana_s0_mm<2, W>), grid, dim3(64*W), mm_ana_lds(2, W), st, a);
-	else         hipLaunchKernelGGL((leg_ana_s0_mm<1, W>), grid, dim3(64*W), mm_ana_lds(1, W), st, a);
+// ---- launches: the kernel of (direction, form, K or ng); the ring pairs per lane the host's rules select are 4 and 2 (synthesis), 8, 4 and 2 (analysis) ----
+void launch_leg_s0(bool analysis, int ng, int K, dim3 grid, hipStream_t st, const LegK& a) {
+	static const bool once = leg_mm_lds_optin({leg_ana_s0_mm<2, MM_WAVES>, leg_ana_s0_mm<1, MM_WAVES>}); (void)once;
+	const LegKernel k = analysis ? (ng == 2 ? leg_ana_s0_mm<2, MM_WAVES> : ng ? leg_ana_s0_mm<1, MM_WAVES> : K == 8 ? leg_ana_s0<8> : K == 2 ? leg_ana_s0<2> : leg_ana_s0<4>)
+	                             : (ng == 2 ? leg_syn_s0_mm<2> : ng ? leg_syn_s0_mm<1> : K == 2 ? leg_syn_s0<2> : leg_syn_s0<4>);
+	leg_launch(k, analysis, ng, grid, st, a);
 }
 
 } // namespace pxs

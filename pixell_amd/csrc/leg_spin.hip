@@ -56,7 +56,14 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 	return alive_any;
 }
 
-// phase A of the spin kernels (see S0_PHASE_A): 4 steps per rescale / activity test; sgn is unchanged by 4 steps
+// The two VALU kernels below write the phase skeleton (seeds, phases A / B / C) out, with four macros, as leg_syn_s0 / leg_ana_s0 do (leg_s0.hip).  One driver
+// with the chain state and the accumulators as policies was built for the four and taken out again.  The spin-0 synthesis on it lost its 52 bytes of scratch and was
+// 7 % slower all the same (profiles/README.md).  These two
+// on that driver fit the same registers (96 / 69 VGPRs synthesis, 152 / 124 / 96 analysis, no scratch) but computed the values of these kernels to rounding only: in
+// phase A the compiler contracts a x + c into one FMA or leaves multiply and add apart depending on the basic block the addition ends up in, and for which slots
+// it does so follows the code around the loop, not the expression (here: the G- chain of one slot unfused, on the driver of two).  Bit for bit is what a
+// refactor owes, and no way of writing the expression pins the compiler's choice to the present one.  Change the two copies together.
+// phase A of the spin kernels: 4 steps per rescale / activity test; sgn is unchanged by 4 steps
 #define SPIN_PHASE_A \
 	while (j + 4 <= nl) { \
 		bool act = false; \
@@ -73,6 +80,25 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 			if (S.scm[s] < 0 && fabs(S.gm2[s]) > SC_BIG) { S.gm1[s] *= SC_SMALL; S.gm2[s] *= SC_SMALL; S.scm[s]++; } \
 		} \
 		j += 4; \
+	}
+
+// phase A with the recurrence seeds (legendre_dev.hpp): mode 2 loads the state and the step reached, mode 1 records them after running phase A
+#define SPIN_SEEDED_PHASE_A \
+	if (a.seed_mode == 2) { \
+		const double* sd = a.seed_d + ((long)m*a.nwave + wv)*(4*K*64); const int* si = a.seed_i + ((long)m*a.nwave + wv)*((2*K+1)*64); \
+		j = PXS_UNIFORM_INT(si[2*K*64]); \
+		_Pragma("unroll") for (int s = 0; s < K; s++) { \
+			S.gp1[s] = sd[s*64 + lane]; S.gp2[s] = sd[(K+s)*64 + lane]; S.gm1[s] = sd[(2*K+s)*64 + lane]; S.gm2[s] = sd[(3*K+s)*64 + lane]; \
+			S.scp[s] = si[s*64 + lane]; S.scm[s] = si[(K+s)*64 + lane]; } \
+	} else { \
+		SPIN_PHASE_A \
+		if (a.seed_mode == 1) { \
+			double* sd = a.seed_d + ((long)m*a.nwave + wv)*(4*K*64); int* si = a.seed_i + ((long)m*a.nwave + wv)*((2*K+1)*64); \
+			_Pragma("unroll") for (int s = 0; s < K; s++) { \
+				sd[s*64 + lane] = S.gp1[s]; sd[(K+s)*64 + lane] = S.gp2[s]; sd[(2*K+s)*64 + lane] = S.gm1[s]; sd[(3*K+s)*64 + lane] = S.gm2[s]; \
+				si[s*64 + lane] = S.scp[s]; si[(K+s)*64 + lane] = S.scm[s]; } \
+			if (lane == 0) si[2*K*64] = j; \
+		} \
 	}
 
 // (step coefficient a x +- b as one FMA with the additive constant copied to a VGPR once per step -- gfx950 allows one
@@ -352,261 +378,117 @@ struct SpinChain {
 		p[0] *= se; p[1] *= so; p[2] *= se; p[3] *= so;
 	}
 };
-__device__ __forceinline__ bool spin_chain_init(const LegK& a, int p, int m, int half, bool polar, SpinChain& C) {
-	const int s_ = a.spin;
-	const bool valid = p < a.npairs;
-	const double cth = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0, shh = valid ? a.sh2[p] : 0.0;
-	C.x = polar ? -2.0*shh*shh : cth; C.sgl = half ? -1.0 : 1.0; C.pa = polar ? 1.0 : 0.0; C.half = half; C.par = max(m, s_) + m;
-	const double t1 = a.lmax*sth + a.ofs, b = -2.0*s_*fabs(cth), c = (double)s_*s_ - t1*t1, discr = b*b - 4*c;      // (libsharp's m-limit generalised to spin, as spin_init)
-	const double mlim = discr <= 0 ? a.lmax : fmin((double)a.lmax, 0.5*(-b + sqrt(discr)));
-	const bool alive = valid && ((double)m <= mlim + 0.5);
-	C.g1 = 0; C.g2 = 0; C.sc = 0;
-	if (alive) {
-		const double sh = shh, ch = a.ch2[p];
-		double m1, m2; int e1, e2;
-		// exponents of sin(theta/2), cos(theta/2) of the start value: G+ (m + s, m - s) / G- (m - s, m + s) for m >= s, (s + m, s - m) / (s - m, s + m) below
-		const int es = m >= s_ ? (half ? m - s_ : m + s_) : (half ? s_ - m : s_ + m), ec = m >= s_ ? (half ? m + s_ : m - s_) : (half ? s_ + m : s_ - m);
-		pow_scaled(sh, es, m1, e1); pow_scaled(ch, ec, m2, e2);
-		double mt = m1*m2; int e = e1 + e2 + (m >= s_ ? m : 0); frexp_norm(mt, e); to_scaled(mt, e, C.g2, C.sc);
-		if (m < s_ && half && ((s_ - m) & 1)) C.g2 = -C.g2;
+// the spin-s side of leg_ana_mm / leg_syn_mm (legendre_dev.hpp): one chain per half-wave, 32 ring pairs per wave; the polar form is folded into the chain (SpinChain::coef)
+struct SpinMm {
+	typedef SpinChain Chain;
+	static constexpr int SLOTS = 32;
+	static constexpr bool SIGNED = true;
+	static constexpr bool BREG_SYNC = false;      // (the spin-0 analysis has one: kept as it was, kernel by kernel)
+	static __device__ __forceinline__ int steps(const LegK& a, int m, int& par) { const int l0 = max(m, a.spin); par = l0 + m; return a.lmax - l0 + 1; }
+	static __device__ __forceinline__ bool init(const LegK& a, int p, int m, int half, bool polar, SpinChain& C) {
+		const int s_ = a.spin;
+		const bool valid = p < a.npairs;
+		const double cth = valid ? a.cth[p] : 0.0, sth = valid ? a.sth[p] : 0.0, shh = valid ? a.sh2[p] : 0.0;
+		C.x = polar ? -2.0*shh*shh : cth; C.sgl = half ? -1.0 : 1.0; C.pa = polar ? 1.0 : 0.0; C.half = half; C.par = max(m, s_) + m;
+		const double t1 = a.lmax*sth + a.ofs, b = -2.0*s_*fabs(cth), c = (double)s_*s_ - t1*t1, discr = b*b - 4*c;      // (libsharp's m-limit generalised to spin, as spin_init)
+		const double mlim = discr <= 0 ? a.lmax : fmin((double)a.lmax, 0.5*(-b + sqrt(discr)));
+		const bool alive = valid && ((double)m <= mlim + 0.5);
+		C.g1 = 0; C.g2 = 0; C.sc = 0;
+		if (alive) {
+			const double sh = shh, ch = a.ch2[p];
+			double m1, m2; int e1, e2;
+			// exponents of sin(theta/2), cos(theta/2) of the start value: G+ (m + s, m - s) / G- (m - s, m + s) for m >= s, (s + m, s - m) / (s - m, s + m) below
+			const int es = m >= s_ ? (half ? m - s_ : m + s_) : (half ? s_ - m : s_ + m), ec = m >= s_ ? (half ? m + s_ : m - s_) : (half ? s_ + m : s_ - m);
+			pow_scaled(sh, es, m1, e1); pow_scaled(ch, ec, m2, e2);
+			double mt = m1*m2; int e = e1 + e2 + (m >= s_ ? m : 0); frexp_norm(mt, e); to_scaled(mt, e, C.g2, C.sc);
+			if (m < s_ && half && ((s_ - m) & 1)) C.g2 = -C.g2;
+		}
+		return alive;
 	}
-	return alive;
-}
-// phase A: recurrence only until the first lane of the wave is live (LEG_LIVE); returns the step reached (tab: (a, b) of step k at tab[2 k])
-__device__ __forceinline__ int spin_chain_phase_a(SpinChain& C, const double* __restrict__ tab, int n) {
-	int k = 0;
-	while (k + 4 <= n) {
-		if (__any(LEG_IS_LIVE(C.g2, C.sc))) break;
-		double cq[8];
+	static __device__ __forceinline__ const double* table(const LegK& a, bool, long row0) { return reinterpret_cast<const double*>(a.coef2) + 2*row0; }
+	// phase A on the compact table: recurrence only until the first lane of the wave is live (LEG_LIVE); returns the step reached
+	static __device__ __forceinline__ int phase_a(const LegK& a, SpinChain& C, long row0, bool polar, int n) {
+		const double* __restrict__ tab = table(a, polar, row0);
+		int k = 0;
+		while (k + 4 <= n) {
+			if (__any(LEG_IS_LIVE(C.g2, C.sc))) break;
+			double cq[8];
 #pragma unroll
-		for (int i = 0; i < 8; i++) cq[i] = LDCD(tab, 2L*k + i);
+			for (int i = 0; i < 8; i++) cq[i] = LDCD(tab, 2L*k + i);
 #pragma unroll
-		for (int i = 0; i < 4; i++) C.step(cq[2*i], cq[2*i + 1]);
-		if (C.sc < 0) C.rescale();
-		k += 4;
+			for (int i = 0; i < 4; i++) C.step(cq[2*i], cq[2*i + 1]);
+			if (C.sc < 0) C.rescale();
+			k += 4;
+		}
+		return k;
 	}
-	return k;
-}
-
-template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_mm(const LegK a)
-{
-	PXS_SHARED(double, sh);
-	double* __restrict__ ptile = sh;                              // [W][16][MM_PSTRIDE]
-	double* __restrict__ red = sh + W*16*MM_PSTRIDE;              // [2][4 NG][64]
-	int* __restrict__ s_kmin = reinterpret_cast<int*>(sh + mm_lds_doubles(NG, W));
-	const int tid = threadIdx.x, lane = tid & 63, w = PXS_UNIFORM_INT(tid >> 6), half = lane >> 5;
-	int wv, m, bb;
-	if (!leg_block(a, wv, m, bb)) return;
-	const int l0 = max(m, a.spin);
-	const int nl = a.lmax - l0 + 1;
-	if (nl <= 0) return;
-	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
-	const int pbase = wv*32*W;
-	const bool polar = mm_wave_polar(a, pbase + 32*(w + 1));      // (per wave)
-	const int pmine_ = pbase + 32*w + (lane & 31);       // ring pair of this lane's chain
-	SpinChain C;
-	const bool alive = spin_chain_init(a, pmine_, m, half, polar, C);
-	const double* __restrict__ tab = reinterpret_cast<const double*>(a.coef2) + 2*row0;      // (a, b) of step k at tab[2 k]
-	if (tid == 0) *s_kmin = nl;
-	__syncthreads();
-	// phase A, per wave: recurrence only until the first lane of the wave is live
-	const bool wave_alive = __any(alive);
-	const int kw = PXS_UNIFORM_INT(wave_alive ? spin_chain_phase_a(C, tab, nl) : nl + 16);
-	if (lane == 0) atomicMin(s_kmin, kw);
-	__syncthreads();
-	const int kmin = PXS_UNIFORM_INT(*s_kmin);
-	if (kmin >= nl) return;      // (workgroup-uniform) no ring of this chunk carries signal at this m
-	// B operands through the LDS: thread = slot (chain of a ring pair), 4 maps per round: G+ slots (T+_N re, im, T-_S re, im), G- slots (T+_S re, im, T-_N re, im)
-	double breg[NG][16];
-	{
-		const bool ok = pmine_ < a.npairs;
-		const int rn = ok ? a.ring_n[pmine_] : -1, rs = ok ? a.ring_s[pmine_] : -1;
-		double* __restrict__ ent = sh + tid*MM_ESTRIDE;
-		const double* __restrict__ rd = sh + (64*w + 16*(lane >> 4))*MM_ESTRIDE + (lane & 15);
+	// analysis prologue: Q and U of the north and south rings of the slot's pair in the 4 maps from map0 on, parked per map as (T+_N re, im, T-_S re, im) on the G+
+	// slots and (T+_S re, im, T-_N re, im) on the G- slots; T+ = Q + iU, T- = Q - iU
+	struct Data { double2 qn[4], un[4], qs[4], us[4]; };
+	static __device__ __forceinline__ void load(const LegK& a, int m, int map0, int rn, int rs, Data& d) {
+#pragma unroll
+		for (int mm = 0; mm < 4; mm++) {
+			const int map = map0 + mm;
+			const double2* __restrict__ inq = a.leg + (long)map*a.leg_bs + (long)m*a.ld;
+			const double2* __restrict__ inu = a.leg + (long)map*a.leg_bs + ((long)a.nm + m)*a.ld;
+			const bool okm = map < a.nmaps;
+			d.qn[mm] = (okm && rn >= 0) ? inq[rn] : make_double2(0, 0); d.un[mm] = (okm && rn >= 0) ? inu[rn] : make_double2(0, 0);
+			d.qs[mm] = (okm && rs >= 0) ? inq[rs] : make_double2(0, 0); d.us[mm] = (okm && rs >= 0) ? inu[rs] : make_double2(0, 0);
+		}
+	}
+	static __device__ __forceinline__ void park(const Data& d, double, int half, double* __restrict__ ent) {
+#pragma unroll
+		for (int mm = 0; mm < 4; mm++) {
+			const double tpn_r = d.qn[mm].x - d.un[mm].y, tpn_i = d.qn[mm].y + d.un[mm].x, tmn_r = d.qn[mm].x + d.un[mm].y, tmn_i = d.qn[mm].y - d.un[mm].x;
+			const double tps_r = d.qs[mm].x - d.us[mm].y, tps_i = d.qs[mm].y + d.us[mm].x, tms_r = d.qs[mm].x + d.us[mm].y, tms_i = d.qs[mm].y - d.us[mm].x;
+			ent[4*mm + 0] = half ? tps_r : tpn_r; ent[4*mm + 1] = half ? tps_i : tpn_i;
+			ent[4*mm + 2] = half ? tmn_r : tms_r; ent[4*mm + 3] = half ? tmn_i : tms_i;
+		}
+	}
+	// synthesis epilogue.  Register r of acc[g][rb] at lane (i4 = lane / 16, jc = lane % 16): slot 16 rb + 4 r + i4 (rb < 2: G+ of ring pair 16 rb + 4 r + i4, rb >= 2: G- of pair
+	// 16 (rb - 2) + 4 r + i4), column 4 (map in the group) + c.  G+ rows: c = 0, 1: P re / im (north); 2, 3: M' re / im (south).  G- rows: c = 0, 1: P' re / im
+	// (south); 2, 3: M re / im (north).  Q = (P + M) / 2, U = -i (P - M) / 2: lanes c < 2 write the north ring, lanes c >= 2 the south ring; even c the
+	// real part of Q and the imaginary part of U, odd c the other two.
+	template<int NG> static __device__ __forceinline__ void store(const LegK& a, int m, int bb, int pbase, int lane, mm_acc (&acc)[NG][4]) {
+		const int c = lane & 3;
 #pragma unroll
 		for (int g = 0; g < NG; g++) {
-			double2 qn[4], un[4], qs[4], us[4];
+			const int map = (bb*NG + g)*4 + ((lane & 15) >> 2);
+			double* __restrict__ outq = reinterpret_cast<double*>(a.leg + (long)(map < a.nmaps ? map : 0)*a.leg_bs + (long)m*a.ld);
+			double* __restrict__ outu = reinterpret_cast<double*>(a.leg + (long)(map < a.nmaps ? map : 0)*a.leg_bs + ((long)a.nm + m)*a.ld);
 #pragma unroll
-			for (int mm = 0; mm < 4; mm++) {
-				const int map = (bb*NG + g)*4 + mm;
-				const double2* __restrict__ inq = a.leg + (long)map*a.leg_bs + (long)m*a.ld;
-				const double2* __restrict__ inu = a.leg + (long)map*a.leg_bs + ((long)a.nm + m)*a.ld;
-				const bool okm = map < a.nmaps;
-				qn[mm] = (okm && rn >= 0) ? inq[rn] : make_double2(0, 0); un[mm] = (okm && rn >= 0) ? inu[rn] : make_double2(0, 0);
-				qs[mm] = (okm && rs >= 0) ? inq[rs] : make_double2(0, 0); us[mm] = (okm && rs >= 0) ? inu[rs] : make_double2(0, 0);
-			}
-			if (g > 0) __syncthreads();      // the reads of the previous round
+			for (int rb = 0; rb < 2; rb++)
 #pragma unroll
-			for (int mm = 0; mm < 4; mm++) {
-				// T+ = Q + iU, T- = Q - iU
-				const double tpn_r = qn[mm].x - un[mm].y, tpn_i = qn[mm].y + un[mm].x, tmn_r = qn[mm].x + un[mm].y, tmn_i = qn[mm].y - un[mm].x;
-				const double tps_r = qs[mm].x - us[mm].y, tps_i = qs[mm].y + us[mm].x, tms_r = qs[mm].x + us[mm].y, tms_i = qs[mm].y - us[mm].x;
-				ent[4*mm + 0] = half ? tps_r : tpn_r; ent[4*mm + 1] = half ? tps_i : tpn_i;
-				ent[4*mm + 2] = half ? tmn_r : tms_r; ent[4*mm + 3] = half ? tmn_i : tms_i;
-			}
-			__syncthreads();
-#pragma unroll
-			for (int q = 0; q < 16; q++) breg[g][q] = rd[q*MM_ESTRIDE];
+				for (int r = 0; r < 4; r++) {
+					const int p = pbase + 16*rb + 4*r + (lane >> 4);
+					const bool valid = p < a.npairs && map < a.nmaps;
+					const double own = acc[g][rb][r], oth = MMS_XOR2(acc[g][rb + 2][r]);
+					const double P = c < 2 ? own : oth, M = c < 2 ? oth : own;
+					const double sum = 0.5*(P + M), dif = 0.5*(P - M);
+					const int ring = valid ? (c < 2 ? a.ring_n[p] : a.ring_s[p]) : -1;
+					if (ring >= 0) {
+						if (c & 1) { outq[2*ring + 1] = sum; outu[2*ring] = dif; }
+						else       { outq[2*ring] = sum; outu[2*ring + 1] = -dif; }
+					}
+				}
 		}
-		__syncthreads();
-		for (int i = tid; i < 2*NG*4*64; i += 64*W) red[i] = 0.0;
-		__syncthreads();
 	}
-	bool pend = __any(C.sc < 0);
-	double* __restrict__ pmine = ptile + w*16*MM_PSTRIDE;
-	const double* __restrict__ pread = pmine + (lane & 15)*MM_PSTRIDE + 16*(lane >> 4);
-	double cf[32];      // (a, b) of the 16 steps of a tile, requested a tile ahead
-	int cf_tile = -1;
-	long ntile = 0;
-	auto flush = [&](int tf) { mm_flush<NG, W, true>(a, red, tf, w, lane, bb, nl, row0, l0 + m); };
-	int tlast = -1;
-	for (int t = kmin >> 4; 16*t < nl; t++) {
-		const int k0 = 16*t;
-		double* __restrict__ redt = red + (t & 1)*NG*4*64;
-		if (k0 + 16 > kw) {      // (wave-uniform) this wave has steps in the tile
-			ntile++;
-			if (cf_tile != t) mm_load_cf(cf, tab, k0);
-			mm_park_tile<MM_PSTRIDE>(C, cf, k0, kw, nl, pend, pmine, lane);
-			MM_WAVE_SYNC();
-			double av[4];
-#pragma unroll
-			for (int q = 0; q < 4; q++) av[q] = pread[q];
-			MM_WAVE_SYNC();
-			if (k0 + 16 < nl) { mm_load_cf(cf, tab, k0 + 16); cf_tile = t + 1; }
-			mm_acc acc[NG];
-#pragma unroll
-			for (int g = 0; g < NG; g++) { acc[g][0] = 0; acc[g][1] = 0; acc[g][2] = 0; acc[g][3] = 0; }
-#pragma unroll
-			for (int q = 0; q < 16; q++) {
-				const double aq = q < 4 ? av[q] : pread[q];
-#pragma unroll
-				for (int g = 0; g < NG; g++) acc[g] = mm_mfma(aq, breg[g][q], acc[g]);
-			}
-			if (tlast >= 0) { flush(tlast); tlast = -1; }
-#pragma unroll
-			for (int g = 0; g < NG; g++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) mm_lds_add(redt + (g*4 + r)*64 + lane, acc[g][r]);
-		}
-		if (tlast >= 0) flush(tlast);
-		tlast = t;
-		__syncthreads();
-	}
-	if (tlast >= 0) flush(tlast);
-	PXS_COUNT(1, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
-}
+};
+template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_mm(const LegK a) { leg_ana_mm<SpinMm, NG, W>(a); }
 
 // ---- batched spin-s synthesis as an FP64-MFMA GEMM (round 5) ----------------------------------------------------------------------
 // The transpose of leg_ana_spin_mm (cf. leg_syn_spin): north  P = sum_l G+ a+, M = sum_l G- a-;  south  P' = sum_l sgn_l G- a+, M' = sum_l sgn_l G+ a-.
 // One chain per half-wave as in the analysis: the 64 rows of a wave's accumulators are the G+ slots of 32 ring pairs (row blocks 0, 1) and their
 // G- slots (row blocks 2, 3); the G- lanes park sgn_l G-, and with B = (a+, sgn_l a-) -- ONE B for all rows -- the G+ rows come out as (P, M') and the G-
 // rows as (P', M).  The shape of leg_syn_s0_mm: one P tile, 4 x 8 accumulator VGPRs per group of 4 maps, one wave per workgroup, no cross-wave step.
-template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const LegK a)
-{
-	PXS_SHARED(double, pmine);      // [16][MMS_PSTRIDE]
-	const int lane = threadIdx.x, half = lane >> 5;
-	int wv, m, bb;
-	if (!leg_block(a, wv, m, bb)) return;
-	const int l0 = max(m, a.spin);
-	const int nl = a.lmax - l0 + 1;
-	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
-	const int pbase = wv*32;
-	const bool polar = mm_wave_polar(a, pbase + 32);
-	SpinChain C;
-	const bool alive = spin_chain_init(a, pbase + (lane & 31), m, half, polar, C);
-	mm_acc acc[NG][4];
-#pragma unroll
-	for (int g = 0; g < NG; g++)
-#pragma unroll
-		for (int rb = 0; rb < 4; rb++) { acc[g][rb][0] = 0; acc[g][rb][1] = 0; acc[g][rb][2] = 0; acc[g][rb][3] = 0; }
-	long ntile = 0;
-	const double* __restrict__ tab = reinterpret_cast<const double*>(a.coef2) + 2*row0;      // (a, b) of step k at tab[2 k]
-	// phase A: recurrence only until the first lane of the wave is live (a wave without a live ring skips the loop below)
-	const bool wave_alive = nl > 0 && __any(alive);
-	const int kw = PXS_UNIFORM_INT(wave_alive ? spin_chain_phase_a(C, tab, nl) : max(nl, 0) + 16);
-	{
-		MmSynB<NG, true> B; B.init(a, bb, row0, lane, l0 + m);      // (a+ re, a+ im, sgn_l a- re, sgn_l a- im)
-		bool pend = __any(C.sc < 0);
-		const double* __restrict__ pread = pmine + 4*(lane >> 4)*MMS_PSTRIDE + (lane & 15);
-		double cf[32];      // (a, b) of the 16 steps of the tile, requested a tile ahead (every tile from the wave's first one on is run)
-		double bcur[NG][4], bnxt[NG][4];
-		B.load(16*(kw >> 4), nl, bcur);
-		if (kw < nl) mm_load_cf(cf, tab, 16*(kw >> 4));
-		for (int t = kw >> 4; 16*t < nl; t++) {
-			const int k0 = 16*t;
-			ntile++;
-			mm_park_tile<MMS_PSTRIDE>(C, cf, k0, kw, nl, pend, pmine, lane);
-			MM_WAVE_SYNC();
-			double av[4];
-#pragma unroll
-			for (int rb = 0; rb < 4; rb++) av[rb] = pread[16*rb];
-			MM_WAVE_SYNC();
-			if (k0 + 16 < nl) { mm_load_cf(cf, tab, k0 + 16); B.load(k0 + 16, nl, bnxt); }      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
-#pragma unroll
-			for (int q = 0; q < 4; q++)
-#pragma unroll
-				for (int rb = 0; rb < 4; rb++) {
-					const double aq = q == 0 ? av[rb] : pread[q*MMS_PSTRIDE + 16*rb];
-#pragma unroll
-					for (int g = 0; g < NG; g++) acc[g][rb] = mm_mfma(aq, bcur[g][q], acc[g][rb]);
-				}
-			MM_WAVE_SYNC();      // the A operands are out of the tile before the next one is written
-#pragma unroll
-			for (int g = 0; g < NG; g++)
-#pragma unroll
-				for (int q = 0; q < 4; q++) bcur[g][q] = bnxt[g][q];
-		}
-	}
-	// register r of acc[g][rb] at lane (i4 = lane / 16, jc = lane % 16): slot 16 rb + 4 r + i4 (rb < 2: G+ of ring pair 16 rb + 4 r + i4, rb >= 2: G- of pair
-	// 16 (rb - 2) + 4 r + i4), column 4 (map in the group) + c.  G+ rows: c = 0, 1: P re / im (north); 2, 3: M' re / im (south).  G- rows: c = 0, 1: P' re / im
-	// (south); 2, 3: M re / im (north).  Q = (P + M) / 2, U = -i (P - M) / 2: lanes c < 2 write the north ring, lanes c >= 2 the south ring; even c the
-	// real part of Q and the imaginary part of U, odd c the other two.
-	const int c = lane & 3;
-#pragma unroll
-	for (int g = 0; g < NG; g++) {
-		const int map = (bb*NG + g)*4 + ((lane & 15) >> 2);
-		double* __restrict__ outq = reinterpret_cast<double*>(a.leg + (long)(map < a.nmaps ? map : 0)*a.leg_bs + (long)m*a.ld);
-		double* __restrict__ outu = reinterpret_cast<double*>(a.leg + (long)(map < a.nmaps ? map : 0)*a.leg_bs + ((long)a.nm + m)*a.ld);
-#pragma unroll
-		for (int rb = 0; rb < 2; rb++)
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				const int p = pbase + 16*rb + 4*r + (lane >> 4);
-				const bool valid = p < a.npairs && map < a.nmaps;
-				const double own = acc[g][rb][r], oth = MMS_XOR2(acc[g][rb + 2][r]);
-				const double P = c < 2 ? own : oth, M = c < 2 ? oth : own;
-				const double sum = 0.5*(P + M), dif = 0.5*(P - M);
-				const int ring = valid ? (c < 2 ? a.ring_n[p] : a.ring_s[p]) : -1;
-				if (ring >= 0) {
-					if (c & 1) { outq[2*ring + 1] = sum; outu[2*ring] = dif; }
-					else       { outq[2*ring] = sum; outu[2*ring + 1] = -dif; }
-				}
-			}
-	}
-	PXS_COUNT(0, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
-}
+template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const LegK a) { leg_syn_mm<SpinMm, NG>(a); }
 
-// ---- launchers ----
-void launch_leg_syn_spin(int K, dim3 grid, hipStream_t st, const LegK& a) {
-	// (ring pairs per lane the host's rules select: 3 and 2 for the synthesis, 4, 3 and 2 for the analysis)
-	if (K == 3) hipLaunchKernelGGL(leg_syn_spin<3>, grid, dim3(64), 0, st, a);
-	else        hipLaunchKernelGGL(leg_syn_spin<2>, grid, dim3(64), 0, st, a);
-}
-void launch_leg_ana_spin(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a) {
-	if (K >= 4)      hipLaunchKernelGGL(leg_ana_spin<4>, grid, dim3(64), lds, st, a);
-	else if (K == 3) hipLaunchKernelGGL(leg_ana_spin<3>, grid, dim3(64), lds, st, a);
-	else             hipLaunchKernelGGL(leg_ana_spin<2>, grid, dim3(64), lds, st, a);
-}
-void launch_leg_syn_spin_mm(int ng, dim3 grid, hipStream_t st, const LegK& a) {
-	if (ng == 2) hipLaunchKernelGGL(leg_syn_spin_mm<2>, grid, dim3(64), mm_syn_lds(), st, a);
-	else         hipLaunchKernelGGL(leg_syn_spin_mm<1>, grid, dim3(64), mm_syn_lds(), st, a);
-}
-void launch_leg_ana_spin_mm(int ng, dim3 grid, hipStream_t st, const LegK& a) {
-	constexpr int W = MM_WAVES;
-	static const bool once = [] { (void)hipFuncSetAttribute((const void*)leg_ana_spin_mm<2, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-		(void)hipFuncSetAttribute((const void*)leg_ana_spin_mm<1, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256); return true; }(); (void)once;
-	if (ng == 2) hipLaunchKernelGGL((leg_ana_spin_mm<2, W>), grid, dim3(64*W), mm_ana_lds(2, W), st, a);
-	else         hipLaunchKernelGGL((leg_ana_spin_mm<1, W>), grid, dim3(64*W), mm_ana_lds(1, W), st, a);
+// ---- launches: the kernel of (direction, form, K or ng); the ring pairs per lane the host's rules select are 3 and 2 (synthesis), 4, 3 and 2 (analysis) ----
+void launch_leg_spin(bool analysis, int ng, int K, dim3 grid, hipStream_t st, const LegK& a) {
+	static const bool once = leg_mm_lds_optin({leg_ana_spin_mm<2, MM_WAVES>, leg_ana_spin_mm<1, MM_WAVES>}); (void)once;
+	const LegKernel k = analysis ? (ng == 2 ? leg_ana_spin_mm<2, MM_WAVES> : ng ? leg_ana_spin_mm<1, MM_WAVES> : K >= 4 ? leg_ana_spin<4> : K == 3 ? leg_ana_spin<3> : leg_ana_spin<2>)
+	                             : (ng == 2 ? leg_syn_spin_mm<2> : ng ? leg_syn_spin_mm<1> : K == 3 ? leg_syn_spin<3> : leg_syn_spin<2>);
+	leg_launch(k, analysis, ng, grid, st, a);
 }
 
 } // namespace pxs

@@ -23,8 +23,13 @@
 //    v_permlane32_swap / v_permlane16_swap, one ds_write_b64 per step parks them in a tile of 16 steps; at a flush lane j owns
 //    output j, adds its 16 partial sums and the wave issues one contiguous 512-byte global_atomic_add_f64 into the moments
 //    (PXS_DETERMINISTIC=1: per-wave partial moments summed in wave order by reduce_partials instead).
-// Translation units: this file holds the host side (tables, seeds, dispatch), the alm pre / post kernels and the table kernels; leg_s0.hip and leg_spin.hip the
-// Legendre kernels themselves, legendre_dev.hpp what they share.
+// Translation units: this file holds the host side (tables, seeds, dispatch), the alm pre / post kernels and the table kernels.  legendre_dev.hpp holds the
+// code of the kernels that does not depend on spin or direction: the pair map, the reduction tile, and leg_ana_mm<Sys, NG, W> / leg_syn_mm<Sys, NG>, the one
+// analysis and the one synthesis body of the four MFMA kernels.  leg_s0.hip and leg_spin.hip hold the 18 kernel instantiations and what differs between the MFMA
+// kernels, as the policies S0Mm / SpinMm (chain, phase A, table, slots per wave, the parked ring data, the synthesis epilogue).  The four VALU kernels (leg_syn_s0,
+// leg_ana_s0, leg_syn_spin, leg_ana_spin) each write the phase skeleton out, with the macros S0_* / SPIN_* at the head of their file: one driver with policies was
+// built for them and is not here (leg_spin.hip and profiles/README.md say why) -- change the four copies together.  launch_leg_s0 / launch_leg_spin pick the
+// kernel of (direction, form, K or ng).
 #include "legendre_dev.hpp"
 #include <thread>
 #include <memory>
@@ -681,8 +686,7 @@ void leg_synthesis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWo
 		LegWork::Seeds* sb = nullptr;
 		if (!l.ng) { sb = seeds_for(wk, rs, tb, 0, K, a); seeds_wait(sb, st); }
 		if (prof) prof->begin(st, 0);
-		if (tb.spin == 0) { if (l.ng) launch_leg_syn_s0_mm(l.ng, leg_grid(a), st, a); else launch_leg_syn_s0(K, leg_grid(a), st, a); }
-		else              { if (l.ng) launch_leg_syn_spin_mm(l.ng, leg_grid(a), st, a); else launch_leg_syn_spin(K, leg_grid(a), st, a); }
+		(tb.spin == 0 ? launch_leg_s0 : launch_leg_spin)(false, l.ng, K, leg_grid(a), st, a);
 		if (prof) prof->end(st, 0);
 		seeds_written(sb, st);
 	}
@@ -716,7 +720,6 @@ static void leg_analysis_valu(hipStream_t st, const RingSet& rs, const LegTables
 		for (size_t c = 0; c+1 < cuts.size(); c++) maxm = std::max<size_t>(maxm, (size_t)(cuts[c+1]-cuts[c]));
 		wk.first.ensure(sizeof(int)*(size_t)nwave*maxm);
 	}
-	const size_t sh = sizeof(double)*LEG_RED_DOUBLES;
 	LegWork::Seeds* seeds = nullptr;
 	for (size_t c = 0; c+1 < cuts.size(); c++) {
 		const int m0 = cuts[c], m1 = cuts[c+1];
@@ -732,8 +735,7 @@ static void leg_analysis_valu(hipStream_t st, const RingSet& rs, const LegTables
 		}
 		if (prof) prof->begin(st, 1);
 		const dim3 grid = leg_grid(a);
-		if (tb.spin == 0) launch_leg_ana_s0(K, grid, sh, st, a);
-		else              launch_leg_ana_spin(K, grid, sh, st, a);
+		(tb.spin == 0 ? launch_leg_s0 : launch_leg_spin)(true, 0, K, grid, st, a);
 		if (prof) prof->end(st, 1);
 		if (atomic) continue;
 		const long maxrow = tb.row[m0+1] - tb.row[m0];       // rows per m shrink with m
@@ -766,8 +768,7 @@ void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWor
 		LegK a = make_legk_mm(rs, tb, wk, const_cast<double2*>(legl), ld, mm_pairs, l.n, l.ng, leg_bstride);
 		a.mom = mom; a.part = mom; a.atomic = 1;
 		if (prof) prof->begin(st, 1);
-		if (tb.spin == 0) launch_leg_ana_s0_mm(l.ng, leg_grid(a), st, a);
-		else              launch_leg_ana_spin_mm(l.ng, leg_grid(a), st, a);
+		(tb.spin == 0 ? launch_leg_s0 : launch_leg_spin)(true, l.ng, K, leg_grid(a), st, a);
 		if (prof) prof->end(st, 1);
 	}
 	AlmK ak = make_almk(tb, wk, alm, alm_dtype, alm_cstride, d_mstart, lstride, deriv1, alm_bstride);

@@ -46,7 +46,7 @@ struct LegWork {     // scratch owned by the SHT plan
 	DevBuf part;     // [nwave][nrows][4] doubles (analysis partial moments)
 	DevBuf mom;      // [nrows][4] reduced moments
 	DevBuf first;    // [nwave][m chunk] int: 1 + first row a wave wrote for that m (0: the wave had no live ring and wrote nothing)
-	// recurrence seeds (legendre_dev.hpp, S0_SEEDED_PHASE_A): one set per (ring set, spin, direction, K), recorded by the first launch
+	// recurrence seeds (S0_SEEDED_PHASE_A, leg_s0.hip; SPIN_SEEDED_PHASE_A, leg_spin.hip): one set per (ring set, spin, direction, K), recorded by the first launch
 	struct Seeds { DevBuf d, i; bool ready = false, refused = false; hipEvent_t written = nullptr; hipStream_t wstream = nullptr;
 	               ~Seeds() { if (written) (void)hipEventDestroy(written); } };
 	std::map<std::tuple<const void*, int, int, int>, Seeds> seeds;

@@ -1,10 +1,13 @@
 // Device-side pieces shared by the Legendre translation units (legendre.hip: host side, alm kernels, tables; leg_s0.hip: spin-0 kernels;
-// leg_spin.hip: spin-s kernels): kernel arguments, block -> (m, ring chunk) order, extended-exponent helpers, the phase-A macros, the
-// lane-sum reduction tile of the VALU analysis kernels and the MFMA helpers of the batched kernels.  Design notes: head of legendre.hip.
+// leg_spin.hip: spin-s kernels): kernel arguments, block -> (m, ring chunk) order, extended-exponent helpers, the pair map, the lane-sum
+// reduction tile of the VALU analysis kernels, the MFMA helpers and the two bodies of the four batched kernels (leg_ana_mm, leg_syn_mm; the
+// spin-0 / spin-s side is a policy defined next to the kernels) and the launch helper.  The four VALU kernels keep a copy of the phase skeleton
+// each, held together by the macros at the head of leg_s0.hip and leg_spin.hip (leg_spin.hip says why).  Design notes: head of legendre.hip.
 #pragma once
 #include "legendre.hpp"
 #include <cmath>
 #include <algorithm>
+#include <initializer_list>
 
 namespace pxs {
 
@@ -183,6 +186,16 @@ __device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { r
 #define PXS_VCOPY(dst, src) double dst; asm("v_mov_b64 %0, %1" : "=v"(dst) : "s"(src))
 #endif
 
+// a per-lane value the compiler has to take as new at this point.  The synthesis epilogue of the MFMA kernels takes its lane through it: computed from the lane
+// itself, its map index was shared with the one of the B operands (MmSynB::init) and kept through the tile loop as sign-extended 64-bit values, which
+// leg_syn_spin_mm<2>, at the 128-VGPR line, paid with 36 bytes of scratch (24 before there was one body; none with this)
+#ifdef PXS_HOST_SIM
+#define PXS_FRESH_INT(x) (x)
+#else
+__device__ __forceinline__ int pxs_fresh_int(int x) { asm("" : "+v"(x)); return x; }
+#define PXS_FRESH_INT(x) pxs_fresh_int(x)
+#endif
+
 // (An L2 prefetch of the coefficient streams via global_load_lds into an LDS sink was tried to hide SMEM
 // miss latency and measured SLOWER on MI355X: leg_syn 10.8 -> 12.4 ms at config 2; removed.)
 
@@ -201,58 +214,7 @@ __device__ __forceinline__ int leg_pair_u(const LegK& a, int wv, int K, int s, i
 // Recurrence seeds.  Phase A (recurrence only, no accumulation, until the first lane of the wave is live, LEG_LIVE) is the same
 // for every transform on a plan: ~18 % of the steps of a live (wave, m) at a third of the cost of an accumulating step, i.e.
 // ~5 % of the Legendre time, plus the sin^m start values.  The first launch on a ring set records the state it ends in, later
-// launches load it: K x 20 bytes (spin 0) or K x 40 bytes (spin s) per lane.
-#define S0_SEEDED_PHASE_A \
-	if (a.seed_mode == 2) { \
-		const double* sd = a.seed_d + ((long)m*a.nwave + wv)*(2*K*64); const int* si = a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64); \
-		k = PXS_UNIFORM_INT(si[K*64]); \
-		_Pragma("unroll") for (int s = 0; s < K; s++) { lam1[s] = sd[s*64 + lane]; lam2[s] = sd[(K+s)*64 + lane]; sc[s] = si[s*64 + lane]; } \
-	} else { \
-		S0_PHASE_A \
-		if (a.seed_mode == 1) { \
-			double* sd = a.seed_d + ((long)m*a.nwave + wv)*(2*K*64); int* si = a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64); \
-			_Pragma("unroll") for (int s = 0; s < K; s++) { sd[s*64 + lane] = lam1[s]; sd[(K+s)*64 + lane] = lam2[s]; si[s*64 + lane] = sc[s]; } \
-			if (lane == 0) si[K*64] = k; \
-		} \
-	}
-#define SPIN_SEEDED_PHASE_A \
-	if (a.seed_mode == 2) { \
-		const double* sd = a.seed_d + ((long)m*a.nwave + wv)*(4*K*64); const int* si = a.seed_i + ((long)m*a.nwave + wv)*((2*K+1)*64); \
-		j = PXS_UNIFORM_INT(si[2*K*64]); \
-		_Pragma("unroll") for (int s = 0; s < K; s++) { \
-			S.gp1[s] = sd[s*64 + lane]; S.gp2[s] = sd[(K+s)*64 + lane]; S.gm1[s] = sd[(2*K+s)*64 + lane]; S.gm2[s] = sd[(3*K+s)*64 + lane]; \
-			S.scp[s] = si[s*64 + lane]; S.scm[s] = si[(K+s)*64 + lane]; } \
-	} else { \
-		SPIN_PHASE_A \
-		if (a.seed_mode == 1) { \
-			double* sd = a.seed_d + ((long)m*a.nwave + wv)*(4*K*64); int* si = a.seed_i + ((long)m*a.nwave + wv)*((2*K+1)*64); \
-			_Pragma("unroll") for (int s = 0; s < K; s++) { \
-				sd[s*64 + lane] = S.gp1[s]; sd[(K+s)*64 + lane] = S.gp2[s]; sd[(2*K+s)*64 + lane] = S.gm1[s]; sd[(3*K+s)*64 + lane] = S.gm2[s]; \
-				si[s*64 + lane] = S.scp[s]; si[(K+s)*64 + lane] = S.scm[s]; } \
-			if (lane == 0) si[2*K*64] = j; \
-		} \
-	}
-
-// Phase A of the spin-0 kernels: no lane of the wave is live yet (scale 0 and |value| >= LEG_LIVE), so nothing is
-// accumulated.  Four recurrence steps per iteration with the four coefficient rows fetched together;
-// the rescale / activity test runs once per 4 steps (a chain grows by < 2^60 in 4 steps, far from
-// overflow at 2^1024; what the late start drops: see LEG_LIVE).
-#define S0_PHASE_A \
-	while (k + 4 <= nk) { \
-		bool act = false; \
-		_Pragma("unroll") for (int s = 0; s < K; s++) act |= LEG_IS_LIVE(lam2[s], sc[s]); \
-		if (__any(act)) break; \
-		const double4_t q0 = LDC(coef, k), q1 = LDC(coef, k+1), q2 = LDC(coef, k+2), q3 = LDC(coef, k+3); \
-		const double b0 = polar ? q0.c : q0.b, b1 = polar ? q1.c : q1.b, b2 = polar ? q2.c : q2.b, b3 = polar ? q3.c : q3.b; \
-		_Pragma("unroll") for (int s = 0; s < K; s++) { \
-			lam1[s] = fma(fma(q0.a, csq[s], b0), lam2[s], lam1[s]); \
-			lam2[s] = fma(fma(q1.a, csq[s], b1), lam1[s], lam2[s]); \
-			lam1[s] = fma(fma(q2.a, csq[s], b2), lam2[s], lam1[s]); \
-			lam2[s] = fma(fma(q3.a, csq[s], b3), lam1[s], lam2[s]); \
-			if (sc[s] < 0 && fabs(lam2[s]) > SC_BIG) { lam1[s] *= SC_SMALL; lam2[s] *= SC_SMALL; sc[s]++; } \
-		} \
-		k += 4; \
-	}
+// launches load it: K x 20 bytes (spin 0) or K x 40 bytes (spin s) per lane (S0_SEEDED_PHASE_A, leg_s0.hip; SPIN_SEEDED_PHASE_A, leg_spin.hip).
 
 // Phase B history: it used to be a per-step loop with per-lane gating (cndmask) and a rescale test in every step:
 // 207 instructions per step for leg_ana_spin<6> against 97 per step in the fast loop, ~18 % of the kernel time in a
@@ -480,14 +442,183 @@ __device__ __forceinline__ double mms_xor2(double v) {      // value of lane ^ 2
 #define MMS_XOR2(v) mms_xor2(v)
 #endif
 
-// launchers (defined next to the kernels; K = ring pairs per lane, ng = groups of 4 maps per wave / workgroup)
-void launch_leg_syn_s0(int K, dim3 grid, hipStream_t st, const LegK& a);
-void launch_leg_ana_s0(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a);
-void launch_leg_syn_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);
-void launch_leg_ana_s0_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);
-void launch_leg_syn_spin(int K, dim3 grid, hipStream_t st, const LegK& a);
-void launch_leg_ana_spin(int K, dim3 grid, size_t lds, hipStream_t st, const LegK& a);
-void launch_leg_syn_spin_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);
-void launch_leg_ana_spin_mm(int ng, dim3 grid, hipStream_t st, const LegK& a);
+// ---- the MFMA kernels: one analysis body, one synthesis body ----
+// leg_ana_mm<Sys, NG, W> is the body of leg_ana_s0_mm / leg_ana_spin_mm, leg_syn_mm<Sys, NG> that of leg_syn_s0_mm / leg_syn_spin_mm; Sys = S0Mm (leg_s0.hip)
+// or SpinMm (leg_spin.hip) supplies
+//   Chain, init(a, p, m, half, polar, C): the chain of a slot and its start value;  SLOTS: ring pairs per wave (64, or 32 pairs x 2 half-wave chains);
+//   steps(a, m, par): step count of the m and the parity of its first step (spin s; a count <= 0 ends the kernel or leaves the wave idle);
+//   table(a, polar, row0): the compact step table (a, b') the tiles read;  phase_a(a, C, row0, polar, n): phase A, returns the step reached;
+//   SIGNED: the last two columns carry sgn_l (MmSynB, mm_flush);
+//   Data, load(...), park(...): the 16 doubles a thread parks per slot and group of 4 maps in the analysis prologue, BREG_SYNC: a wave sync after the B registers
+//   of a group are read;  store<NG>(...): the synthesis epilogue.
+template<class Sys, int NG, int W> __device__ __forceinline__ void leg_ana_mm(const LegK& a)
+{
+	PXS_SHARED(double, sh);
+	double* __restrict__ ptile = sh;                              // [W][16][MM_PSTRIDE]
+	double* __restrict__ red = sh + W*16*MM_PSTRIDE;              // [2][4 NG][64]: the accumulators of a tile summed over the waves
+	int* __restrict__ s_kmin = reinterpret_cast<int*>(sh + mm_lds_doubles(NG, W));
+	const int tid = threadIdx.x, lane = tid & 63, w = PXS_UNIFORM_INT(tid >> 6), half = lane/Sys::SLOTS;
+	int wv, m, bb;
+	if (!leg_block(a, wv, m, bb)) return;
+	int par;
+	const int n = Sys::steps(a, m, par);
+	if (n <= 0) return;
+	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
+	const int pbase = wv*Sys::SLOTS*W;
+	const bool polar = mm_wave_polar(a, pbase + Sys::SLOTS*(w + 1));      // (per wave: its own pairs, its own coefficient stream)
+	const int pmine_ = pbase + Sys::SLOTS*w + (lane & (Sys::SLOTS - 1));       // ring pair of this lane's chain: wave w owns the pairs [SLOTS w, SLOTS (w + 1)) of the chunk
+	typename Sys::Chain C;
+	const bool alive = Sys::init(a, pmine_, m, half, polar, C);
+	if (tid == 0) *s_kmin = n;
+	__syncthreads();
+	// phase A, per wave: recurrence only until the first lane of the wave is live; kw = the first step this wave contributes to
+	const bool wave_alive = __any(alive);
+	const int kw = PXS_UNIFORM_INT(wave_alive ? Sys::phase_a(a, C, row0, polar, n) : n + 16);
+	if (lane == 0) atomicMin(s_kmin, kw);
+	__syncthreads();
+	const int kmin = PXS_UNIFORM_INT(*s_kmin);
+	if (kmin >= n) return;      // (workgroup-uniform) no ring of this chunk carries signal at this m
+	// B operands through the LDS: thread = slot (a chain of a ring pair), 4 maps per round
+	double breg[NG][16];
+	{
+		const bool ok = pmine_ < a.npairs;
+		const int rn = ok ? a.ring_n[pmine_] : -1, rs = ok ? a.ring_s[pmine_] : -1;
+		const double x = ok ? a.cth[pmine_] : 0.0;
+		double* __restrict__ ent = sh + tid*MM_ESTRIDE;
+		const double* __restrict__ rd = sh + (64*w + 16*(lane >> 4))*MM_ESTRIDE + (lane & 15);
+#pragma unroll
+		for (int g = 0; g < NG; g++) {
+			typename Sys::Data d;
+			Sys::load(a, m, (bb*NG + g)*4, rn, rs, d);
+			if (g > 0) __syncthreads();      // the reads of the previous round
+			Sys::park(d, x, half, ent);
+			__syncthreads();
+#pragma unroll
+			for (int q = 0; q < 16; q++) breg[g][q] = rd[q*MM_ESTRIDE];
+			if (Sys::BREG_SYNC) MM_WAVE_SYNC();
+		}
+		__syncthreads();
+		for (int i = tid; i < 2*NG*4*64; i += 64*W) red[i] = 0.0;
+		__syncthreads();
+	}
+	const double* __restrict__ tab = Sys::table(a, polar, row0);      // (a, b') of step k at tab[2 k]
+	bool pend = __any(C.sc < 0);
+	double* __restrict__ pmine = ptile + w*16*MM_PSTRIDE;
+	const double* __restrict__ pread = pmine + (lane & 15)*MM_PSTRIDE + 16*(lane >> 4);
+	double cf[32]; int cf_tile = -1;      // coefficients of the 16 steps of tile cf_tile, requested a tile ahead
+	long ntile = 0;
+	auto flush = [&](int tf) { mm_flush<NG, W, Sys::SIGNED>(a, red, tf, w, lane, bb, n, row0, par); };
+	int tlast = -1;
+	for (int t = kmin >> 4; 16*t < n; t++) {
+		const int k0 = 16*t;
+		double* __restrict__ redt = red + (t & 1)*NG*4*64;
+		if (k0 + 16 > kw) {      // (wave-uniform) this wave has steps in the tile
+			ntile++;
+			if (cf_tile != t) mm_load_cf(cf, tab, k0);
+			mm_park_tile<MM_PSTRIDE>(C, cf, k0, kw, n, pend, pmine, lane);
+			MM_WAVE_SYNC();
+			double av[4];
+#pragma unroll
+			for (int q = 0; q < 4; q++) av[q] = pread[q];
+			MM_WAVE_SYNC();
+			if (k0 + 16 < n) { mm_load_cf(cf, tab, k0 + 16); cf_tile = t + 1; }      // the rows of the next tile, on their way during the MFMAs (requested after the first A operands have landed)
+			mm_acc acc[NG];
+#pragma unroll
+			for (int g = 0; g < NG; g++) { acc[g][0] = 0; acc[g][1] = 0; acc[g][2] = 0; acc[g][3] = 0; }
+#pragma unroll
+			for (int q = 0; q < 16; q++) {
+				const double aq = q < 4 ? av[q] : pread[q];
+#pragma unroll
+				for (int g = 0; g < NG; g++) acc[g] = mm_mfma(aq, breg[g][q], acc[g]);
+			}
+			if (tlast >= 0) { flush(tlast); tlast = -1; }
+#pragma unroll
+			for (int g = 0; g < NG; g++)
+#pragma unroll
+				for (int r = 0; r < 4; r++) mm_lds_add(redt + (g*4 + r)*64 + lane, acc[g][r]);
+		}
+		if (tlast >= 0) flush(tlast);
+		tlast = t;
+		__syncthreads();
+	}
+	if (tlast >= 0) flush(tlast);
+	PXS_COUNT(1, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
+}
+
+template<class Sys, int NG> __device__ __forceinline__ void leg_syn_mm(const LegK& a)
+{
+	PXS_SHARED(double, pmine);      // [16][MMS_PSTRIDE]
+	const int lane = threadIdx.x, half = lane/Sys::SLOTS;
+	int wv, m, bb;
+	if (!leg_block(a, wv, m, bb)) return;
+	int par;
+	const int n = Sys::steps(a, m, par);
+	const long row0 = PXS_UNIFORM_LONG(a.row[m]);
+	const int pbase = wv*Sys::SLOTS;
+	const bool polar = mm_wave_polar(a, pbase + Sys::SLOTS);
+	typename Sys::Chain C;
+	const bool alive = Sys::init(a, pbase + (lane & (Sys::SLOTS - 1)), m, half, polar, C);
+	mm_acc acc[NG][4];
+#pragma unroll
+	for (int g = 0; g < NG; g++)
+#pragma unroll
+		for (int rb = 0; rb < 4; rb++) { acc[g][rb][0] = 0; acc[g][rb][1] = 0; acc[g][rb][2] = 0; acc[g][rb][3] = 0; }
+	long ntile = 0;
+	// phase A: recurrence only until the first lane of the wave is live (a wave without a live ring skips the loop below)
+	const bool wave_alive = n > 0 && __any(alive);
+	const int kw = PXS_UNIFORM_INT(wave_alive ? Sys::phase_a(a, C, row0, polar, n) : max(n, 0) + 16);      // (explicitly wave-uniform: left as a select, the loop below was compiled as divergent and the prefetched coefficient rows went to VGPRs)
+	{
+		const double* __restrict__ tab = Sys::table(a, polar, row0);      // (a, b') of step k at tab[2 k]
+		MmSynB<NG, Sys::SIGNED> B; B.init(a, bb, row0, lane, par);
+		bool pend = __any(C.sc < 0);
+		const double* __restrict__ pread = pmine + 4*(lane >> 4)*MMS_PSTRIDE + (lane & 15);
+		double cf[32];      // coefficients of the 16 steps of the tile, requested a tile ahead (every tile from the wave's first one on is run)
+		double bcur[NG][4], bnxt[NG][4];
+		B.load(16*(kw >> 4), n, bcur);
+		if (kw < n) mm_load_cf(cf, tab, 16*(kw >> 4));
+		for (int t = kw >> 4; 16*t < n; t++) {
+			const int k0 = 16*t;
+			ntile++;
+			mm_park_tile<MMS_PSTRIDE>(C, cf, k0, kw, n, pend, pmine, lane);
+			MM_WAVE_SYNC();
+			double av[4];
+#pragma unroll
+			for (int rb = 0; rb < 4; rb++) av[rb] = pread[16*rb];
+			MM_WAVE_SYNC();
+			if (k0 + 16 < n) { mm_load_cf(cf, tab, k0 + 16); B.load(k0 + 16, n, bnxt); }      // the rows of the next tile (coefficients and pre-scaled alm), on their way during the MFMAs
+#pragma unroll
+			for (int q = 0; q < 4; q++)
+#pragma unroll
+				for (int rb = 0; rb < 4; rb++) {
+					const double aq = q == 0 ? av[rb] : pread[q*MMS_PSTRIDE + 16*rb];
+#pragma unroll
+					for (int g = 0; g < NG; g++) acc[g][rb] = mm_mfma(aq, bcur[g][q], acc[g][rb]);
+				}
+			MM_WAVE_SYNC();      // the A operands are out of the tile before the next one is written
+#pragma unroll
+			for (int g = 0; g < NG; g++)
+#pragma unroll
+				for (int q = 0; q < 4; q++) bcur[g][q] = bnxt[g][q];
+		}
+	}
+	Sys::template store<NG>(a, m, bb, pbase, PXS_FRESH_INT(lane), acc);      // (the epilogue's map index and addresses are computed here, after the loop)
+	PXS_COUNT(0, ntile*(NG*256L + 32L) + (wave_alive ? (long)kw*2 : 0L));
+}
+
+// ---- launches ----
+// the kernel of (direction, form, K or ng) is picked next to the kernels (launch_leg_s0, launch_leg_spin); ng: groups of 4 maps per wave / workgroup (0: VALU form)
+typedef void (*LegKernel)(const LegK);
+// (waves per workgroup of the MFMA analysis measured at C4: 2 waves 95 ms, 4: 78, 8: 77, 16: 82 per 64 maps)
+static inline bool leg_mm_lds_optin(std::initializer_list<LegKernel> ks) {
+	for (LegKernel k : ks) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
+	return true;
+}
+static inline void leg_launch(LegKernel k, bool analysis, int ng, dim3 grid, hipStream_t st, const LegK& a) {
+	const int W = analysis && ng ? MM_WAVES : 1;
+	const size_t lds = ng ? (analysis ? mm_ana_lds(ng, MM_WAVES) : mm_syn_lds()) : analysis ? sizeof(double)*LEG_RED_DOUBLES : 0;
+	hipLaunchKernelGGL(k, grid, dim3(64*W), lds, st, a);
+}
+void launch_leg_s0(bool analysis, int ng, int K, dim3 grid, hipStream_t st, const LegK& a);
+void launch_leg_spin(bool analysis, int ng, int K, dim3 grid, hipStream_t st, const LegK& a);
 
 } // namespace pxs

@@ -14,6 +14,9 @@ GPU: lmax + 2 equidistant rings at lmax 2900 = 1451 ring pairs, above k_small_gr
 leg_syn_spin<3>, leg_ana_spin<4>); 1451 = 7 192 + 107 = 5 256 + 171 = 2 512 + 427: the first wave is part padding for K = 3, 4 and 8.
 Host simulator (PXS_K_SMALL_OFF=1, as test_grid_default_k_hostsim): fewer than 64 pairs (one wave, K - 1 blocks of padding only), 64 K + 5 pairs for
 the kernel's K (wave 0 holds 5 pairs), and a ring set crowded towards the poles at lmax 160 whose blocks of 64 pairs go live at different steps.
+Both: 768 ring pairs (200 over theta in [0.01, 1.2], 568 over [1.25, pi/2 - 0.005]) under k_small_grid's own rules, the one shape that takes the spin analysis to
+K = 3 (the first wave of K = 4 ends at pair 255, not polar-eligible; that of K = 3 at pair 191, eligible), the scalar analysis to K = 4 and both syntheses to
+K = 2 between 513 and 1400 pairs: leg_ana_spin<3>, leg_ana_s0<4>, leg_syn_s0<2>, leg_syn_spin<2>.
 Every reference is computed once per session and shared."""
 import functools
 import numpy as np
@@ -63,6 +66,11 @@ def crowded(npairs, tmin=2e-3):
 	tn = tmin*((np.pi/2-0.01)/tmin)**(np.arange(npairs)/(npairs-1.0))
 	return np.concatenate([tn, (np.pi-tn)[::-1]])
 
+def mid768():
+	"""768 ring pairs: 200 over theta in [0.01, 1.2], 568 over [1.25, pi/2 - 0.005], and their mirror images"""
+	tn = np.concatenate([np.linspace(0.01, 1.2, 200), np.linspace(1.25, np.pi/2-0.005, 568)])
+	return np.concatenate([tn, (np.pi-tn)[::-1]])
+
 def masked_alm(lmax, spin, mmin, seed=6):
 	"""Gaussian alm with nothing below m = mmin: its map is tiny on the polar rings"""
 	alm = so.rand_alm_simple(lmax, 1 if spin == 0 else 2, seed, spin=(spin,))
@@ -79,7 +87,8 @@ def single_alm(lmax, spin):
 def case(kind, lmax, nr, spin, mmin=0):
 	"""ring set, Gaussian alm (nothing below mmin) and its port map on the subset; a Gaussian map supported on the subset and its port adjoint synthesis"""
 	nc = 1 if spin == 0 else 2
-	th = equidistant(nr) if kind == "eq" else crowded(nr//2)
+	th = equidistant(nr) if kind == "eq" else mid768() if kind == "mid" else crowded(nr//2)
+	assert len(th) == nr
 	sub = subset(nr, extra=np.arange(0, nr//2, 3) if kind == "crowded" else ())
 	alm = masked_alm(lmax, spin, mmin)
 	ref = port_syn(alm, spin, lmax, th[sub])
@@ -120,11 +129,11 @@ def check_tiny(out, ref, sub, need):
 # ---- GPU: 1451 ring pairs, the default-K kernels ----
 GPU_LMAX = 2900
 
-def body_seeded(spin, ordered, monkeypatch):
+def body_seeded(spin, ordered, monkeypatch, c=None):
 	"""synthesis and adjoint synthesis against the port; the calls repeated on the same plan, so that the first records the seeds and the later ones
 	load them (mode 2), and a plan without seeds: as test_sht_parity.check_seeds, bit for bit (the adjoint in the ordered mode; with atomic adds it
 	repeats to rounding, 1e-14 rms as test_deterministic_mode_gpu has it)"""
-	c = case("eq", GPU_LMAX, GPU_LMAX+2, spin)
+	if c is None: c = case("eq", GPU_LMAX, GPU_LMAX+2, spin)
 	def run(): return [(run_syn(c), run_adj(c)) for rep in range(3)]
 	monkeypatch.setattr(sht, "_deterministic", ordered); monkeypatch.setenv("PXS_SEED_MIN_LMAX", "0"); sht.clear_plans()
 	try:
@@ -192,3 +201,22 @@ def test_blocks_go_live_apart_hostsim(default_k, spin):
 	c = case("crowded", 160, 600, spin, mmin=40)
 	check_tiny(run_syn(c), c["ref"], c["sub"], 2.0**-140)
 	check_case(c, what=("adj",))
+
+# ---- 768 ring pairs: the mid-grid kernels under k_small_grid's own rules (no PXS_K_SMALL_OFF) ----
+def body_mid(spin, ordered, lmax, monkeypatch):
+	c = case("mid", lmax, 1536, spin)
+	cos2 = np.cos(c["th"][:768])**2
+	# K = 4: 3 full waves, wave 0 ends at pair 255, not polar-eligible; K = 3: 4 full waves, wave 0 ends at pair 191, eligible (PXS_POLAR_COS2 = 0.1)
+	assert cos2[255] < 0.1 and cos2[191] > 0.1, "the ring set does not take the spin analysis to K = 3"
+	monkeypatch.delenv("PXS_K_SMALL_OFF", raising=False); sht.clear_plans()
+	body_seeded(spin, ordered, monkeypatch, c)
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spin", [0, 2])
+@pytest.mark.parametrize("ordered", [False, True])
+def test_mid_grid_kernels_gpu(spin, ordered, monkeypatch): body_mid(spin, ordered, 400, monkeypatch)
+
+@pytest.mark.hostsim
+@pytest.mark.parametrize("spin", [0, 2])
+@pytest.mark.parametrize("ordered", [False, True])
+def test_mid_grid_kernels_hostsim(spin, ordered, monkeypatch): body_mid(spin, ordered, 48, monkeypatch)
