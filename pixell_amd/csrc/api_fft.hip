@@ -176,7 +176,7 @@ static void fft_axis(FftContext& fc, hipStream_t st, long n, bool forward, std::
 }
 
 // nlines dense complex lines of n points each, in -> out (may alias), any n (Bluestein where the mixed-radix engine has no
-// factorisation): the ring FFTs of ring sets with per-ring lengths (sht.hip, general rings)
+// factorisation): the ring FFTs of ring sets with per-ring lengths (sht_general.hip)
 void fft_dense_lines(int device, hipStream_t st, long n, bool forward, long nlines, const double2* in, double2* out) {
 	if (nlines <= 0 || n <= 0) return;
 	if (n == 1) { if (in != out) PXS_HIP(hipMemcpyAsync(out, in, sizeof(double2)*(size_t)nlines, hipMemcpyDeviceToDevice, st)); return; }

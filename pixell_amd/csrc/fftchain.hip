@@ -888,7 +888,6 @@ static double modulus_pref(long g) { return 1.0 + 0.02*std::max(0.0, std::log2((
 ThetaPlan FftChain::plan_theta(long N, int lmax) {
 	ThetaPlan best; double bestc = 1e300;
 	static const long gforce = [] { const char* e = lab_getenv("PXS_THETA_G"); return e ? atol(e) : 0L; }();     // experiments: force the shared modulus
-	static const bool ducc_size = [] { const char* e = lab_getenv("PXS_THETA_DUCC_NCC"); return e ? atoi(e) != 0 : true; }();     // 0: the planner's own N_cc only (rounds 1-3)
 	const long Nd = ducc_ncc(lmax);
 	auto consider = [&](long g, long ac) {
 		ThetaPlan t; t.N = N; t.g = g; t.bN = N/g; t.ac = ac; t.Ncc = g*ac;
@@ -907,16 +906,16 @@ ThetaPlan FftChain::plan_theta(long N, int lmax) {
 		// (the fine-CC form: middle circle of 2 N_cc points) and of the synthesis move, each over the fill of its tiles, with a slight
 		// preference among equals for moduli of 64 ... 160 (modulus_pref).
 		// ducc0's own N_cc wins whenever some g realises it: the fine-CC form of the analysis then cuts the theta spectrum of a map
-		// that is not band-limited where ducc0 does (sht.hip, ana_set), and it is the smallest size ducc0 considers good.
+		// that is not band-limited where ducc0 does (sht.hip, ana_form), and it is the smallest size ducc0 considers good.
 		const double lmin = 2.0*lmax + 2, M2 = 2.0*t.Ncc;
 		const double ana = (2.0*N + 2.0*M2 + 1.5*t.Ncc)/tile_fill(g) + (N + M2)/tile_fill(std::max(t.bN, 2*t.ac)) + (M2 + t.Ncc)/tile_fill(2*t.ac);
 		double c = 60.0*(t.Ncc - lmin)/lmin + (ana*modulus_pref(g) + gsc)/(3.0*N + 4.0*M2 + 2.5*t.Ncc + 3.0*t.Ncc + 2.5*N);
-		if (ducc_size && t.Ncc == Nd) c -= 1000.0;
+		if (t.Ncc == Nd) c -= 1000.0;
 		if (c < bestc) { bestc = c; best = t; best.ok = true; }
 	};
 	for (long g = 2; g <= 1024 && g <= N/2; g++) if (N % g == 0 && sub_ok7(g) && sub_ok7(N/g) && (!gforce || g == gforce)) {
 		consider(g, smooth_at_least((2L*lmax + 2 + g - 1)/g, true, g));
-		if (ducc_size && Nd % g == 0) consider(g, Nd/g);
+		if (Nd % g == 0) consider(g, Nd/g);
 	}
 	return best;
 }
@@ -1064,15 +1063,15 @@ static int theta_comp_chunk(int nc, size_t need1_per_comp, size_t need2_per_comp
 	return (int)std::max<size_t>(1, std::min<size_t>((size_t)nc, budget/std::max<size_t>(per, 1)));
 }
 // points per component that a theta chain keeps in s1_ (n1) and s2_ (n2): the largest of the intermediates its builders put there
-static void theta_need(const ThetaPlan& tp, int nm, int kind, size_t& n1, size_t& n2) {
+static void theta_need(ThetaOp op, const ThetaPlan& tp, int nm, size_t& n1, size_t& n2) {
 	const size_t npair = (size_t)(nm + 1)/2;
-	if (kind == 0)      { n1 = npair*std::max(tp.g*FftChain::pad8(tp.bN), tp.g*FftChain::pad8(tp.g2)); n2 = npair*std::max(tp.g2*FftChain::pad8(tp.g), tp.ac*FftChain::pad8(tp.g)); }   // to_cc
-	else if (kind == 1) { n1 = npair*tp.g*FftChain::pad8(tp.bN); n2 = npair*tp.ac*FftChain::pad8(tp.g); }                                                    // from_cc_adjoint
-	else if (kind == 2) { n1 = npair*tp.gs*FftChain::pad8(tp.bs); n2 = npair*tp.aNs*FftChain::pad8(tp.gs); }                                                  // from_cc
-	else                { n1 = npair*std::max(tp.g*FftChain::pad8(tp.ac), tp.g*FftChain::pad8(tp.g2)); n2 = npair*std::max(tp.g2*FftChain::pad8(tp.g), tp.bN*FftChain::pad8(tp.g)); }   // to_cc_adjoint
+	if (op == TH_TO_CC) { n1 = npair*std::max(tp.g*FftChain::pad8(tp.bN), tp.g*FftChain::pad8(tp.g2)); n2 = npair*std::max(tp.g2*FftChain::pad8(tp.g), tp.ac*FftChain::pad8(tp.g)); }
+	else if (op == TH_FROM_CC_ADJ) { n1 = npair*tp.g*FftChain::pad8(tp.bN); n2 = npair*tp.ac*FftChain::pad8(tp.g); }
+	else if (op == TH_FROM_CC) { n1 = npair*tp.gs*FftChain::pad8(tp.bs); n2 = npair*tp.aNs*FftChain::pad8(tp.gs); }
+	else { n1 = npair*std::max(tp.g*FftChain::pad8(tp.ac), tp.g*FftChain::pad8(tp.g2)); n2 = npair*std::max(tp.g2*FftChain::pad8(tp.g), tp.bN*FftChain::pad8(tp.g)); }
 }
-void FftChain::theta_scratch(const ThetaPlan& tp, int nm, int nc, int kind, size_t& b1, size_t& b2) {
-	size_t n1, n2; theta_need(tp, nm, kind, n1, n2);
+void FftChain::theta_scratch(ThetaOp op, const ThetaPlan& tp, int nm, int nc, size_t& b1, size_t& b2) {
+	size_t n1, n2; theta_need(op, tp, nm, n1, n2);
 	const int cc = theta_comp_chunk(nc, n1, n2);
 	b1 = sizeof(double2)*n1*cc; b2 = sizeof(double2)*n2*cc;
 }
@@ -1081,35 +1080,38 @@ void FftChain::ring_scratch(long nring, int nc, bool analysis, size_t& b1, int m
 	const long npair = (nring + 1)/2, a = analysis ? ra_.a : rs_.a, b = analysis ? ra_.b : rs_.b;
 	b1 = sizeof(double2)*(size_t)nc*npair*a*pad8(b);       // (ring_chunk only shrinks it)
 }
-// the loop of a theta chain (kind as in theta_scratch) over the component chunks that fit its scratch: stages(c0, ncl) runs the chain for
+// the loop of a theta chain over the component chunks that fit its scratch: stages(c0, ncl) runs the chain for
 // the ncl components from c0 on.
 // All components of a chunk go through each stage in ONE launch (outer index = component * npair + pair; batched maps are
 // components here): 64 maps of 5400 rings are 5 launches of ~150 000 workgroups instead of 320 of ~10 000 with their tails.
-template<class F> void FftChain::theta_chunks(const ThetaPlan& tp, int nm, int nc, int kind, F&& stages) {
-	size_t n1, n2; theta_need(tp, nm, kind, n1, n2);
+template<class F> void FftChain::theta_chunks(ThetaOp op, const ThetaCall& c, F&& stages) {
+	const int nc = c.nc; size_t n1, n2; theta_need(op, *c.tp, c.nm, n1, n2);
 	const int cchunk = theta_comp_chunk(nc, n1, n2);
 	ensure1(sizeof(double2)*n1*cchunk); ensure2(sizeof(double2)*n2*cchunk);
 	for (int c0 = 0; c0 < nc; c0 += cchunk) stages(c0, (long)std::min(cchunk, nc - c0));
 	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
-void FftChain::to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
-                     int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* wcc)
-{
-	if (dry_ ? line_takes(tp, true) : line_analysis(st, tp, true, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, sigma, wcc, nullptr)) return;
-	const long npair = (nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
-	const double2* ph = ph_shift;
+// The four stage lists.  c.map is leg on the map's rings for the two that read them, h for the two that write them.
+void FftChain::theta(hipStream_t st, ThetaOp op, const ThetaCall& c) {
+	if (op == TH_TO_CC) to_cc(st, c); else if (op == TH_FROM_CC_ADJ) from_cc_adjoint(st, c); else if (op == TH_FROM_CC) from_cc(st, c); else if (op == TH_TO_CC_ADJ) to_cc_adjoint(st, c);
+}
+
+void FftChain::to_cc(hipStream_t st, const ThetaCall& c) {
+	if (dry_ ? line_takes(*c.tp, true) : line_analysis(st, true, c)) return;
+	const ThetaPlan& tp = *c.tp; const long npair = (c.nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
+	const double2* ph = c.ph;
 #ifdef PXS_LAB
 	{ static const int noph = [] { const char* e = getenv("PXS_CH_NOPH"); return e ? atoi(e) : 0; }(); if (noph) ph = nullptr; }     // timing experiments only (wrong results)
 #endif
-	theta_chunks(tp, nm, nc, 0, [&](int c0, long ncl) {
-		run_first<StFirst>(st, pair_src(leg + (size_t)c0*nm*ldleg, ldleg, nr, tp.N, mir_c, spin, nm, nullptr), ncl, npair, g, bN);      // RA1
+	theta_chunks(TH_TO_CC, c, [&](int c0, long ncl) {
+		run_first<StFirst>(st, pair_src(c.map + (size_t)c0*c.nm*c.ldmap, c.ldmap, c.nr, tp.N, c.mir_c, c.spin, c.nm, nullptr), ncl, npair, g, bN);      // RA1
 		// RA2.  M > N (the interpolant form; the fine-CC form on grids below ~2 lmax rings): zero padding, Nyquist bin of N split;
 		// M <= N (the fine-CC form on larger grids): low pass, |k| < M/2 kept
 		run_resize(st, ncl*npair, bN, g2, g, tp.M > tp.N ? -1 : (int)(tp.M/2 - 1), tp.M > tp.N ? 1 : 0, 0, ph);
-		run_sigma(st, ncl*npair, g, g2, sigma);      // RA3
-		run_resize(st, ncl*npair, g2, ac, g, lmax, 0, 0, nullptr);      // RA4: keep |k| <= lmax
-		run_split<0>(st, ncl, npair, nm, spin, ac, g, 0, ncc, leg_cc + (size_t)c0*nm*ldcc, ldcc, (long)nm*ldcc, wcc, nullptr, 1.0, 0);      // RA5
+		run_sigma(st, ncl*npair, g, g2, c.sigma);      // RA3
+		run_resize(st, ncl*npair, g2, ac, g, c.lmax, 0, 0, nullptr);      // RA4: keep |k| <= lmax
+		run_split<0>(st, ncl, npair, c.nm, c.spin, ac, g, 0, c.ncc, c.cc + (size_t)c0*c.nm*c.ldcc, c.ldcc, (long)c.nm*c.ldcc, c.wcc, nullptr, 1.0, 0);      // RA5
 	});
 }
 
@@ -1117,17 +1119,15 @@ void FftChain::to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, lo
 // without self-mirrored rings (F1).  With U = S F_N^-1 D(e^{ik theta0}) Pad F_Ncc E (E: mirror extension of the CC samples,
 // S: sampling at the rings), U^T = E^T F_Ncc^-1 Trunc D(e^{-ik theta0}) F_N S^T up to the scalar; E^T A S^T = R A E' for any
 // operator A that commutes with the reflection (E': mirror extension of the ring samples, R: restriction to the CC rings) except
-// at the CC pole rings, which E' counts twice: weight 1/2 there (w).  So: RA1, the resize N -> N_cc directly, RA5.
-void FftChain::from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
-                               int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* w, const double2* wring)
-{
-	if (dry_ ? line_takes(tp, false) : line_analysis(st, tp, false, leg, ldleg, nr, mir_c, leg_cc, ldcc, ncc, nc, nm, spin, lmax, ph_shift, nullptr, w, wring)) return;
-	const long npair = (nm + 1)/2, g = tp.g, bN = tp.bN, ac = tp.ac;
-	theta_chunks(tp, nm, nc, 1, [&](int c0, long ncl) {
+// at the CC pole rings, which E' counts twice: weight 1/2 there (c.wcc).  So: RA1, the resize N -> N_cc directly, RA5.
+void FftChain::from_cc_adjoint(hipStream_t st, const ThetaCall& c) {
+	if (dry_ ? line_takes(*c.tp, false) : line_analysis(st, false, c)) return;
+	const ThetaPlan& tp = *c.tp; const long npair = (c.nm + 1)/2, g = tp.g, bN = tp.bN, ac = tp.ac;
+	theta_chunks(TH_FROM_CC_ADJ, c, [&](int c0, long ncl) {
 		// (wring: quadrature weights of the map's rings: the weights form of the analysis)
-		run_first<StFirst>(st, pair_src(leg + (size_t)c0*nm*ldleg, ldleg, nr, tp.N, mir_c, spin, nm, wring), ncl, npair, g, bN);
-		run_resize(st, ncl*npair, bN, ac, g, lmax, 0, 0, ph_shift);
-		run_split<0>(st, ncl, npair, nm, spin, ac, g, 0, ncc, leg_cc + (size_t)c0*nm*ldcc, ldcc, (long)nm*ldcc, w, nullptr, 1.0, 0);
+		run_first<StFirst>(st, pair_src(c.map + (size_t)c0*c.nm*c.ldmap, c.ldmap, c.nr, tp.N, c.mir_c, c.spin, c.nm, c.wring), ncl, npair, g, bN);
+		run_resize(st, ncl*npair, bN, ac, g, c.lmax, 0, 0, c.ph);
+		run_split<0>(st, ncl, npair, c.nm, c.spin, ac, g, 0, c.ncc, c.cc + (size_t)c0*c.nm*c.ldcc, c.ldcc, (long)c.nm*c.ldcc, c.wcc, nullptr, 1.0, 0);
 	});
 }
 
@@ -1138,33 +1138,29 @@ void FftChain::from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double
 // parity (times 2), every operator in between commutes with the reflection, so the zero extension may be replaced by the parity
 // mirror extension of W x with weight 1/2 off the poles: the chain then has the shape of from_cc -- pairs of columns of opposite
 // parity packed into one sequence and separated by reflection symmetry at the end, written ring-major for the ring FFT.
-void FftChain::to_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
-                             int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* whalf, const double2* tab, double scale)
-{
-	const long npair = (nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
-	theta_chunks(tp, nm, nc, 3, [&](int c0, long ncl) {
+void FftChain::to_cc_adjoint(hipStream_t st, const ThetaCall& c) {
+	const ThetaPlan& tp = *c.tp; const long npair = (c.nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
+	theta_chunks(TH_TO_CC_ADJ, c, [&](int c0, long ncl) {
 		// weighted mirror-pair extension on the CC circle, pass 1 of FFT_Ncc
-		run_first<StFirst>(st, pair_src(leg_cc + (size_t)c0*nm*ldcc, ldcc, ncc, tp.Ncc, 0, spin, nm, whalf), ncl, npair, g, ac);
+		run_first<StFirst>(st, pair_src(c.cc + (size_t)c0*c.nm*c.ldcc, c.ldcc, c.ncc, tp.Ncc, 0, c.spin, c.nm, c.wcc), ncl, npair, g, ac);
 		// pass 2 of FFT_Ncc, |k| <= lmax embedded in the M spectrum, pass 1 of IFFT_M
-		run_resize(st, ncl*npair, ac, g2, g, lmax, 0, 0, nullptr);
+		run_resize(st, ncl*npair, ac, g2, g, c.lmax, 0, 0, nullptr);
 		// pass 2 of IFFT_M, x |sin| series, pass 1 of FFT_M
-		run_sigma(st, ncl*npair, g, g2, sigma);
+		run_sigma(st, ncl*npair, g, g2, c.sigma);
 		// pass 2 of FFT_M, transposed padding M -> N (conjugate phase, Nyquist bins combined), pass 1 of IFFT_N
 		// (M <= N: transpose of the low pass = zero padding of |k| < M/2)
-		run_resize(st, ncl*npair, g2, bN, g, tp.M > tp.N ? -1 : (int)(tp.M/2 - 1), 0, 1, ph_shift);
+		run_resize(st, ncl*npair, g2, bN, g, tp.M > tp.N ? -1 : (int)(tp.M/2 - 1), 0, 1, c.ph);
 		// pass 2 of IFFT_N, the two parities apart, rings of the map, ring-major
-		run_split<1>(st, ncl, npair, nm, spin, bN, g, mir_c, nr, h + (size_t)c0*nr*ldh, ldh, (long)nr*ldh, nullptr, tab, scale, 1);
+		run_split<1>(st, ncl, npair, c.nm, c.spin, bN, g, c.mir_c, c.nr, c.map + (size_t)c0*c.nr*c.ldmap, c.ldmap, (long)c.nr*c.ldmap, nullptr, c.tab, c.scale, 1);
 	});
 }
 
-void FftChain::from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
-                       int nc, int nm, int spin, int lmax, const double2* ph_up, const double2* tab, double scale, const double2* wring)
-{
-	const long npair = (nm + 1)/2, gs = tp.gs, bs = tp.bs, aN = tp.aNs;
-	theta_chunks(tp, nm, nc, 2, [&](int c0, long ncl) {
-		run_first<StFirst>(st, pair_src(leg_cc + (size_t)c0*nm*ldcc, ldcc, ncc, tp.Ncc, 0, spin, nm, nullptr), ncl, npair, gs, bs);      // RS1
-		run_resize(st, ncl*npair, bs, aN, gs, lmax, 0, 0, ph_up);      // RS2
-		run_split<1>(st, ncl, npair, nm, spin, aN, gs, mir_c, nr, h + (size_t)c0*nr*ldh, ldh, (long)nr*ldh, wring, tab, scale, 0);      // RS3
+void FftChain::from_cc(hipStream_t st, const ThetaCall& c) {
+	const ThetaPlan& tp = *c.tp; const long npair = (c.nm + 1)/2, gs = tp.gs, bs = tp.bs, aN = tp.aNs;
+	theta_chunks(TH_FROM_CC, c, [&](int c0, long ncl) {
+		run_first<StFirst>(st, pair_src(c.cc + (size_t)c0*c.nm*c.ldcc, c.ldcc, c.ncc, tp.Ncc, 0, c.spin, c.nm, nullptr), ncl, npair, gs, bs);      // RS1
+		run_resize(st, ncl*npair, bs, aN, gs, c.lmax, 0, 0, c.ph);      // RS2
+		run_split<1>(st, ncl, npair, c.nm, c.spin, aN, gs, c.mir_c, c.nr, c.map + (size_t)c0*c.nr*c.ldmap, c.ldmap, (long)c.nr*c.ldmap, c.wring, c.tab, c.scale, 0);      // RS3
 	});
 }
 

@@ -28,6 +28,18 @@ struct ThetaPlan {            // sizes of the theta chains of a grid plan
 	long gs = 0, bs = 0, aNs = 0;            // synthesis: Ncc = gs*bs, N = aNs*gs
 };
 
+// the four theta operations between the map's rings and the CC grid, and what one of them takes
+enum ThetaOp { TH_NONE = -1, TH_TO_CC = 0, TH_FROM_CC_ADJ = 1, TH_FROM_CC = 2, TH_TO_CC_ADJ = 3 };
+struct ThetaCall {
+	const ThetaPlan* tp = nullptr;
+	int nc = 0, nm = 0, spin = 0, lmax = 0, mir_c = 0;
+	double2* map = nullptr; long ldmap = 0; int nr = 0;       // map side: leg[c][m][ring] (read: TH_TO_CC, TH_FROM_CC_ADJ) or h[c][ring][m] (written)
+	double2* cc = nullptr; long ldcc = 0; int ncc = 0;        // CC side: leg_cc[c][m][cc ring]
+	// tables: shift phase per k; pointwise table on the M circle; weight (.x) per CC ring (TH_FROM_CC_ADJ: 1/N_cc, half at the poles;
+	// TH_TO_CC_ADJ: the TH_TO_CC weights halved off the poles); optional weight (.x) per ring of the map; h = ... * conj(tab[m]) * scale
+	const double2 *ph = nullptr, *sigma = nullptr, *wcc = nullptr, *wring = nullptr, *tab = nullptr; double scale = 1.0;
+};
+
 class FftChain {
 public:
 	explicit FftChain(FftContext* fc) : fc_(fc) {}
@@ -50,33 +62,25 @@ public:
 	// h[c][ring][m] (row stride ldh) -> map
 	// (hcomp: rows of h per component when the map's rings are a row range of a larger h; 0 = the map's ring count)
 	void h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& m, int nc, int mmax, long hcomp = 0);
-	// leg on the map's rings -> quadrature-weighted leg on the CC grid (columns paired by parity)
-	void to_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
-	           int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* wcc);
-	// band-limited leg on the CC grid -> h[c][ring][m] * conj(tab[m]) * scale on the map's rings
-	void from_cc(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
-	             int nc, int nm, int spin, int lmax, const double2* ph_up, const double2* tab, double scale, const double2* wring = nullptr);      // wring: optional weight (.x) per output ring
-	// exact transpose of from_cc for grids without self-mirrored rings: leg on the map's rings -> leg on the CC grid (w: 1/N_cc, half at the poles)
-	void from_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
-	                     int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* w, const double2* wring = nullptr);      // wring: optional weight (.x) per input ring
-	// exact adjoint of to_cc: leg on the CC grid -> h[c][ring][m] * conj(tab[m]) * scale on the map's rings (whalf: the to_cc weights, halved off the poles)
-	void to_cc_adjoint(hipStream_t st, const ThetaPlan& tp, const double2* leg_cc, long ldcc, int ncc, double2* h, long ldh, int nr, int mir_c,
-	                   int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* whalf, const double2* tab, double scale);
+	// the theta operation `op` on c.nc components, paired by column parity (theta_scratch: what it keeps in the ping-pong scratch).
+	// TH_TO_CC: leg on the map's rings -> quadrature-weighted leg on the CC grid.  TH_FROM_CC: band-limited leg on the CC grid ->
+	// h[c][ring][m] * conj(tab[m]) * scale on the map's rings.  TH_FROM_CC_ADJ: exact transpose of TH_FROM_CC for grids without
+	// self-mirrored rings.  TH_TO_CC_ADJ: exact adjoint of TH_TO_CC, written like TH_FROM_CC.
+	void theta(hipStream_t st, ThetaOp op, const ThetaCall& c);
 	// 2-D FFT of real [npre][ny][nx] (float32 / float64) into complex128 [npre][ny][nx]; false if nx or ny has no usable factorisation
 	bool fft2_real(hipStream_t st, const void* in, int in_dtype, double2* out, long npre, long ny, long nx, bool forward, double scale);
 	// 2-D FFT of complex128 [npre][ny][nx] (in == out allowed); false if nx or ny has no usable factorisation
 	bool fft2_c2c(hipStream_t st, const double2* in, double2* out, long npre, long ny, long nx, bool forward, double scale);
-	// single-kernel form of to_cc (has_mid) / from_cc_adjoint for lines that fit a CU (thetaline.hip): one workgroup per pair of columns,
+	// single-kernel form of TH_TO_CC (has_mid) / TH_FROM_CC_ADJ for lines that fit a CU (thetaline.hip): one workgroup per pair of columns,
 	// no HBM intermediates.  false: not eligible (sizes, radices) or switched off (PXS_THETA_LINE=0) -- the caller runs the stage chain.
-	bool line_analysis(hipStream_t st, const ThetaPlan& tp, bool has_mid, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
-	                   int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* w, const double2* wring);
+	bool line_analysis(hipStream_t st, bool has_mid, const ThetaCall& c);
 	static bool line_takes(const ThetaPlan& tp, bool has_mid);      // ... would it (then the call needs no theta scratch)
 	// single-kernel form of h2map for ring lengths compiled into ringline.hip: one workgroup per ring pair, no HBM intermediate
 	bool line_h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& m, int nc, int mmax, long hcomp);
 	static bool line_h2map_takes(long nphi, int mmax);
 	size_t scratch_bytes() const { return s1_.bytes + s2_.bytes; }
-	// scratch a call needs, so that the plan can size it before the first launch of the call (kind 0: to_cc, 1: from_cc_adjoint, 2: from_cc, 3: to_cc_adjoint)
-	static void theta_scratch(const ThetaPlan& tp, int nm, int nc, int kind, size_t& b1, size_t& b2);
+	// scratch a call needs, so that the plan can size it before the first launch of the call
+	static void theta_scratch(ThetaOp op, const ThetaPlan& tp, int nm, int nc, size_t& b1, size_t& b2);
 	void ring_scratch(long nring, int nc, bool analysis, size_t& b1, int mmax = -1) const;      // (mmax given: 0 for a synthesis that ringline.hip takes)
 	void reserve(size_t b1, size_t b2) { s1_.ensure(b1); s2_.ensure(b2); }
 	// Compile-time-planned stage kernels (chain_kernel_static, chain_static_table.hpp).  A dry run: between dry_begin and dry_end the
@@ -104,7 +108,8 @@ private:
 	template<int MODE> void run_split(hipStream_t st, long ncomp, long npair, int nm, int spin, long a, long g, int mir_c, int nr_out,
 	                                  double2* out, long ld, long ocstride, const double2* w, const double2* tab, double scale, int self_half);
 	void run_colout(hipStream_t st, long npre, long nlines, long a, long b, double2* out, long ldo, long ocomp, int conj, double scale, long herm_ny = 0, long herm_nx = 0);
-	template<class F> void theta_chunks(const ThetaPlan& tp, int nm, int nc, int kind, F&& stages);
+	template<class F> void theta_chunks(ThetaOp op, const ThetaCall& c, F&& stages);
+	void to_cc(hipStream_t st, const ThetaCall& c), from_cc(hipStream_t st, const ThetaCall& c), from_cc_adjoint(hipStream_t st, const ThetaCall& c), to_cc_adjoint(hipStream_t st, const ThetaCall& c);
 	std::mutex mu_;
 	std::map<std::tuple<long, int, int>, DevBuf> stw_;
 	FftContext* fc_;

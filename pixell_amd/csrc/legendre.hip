@@ -569,7 +569,7 @@ static LegWork::Seeds* seeds_for(LegWork& wk, const RingSet& rs, const LegTables
 	return &sb;
 }
 // after the recording launch: later launches on OTHER streams wait for it (a plan serves one call at a time, but the next call may
-// come on another stream).  The entry points of a plan now order whole calls across streams (PlanUse, sht.hip), which covers this
+// come on another stream).  The entry points of a plan now order whole calls across streams (PlanUse, sht_plan.hpp), which covers this
 // too; the event stays for callers of leg_synthesis / leg_analysis that do not come through a plan's entry point.
 static void seeds_written(LegWork::Seeds* sb, hipStream_t st) {
 	if (!sb || sb->ready) return;

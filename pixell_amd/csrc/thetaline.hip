@@ -331,10 +331,11 @@ bool FftChain::line_takes(const ThetaPlan& tp, bool has_mid) {
 	return false;
 }
 
-bool FftChain::line_analysis(hipStream_t st, const ThetaPlan& tp, bool has_mid, const double2* leg, long ldleg, int nr, int mir_c, double2* leg_cc, long ldcc, int ncc,
-                             int nc, int nm, int spin, int lmax, const double2* ph_shift, const double2* sigma, const double2* w, const double2* wring)
+bool FftChain::line_analysis(hipStream_t st, bool has_mid, const ThetaCall& c)
 {
-	if (!line_enabled()) return false;
+	if (!line_enabled()) return false;      // (c.ph, the table of e^{-i k theta_0}, is not used: the engine keeps its own two-level form in the LDS)
+	const ThetaPlan& tp = *c.tp; const int nr = c.nr, mir_c = c.mir_c, ncc = c.ncc, nm = c.nm;
+	const double2* sigma = has_mid ? c.sigma : nullptr;
 	const LineEntry* e = nullptr;
 	for (const LineEntry& c : LINE_CONFIGS) if (c.N == tp.N && c.Ncc == tp.Ncc && c.M == (has_mid ? tp.M : 0)) e = &c;
 	if (!e || nr > tp.N/2 + 1 || ncc != tp.Ncc/2 + 1) return false;
@@ -379,20 +380,19 @@ bool FftChain::line_analysis(hipStream_t st, const ThetaPlan& tp, bool has_mid, 
 #endif
 		}
 	}
-	(void)ph_shift;      // (the table of e^{-i k theta_0}: the engine keeps its own two-level form in the LDS)
 	const long npair = (nm + 1)/2;
 	LineArgs a; memset(&a, 0, sizeof(a));
 	a.tw = tw; a.ntw = e->ntw; a.has_ph = mir_c != 0 ? 1 : 0;
-	a.leg = leg; a.cstride = (long)nm*ldleg; a.ldleg = ldleg; a.nr = nr; a.mir_c = mir_c; a.wring = wring;
-	a.lmax = lmax; a.sigma = sigma; a.sig_half = sig_half;
+	a.leg = c.map; a.cstride = (long)nm*c.ldmap; a.ldleg = c.ldmap; a.nr = nr; a.mir_c = mir_c; a.wring = has_mid ? nullptr : c.wring;
+	a.lmax = c.lmax; a.sigma = sigma; a.sig_half = sig_half;
 #ifdef PXS_LAB_TL_NOSIGHALF
 	a.sig_half = nullptr;
 #endif
-	a.nr_out = ncc; a.a_odd = spin & 1; a.ncol = nm; a.npair = (int)npair; a.dnp = make_fastdiv((uint32_t)npair);
-	const long ntask = (long)nc*npair;
+	a.nr_out = ncc; a.a_odd = c.spin & 1; a.ncol = nm; a.npair = (int)npair; a.dnp = make_fastdiv((uint32_t)npair);
+	const long ntask = (long)c.nc*npair;
 	PXS_REQUIRE(ntask < (1L << 31), "internal: theta line grid too large");
 	a.ntask = (int)ntask;
-	a.out = leg_cc; a.ld = ldcc; a.ocstride = (long)nm*ldcc; a.w = w; a.scale = 1.0;
+	a.out = c.cc; a.ld = c.ldcc; a.ocstride = (long)nm*c.ldcc; a.w = c.wcc; a.scale = 1.0;
 	const long per_cu = std::max<long>(1, std::min<long>(2048/e->nt, (long)(160*1024)/(long)e->lds));
 	long nwg = std::min<long>(ntask, (long)tl_->ncu*per_cu);
 	if (const char* ev = lab_getenv("PXS_TL_NWG")) nwg = std::max<long>(1, std::min<long>(nwg, atol(ev)));      // (lab builds: fewer workgroups, to see a line's phases without the other CUs' traffic)

@@ -523,7 +523,7 @@ def alm_real2complex(ralm, ainfo=None):
 	return out
 
 # ---------------------------------------------------------------------------------------
-# healpix maps: the same ring transforms on ring tables with per-ring nphi / phi0 (the general ring path of sht.hip)
+# healpix maps: the same ring transforms on ring tables with per-ring nphi / phi0 (the general ring path of sht_general.hip)
 # ---------------------------------------------------------------------------------------
 def npix2nside(npix): return nint((npix/12)**0.5)
 def get_ring_info_healpix(nside, rings=None): return _geo.healpix_rings(nside, rings)

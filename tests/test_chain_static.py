@@ -219,3 +219,41 @@ def fft_round_trip(monkeypatch):
 def test_fft2_round_trip_gpu(monkeypatch): fft_round_trip(monkeypatch)
 @pytest.mark.hostsim
 def test_fft2_round_trip_hostsim(monkeypatch): fft_round_trip(monkeypatch)
+
+# ---- 6. the timing entry of tools/chain_lab.py ------------------------------------------------------------------------------------
+def debug_chain_leaves_the_plan_intact():
+	"""pxs_debug_chain on the `tiny` shape of tools/chain_lab.py (F1 90 x 180, lmax 60): every stage group runs and reports a time, an
+	unknown group is refused, and the cached plan it ran on (it uses the plan's own scratch) transforms bit for bit as before"""
+	import ctypes
+	nt, nph, lmax = 90, 180, 60
+	lib = _lib.load()
+	sht.set_deterministic(True)
+	try:
+		kw = dict(spin=2, lmax=lmax, geometry="F1", phi0=0.3)
+		rng = np.random.default_rng(7); n = (lmax + 1)*(lmax + 2)//2
+		alm = rng.standard_normal((2, n)) + 1j*rng.standard_normal((2, n)); alm[:, :lmax + 1] = alm[:, :lmax + 1].real
+		pix = rng.standard_normal((2, nt, nph))
+		def both():
+			m = np.zeros((2, nt, nph)); plan = sht.synthesis_2d(alm=alm, map=m, return_plan=True, **kw)
+			a = np.zeros_like(alm); assert sht.analysis_2d(alm=a, map=pix, return_plan=True, **kw) is plan
+			return m, a, plan
+		m0, a0, plan = both()
+		assert np.abs(m0).max() > 0 and np.abs(a0).max() > 0
+		ms = ctypes.c_double(-1.0)
+		for nc, spin in ((1, 0), (2, 2)):
+			for kind in range(5):
+				ms.value = -1.0
+				assert lib.pxs_debug_chain(plan.handle, kind, nc, spin, 1, ctypes.byref(ms)) == 0, (kind, nc, lib.pxs_last_error())
+				print("pxs_debug_chain kind %d nc %d: %.3f ms" % (kind, nc, ms.value))
+				assert np.isfinite(ms.value) and ms.value >= 0, (kind, nc, ms.value)
+		assert lib.pxs_debug_chain(plan.handle, 5, 1, 0, 1, ctypes.byref(ms)) != 0
+		m1, a1, plan1 = both()
+		assert plan1 is plan
+		assert m1.tobytes() == m0.tobytes() and a1.tobytes() == a0.tobytes()
+	finally:
+		sht.set_deterministic(None)
+
+@pytest.mark.gpu
+def test_debug_chain_leaves_the_plan_intact_gpu(): debug_chain_leaves_the_plan_intact()
+@pytest.mark.hostsim
+def test_debug_chain_leaves_the_plan_intact_hostsim(): debug_chain_leaves_the_plan_intact()

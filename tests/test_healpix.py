@@ -1,4 +1,4 @@
-"""The healpix layer of pixell_amd.curvedsky (ring tables with per-ring nphi / phi0 through the general ring path of sht.hip)
+"""The healpix layer of pixell_amd.curvedsky (ring tables with per-ring nphi / phi0 through the general ring path of sht_general.hip)
 against tests/golden/healpix.npz, which tests/golden/make_healpix.py recorded from the REFERENCE's own
 get_ring_info_healpix / get_ring_info_radial / alm2map_healpix / map2alm_healpix (pixell/curvedsky.py:312-403, 1192-1234) over the
 long-double oracle."""

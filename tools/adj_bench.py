@@ -1,4 +1,4 @@
-"""alm2map_adjoint (adjoint_synthesis_2d) at C3 / C2: through the CC grid (default) or directly on the map's rings (PXS_ADJ_VIA_CC=0)"""
+"""alm2map_adjoint (adjoint_synthesis_2d) at C3 / C2: through the CC grid, as every grid with a fused theta chain and clearly more rings than lmax takes it"""
 import sys, time, numpy as np, torch
 sys.path.insert(0, ".")
 from pixell_amd import curvedsky, enmap

@@ -1,5 +1,5 @@
 """A/B of two builds of the library, route by route: the same seeded calls through each (one fresh process per library, selected with
-PIXELL_AMD_LIB), outputs dumped and compared.  The case list reaches every value of the route enum of csrc/sht.hip, both directions.
+PIXELL_AMD_LIB), outputs dumped and compared.  The case list reaches every value of the route enum of csrc/sht_plan.hpp, both directions.
 
   PIXELL_AMD_LIB=<lib> PXS_CHAIN_VERBOSE=1 python tools/route_ab.py run OUT.npz [--split] 2> OUT.log
   python tools/route_ab.py compare A.npz B.npz B.log     # B.log: the verbose log of a build that prints its routes
@@ -79,6 +79,8 @@ def cases(split):
 			for what in ("syn", "adj"): cs.append(grid("%s %s s%d" % (what, nm, spin), *g, spin, what))
 	cs += [rings("%s band s%d" % (w, s), band(), 24, s, w) for s in (0, 2) for w in ("syn", "adj")]
 	cs += [rings("%s healpix s%d" % (w, s), healpix(4), 14, s, w) for s in (0, 2) for w in ("syn", "adj")]
+	# 16 ring lengths: 16 (spin 0) and 32 (spin 2) FFT jobs, so the ring FFTs fork to the side streams (sht_general.hip); nside 4 never does
+	cs += [rings("%s healpix16 s%d" % (w, s), healpix(16), 32, s, w) for s in (0, 2) for w in ("syn", "adj")]
 	for what in ("ana", "adjana"):
 		cs += [grid("%s DH s0" % what, "DH", 22, 44, 10, 0, what), grid("%s F2 s2" % what, "F2", 21, 44, 10, 2, what),
 			grid("%s H weights s0" % what, *H, 0, what, analysis="weights"), grid("%s H weights s2" % what, *H, 2, what, analysis="weights"),
