@@ -524,7 +524,7 @@ static LegK make_legk(const RingSet& rs, const LegTables& tb, LegWork& wk, doubl
 	a.nmc = a.nm; a.xcd = 1;      // (the XCD-aware block order, always: see leg_block)
 	a.count = wk.count_on ? wk.count.as<double>() : nullptr;
 	a.nb = nb; a.leg_bs = leg_bs; a.almt_bs = leg_almt_stride(tb); a.mom_bs = leg_mom_stride(tb);
-	PXS_REQUIRE((long)8*((a.nm + 7)/8)*a.nwave*nb < (1L << 31), "internal: Legendre grid too large for one launch");
+	PXS_REQUIRE((long)8*((a.nm + 7)/8)*leg_blocks_per_m(a.nwave, nb) < (1L << 31), "internal: Legendre grid too large for one launch");
 	return a;
 }
 // ... of an MFMA launch: nmaps maps from `leg` on in groups of 4 ng, one group per wave (synthesis) or workgroup (analysis)
@@ -534,13 +534,13 @@ static LegK make_legk_mm(const RingSet& rs, const LegTables& tb, LegWork& wk, do
 	return a;
 }
 
-// maps (MFMA forms: groups) one launch can take: all of them share one grid of 8 ceil(nm / 8) nwave blocks each (a large batch of
+// maps (MFMA forms: groups) one launch can take: all of them share one grid of 8 ceil(nm / 8) leg_blocks_per_m(nwave, nb) blocks (a large batch of
 // small-ring, high-lmax maps goes out as several launches instead of tripping make_legk's grid check)
 // (the spin MFMA runs used to be cut at half the spin-0 synthesis limit and at the limit of 128 pairs per workgroup: lower than the grid needs; now every form is cut by its own
 // pairs per workgroup.  Out of reach at real sizes: tens of thousands of maps in one call)
 static int leg_max_batch(const RingSet& rs, const LegTables& tb, int pairs) {
-	const long nwave = (rs.npairs + (long)pairs - 1)/pairs, per = 8L*((tb.mmax + 1 + 7)/8)*std::max<long>(nwave, 1);
-	return (int)std::max<long>(1, std::min<long>(1 << 20, ((1L << 31) - 1)/per));
+	const long nwave = (rs.npairs + (long)pairs - 1)/pairs, per_m = ((1L << 31) - 1)/(8L*((tb.mmax + 1 + 7)/8));      // blocks per m one grid can hold: nwave nb, or one more (leg_blocks_per_m)
+	return (int)std::max<long>(1, std::min<long>(1 << 20, (per_m - 1)/std::max<long>(nwave, 1)));
 }
 // seeds of (ring set, spin, direction, K): allocate on first use if the plan's budget allows; returns the mode for this launch.
 // The step a seed records depends on the rule that ends phase A (LEG_LIVE).  That rule is a compile-time constant of the library, and

@@ -108,19 +108,35 @@ struct LegK {
 // one reader misses and the others hit in L2.
 // (Workgroups of 2-4 independent waves of the same m -- to share the rows in the CU's scalar cache -- were measured twice:
 // with __launch_bounds__(256) and the lane taken as threadIdx.x & 63 every kernel got slower even at one wave per workgroup
-// (config 3: leg_syn 106 -> 113 ms, leg_ana 144 -> 151 ms), 4 waves per workgroup 128 / 165 ms.  One wave per workgroup stays.)
+// (config 3: leg_syn 106 -> 113 ms, leg_ana 144 -> 151 ms), 4 waves per workgroup 128 / 165 ms.  One wave per workgroup stays.
+// A third time with the waves per workgroup NW a template parameter of the four VALU kernels, so that NW = 1 compiles to the code below, NW waves on
+// adjacent chunks of one m, one reduction tile per wave: FETCH_SIZE fell (C3, NW = 4: leg_syn_s0<4> 14.3 -> 10.4 GB per launch, leg_ana_spin<4>
+// 8.6 -> 7.8, leg_syn_spin<3> 25.5 -> 24.0) but the time did not follow it: C3 -7 % to +11 % per kernel at NW = 2 / 4 and up to +50 % at NW = 8, lmax 8000
+// up to +21 % (leg_ana_spin<4>, NW = 4), C2 +5 %; a workgroup needs NW free wave slots on one CU at once, and the waves of a group end far apart.
+// Where grouping had gained it had made the number of blocks per m odd (C3, NW = 4: 20 chunks in 5 groups; where it lost, even: C2: 8 in 2):
+// that is what leg_blocks_per_m now does for one wave per workgroup, and with it no NW > 1 is ahead.  profiles/README.md, "Wave groups".)
+// An m takes an ODD number of blocks: with an even count of chunks and maps, nwave nb, one block more that returns at once (leg_blocks_per_m).  The
+// chunks of an m differ in cost by an order of magnitude -- the equatorial ones run every step, the polar ones few or none -- and an XCD deals its
+// queue to its shader engines and CUs in turn: with an even period the heavy chunks of every m meet the same part of the XCD, the light ones the
+// rest, and the kernel ends on the heavy part alone; an odd period walks through them.  (The cause is inferred from the rule, not read off a counter;
+// the rule is what is measured: odd counts are faster at every size tried.)  Measured on MI355X, kernel by kernel against the even count
+// (profiles/README.md, "Wave groups"): C3 (20 chunks of 256 pairs) leg_ana_spin<4> 96.8 -> 92.5 ms, leg_ana_s0<8> (10 chunks) 25.3 -> 24.4,
+// leg_syn_s0<4> 21.5 -> 20.5, leg_syn_spin<3> (27 chunks, odd before) level; lmax 8000: -5 %, -9 %, -1 %; C2: -11 %, -9 %, +1 %.  What a wave
+// computes and where it puts it is keyed on wv and untouched.
+__host__ __device__ constexpr unsigned leg_blocks_per_m(unsigned nwave, unsigned nb) { return (nwave*nb) | 1u; }
+static_assert(leg_blocks_per_m(20, 1) == 21 && leg_blocks_per_m(27, 1) == 27 && leg_blocks_per_m(4, 8) == 33 && leg_blocks_per_m(3, 2) == 7, "blocks per m: odd, at most one more than chunks x maps");
 __device__ __forceinline__ bool leg_block(const LegK& a, int& wv, int& m, int& bb) {
 	if (!a.xcd) { wv = blockIdx.x; m = blockIdx.y + a.m0; bb = blockIdx.z; return true; }
 	const unsigned b = blockIdx.x, x = b & 7u, j = b >> 3;
-	const unsigned per_m = (unsigned)a.nwave*(unsigned)a.nb;
+	const unsigned per_m = leg_blocks_per_m((unsigned)a.nwave, (unsigned)a.nb);
 	const unsigned ml = j / per_m, r = j - ml*per_m;
 	bb = (int)(r / (unsigned)a.nwave);
 	wv = (int)(r - (unsigned)bb*a.nwave);
 	const unsigned mi = ml*8u + x;
 	m = (int)mi + a.m0;
-	return mi < (unsigned)a.nmc;
+	return mi < (unsigned)a.nmc && bb < a.nb;      // (bb == nb: the block that makes the count odd)
 }
-static inline dim3 leg_grid(const LegK& a) { return a.xcd ? dim3((unsigned)(8*((a.nmc+7)/8)*a.nwave*a.nb)) : dim3(a.nwave, a.nmc, a.nb); }
+static inline dim3 leg_grid(const LegK& a) { return a.xcd ? dim3((unsigned)(8*((a.nmc+7)/8)*leg_blocks_per_m(a.nwave, a.nb))) : dim3(a.nwave, a.nmc, a.nb); }
 
 // ---------------------------------------------------------------------------------
 // scaled powers
@@ -225,9 +241,11 @@ __device__ __forceinline__ int leg_pair_u(const LegK& a, int wv, int K, int s, i
 // Workgroups are ONE wave: lanes run in lockstep and a wave's LDS operations execute in order, so
 // cross-lane visibility of the LDS tile only needs the LDS counter drained -- not an s_barrier, whose
 // compiler-inserted s_waitcnt vmcnt(0) would also wait for the (slow, fire-and-forget) global store
-// of the previous flush.
+// of the previous flush.  (The simulator's lanes do not run in lockstep: there it is the rendezvous of the lanes of ONE wave, pxsim::wave_sync, the
+// same thing whatever the waves per workgroup -- a block barrier would deadlock waves of differing trip counts, as the lab build with NW waves
+// per workgroup had them.)
 #ifdef PXS_HOST_SIM
-#define PXS_WAVE_LDS_SYNC() __syncthreads()
+#define PXS_WAVE_LDS_SYNC() pxsim::wave_sync()
 #else
 #define PXS_WAVE_LDS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #endif
