@@ -296,6 +296,27 @@ int pxm_distance_from(int ny, int nx, double dec0, double ddec, double ra0, doub
                       const int64_t* d_pt_pix, double rmax, const uint8_t* d_skip, void* d_omap, int map_dtype, int32_t* d_domains, int32_t* d_visits,
                       int device, void* stream);
 
+/* spline interpolation of maps at positions (pixell/utils.py:630-783 interpol / SplineInterpolator: scipy.ndimage.spline_filter, then
+ * map_coordinates(prefilter=False); enmap.at, enmap.project, enmap.py:561-638, 796-842).  All arrays DEVICE, FP64 arithmetic, no wait.
+ * pxm_spline_filter: the cubic B-spline coefficients of nmap maps [ny][nx] (f32 | f64, in_mstride elements apart) into d_out, f64
+ *   [nmap][ny][nx]: along each axis the solution of B c = f, B the (1/6, 4/6, 1/6) collocation matrix under the extension rule
+ *   0 whole-sample mirror (period 2(n-1)), 1 half-sample reflect (period 2n), 2 periodic.  d_tmp: f64 [nmap][ny][nx] scratch of the
+ *   caller's (the y pass writes it, the x pass reads it); the input, the scratch and the output are three different arrays.
+ * pxm_interpol: d_out[m][i] = the value of map m at point i, in the maps' dtype.  order 0: the nearest sample, maps f32 | f64 | uint8
+ *   (code 4) | int32 (code 5); order 1: linear, f32 | f64 maps; order 3: cubic, d_maps being the f64 coefficients of pxm_spline_filter.
+ *   Point i is (d_pts[i], d_pts[npts + i]) (f64 [2][npts]) or, with d_pts = NULL, (i / onx, i % onx) of a grid [ony][onx] with
+ *   ony onx = npts.  Its pixel coordinate on each axis is off + scale p, then, where per > 0, ref + ((pix - ref + per/2) mod per) - per/2
+ *   (enmap.sky2pix(safe=True), enmap.py:509-519).  border (n the axis length, x the coordinate): 0 "nearest": tap indices clamped to
+ *   [0, n-1]; 1 "mirror": indices mirrored with period 2(n-1); 2 "constant": cval where x < 0 or x > n-1 on an axis, indices mirrored;
+ *   3 "wrap" (scipy's legacy rule): x outside [0, n-1] folded with period n-1, indices mirrored; 4 "grid-wrap": indices modulo n.  Taps:
+ *   floor(x + 1/2) (order 0), floor(x), floor(x) + 1 (order 1), floor(x) - 1 .. floor(x) + 2 (order 3).  A coordinate that is not a number
+ *   gives cval. */
+int pxm_spline_filter(int nmap, int ny, int nx, const void* d_in, int in_dtype, int64_t in_mstride, double* d_tmp, double* d_out, int extension,
+                      int device, void* stream);
+int pxm_interpol(int nmap, int ny, int nx, const void* d_maps, int map_dtype, int64_t mstride, int64_t npts, const double* d_pts, int ony, int onx,
+                 double yoff, double yscale, double xoff, double xscale, double yref, double yper, double xref, double xper,
+                 int order, int border, double cval, void* d_out, int device, void* stream);
+
 /* 1 if the engine can transform this length (2,3,5-smooth or prime factors small enough) */
 int pxf_fft_supported(int64_t n);
 int64_t pxf_fft_good_size(int64_t n);

@@ -85,7 +85,7 @@ inline FastDiv make_fastdiv(uint32_t d) {
 	return f;
 }
 
-enum DType : int { PX_F32 = 0, PX_F64 = 1, PX_C64 = 2, PX_C128 = 3 };
+enum DType : int { PX_F32 = 0, PX_F64 = 1, PX_C64 = 2, PX_C128 = 3, PX_U8 = 4, PX_I32 = 5 };      // (the integer types: maps that pxm_interpol copies from)
 
 // the alm and the maps of an SHT call as the C ABI hands them over: component c of batch member b starts at element
 // b*bstride + c*cstride of `dtype`; from(b): the same arrays from batch member b on

@@ -539,6 +539,8 @@ for _cls in (ndmap, dmap):
 	_cls.modlmap  = lambda self, **kw: modlmap(self.shape, self.wcs, **kw)
 	_cls.lbin     = lambda self, *a, **kw: lbin(self, *a, **kw)
 	_cls.posmap   = lambda self, **kw: posmap(self.shape, self.wcs, **kw)
+	_cls.at       = lambda self, pos, **kw: at(self, pos, **kw)
+	_cls.project  = lambda self, shape, wcs, **kw: project(self, shape, wcs, **kw)
 
 # ---------------------------------------------------------------------------------------
 # bounding boxes and pixel sizes of separable CAR geometries (what pixell_amd.wavelets builds its per-scale geometries from)
@@ -604,6 +606,53 @@ def sky2pix(shape, wcs, coords, safe=True, corner=False):
 	x, y = wcsutils.world2pix(wcs, coords[1]/degree, coords[0]/degree)
 	res = np.array([y, x])
 	return res+0.5 if corner else res
+
+# ---------------------------------------------------------------------------------------
+# reading a map at positions and on another geometry (enmap.py:561-638, 796-842); the kernels are behind pixell_amd.interpol
+# ---------------------------------------------------------------------------------------
+def _rewind_of(shape, wcs, safe):
+	"""(ref, per) per pixel axis {y,x} of the rewind of the reference's sky2pix(safe=True) (enmap.py:509-519): pixel coordinates are brought
+	within half a turn of the sky, |360/cdelt| pixels, of the middle of the map, on both axes; no rewind without safe"""
+	if not safe: return ((0.0, 0.0), (0.0, 0.0))
+	w = wcs.wcs
+	return ((shape[-2]/2.0, abs(360.0/w.cdelt[1])), (shape[-1]/2.0, abs(360.0/w.cdelt[0])))
+
+def _need_separable(wcs, what):
+	if not wcsutils.is_separable(wcs): raise NotImplementedError("%s: only separable cylindrical geometries" % what)
+
+def at(map, pos, mode="spline", order=3, border="constant", cval=0.0, unit="coord", safe=True, ip=None):
+	"""The values of map [..., ny, nx] at pos [{dec,ra}, ...] in radians (unit="coord") or [{y,x}, ...] in pixels (unit="pix"), interpolated:
+	[..., ...] (enmap.at, enmap.py:796-842).  mode, order, border and cval as in interpol.interpol; safe: positions a whole turn of the sky
+	away land where they belong.  ip: an interpol.interpolator of the map to use again (the prefilter of order 3 then does not run).  One
+	launch: the kernel turns positions into pixels itself.  Host maps give numpy arrays, dmaps tensors."""
+	from . import interpol
+	if unit not in ("coord", "pix"): raise ValueError("Unrecognized unit '%s'" % str(unit))
+	if ip is None: ip = interpol.interpolator(map, npre=map.ndim-2, mode=mode, order=order, border=border, cval=cval)
+	pos = _data(pos)
+	if not A.is_tensor(pos): pos = np.asarray(pos, np.float64)
+	if pos.ndim < 1 or pos.shape[0] != 2: raise ValueError("pos must be [{dec,ra},...] or [{y,x},...]")
+	if unit == "pix": return ip.evaluate(tuple(pos.shape[1:]), pts=pos)
+	_need_separable(map.wcs, "at")
+	w = map.wcs.wcs
+	affine = tuple((float(-w.crval[k]/w.cdelt[k]+w.crpix[k]-1), float(1.0/(degree*w.cdelt[k]))) for k in (1, 0))
+	return ip.evaluate(tuple(pos.shape[1:]), pts=pos, affine=affine, rewind=_rewind_of(map.shape, map.wcs, safe))
+
+def project(map, shape, wcs, mode="spline", order=3, border="constant", cval=0.0, force=False, safe=True, ip=None):
+	"""map [..., ny, nx] on the geometry (shape, wcs), interpolated: [..., shape[-2], shape[-1]] (enmap.project, enmap.py:561-638).  Both
+	geometries separable and cylindrical; the whole output is one launch that computes the input pixel of every output pixel itself.
+	Equal geometries give a copy (force: interpolate anyway).  The result has the interpolation's dtype: float64 at order 3.  The
+	reference's blocks of 1000 output rows, each on an apodised band of the input, are a way to save memory and are not reproduced
+	(INTEGRATION.md E)."""
+	from . import interpol
+	oshape = (int(shape[-2]), int(shape[-1]))
+	if not force and ip is None and _geo_key(map.shape, map.wcs) == _geo_key(oshape, wcs) and _geo_key(oshape, wcs) is not None: return map.copy()
+	_need_separable(map.wcs, "project"); _need_separable(wcs, "project")
+	if ip is None: ip = interpol.interpolator(map, npre=map.ndim-2, mode=mode, order=order, border=border, cval=cval)
+	wi, wo = map.wcs.wcs, wcs.wcs
+	# output pixel o lies at crval_o + (o + 1 - crpix_o) cdelt_o, which is input pixel (that - crval_i)/cdelt_i + crpix_i - 1
+	affine = tuple((float((wo.crval[k]+(1-wo.crpix[k])*wo.cdelt[k]-wi.crval[k])/wi.cdelt[k]+wi.crpix[k]-1), float(wo.cdelt[k]/wi.cdelt[k])) for k in (1, 0))
+	res = ip.evaluate(oshape, affine=affine, rewind=_rewind_of(map.shape, map.wcs, safe))
+	return dmap(res, wcs) if A.is_tensor(res) else ndmap(res, wcs)
 
 def pixwin_1d(f, order=0):
 	"""the pixel window along one axis at the dimensionless frequency f (pixel pitch 1): nearest-neighbour (order 0) or linear (order 1)
