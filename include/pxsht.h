@@ -91,7 +91,8 @@ void pxs_plan_destroy(pxs_plan* plan);
  * alm_cstride / map_cstride: distance between components in elements of the respective dtype.
  * nbatch independent maps per call (the loop over pre-dimensions at curvedsky.py:763-765, 910-924): map b starts at
  * map + b*map_bstride, its alm at alm + b*alm_bstride (elements); nbatch = 1 ignores the batch strides.  The ring FFTs of a
- * batch run as one launch per pass; the plan's scratch bounds the maps per pass (PXS_BATCH_GB, default 32). */
+ * batch run as one launch per pass; the plan's scratch bounds the maps per pass (PXS_BATCH_GB, default 64; pxs_plan_query
+ * "passes_batch" tells how a call went). */
 int pxs_synthesis(pxs_plan* plan, int spin, int mode, int adjoint, int nbatch,
                   void* alm, int alm_dtype, int64_t alm_cstride, int64_t alm_bstride,
                   void* map, int map_dtype, int64_t map_cstride, int64_t map_bstride, void* stream);
@@ -125,7 +126,14 @@ int pxs_analysis(pxs_plan* plan, int spin, int adjoint, int nbatch,
  *   The promise is run-to-run repeatability of the SAME call.  A map transformed inside a batch of 4 or more takes the FP64-MFMA
  *   kernels (another summation order) and equals its single-map call to rounding (1e-13), not bit for bit, with or without this
  *   option -- the reference loops over the maps and is identical per map; PXS_SYN_MM_MIN=0 / PXS_ANA_MM_MIN=0 keep batches on the
- *   single-map kernels. */
+ *   single-map kernels.
+ * "leg_max_batch" (value = n >= 0; default 0 = no bound): at most n maps per launch of the single-map (VALU) Legendre kernels and 8 n per
+ *   launch of the FP64-MFMA kernels.  The only limit otherwise is the grid size (2^31 blocks: tens of thousands of maps in one call);
+ *   the option exists so that the launch loop can be tested.  Same results.
+ * Memory budgets from the environment (PXS_BATCH_GB, PXS_PART_GB, PXS_SEED_GB, PXS_CHAIN_SCRATCH_GB in GB; PXS_FFT_TEMP_MB,
+ *   PXS_RESAMPLE_MB, PXS_RING_CHUNK_MB in MB) are real numbers of their unit (0.004 GB = 4 MB), read as the plan is made (PXS_PART_GB,
+ *   PXS_RESAMPLE_MB), per call (the others) or per transform of the FFT engine (PXS_FFT_TEMP_MB: pxf_fft_nd and plans alike).
+ *   PXS_PART_GB=0: one m per pass; PXS_BATCH_GB unset or 0: the default rule (64 GB, at most 40 % of the free memory). */
 int pxs_plan_option(pxs_plan* plan, const char* name, int64_t value);
 
 /* What a plan does: "analysis_form" = the form pxs_analysis runs now (0 interpolant, 1 ring weights, 2 fine-CC form of ducc0's
@@ -135,7 +143,16 @@ int pxs_plan_option(pxs_plan* plan, const char* name, int64_t value);
  * "chain_stages": the distinct FFT chain stage shapes (stage, transform lengths, lines per tile) of the plan's standard calls (analysis
  * under its current option, synthesis of spin 0 and 2); "chain_static": how many of them have a compile-time-planned kernel
  * (csrc/chain_static_table.hpp; PXS_CHAIN_STATIC=0, read per call, runs the run-time kernel for all: same results to rounding);
- * "chain_static_table": entries of that table, each checked against the FFT engine's plan of its lengths (an error if one differs). */
+ * "chain_static_table": entries of that table, each checked against the FFT engine's plan of its lengths (an error if one differs).
+ * "passes_<seam>": how many passes the plan's most recent pxs_synthesis / pxs_analysis took at one of the places where a memory budget
+ *   cuts a call, counted by the loop that launched them (0: the call did not come by that place); "passes_<seam>_first", "_prev",
+ *   "_last": the sizes of the first pass, the one before the last and the last.  Seams and their sizes: "batch" maps per pass of a
+ *   batched call (PXS_BATCH_GB); "leg_m" m per range of the ordered Legendre analysis (PXS_PART_GB; of the last map); "theta" components
+ *   per pass of a theta chain (PXS_CHAIN_SCRATCH_GB); "ring" ring pairs per pass of the two ring FFT stages (PXS_RING_CHUNK_MB);
+ *   "resample" column pairs or columns per pass of an unfused theta resampler (PXS_RESAMPLE_MB; at least 32); "leg_valu" / "leg_mm" maps
+ *   per launch of the single-map / FP64-MFMA Legendre kernels (option "leg_max_batch"); of a batched call in several passes: those of
+ *   its last pass.  "passes_fft" is device-wide and takes plan = NULL (the current device) as well: lines per pass of the most recent
+ *   four-step transform of the FFT engine (PXS_FFT_TEMP_MB), whoever issued it.  Diagnostics: not synchronised with calls in flight. */
 int pxs_plan_query(const pxs_plan* plan, const char* name, int64_t* value);
 
 /* ducc0.sht.experimental.get_gridweights (curvedsky.py:501, 855): out[ntheta], sum = 4 pi. Host memory. */

@@ -30,7 +30,7 @@ def _declare(lib):
 	lib.pxs_grid_maxlmax.argtypes = [c.c_char_p, i32]
 	lib.pxs_plan_info.argtypes = [vp, c.POINTER(i32), c.POINTER(i32), c.POINTER(i64)]
 	lib.pxs_plan_option.argtypes = [vp, c.c_char_p, i64]
-	lib.pxs_plan_query.argtypes = [vp, c.c_char_p, c.POINTER(i64)]      # names: include/pxsht.h ("analysis_form", "ncc_circle", "ducc_ncc_circle", "theta_line", "chain_stages", "chain_static", "chain_static_table")
+	lib.pxs_plan_query.argtypes = [vp, c.c_char_p, c.POINTER(i64)]      # names: include/pxsht.h ("analysis_form", "ncc_circle", "ducc_ncc_circle", "theta_line", "chain_stages", "chain_static", "chain_static_table", "passes_<seam>": plan may be NULL for "passes_fft")
 	lib.pxs_profile.argtypes = [vp, i32]; lib.pxs_profile_read.argtypes = [vp, vp, vp, i32]; lib.pxs_profile_flops.argtypes = [vp, vp, i32]
 	lib.pxs_debug_theta_plan.argtypes = [i64, i32, vp]; lib.pxs_debug_chain.argtypes = [vp, i32, i32, i32, i32, vp]
 	lib.pxs_memory.argtypes = [i32, vp]

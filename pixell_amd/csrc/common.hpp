@@ -103,4 +103,22 @@ inline const char* lab_getenv(const char* name) { return getenv(name); }
 inline const char* lab_getenv(const char*) { return nullptr; }
 #endif
 
+// A memory budget of the product's environment (PXS_*_GB: shift 30, PXS_*_MB: shift 20): a real number of that unit, so that
+// PXS_BATCH_GB=0.004 means 4 MB and whole numbers mean what they always did.  false: unset or empty (the caller keeps its default).
+// Read where it applies -- as a plan is made or per call -- never once per process.
+inline bool env_budget(const char* name, int shift, size_t& bytes) {
+	const char* e = getenv(name);
+	if (!e || !*e) return false;
+	const double v = strtod(e, nullptr);
+	bytes = v > 0 ? (size_t)(v*(double)(size_t(1) << shift)) : 0;
+	return true;
+}
+// The passes a call took at one of the places where the library cuts it to stay within such a budget, counted by the loop that
+// launches them (pxs_plan_query "passes_<seam>"): n passes, the sizes of the first, the last and the one before the last
+struct PassLog {
+	long n = 0, first = 0, prev = 0, last = 0;
+	void begin() { n = first = prev = last = 0; }
+	void add(long size) { if (n == 0) first = size; prev = n ? last : 0; last = size; n++; }
+};
+
 } // namespace pxs

@@ -604,7 +604,8 @@ void FftContext::exec(hipStream_t st, long n, bool forward, const FftDims& d, co
 	auto s1 = sub(n1); auto s2 = sub(n2);
 	const double2* btw = bigtw(n);
 	// chunk lines so that the scratch stays below temp_budget
-	long lines_budget = std::max<long>(1, (long)(temp_budget/(sizeof(double2)*n)));
+	size_t budget = temp_budget; env_budget("PXS_FFT_TEMP_MB", 20, budget);
+	long lines_budget = std::max<long>(1, (long)(budget/(sizeof(double2)*n)));
 	DevBuf* tbuf = nullptr;
 	{
 		std::lock_guard<std::mutex> g(mu_);
@@ -616,10 +617,12 @@ void FftContext::exec(hipStream_t st, long n, bool forward, const FftDims& d, co
 	long o1_per = 1, i_per = d.n_i;
 	if (d.n_i <= lines_budget) { o1_per = std::min<long>(d.n_o1, std::max<long>(1, lines_budget/d.n_i)); }
 	else i_per = lines_budget;
+	pass_lines.begin();
 	for (long o2 = 0; o2 < d.n_o2; o2++)
 	for (long o1 = 0; o1 < d.n_o1; o1 += o1_per)
 	for (long i0 = 0; i0 < d.n_i; i0 += i_per) {
 		long no1 = std::min(o1_per, d.n_o1 - o1), ni = std::min(i_per, d.n_i - i0);
+		pass_lines.add(no1*ni);
 		KArgs a = k;
 		a.d.n_o1 = no1; a.d.n_o2 = 1; a.i_base = i0; a.i_count = ni;
 		// shift base pointers

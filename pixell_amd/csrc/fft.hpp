@@ -66,7 +66,8 @@ public:
 	SubView view(long n, int maxr = 1000);      // maxr: largest composite register radix the calling kernel has compiled in
 	const double2* twiddle_table(long n) { return bigtw(n); }
 	void release_stream(hipStream_t st) { std::lock_guard<std::mutex> g(mu_); temps_.erase(st); }   // four-step scratch of a stream that is going away
-	size_t temp_budget = size_t(4) << 30;   // bytes of four-step scratch per stream (set from the free memory in the constructor)
+	size_t temp_budget = size_t(4) << 30;   // bytes of four-step scratch per stream (set from the free memory in the constructor; PXS_FFT_TEMP_MB, read per exec, overrides)
+	PassLog pass_lines;                     // passes of the most recent four-step exec on this device, lines per pass (pxs_plan_query(NULL, "passes_fft"))
 private:
 	int device_;
 	std::mutex mu_;

@@ -926,9 +926,9 @@ ThetaPlan FftChain::plan_theta(long N, int lmax) {
 // trip): all at once 47.3, 2048 MB 46.7, 512 MB 47.6, 200 MB 50.9, 128 MB 49.3, 64 MB 55.4 -- the cache does not pay for the
 // shorter launches.
 static long ring_chunk(long npair, long bytes_per_pair, int mult) {
-	static const long mb = [] { const char* e = getenv("PXS_RING_CHUNK_MB"); return e ? atol(e) : 0L; }();
-	if (mb <= 0) return npair;
-	long q = std::max<long>(mult, ((mb << 20)/std::max<long>(bytes_per_pair, 1))/mult*mult);
+	size_t budget = 0; env_budget("PXS_RING_CHUNK_MB", 20, budget);      // (per call)
+	if (budget == 0) return npair;
+	long q = std::max<long>(mult, ((long)budget/std::max<long>(bytes_per_pair, 1))/mult*mult);
 	return std::min(q, npair);
 }
 
@@ -1011,8 +1011,10 @@ void FftChain::map2leg(hipStream_t st, const MapDesc& m, int nc, int mmax, doubl
 	const int T2 = pair_lines<StRingA2>(b, 2*npair_all);
 	const long qchunk = ring_chunk(npair_all, (long)sizeof(double2)*nc*a*ldY, T2/2);
 	ensure1(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
+	if (!dry_) pass_ring.begin();
 	for (long q_lo = 0; q_lo < npair_all; q_lo += qchunk) {
 		const long npair = std::min(qchunk, npair_all - q_lo);
+		if (!dry_) pass_ring.add(npair);
 		const int nring = m.nring - (int)(2*q_lo);           // rings from the first pair of this pass on (the odd-last-ring tests are local)
 		{	StRingA1 s = new_stage<StRingA1>(a, 0);
 			s.m = map_addr(m); s.m.off0 += 2*q_lo*m.ring_stride; s.m.nring = nring;
@@ -1033,12 +1035,15 @@ void FftChain::map2leg(hipStream_t st, const MapDesc& m, int nc, int mmax, doubl
 
 void FftChain::h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& m, int nc, int mmax, long hcomp) {
 	PXS_REQUIRE(rings_ok() && m.nphi == nphi_, "internal: ring chain not planned");
+	if (!dry_) pass_ring.begin();
 	if (dry_ ? line_h2map_takes(nphi_, mmax) : line_h2map(st, h, ldh, m, nc, mmax, hcomp)) return;      // (ring lengths compiled into ringline.hip: one kernel, no intermediate)
 	const long npair_all = (m.nring + 1)/2, a = rs_.a, b = rs_.b, ldY = pad8(b);
 	const long qchunk = ring_chunk(npair_all, (long)sizeof(double2)*nc*a*ldY, 1);
 	ensure1(sizeof(double2)*(size_t)nc*qchunk*a*ldY);
+	if (!dry_) pass_ring.begin();
 	for (long q_lo = 0; q_lo < npair_all; q_lo += qchunk) {
 		const long npair = std::min(qchunk, npair_all - q_lo);
+		if (!dry_) pass_ring.add(npair);
 		const int nring = m.nring - (int)(2*q_lo);
 		{	StRingS1 s = new_stage<StRingS1>(a, 0);
 			s.h = h + 2*q_lo*ldh; s.ldh = ldh; s.hcomp = hcomp > 0 ? hcomp : m.nring; s.b = (int)b; s.X = (int)nphi_; s.npair = (int)npair; s.nring = nring; s.mmax = mmax;
@@ -1058,7 +1063,7 @@ void FftChain::h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& 
 
 // components per pass of a theta chain: all of them unless the two ping-pong buffers would exceed PXS_CHAIN_SCRATCH_GB (12) each
 static int theta_comp_chunk(int nc, size_t need1_per_comp, size_t need2_per_comp) {
-	static const size_t budget = [] { const char* e = getenv("PXS_CHAIN_SCRATCH_GB"); return (size_t)(e ? atol(e) : 12) << 30; }();
+	size_t budget = (size_t)12 << 30; env_budget("PXS_CHAIN_SCRATCH_GB", 30, budget);      // (per call: the sizing of the scratch and the loop read the same value)
 	const size_t per = sizeof(double2)*std::max(need1_per_comp, need2_per_comp);
 	return (int)std::max<size_t>(1, std::min<size_t>((size_t)nc, budget/std::max<size_t>(per, 1)));
 }
@@ -1088,12 +1093,17 @@ template<class F> void FftChain::theta_chunks(ThetaOp op, const ThetaCall& c, F&
 	const int nc = c.nc; size_t n1, n2; theta_need(op, *c.tp, c.nm, n1, n2);
 	const int cchunk = theta_comp_chunk(nc, n1, n2);
 	ensure1(sizeof(double2)*n1*cchunk); ensure2(sizeof(double2)*n2*cchunk);
-	for (int c0 = 0; c0 < nc; c0 += cchunk) stages(c0, (long)std::min(cchunk, nc - c0));
+	if (!dry_) pass_theta.begin();
+	for (int c0 = 0; c0 < nc; c0 += cchunk) {
+		if (!dry_) pass_theta.add(std::min(cchunk, nc - c0));
+		stages(c0, (long)std::min(cchunk, nc - c0));
+	}
 	if (!dry_) PXS_HIP(hipGetLastError());
 }
 
 // The four stage lists.  c.map is leg on the map's rings for the two that read them, h for the two that write them.
 void FftChain::theta(hipStream_t st, ThetaOp op, const ThetaCall& c) {
+	if (!dry_) pass_theta.begin();      // (stays empty where the single-kernel form takes the call)
 	if (op == TH_TO_CC) to_cc(st, c); else if (op == TH_FROM_CC_ADJ) from_cc_adjoint(st, c); else if (op == TH_FROM_CC) from_cc(st, c); else if (op == TH_TO_CC_ADJ) to_cc_adjoint(st, c);
 }
 

@@ -90,6 +90,9 @@ public:
 	int static_check(int maxr = 0);      // table entries (of the stages with this largest radix; 0: all) against the engine's plans; throws on a mismatch
 	static bool static_has(int sid, int na, int nb, int T);
 	static void static_shapes(std::vector<ChainShape>& out);
+	// passes of the most recent theta chain (components per pass) and of the most recent map2leg / h2map through the two ring stages
+	// (ring pairs per pass; none where the single-kernel form took the call); a dry run leaves them alone
+	PassLog pass_theta, pass_ring;
 private:
 	void ensure1(size_t b) { if (!dry_) s1_.ensure(b); }
 	void ensure2(size_t b) { if (!dry_) s2_.ensure(b); }

@@ -538,9 +538,11 @@ static LegK make_legk_mm(const RingSet& rs, const LegTables& tb, LegWork& wk, do
 // small-ring, high-lmax maps goes out as several launches instead of tripping make_legk's grid check)
 // (the spin MFMA runs used to be cut at half the spin-0 synthesis limit and at the limit of 128 pairs per workgroup: lower than the grid needs; now every form is cut by its own
 // pairs per workgroup.  Out of reach at real sizes: tens of thousands of maps in one call)
-static int leg_max_batch(const RingSet& rs, const LegTables& tb, int pairs) {
+// (cap: pxs_plan_option "leg_max_batch", 0 = none: a lower bound for the tests of the launch seam, which the grid limit never reaches)
+static int leg_max_batch(const RingSet& rs, const LegTables& tb, int pairs, int cap) {
 	const long nwave = (rs.npairs + (long)pairs - 1)/pairs, per_m = ((1L << 31) - 1)/(8L*((tb.mmax + 1 + 7)/8));      // blocks per m one grid can hold: nwave nb, or one more (leg_blocks_per_m)
-	return (int)std::max<long>(1, std::min<long>(1 << 20, (per_m - 1)/std::max<long>(nwave, 1)));
+	const long grid = std::max<long>(1, std::min<long>(1 << 20, (per_m - 1)/std::max<long>(nwave, 1)));
+	return (int)(cap > 0 ? std::min<long>(grid, cap) : grid);
 }
 // seeds of (ring set, spin, direction, K): allocate on first use if the plan's budget allows; returns the mode for this launch.
 // The step a seed records depends on the rule that ends phase A (LEG_LIVE).  That rule is a compile-time constant of the library, and
@@ -548,7 +550,7 @@ static int leg_max_batch(const RingSet& rs, const LegTables& tb, int pairs) {
 // under; the two directions of a plan record their own seeds (dir is part of the key) under the same constant.
 static LegWork::Seeds* seeds_for(LegWork& wk, const RingSet& rs, const LegTables& tb, int dir, int K, LegK& a) {
 	a.seed_mode = 0; a.seed_d = nullptr; a.seed_i = nullptr;
-	{ const char* e = getenv("PXS_SEED_GB"); if (e) wk.seed_budget = (size_t)atol(e) << 30; }
+	env_budget("PXS_SEED_GB", 30, wk.seed_budget);
 	if (wk.seed_budget == 0) return nullptr;
 	// loading a seed costs 20 / 40 bytes per lane and m, running phase A ~0.09 lmax recurrence steps: measured on MI355X the seeds
 	// win at lmax 10^4 (C3 341.8 -> 327.6 ms per round trip) and for spin 2 at lmax 4000 (C2 28.7 -> 28.0 ms), and lose for spin 0
@@ -635,8 +637,8 @@ static int k_small_grid(const RingSet& rs, int kdef, std::initializer_list<int> 
 enum LegForm { LEG_VALU, LEG_MM8, LEG_MM4 };
 struct LegLaunch { int b0, n; LegForm form; int ng; };      // maps [b0, b0 + n); ng: groups of 4 maps per wave / workgroup (MFMA forms)
 static int mm_min(const char* name) { const char* e = getenv(name); const int x = e ? atoi(e) : 4; return x <= 0 ? (1 << 30) : std::max(2, x); }
-static int syn_mm_min() { static const int v = mm_min("PXS_SYN_MM_MIN"); return v; }
-static int ana_mm_min() { static const int v = mm_min("PXS_ANA_MM_MIN"); return v; }
+static int syn_mm_min() { return mm_min("PXS_SYN_MM_MIN"); }      // (read per call, like the budgets)
+static int ana_mm_min() { return mm_min("PXS_ANA_MM_MIN"); }
 // seeds_pending: will a VALU launch record seeds; max_valu / max_mm8: maps one launch can take (grid limit).  seeds_pending is a callable, not a bool, because asking
 // ALLOCATES the seed buffers of the VALU kernel (seeds_for): it is asked only where the parent asked, with more than one map left to the VALU kernel
 static std::vector<LegLaunch> leg_batch_plan(int nb, int spin, bool analysis, int deriv1, bool deterministic, const std::function<bool()>& seeds_pending, int max_valu, int max_mm8) {
@@ -676,9 +678,11 @@ void leg_synthesis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWo
 	if (tb.spin == 0) hipLaunchKernelGGL(alm_pre_s0, alm_grid(tb.lmax/2 + 1, nm, nb), dim3(256), 0, st, ak);
 	else              hipLaunchKernelGGL(alm_pre_spin, alm_grid(tb.lmax + 1, nm, nb), dim3(256), 0, st, ak);
 	const std::vector<LegLaunch> plan = leg_batch_plan(nb, tb.spin, false, deriv1, wk.deterministic, [&] { return seeds_pending(wk, rs, tb, 0, K); },
-		leg_max_batch(rs, tb, 64*K), 8*leg_max_batch(rs, tb, mm_pairs));
+		leg_max_batch(rs, tb, 64*K, wk.max_batch), 8*leg_max_batch(rs, tb, mm_pairs, wk.max_batch));
 	print_batch_plan(false, tb.spin, nb, plan);
+	wk.pass_valu.begin(); wk.pass_mm.begin();
 	for (const LegLaunch& l : plan) {
+		(l.ng ? wk.pass_mm : wk.pass_valu).add(l.n);
 		double2* legl = leg + (size_t)l.b0*leg_bstride;
 		if (l.ng) ensure_coef2(st, tb);
 		LegK a = l.ng ? make_legk_mm(rs, tb, wk, legl, ld, mm_pairs, l.n, l.ng, leg_bstride) : make_legk(rs, tb, wk, legl, ld, 64*K, l.n, leg_bstride);
@@ -721,10 +725,12 @@ static void leg_analysis_valu(hipStream_t st, const RingSet& rs, const LegTables
 		wk.first.ensure(sizeof(int)*(size_t)nwave*maxm);
 	}
 	LegWork::Seeds* seeds = nullptr;
+	wk.pass_m.begin();
 	for (size_t c = 0; c+1 < cuts.size(); c++) {
 		const int m0 = cuts[c], m1 = cuts[c+1];
 		const long rows = tb.row[m1]-tb.row[m0];
 		if (rows <= 0) continue;
+		wk.pass_m.add(m1 - m0);
 		LegK a = make_legk(rs, tb, wk, const_cast<double2*>(leg), ld, 64*K, nb, leg_bstride);
 		a.mom = mom; a.m0 = m0; a.rowbase = tb.row[m0]; a.rows_chunk = rows; a.nmc = m1-m0; a.atomic = atomic ? 1 : 0;
 		seeds = seeds_for(wk, rs, tb, 1, K, a); seeds_wait(seeds, st);
@@ -755,12 +761,14 @@ void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWor
 	const int nm = tb.mmax+1;
 	const int mm_pairs = (tb.spin == 0 ? 64 : 32)*MM_WAVES;      // ring pairs per workgroup of the MFMA form
 	const std::vector<LegLaunch> plan = leg_batch_plan(nb, tb.spin, true, deriv1, wk.deterministic, [&] { return seeds_pending(wk, rs, tb, 1, K); },
-		leg_max_batch(rs, tb, 64*K), 8*leg_max_batch(rs, tb, mm_pairs));
+		leg_max_batch(rs, tb, 64*K, wk.max_batch), 8*leg_max_batch(rs, tb, mm_pairs, wk.max_batch));
 	print_batch_plan(true, tb.spin, nb, plan);
 	const size_t nmom = (size_t)leg_mom_stride(tb);
 	wk.mom.ensure(sizeof(double)*nmom*nb);
 	if (!wk.deterministic) PXS_HIP(hipMemsetAsync(wk.mom.p, 0, sizeof(double)*nmom*nb, st));      // (the ordered scheme writes every row it reads)
+	wk.pass_valu.begin(); wk.pass_mm.begin();
 	for (const LegLaunch& l : plan) {
+		(l.ng ? wk.pass_mm : wk.pass_valu).add(l.n);
 		const double2* legl = leg + (size_t)l.b0*leg_bstride;
 		double* mom = wk.mom.as<double>() + nmom*l.b0;
 		if (!l.ng) { leg_analysis_valu(st, rs, tb, wk, K, legl, mom, prof, ld, l.n, leg_bstride); continue; }

@@ -34,15 +34,14 @@ void plan_common(pxs_plan* p, int lmax, int mmax, const uint64_t* mstart, int64_
 	std::vector<uint64_t> ms(mstart, mstart+mmax+1);
 	p->d_mstart = upload(ms);
 	p->fc = &fft_context(device);
-	{ const char* e = getenv("PXS_FFT_TEMP_MB"); if (e) p->fc->temp_budget = (size_t)atol(e) << 20; }
 	{	// scratch for the per-wave partial moments of the analysis: 16 GiB where the device has room (MI355X: 288 GB),
 		// never more than 1/8 of what is free now.  Measured at config 3: 4 GiB 448.8, 8 GiB 442.7, 16 GiB 438.0, 24 GiB 437.7 ms.
 		size_t fr = 0, tot = 0;
 		if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0) p->wk.part_budget = std::min<size_t>(size_t(2) << 30, std::max<size_t>(fr/8, size_t(256) << 20));      // (ordered analysis only: <= 2 GB of partial moments, m in chunks)
-		const char* e = getenv("PXS_PART_GB"); if (e) p->wk.part_budget = (size_t)atol(e) << 30;
+		env_budget("PXS_PART_GB", 30, p->wk.part_budget);      // (0: one m per pass)
 		{ const char* d = getenv("PXS_DETERMINISTIC"); p->wk.deterministic = d && atoi(d) != 0; }      // default of pxs_plan_option("deterministic")
 	}
-	{ const char* e = getenv("PXS_RESAMPLE_MB"); if (e) p->resample_chunk_bytes = (size_t)atol(e) << 20; }
+	env_budget("PXS_RESAMPLE_MB", 20, p->resample_chunk_bytes);
 	{ const char* e = getenv("PXS_ANALYSIS"); if (e) { const std::string v(e); p->ana_weights = v == "weights" ? 1 : (v == "ducc0" ? 2 : (v == "interpolant" ? 0 : p->ana_weights)); } }
 	if (p->general) return;      // per-ring lengths and phases: see GenRings::setup
 	std::string why;
@@ -286,6 +285,9 @@ int pxs_plan_option(pxs_plan* p, const char* name, int64_t value) {
 		PXS_REQUIRE(value >= 0 && value <= p->lmax + 1, "pxs_plan_option: build_tables takes a spin");
 		PXS_HIP(hipSetDevice(p->device));
 		(void)p->table((int)value);
+	} else if (std::string(name) == "leg_max_batch") {      // upper bound on the maps of one Legendre launch (8 x as many for the MFMA form); 0: the grid limit alone
+		PXS_REQUIRE(value >= 0 && value <= (1 << 20), "pxs_plan_option: leg_max_batch takes 0 (no bound) or a number of maps");
+		p->wk.max_batch = (int)value;
 	} else throw Error(PXS_ERR_ARG, std::string("pxs_plan_option: unknown option '") + name + "'");
 	PXS_CATCH
 }
@@ -341,8 +343,28 @@ static std::vector<ChainShape> chain_shapes(const pxs_plan* cp) {
 }
 int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	PXS_TRY
-	PXS_REQUIRE(p && name && value, "pxs_plan_query: null argument");
+	PXS_REQUIRE(name && value, "pxs_plan_query: null argument");
 	const std::string n(name);
+	if (n.compare(0, 7, "passes_") == 0) {      // passes of the most recent call at a memory-budget seam (include/pxsht.h), as its launch loop counted them
+		std::string seam = n.substr(7); int which = 0;      // 0: how many, 1 / 2 / 3: size of the first / the one before the last / the last
+		static const char* const sufs[3] = {"_first", "_prev", "_last"};
+		for (int i = 0; i < 3 && !which; i++) {
+			const size_t k = strlen(sufs[i]);
+			if (seam.size() > k && seam.compare(seam.size() - k, k, sufs[i]) == 0) { seam.resize(seam.size() - k); which = i + 1; }
+		}
+		const PassLog* l = nullptr;
+		if (seam == "fft") { int dev = p ? p->device : 0; if (!p) PXS_HIP(hipGetDevice(&dev)); l = &fft_context(dev).pass_lines; }      // device-wide: plan may be NULL
+		else {
+			PXS_REQUIRE(p && !p->pts, "pxs_plan_query: the passes of this seam belong to a grid or ring plan");
+			if (seam == "batch") l = &p->pass_batch; else if (seam == "resample") l = &p->pass_resample;
+			else if (seam == "leg_m") l = &p->wk.pass_m; else if (seam == "leg_valu") l = &p->wk.pass_valu; else if (seam == "leg_mm") l = &p->wk.pass_mm;
+			else if ((seam == "theta" || seam == "ring") && p->chain) l = seam == "theta" ? &p->chain->pass_theta : &p->chain->pass_ring;
+		}
+		if (!l) throw Error(PXS_ERR_ARG, std::string("pxs_plan_query: unknown name '") + name + "'");
+		*value = which == 0 ? l->n : which == 1 ? l->first : which == 2 ? l->prev : l->last;
+		return 0;
+	}
+	PXS_REQUIRE(p, "pxs_plan_query: null argument");
 	if (p->pts) *value = points_query(p->pts, n);
 	else if (n == "analysis_form") { const Route r = analysis_route_now(p); *value = (r.kind == R_RING_WEIGHTS || r.kind == R_CC_WEIGHTS) ? 1 : (r.form->fine ? 2 : 0); }
 	else if (n == "ncc_circle") *value = p->th.ncc > 0 ? p->th.Ncc : 0;
@@ -605,7 +627,7 @@ static int batch_chunk(const pxs_plan* p, int nbatch, int ncm) {
 	const size_t per_map = sizeof(double2)*(size_t)ncm*((size_t)(p->mmax+1)*(p->nring + (p->th.ncc > 0 ? p->th.ncc : 0))*2 + (size_t)p->nring*p->nphi);
 	// scratch budget of one pass: PXS_BATCH_GB, default 64 GB (MI355X: 288 GB; 8 maps of config 5 = 56 GB, so that the batched Legendre kernels get
 	// their 8-map groups there; it was 32 in rounds 2-4), never more than 40 % of what is free on the device now beyond what the plan holds already
-	static const size_t budget_env = [] { const char* e = getenv("PXS_BATCH_GB"); return (size_t)(e ? atol(e) : 0) << 30; }();
+	size_t budget_env = 0; env_budget("PXS_BATCH_GB", 30, budget_env);      // (per call; unset or 0: the default rule)
 	size_t budget = budget_env ? budget_env : (size_t)64 << 30;
 	if (!budget_env) {
 		size_t fr = 0, tot = 0;
@@ -627,7 +649,13 @@ static void run_call(pxs_plan* p, bool analysis, int spin, int mode, int adjoint
 	const int chunk = r.batched ? batch_chunk(p, nbatch, r.nc) : 1;
 	if (getenv("PXS_CHAIN_VERBOSE")) fprintf(stderr, "[pxsht] %s route %s, adjoint %d, spin %d, analysis option %d, %d maps in passes of %d\n", analysis ? "analysis" : "synthesis", ROUTE_NAMES[r.kind], adjoint, spin, p->ana_weights, nbatch, chunk);
 	reserve_call(p, r, std::min(chunk, nbatch));
-	for (int b0 = 0; b0 < nbatch; b0 += chunk) run_core(p, r, spin, std::min(chunk, nbatch - b0), alm.from(b0), map.from(b0), st);
+	// the pass reports are those of THIS call: a seam the call does not come by reports no pass
+	p->pass_batch.begin(); p->pass_resample.begin(); p->wk.pass_m.begin(); p->wk.pass_valu.begin(); p->wk.pass_mm.begin();
+	if (p->chain) { p->chain->pass_theta.begin(); p->chain->pass_ring.begin(); }
+	for (int b0 = 0; b0 < nbatch; b0 += chunk) {
+		p->pass_batch.add(std::min(chunk, nbatch - b0));
+		run_core(p, r, spin, std::min(chunk, nbatch - b0), alm.from(b0), map.from(b0), st);
+	}
 }
 
 int pxs_synthesis(pxs_plan* p, int spin, int mode, int adjoint, int nbatch,

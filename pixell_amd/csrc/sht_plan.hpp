@@ -158,6 +158,9 @@ struct pxs_plan {
 	LegProfile prof;
 	size_t resample_chunk_bytes = size_t(1) << 40;    // per intermediate buffer of the unfused theta resamplers (chunking to stay in the
 	                                                  // Infinity Cache was measured slower: 22.4 -> 26.2 ms at config 2; PXS_RESAMPLE_MB re-enables it)
+	// passes of the plan's most recent call (pxs_plan_query "passes_batch", "passes_resample"): maps per pass of run_call; column pairs or
+	// columns per pass of the last unfused theta resampler.  The other seams keep theirs where they loop (wk, chain, the FFT context).
+	PassLog pass_batch, pass_resample;
 
 	LegTables& table(int spin) {
 		auto& p = tables[spin]; if (!p) { p.reset(new LegTables()); p->build(lmax, mmax, spin); }

@@ -240,9 +240,11 @@ void resample_to_cc(pxs_plan* p, hipStream_t st, const double2* leg_in, double2*
 	const ThetaTables& t = p->th; const int nm = p->mmax+1, nr = p->nring; const long M = f.M, N = t.N, Ncc = t.Ncc;
 	const long npair_all = (nm + 1)/2, chunk = resample_chunk(p, npair_all, M);
 	StageScope stage(p->prof, st, PXS_STAGE_RESAMPLE);
+	p->pass_resample.begin();      // (the passes of the last component: every component takes the same ones)
 	for (int c = 0; c < nc; c++)
 	for (long p0 = 0; p0 < npair_all; p0 += chunk) {
 		const long np = std::min<long>(chunk, npair_all - p0);
+		if (c == nc - 1) p->pass_resample.add(np);
 		const long m0 = 2*p0, nlines = std::min<long>(2*np, nm - m0);
 		{	// (a) packed mirror extension of lines (2i, 2i+1), forward FFT_N
 			FftLoad ld; ld.ptr = leg_in + ((size_t)c*nm + m0)*nr; ld.mode = LD_MIRROR_PAIR; ld.ne = nr; ld.mir_c = t.mir_c;
@@ -277,9 +279,11 @@ void resample_to_cc_adjoint(pxs_plan* p, hipStream_t st, const double2* leg_cc, 
 	const ThetaTables& t = p->th; const int nm = p->mmax+1, nr = p->nring; const long M = f.M, N = t.N, Ncc = t.Ncc;
 	const long chunk = resample_chunk(p, nm, M);
 	StageScope stage(p->prof, st, PXS_STAGE_RESAMPLE);
+	p->pass_resample.begin();      // (the passes of the last component: every component takes the same ones)
 	for (int c = 0; c < nc; c++)
 	for (long m0 = 0; m0 < nm; m0 += chunk) {
 		const long nl = std::min<long>(chunk, nm - m0);
+		if (c == nc - 1) p->pass_resample.add(nl);
 		{	// (d)^H: weights, zero-extend the rings to the Ncc circle, forward FFT_Ncc
 			FftLoad ld; ld.ptr = leg_cc + ((size_t)c*nm + m0)*t.ncc; ld.ne = t.ncc; ld.mul = f.wcc.as<double2>();
 			FftStore sf; sf.ptr = p->b1.p;
@@ -314,9 +318,11 @@ void resample_from_cc(pxs_plan* p, hipStream_t st, const double2* leg_cc, double
 	const ThetaTables& t = p->th; const int nm = p->mmax+1, nr = p->nring; const long N = t.N, Ncc = t.Ncc;
 	const long npair_all = (nm + 1)/2, chunk = resample_chunk(p, npair_all, N);
 	StageScope stage(p->prof, st, PXS_STAGE_RESAMPLE);
+	p->pass_resample.begin();      // (the passes of the last component: every component takes the same ones)
 	for (int c = 0; c < nc; c++)
 	for (long p0 = 0; p0 < npair_all; p0 += chunk) {
 		const long np = std::min<long>(chunk, npair_all - p0);
+		if (c == nc - 1) p->pass_resample.add(np);
 		const long m0 = 2*p0, nlines = std::min<long>(2*np, nm - m0);
 		{	// packed mirror extension of the CC rings to the full circle, forward FFT_Ncc
 			FftLoad ld; ld.ptr = leg_cc + ((size_t)c*nm + m0)*t.ncc; ld.mode = LD_MIRROR_PAIR; ld.ne = t.ncc; ld.mir_c = 0;

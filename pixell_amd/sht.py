@@ -94,17 +94,39 @@ class Plan:
 		return f[0], f[1]
 	def set_option(self, name, value):
 		"""pxs_plan_option: "analysis" = 2 (ducc0's route, the default) | 0 (full theta-interpolant) | 1 (ring weights + adjoint synthesis where ntheta >= 2 lmax + 2);
-		"deterministic" = 0 | 1 (ordered, bitwise repeatable analysis sums; see set_deterministic)"""
+		"deterministic" = 0 | 1 (ordered, bitwise repeatable analysis sums; see set_deterministic);
+		"leg_max_batch" = n (at most n maps per single-map Legendre launch, 8 n per FP64-MFMA launch; 0: the grid limit alone -- for tests)"""
 		_lib.check(_lib.load().pxs_plan_option(self.handle, name.encode(), int(value)))
 	def query(self, name):
-		"""pxs_plan_query: "analysis_form", "ncc_circle", "ducc_ncc_circle", "theta_line", "chain_stages", "chain_static", "chain_static_table" """
+		"""pxs_plan_query: "analysis_form", "ncc_circle", "ducc_ncc_circle", "theta_line", "chain_stages", "chain_static", "chain_static_table",
+		"passes_<seam>" (see passes) """
 		v = ctypes.c_int64()
 		_lib.check(_lib.load().pxs_plan_query(self.handle, name.encode(), ctypes.byref(v)))
 		return int(v.value)
+	def passes(self, seam):
+		"""the passes the plan's most recent call took at a memory-budget seam (pxs_plan_query "passes_<seam>", counted by the loop
+		that launched them): dict(n=how many, first=, prev=, last= sizes of the first pass, the one before the last and the last).
+		seam: "batch" (maps per pass, PXS_BATCH_GB), "leg_m" (m per range of the ordered analysis, PXS_PART_GB), "theta" (components per
+		pass of a theta chain, PXS_CHAIN_SCRATCH_GB), "ring" (ring pairs per pass of the ring FFT stages, PXS_RING_CHUNK_MB), "resample"
+		(column pairs or columns per pass of an unfused theta resampler, PXS_RESAMPLE_MB), "leg_valu" / "leg_mm" (maps per VALU / MFMA
+		Legendre launch, option "leg_max_batch"), "fft" (see fft_passes)"""
+		return _passes(self.handle, seam)
 	def info(self):
 		a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
 		_lib.check(_lib.load().pxs_plan_info(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
 		return dict(nring_syn=a.value, nring_ana=b.value, scratch_bytes=c.value)
+
+def _passes(handle, seam):
+	out = {}
+	for key, suffix in (("n", ""), ("first", "_first"), ("prev", "_prev"), ("last", "_last")):
+		v = ctypes.c_int64()
+		_lib.check(_lib.load().pxs_plan_query(handle, ("passes_" + seam + suffix).encode(), ctypes.byref(v)))
+		out[key] = int(v.value)
+	return out
+def fft_passes():
+	"""lines per pass of the most recent four-step FFT on the current device (PXS_FFT_TEMP_MB; pxs_plan_query(NULL, "passes_fft")), as
+	Plan.passes reports the plan-bound seams"""
+	return _passes(None, "fft")
 
 class _PlanCache:
 	"""least-recently-used cache of pxs_plan handles: a plan owns device scratch (tens of GB at the largest configurations), so a
