@@ -42,18 +42,20 @@ namespace pxs {
 	}
 
 // two fast steps of the spin-0 synthesis (lam1/lam2 swap roles)
-#define S0_SYN_PAIR(c0, c1, a0, a1) { \
-	PXS_VCOPY(vb0, polar ? c0.c : c0.b); \
-	PXS_VCOPY(vb1, polar ? c1.c : c1.b); \
+#define S0_SYN_PAIR(c0, c1, a0, a1) S0_SYN_PAIR_C(c0.a, polar ? c0.c : c0.b, c1.a, polar ? c1.c : c1.b, a0, a1)
+// ... on the step coefficients themselves: (ca, cb) of a step = a and the additive constant
+#define S0_SYN_PAIR_C(ca0, cb0, ca1, cb1, a0, a1) { \
+	PXS_VCOPY(vb0, cb0); \
+	PXS_VCOPY(vb1, cb1); \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
 		p1r[s] = fma(lam2[s], a0.a, p1r[s]); p1i[s] = fma(lam2[s], a0.b, p1i[s]); \
 		p2r[s] = fma(lam2[s], a0.c, p2r[s]); p2i[s] = fma(lam2[s], a0.d, p2i[s]); \
-		lam1[s] = fma(fma(c0.a, csq[s], vb0), lam2[s], lam1[s]); \
+		lam1[s] = fma(fma(ca0, csq[s], vb0), lam2[s], lam1[s]); \
 	} \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
 		p1r[s] = fma(lam1[s], a1.a, p1r[s]); p1i[s] = fma(lam1[s], a1.b, p1i[s]); \
 		p2r[s] = fma(lam1[s], a1.c, p2r[s]); p2i[s] = fma(lam1[s], a1.d, p2i[s]); \
-		lam2[s] = fma(fma(c1.a, csq[s], vb1), lam1[s], lam2[s]); \
+		lam2[s] = fma(fma(ca1, csq[s], vb1), lam1[s], lam2[s]); \
 	} }
 
 // K = 4 is asked to fit 7 waves per SIMD (72 instead of 74 VGPRs, no spills): the synthesis kernels are short of waves, not of
@@ -112,24 +114,31 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 		}
 #pragma unroll
 		for (int s = 0; s < K; s++) if (sc[s] < 0) { p1r[s] = p1i[s] = p2r[s] = p2i[s] = 0; lam1[s] = lam2[s] = 0; }   // never reached scale 0
-		// phase C: fast loop, two steps per iteration (lam1/lam2 swap roles, no register moves),
-		// coefficients of the next iteration prefetched with scalar loads (tables are padded by 2 rows)
-		double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1), a0 = LDC(at, k), a1 = LDC(at, k+1);
-		// two pairs per iteration on alternating row sets: the prefetched rows are consumed where they landed (the single-pair loop
-		// rotated them with 8-16 s_mov_b64 per pair; SALU was 27-45 % of the VALU count, profiles/r04_leg_sq_counters_c3.txt)
+		// phase C: fast loop, two steps per pair (lam1/lam2 swap roles, no register moves), two pairs per trip on alternating row sets: the prefetched rows are consumed
+		// where they landed (a single-pair loop rotated them with 8-16 s_mov_b64 per pair; SALU was 27-45 % of the VALU count, profiles/r04_leg_sq_counters_c3.txt).
+		// The rows are the compact ones, (a, b') with b' = b or, in polar waves, a + b, read with one drain per step pair and the rows of the next pair (table and
+		// pre-scaled alm) requested right behind it (legendre_dev.hpp, "Row prefetch")
+		const double2* __restrict__ cf = (const double2*)PXS_UNIFORM_LONG((long)((polar ? a.coef2p : a.coef2) + row0));
+		coef2x2_t f = LDC2(cf, k); double4_t a0 = LDC(at, k), a1 = LDC(at, k+1);
 		while (k + 3 < nk) {
-			double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3), m0 = LDC(at, k+2), m1 = LDC(at, k+3);
-			S0_SYN_PAIR(c0, c1, a0, a1)
-			k += 2;
-			c0 = LDC(coef, k+2); c1 = LDC(coef, k+3); a0 = LDC(at, k+2); a1 = LDC(at, k+3);
-			S0_SYN_PAIR(n0, n1, m0, m1)
-			k += 2;
+			PXS_ROWS_DRAIN();
+			coef2x2_t n = LDC2(cf, k+2); double4_t m0 = LDC(at, k+2), m1 = LDC(at, k+3);
+			PXS_ROWS_ISSUED();
+			S0_SYN_PAIR_C(f.a0, f.b0, f.a1, f.b1, a0, a1)
+			PXS_ROWS_DRAIN();
+			f = LDC2(cf, k+4); a0 = LDC(at, k+4); a1 = LDC(at, k+5);
+			PXS_ROWS_ISSUED();
+			S0_SYN_PAIR_C(n.a0, n.b0, n.a1, n.b1, m0, m1)
+			k += 4;
 		}
 		for (; k + 1 < nk; k += 2) {
-			const double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3), m0 = LDC(at, k+2), m1 = LDC(at, k+3);
-			S0_SYN_PAIR(c0, c1, a0, a1)
-			c0 = n0; c1 = n1; a0 = m0; a1 = m1;
+			PXS_ROWS_DRAIN();
+			const coef2x2_t n = LDC2(cf, k+2); const double4_t m0 = LDC(at, k+2), m1 = LDC(at, k+3);
+			PXS_ROWS_ISSUED();
+			S0_SYN_PAIR_C(f.a0, f.b0, f.a1, f.b1, a0, a1)
+			f = n; a0 = m0; a1 = m1;
 		}
+		PXS_ROWS_DRAIN();
 		if (k < nk) {
 #pragma unroll
 			for (int s = 0; s < K; s++) {
@@ -236,7 +245,8 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 				if (++sc[s] == 0) load_data(s);
 			}
 	}
-	// phase C: every lane at scale 0 (or without data): next coefficients prefetched with scalar loads
+	// phase C: every lane at scale 0 (or without data): next coefficients prefetched with scalar loads (the one-drain loop of leg_syn_s0, the drain between the two steps of
+	// a pair and the flush at that drain: 24.1 -> 23.5 ms at C3, inside three times the spread; not in the tree -- legendre_dev.hpp, "Row prefetch")
 	double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1);
 	while (k + 3 < nk) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
 		double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3);

@@ -184,7 +184,7 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 				pnr[s] = pni[s] = mnr[s] = mni[s] = qsr[s] = qsi[s] = nsr[s] = nsi[s] = 0;
 				S.gp1[s] = S.gp2[s] = S.gm1[s] = S.gm2[s] = 0;
 			}
-		// phase C: fast loop, next coefficients prefetched
+		// phase C: fast loop, next coefficients prefetched (with one drain per step pair and the next rows requested right behind it, as in leg_syn_s0: 67.8 -> 66.4 ms at C3, about three times the spread; not in the tree -- legendre_dev.hpp, "Row prefetch")
 		double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1), a0 = LDC(at, j), a1 = LDC(at, j+1);
 		while (j + 3 < nl) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
 			double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3), m0 = LDC(at, j+2), m1 = LDC(at, j+3);
@@ -324,7 +324,7 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 			if (was && S.scp[s] == 0 && S.scm[s] == 0) load_data(s);
 		}
 	}
-	// phase C: next coefficients prefetched
+	// phase C: next coefficients prefetched (with one drain per step pair, between its two steps, and the flush at that drain: 90.4 -> 89.1 ms at C3, inside three times the spread; not in the tree -- legendre_dev.hpp, "Row prefetch")
 	double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1);
 	while (j + 3 < nl) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
 		double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3);

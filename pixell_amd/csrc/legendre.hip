@@ -215,12 +215,13 @@ __global__ __launch_bounds__(256) void reduce_partials(const double* __restrict_
 	mom[r0*4 + i] = s;
 }
 
-// compact step table: (a, b) or (a, a + b) of the rows of LegTables::coef; 32 rows of padding (a tile reads 16 steps whatever nk is)
+// compact step table: (a, b) or (a, a + b) of the rows of LegTables::coef; 32 rows of padding (a tile reads 16 steps whatever nk is).  c2p: spin 0 only (null otherwise)
 __global__ __launch_bounds__(256) void coef2_kernel(const double4_t* __restrict__ coef, long nrows, double2* __restrict__ c2, double2* __restrict__ c2p) {
 	const long i = (long)blockIdx.x*blockDim.x + threadIdx.x;
 	if (i >= nrows + 32) return;
-	if (i < nrows) { const double4_t c = coef[i]; c2[i] = make_double2(c.a, c.b); c2p[i] = make_double2(c.a, c.c); }
-	else { c2[i] = make_double2(0, 0); c2p[i] = make_double2(0, 0); }
+	const double4_t c = i < nrows ? coef[i] : double4_t{0, 0, 0, 0};
+	c2[i] = make_double2(c.a, c.b);
+	if (c2p) c2p[i] = make_double2(c.a, c.c);
 }
 
 
@@ -364,6 +365,7 @@ void LegTables::build_host(int lmax_, int mmax_, int spin_) {
 	d_row = upload(row);
 	d_coef.alloc(sizeof(double4_t)*(size_t)(nrows + 4)); PXS_HIP(hipMemcpy(d_coef.p, coef, d_coef.bytes, hipMemcpyHostToDevice));
 	d_alpha.alloc(sizeof(double)*(size_t)(nrows + 4)); PXS_HIP(hipMemcpy(d_alpha.p, alpha, d_alpha.bytes, hipMemcpyHostToDevice));
+	build_compact();
 }
 
 
@@ -504,7 +506,18 @@ void LegTables::build(int lmax_, int mmax_, int spin_) {
 	if (spin == 0) hipLaunchKernelGGL(leg_tables_s0, grid, dim3(64), 0, (hipStream_t)0, lmax, mmax, d_row.as<long>(), d_start.as<dd>(), d_coef.as<double4_t>(), d_alpha.as<double>());
 	else           hipLaunchKernelGGL(leg_tables_spin, grid, dim3(64), 0, (hipStream_t)0, lmax, mmax, spin, d_row.as<long>(), d_start.as<dd>(), d_coef.as<double4_t>(), d_alpha.as<double>());
 	PXS_HIP(hipGetLastError());
-	PXS_HIP(hipDeviceSynchronize());      // (d_start goes out of scope; the tables are plan state, built once)
+	build_compact();      // (synchronises the device: d_start goes out of scope; the tables are plan state, built once)
+}
+
+// The compact step tables, built with the tables themselves: 16 bytes per row and table, i.e. half of d_coef again for the spin-s tables (0.8 GB next to 1.6 GB at lmax 10^4)
+// and as much as d_coef again for the two spin-0 ones (0.4 GB each next to 0.8 GB).  They used to be filled by the first batched transform on that call's stream, which
+// a first transform on another stream could overtake; now no transform ever sees them incomplete.
+void LegTables::build_compact() {
+	d_coef2.alloc(sizeof(double2)*(size_t)(nrows + 32));
+	if (spin == 0) d_coef2p.alloc(sizeof(double2)*(size_t)(nrows + 32));
+	hipLaunchKernelGGL(coef2_kernel, dim3((unsigned)((nrows + 32 + 255)/256)), dim3(256), 0, (hipStream_t)0, d_coef.as<double4_t>(), nrows, d_coef2.as<double2>(), d_coef2p.as<double2>());
+	PXS_HIP(hipGetLastError());
+	PXS_HIP(hipDeviceSynchronize());
 }
 
 // doubles per map of the pre-scaled alm / the moments of a batched call
@@ -523,6 +536,7 @@ static LegK make_legk(const RingSet& rs, const LegTables& tb, LegWork& wk, doubl
 	a.ofs = std::max(100.0, 0.01*tb.lmax);
 	a.nmc = a.nm; a.xcd = 1;      // (the XCD-aware block order, always: see leg_block)
 	a.count = wk.count_on ? wk.count.as<double>() : nullptr;
+	a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
 	a.nb = nb; a.leg_bs = leg_bs; a.almt_bs = leg_almt_stride(tb); a.mom_bs = leg_mom_stride(tb);
 	PXS_REQUIRE((long)8*((a.nm + 7)/8)*leg_blocks_per_m(a.nwave, nb) < (1L << 31), "internal: Legendre grid too large for one launch");
 	return a;
@@ -530,7 +544,7 @@ static LegK make_legk(const RingSet& rs, const LegTables& tb, LegWork& wk, doubl
 // ... of an MFMA launch: nmaps maps from `leg` on in groups of 4 ng, one group per wave (synthesis) or workgroup (analysis)
 static LegK make_legk_mm(const RingSet& rs, const LegTables& tb, LegWork& wk, double2* leg, long ld, int pairs, int nmaps, int ng, long leg_bs) {
 	LegK a = make_legk(rs, tb, wk, leg, ld, pairs, (nmaps + 4*ng - 1)/(4*ng), leg_bs);
-	a.nmaps = nmaps; a.coef2 = tb.d_coef2.as<double2>(); a.coef2p = tb.d_coef2p.as<double2>();
+	a.nmaps = nmaps;
 	return a;
 }
 
@@ -598,14 +612,6 @@ static AlmK make_almk(const LegTables& tb, LegWork& wk, const void* alm, int dty
 	return k;
 }
 
-static void ensure_coef2(hipStream_t st, const LegTables& tb) {      // compact step table (a, b) / (a, a + b), built by the first batched transform on the plan
-	if (tb.d_coef2.p) return;
-	tb.d_coef2.alloc(sizeof(double2)*(size_t)(tb.nrows + 32)); tb.d_coef2p.alloc(sizeof(double2)*(size_t)(tb.nrows + 32));
-	hipLaunchKernelGGL(coef2_kernel, dim3((unsigned)((tb.nrows + 32 + 255)/256)), dim3(256), 0, st, tb.d_coef.as<double4_t>(), tb.nrows, tb.d_coef2.as<double2>(), tb.d_coef2p.as<double2>());
-	// the table is plan state that later calls read on THEIR streams with no dependency on this launch: it is complete before the pointer is
-	// handed out (once per plan and spin; the seeds order themselves with events, LegTables::build synchronises the device likewise)
-	PXS_HIP(hipStreamSynchronize(st));
-}
 // Rings per lane of a small ring set.  (1) A wave of 64 K ring pairs takes the polar form of the recurrences (leg_wave_polar) only if its most equatorial ring
 // stays within 71.5 degrees of the pole, so on a grid of a few hundred rings the default K leaves the rings next to the poles in the plain form (l^2 eps there):
 // where a smaller compiled K makes the first wave eligible, take it.  (2) Up to 512 ring pairs (lmax ~1000) the launch is short of waves, not of work per wave
@@ -684,7 +690,6 @@ void leg_synthesis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWo
 	for (const LegLaunch& l : plan) {
 		(l.ng ? wk.pass_mm : wk.pass_valu).add(l.n);
 		double2* legl = leg + (size_t)l.b0*leg_bstride;
-		if (l.ng) ensure_coef2(st, tb);
 		LegK a = l.ng ? make_legk_mm(rs, tb, wk, legl, ld, mm_pairs, l.n, l.ng, leg_bstride) : make_legk(rs, tb, wk, legl, ld, 64*K, l.n, leg_bstride);
 		a.almt += (size_t)l.b0*a.almt_bs;
 		LegWork::Seeds* sb = nullptr;
@@ -772,7 +777,6 @@ void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWor
 		const double2* legl = leg + (size_t)l.b0*leg_bstride;
 		double* mom = wk.mom.as<double>() + nmom*l.b0;
 		if (!l.ng) { leg_analysis_valu(st, rs, tb, wk, K, legl, mom, prof, ld, l.n, leg_bstride); continue; }
-		ensure_coef2(st, tb);
 		LegK a = make_legk_mm(rs, tb, wk, const_cast<double2*>(legl), ld, mm_pairs, l.n, l.ng, leg_bstride);
 		a.mom = mom; a.part = mom; a.atomic = 1;
 		if (prof) prof->begin(st, 1);

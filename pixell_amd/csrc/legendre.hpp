@@ -23,7 +23,8 @@ struct LegTables {
 	std::vector<long> row;      // row[m]: first row of m; rows = k-steps (spin 0: two l per row) or l-steps (spin s)
 	long nrows = 0;
 	DevBuf d_row, d_coef, d_alpha;   // coef[row] = (a,b); alpha[row] = scaling folded into the alm
-	mutable DevBuf d_coef2, d_coef2p; // spin 0, batched analysis (leg_ana_s0_mm): compact rows (a, b) / (a, a + b), built on first use
+	DevBuf d_coef2, d_coef2p;        // compact rows (a, b) of every step and, spin 0 only, (a, a + b) for polar waves (phase C of leg_syn_s0, the MFMA kernels): built with the tables
+	void build_compact();            // d_coef2 / d_coef2p from d_coef; the device is idle when it returns
 	void build(int lmax, int mmax, int spin);        // on the GPU, double-double (legendre.hip)
 	void build_host(int lmax, int mmax, int spin);   // host threads, long double: the reference (PXS_TABLES_HOST=1, tests)
 };

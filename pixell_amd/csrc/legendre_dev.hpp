@@ -65,6 +65,41 @@ __device__ __forceinline__ double ldc_double(const double* p, long i) {
 #define LDCD(p, i) ldc_double((p), (i))
 #endif
 
+// Row prefetch in phase C of the spin-0 synthesis (leg_syn_s0).  A wave needs (a, b') of a step, b' = b or, in a polar wave, a + b: 16 bytes from the compact tables
+// LegK::coef2 / coef2p, two steps in one s_load_dwordx8.  Scalar loads return out of order, so the only wait there is for any of them is lgkmcnt(0), and it drains
+// whatever was requested a moment ago too: left to the compiler, the rows of the next step pair were requested at the bottom of the loop body and awaited at its top
+// (the per-step s_cselect between the polar and the plain column read a freshly loaded row), and every trip exposed a scalar-load latency.  The loop now has ONE
+// drain per step pair, PXS_ROWS_DRAIN, with the rows of the NEXT pair (table and pre-scaled alm) requested right behind it -- up to PXS_ROWS_ISSUED nothing else is
+// scheduled -- and nothing but the rows that were complete at the drain read before the next one: a full step pair of the wave's FMAs lies between request and wait
+// (tools/leg_prefetch_distance.py reads the distances off the assembly: 0-4 FMAs before, 12 K after).  The arithmetic is the same expression on the same values in
+// the same order.  Measured on MI355X at C3, parent and result in one session, launches with the seeds loaded (profiles/leg_prefetch_ab.txt): leg_syn_s0<4>
+// 20.29 -> 16.89 ms, its waitcnt share of the wave cycles 46 -> 25 %.
+// The same loop was built for the other three VALU kernels and is not in the tree: spin-s rows as (a, b) compact / three columns of the 32-byte rows in polar waves, the
+// analysis kernels with the drain BETWEEN the two steps of a pair (the ds_writes of the reduction, which count on lgkmcnt too, a step old there) and the flush of a full
+// tile at that drain.  Every load had its step pair of distance (24 K / 12 K FMAs), registers and waves per SIMD were the parent's, results bit for bit the parent's,
+// and the waitcnt share fell (leg_syn_spin<3> 29 -> 19 %, leg_ana_spin<4> 16 -> 7 %, leg_ana_s0<8> 21 -> 12 %) with the issue stalls rising by as much: at 3-4 waves per
+// SIMD the VALU-active share of a wave's cycles times the waves is 0.94-0.96 before and 0.98-1.0 after -- the other waves of the SIMD already issue into most of the
+// time one wave waits.  Kernel traces, parent / that build / parent in one session: leg_syn_spin<3> 67.85 / 66.37 / 67.71 ms, leg_ana_spin<4> 90.39 / 89.13 / 90.48,
+// leg_ana_s0<8> 24.01 / 23.51 / 24.16 (spreads 0.2-0.6): 0.6-1.4 ms each, at or inside three times the spread.  bench.py, parent / this code / that build alternating
+// in one session: C3 step 279.48 / 276.95 / 275.18 ms (spreads 1.3 / 1.1 / 0.9).  That build was measured and compared bit for bit on the Legendre-only calls but has
+// not been through the whole GPU suite: the three kernels keep their loops here, and putting them on this one is the next step (profiles/README.md).
+struct coef2x2_t { double a0, b0, a1, b1; };
+#ifdef PXS_HOST_SIM
+#define LDC2(p, i) (coef2x2_t{(p)[i].x, (p)[i].y, (p)[(i)+1].x, (p)[(i)+1].y})
+#define PXS_ROWS_DRAIN()
+#define PXS_ROWS_ISSUED()
+#else
+typedef double pxs_d4a16 __attribute__((ext_vector_type(4), aligned(16)));
+__device__ __forceinline__ coef2x2_t ldc_row2(const double2* p, long i) {
+	const __attribute__((address_space(4))) pxs_d4a16* c = (const __attribute__((address_space(4))) pxs_d4a16*)(unsigned long long)(p + i);
+	const pxs_d4a16 v = *c; coef2x2_t r; r.a0 = v.x; r.b0 = v.y; r.a1 = v.z; r.b1 = v.w; return r;
+}
+#define LDC2(p, i) ldc_row2((p), (i))
+// s_waitcnt lgkmcnt(0) (vmcnt and expcnt left open), as an instruction the compiler's own wait insertion sees
+#define PXS_ROWS_DRAIN() do { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define PXS_ROWS_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#endif
+
 struct LegK {
 	int lmax, mmax, spin, nm, npairs, nring, nwave;
 	long ld;                            // row stride of leg[m][ring] (>= nring; rows padded to whole 128-byte lines)
@@ -90,7 +125,7 @@ struct LegK {
 	// share the coefficient rows in L2 and the scalar cache.  Strides in elements of leg (double2), almt and mom (double).
 	int nb; long leg_bs, almt_bs, mom_bs;
 	int nmaps;                          // MFMA kernels (leg_ana_s0_mm): nb counts GROUPS of maps there, nmaps the maps themselves
-	const double2* coef2; const double2* coef2p;      // compact step table (a, b) / (a, a + b) of the MFMA kernels (LegTables::coef2)
+	const double2* coef2; const double2* coef2p;      // compact step tables (a, b) / (a, a + b; spin 0) (LegTables::d_coef2): phase C of the non-polar VALU waves, the MFMA kernels
 };
 // (PXS_NCOUNT slots, one picked by the block index: 200 000 waves adding to ONE address cost ~10 ms per C3 step and 24 ms per C4 step)
 #define PXS_NCOUNT 1024
