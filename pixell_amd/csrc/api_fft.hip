@@ -25,16 +25,14 @@ FftContext& fft_context(int device) {
 
 struct AxisDim { long n, is, os; };
 
-// transform along one axis of an N-d array; other dims become line dims (<= 3 after merging,
-// extra leading dims looped on the host)
-// ---- Bluestein (chirp-z) for lengths the mixed-radix engine cannot factor (a prime factor > 2048) -------------------
+// ---- Bluestein (chirp-z) for lengths the mixed-radix engine cannot factor (a prime factor > 2048) or is slow at (> 128) ----
 // X_k = w_k sum_j (x_j w_j) conj(w)_{k-j}, w_j = e^{-+ i pi j^2/n}: two FFTs of a 5-smooth length M >= 2n-1 with the chirp
 // multiplications and the zero padding as load / store functors (numpy, the reference's fallback engine, takes any n).
 struct BluePlan { long n = 0, M = 0; DevBuf w, wout, bhat; };
-static const BluePlan& blue_plan(FftContext& fc, int device, hipStream_t st, long n, bool forward) {
+static const BluePlan& blue_plan(FftContext& fc, hipStream_t st, long n, bool forward) {
 	static std::mutex mu; static std::map<std::tuple<int, long, int>, std::unique_ptr<BluePlan>> plans;
 	std::lock_guard<std::mutex> g(mu);
-	auto& p = plans[std::make_tuple(device, n, forward ? 1 : 0)];
+	auto& p = plans[std::make_tuple(fc.device(), n, forward ? 1 : 0)];
 	if (p) return *p;
 	p.reset(new BluePlan());
 	typedef long double LD;
@@ -77,10 +75,11 @@ struct F2Entry { std::shared_ptr<FftChain> ch; unsigned long stamp = 0; };
 static std::mutex g_f2_mu; static std::map<std::pair<int, hipStream_t>, F2Entry> g_f2; static unsigned long g_f2_clock = 0;
 static std::shared_ptr<FftChain> f2_chain(int device, hipStream_t st, FftContext& fc) {
 	std::lock_guard<std::mutex> g(g_f2_mu);
-	static const size_t cap = [] { const char* e = getenv("PXF_F2_MAX_STREAMS"); return (size_t)std::max(1, e ? atoi(e) : 4); }();
 	auto key = std::make_pair(device, st);
 	auto it = g_f2.find(key);
 	if (it == g_f2.end()) {
+		const char* e = getenv("PXF_F2_MAX_STREAMS");      // (read as an entry is added: where it applies)
+		const size_t cap = (size_t)std::max(1, e ? atoi(e) : 4);
 		for (;;) {
 			size_t ndev = 0; auto old = g_f2.end();
 			for (auto j = g_f2.begin(); j != g_f2.end(); ++j) if (j->first.first == device) {
@@ -99,15 +98,20 @@ static std::shared_ptr<FftChain> f2_chain(int device, hipStream_t st, FftContext
 // a stream is about to be destroyed: free the scratch keyed by it (a recycled handle must not inherit a stale buffer)
 void fft_release_stream(int device, hipStream_t st) {
 	stream_scratch_release(device, st);
-	{ std::lock_guard<std::mutex> g(g_f2_mu); g_f2.erase(std::make_pair(device, st)); }
-	fft_context(device).release_stream(st);
+	std::lock_guard<std::mutex> g(g_f2_mu); g_f2.erase(std::make_pair(device, st));
 }
 
-static void bluestein_axis(FftContext& fc, int device, hipStream_t st, long n, bool forward, std::vector<AxisDim> dims, long is_e, long os_e,
+// May this transform go through chirp-z?  Plain c2c / r2c / c2r only: the chirps take the places of the functors' multipliers and are
+// indexed by the unshifted element, and the second FFT stores the first n (or ne) bins of a line of its own
+static bool bluestein_ok(const FftLoad& ld, const FftStore& stf) {
+	return (ld.mode == LD_PLAIN || (ld.mode == LD_HERM && !ld.herm_fold)) && !ld.mul && !stf.mul && ld.shift == 0 && stf.shift == 0 && !stf.conj_out
+		&& stf.two_sided_k < 0 && !stf.real_pair;
+}
+static void bluestein_axis(FftContext& fc, hipStream_t st, long n, bool forward, std::vector<AxisDim> dims, long is_e, long os_e,
                            FftLoad ld, FftStore stf) {
-	const bool c2r = ld.mode == LD_HERM && !ld.herm_fold;      // Hermitian half spectrum in, real line out
-	if ((ld.mode != LD_PLAIN && !c2r) || ld.mul || stf.mul) throw Error(PXS_ERR_UNSUPPORTED, "FFT length " + std::to_string(n) + " has a prime factor > 2048: only plain c2c / r2c / c2r transforms are available for it (Bluestein)");
-	const BluePlan& bp = blue_plan(fc, device, st, n, forward);
+	const bool c2r = ld.mode == LD_HERM;      // Hermitian half spectrum in, real line out
+	if (!bluestein_ok(ld, stf)) throw Error(PXS_ERR_UNSUPPORTED, "FFT length " + std::to_string(n) + " has a prime factor > 2048: only plain c2c / r2c / c2r transforms are available for it (Bluestein)");
+	const BluePlan& bp = blue_plan(fc, st, n, forward);
 	const long M = bp.M;
 	// dense scratch [lines][M]
 	std::vector<AxisDim> d1 = dims, d2 = dims;
@@ -115,7 +119,7 @@ static void bluestein_axis(FftContext& fc, int device, hipStream_t st, long n, b
 	for (size_t k = dims.size(); k-- > 0;) { d1[k].os = lines*M; d2[k].is = lines*M; lines *= dims[k].n; }
 	// scratch per stream, grown on demand and kept (common.hpp stream_scratch); owners of private streams give it back with
 	// fft_release_stream before they destroy the stream
-	DevBuf& scratch = stream_scratch(SCR_BLUESTEIN, device, st); scratch.ensure(sizeof(double2)*(size_t)lines*M);
+	DevBuf& scratch = stream_scratch(SCR_BLUESTEIN, fc.device(), st); scratch.ensure(sizeof(double2)*(size_t)lines*M);
 	{	// y = FFT_M(x w, zero padded)
 		FftLoad l1 = ld; l1.mul = bp.w.as<double2>();
 		if (c2r) l1.herm_n = n;                                   // Hermitian extension of n points (times the chirp), zero padded to M
@@ -130,20 +134,20 @@ static void bluestein_axis(FftContext& fc, int device, hipStream_t st, long n, b
 	}
 }
 
-static int g_fft_device = 0;
+static long largest_prime_factor(long n) {
+	long big = 1;
+	for (long q = 2; q*q <= n; q++) while (n % q == 0) { big = q; n /= q; }
+	return std::max(big, n);
+}
+
+// transform along one axis of an N-d array; other dims become line dims (<= 3 after merging,
+// extra leading dims looped on the host)
 static void fft_axis(FftContext& fc, hipStream_t st, long n, bool forward, std::vector<AxisDim> dims, long is_e, long os_e,
                      FftLoad ld, FftStore stf) {
-	if (!FftContext::supported(n)) { bluestein_axis(fc, g_fft_device, st, n, forward, dims, is_e, os_e, ld, stf); return; }
-	{	// the generic radix pass costs n*p for a prime factor p: beyond ~128 two chirp FFTs of a smooth length are cheaper
-		// (healpix ring lengths 4k: alm2map_healpix at nside 2048, lmax 4096, 3 components 270 -> 94 ms)
-		static const long pmin = [] { const char* e = lab_getenv("PXS_BLUESTEIN_MINPRIME"); return e ? atol(e) : 128L; }();
-		const bool plain = (ld.mode == LD_PLAIN || (ld.mode == LD_HERM && !ld.herm_fold)) && !ld.mul && !stf.mul && ld.shift == 0 && stf.shift == 0 && !stf.conj_out
-			&& stf.two_sided_k < 0 && !stf.real_pair;
-		long m = n, big = 1;
-		for (long q = 2; q*q <= m; q++) while (m % q == 0) { big = std::max(big, q); m /= q; }
-		if (m > 1) big = std::max(big, m);
-		if (plain && big > pmin) { bluestein_axis(fc, g_fft_device, st, n, forward, dims, is_e, os_e, ld, stf); return; }
-	}
+	// Chirp-z where the mixed-radix engine has no factorisation, and where it is cheaper: the generic radix pass costs n*p for a prime
+	// factor p, beyond 128 two chirp FFTs of a smooth length win (healpix ring lengths 4k: alm2map_healpix at nside 2048, lmax 4096,
+	// 3 components 270 -> 94 ms)
+	if (!FftContext::supported(n) || (bluestein_ok(ld, stf) && largest_prime_factor(n) > 128)) { bluestein_axis(fc, st, n, forward, dims, is_e, os_e, ld, stf); return; }
 	// drop singleton dims, merge mergeable neighbours (outer,inner): outer.s == inner.s*inner.n for both in and out
 	std::vector<AxisDim> d;
 	for (auto& x : dims) if (x.n > 1) d.push_back(x);
@@ -162,12 +166,11 @@ static void fft_axis(FftContext& fc, hipStream_t st, long n, bool forward, std::
 	if (!d.empty()) { fd.n_o2 = d.back().n; fd.is_o2 = d.back().is; fd.os_o2 = d.back().os; d.pop_back(); }
 	// remaining dims: host loop
 	std::vector<long> idx(d.size(), 0);
-	auto esz = [](int dt) { return dt == PX_F32 ? 4 : dt == PX_F64 ? 8 : dt == PX_C64 ? 8 : 16; };
 	while (true) {
 		long ioff = 0, ooff = 0;
 		for (size_t k = 0; k < d.size(); k++) { ioff += idx[k]*d[k].is; ooff += idx[k]*d[k].os; }
 		FftLoad l2 = ld; FftStore s2 = stf;
-		l2.ptr = (const char*)ld.ptr + ioff*esz(ld.dtype); s2.ptr = (char*)stf.ptr + ooff*esz(stf.dtype);
+		l2.ptr = (const char*)ld.ptr + ioff*dtype_bytes(ld.dtype); s2.ptr = (char*)stf.ptr + ooff*dtype_bytes(stf.dtype);
 		fc.exec(st, n, forward, fd, l2, s2);
 		size_t k = 0;
 		for (; k < d.size(); k++) { if (++idx[k] < d[k].n) break; idx[k] = 0; }
@@ -181,7 +184,6 @@ void fft_dense_lines(int device, hipStream_t st, long n, bool forward, long nlin
 	if (nlines <= 0 || n <= 0) return;
 	if (n == 1) { if (in != out) PXS_HIP(hipMemcpyAsync(out, in, sizeof(double2)*(size_t)nlines, hipMemcpyDeviceToDevice, st)); return; }
 	FftContext& fc = fft_context(device);
-	g_fft_device = device;
 	std::vector<AxisDim> dims; dims.push_back(AxisDim{nlines, n, n});
 	FftLoad ld; ld.ptr = in; FftStore sf; sf.ptr = out;
 	fft_axis(fc, st, n, forward, dims, 1, 1, ld, sf);
@@ -277,101 +279,68 @@ int pxf_fft_nd(int ndim, const int64_t* shape, const int64_t* istride, const int
 	}
 	PXS_HIP(hipSetDevice(device));
 	FftContext& fc = fft_context(device);
-	g_fft_device = device;
 	hipStream_t st = (hipStream_t)stream;
+	if (kind == 0) {
+		// 2-D transforms over the last two axes of dense arrays (enmap.fft / ifft) through the chain stages.  Real maps: two rows per
+		// complex line, the Hermitian half carried through the column passes; complex input: rows into a transposed intermediate, columns back
+		const long minpix = [] { const char* e = getenv("PXS_FFT2_FAST_MINPIX"); return e ? atol(e) : (1L << 16); }();    // (-1: never; read per call: the tests switch it)
+		const bool real_in = in_dtype <= PX_F64;
+		bool dense = ndim >= 2 && naxes == 2 && ((axes[0] == ndim-2 && axes[1] == ndim-1) || (axes[0] == ndim-1 && axes[1] == ndim-2)) && (in != out || !real_in)
+			&& (real_in || in_dtype == PX_C128) && out_dtype == PX_C128 && minpix >= 0 && (long)shape[ndim-1]*shape[ndim-2] >= minpix;
+		long acc = 1, npre = 1;
+		for (int k = ndim-1; k >= 0 && dense; k--) { dense = istride[k] == acc && ostride[k] == acc; acc *= shape[k]; if (k < ndim-2) npre *= shape[k]; }
+		if (dense) {
+			const std::shared_ptr<FftChain> ch = f2_chain(device, st, fc);
+			if (real_in ? ch->fft2_real(st, in, in_dtype, (double2*)out, npre, shape[ndim-2], shape[ndim-1], forward != 0, scale)
+			            : ch->fft2_c2c(st, (const double2*)in, (double2*)out, npre, shape[ndim-2], shape[ndim-1], forward != 0, scale)) return 0;
+		}
+	}
+	// The axis passes, each one 1-d transforms along `ax` from (ld.ptr, is) to (st.ptr, os), last axis first (numpy.fft order):
+	//   c2c, r2r  `in` -> `out`, then in place on `out`
+	//   r2c       the real axis first (numpy.fft.rfftn order), then c2c over the half spectrum in place on `out`
+	//   c2r       c2c over all but the last axis into dense scratch, then the Hermitian c2r of the last axis into `out`
+	struct AxisPass { int ax; long n; bool forward; const std::vector<long>* shape; const int64_t *is, *os; FftLoad ld; FftStore st; };
+	std::vector<AxisPass> passes;
 	const int last = axes.back();
-	const long nlast = shape[last], nh = nlast/2 + 1;
-	// complex-domain shape (half spectrum along `last` for r2c / c2r)
-	std::vector<long> cshape(shape, shape+ndim);
-	if (kind != 0) cshape[last] = nh;
-	auto other_dims = [&](int ax, const std::vector<long>& shp, const int64_t* is, const int64_t* os) {
-		std::vector<AxisDim> d;
-		for (int k = 0; k < ndim; k++) if (k != ax) d.push_back({shp[k], (long)is[k], (long)os[k]});
-		return d;
-	};
-	if (kind >= 3) {
-		// FFTW r2r kinds (pixell/fft.py:211-290): each is the real part of a complex FFT of an extension of the line --
-		// mirror extension or zero padding with a half-sample phase ramp as a load functor, the other phase ramp, the bin
-		// offset and "2 Re" / "-2 Im" in the store functor.  Only the first n bins are stored.
-		std::vector<long> rshape(shape, shape+ndim);
-		for (int t = 0; t < naxes; t++) {
-			int ax = axes[naxes-1-t];
-			bool first = (t == 0), lastpass = (t == naxes-1);
-			const R2RPlan& rp = r2r_plan(device, kind, shape[ax]);
-			FftLoad ld; FftStore stf;
-			ld.ptr = first ? in : out; ld.dtype = first ? in_dtype : out_dtype;
-			ld.mode = rp.mirror ? LD_MIRROR : LD_PLAIN; ld.ne = shape[ax]; ld.mir_c = rp.mir_c; ld.par0 = 0; ld.par_step = 0;
-			ld.shift = rp.ld_shift; ld.mul = rp.ld_mul.p ? rp.ld_mul.as<double2>() : nullptr;
-			stf.ptr = out; stf.dtype = out_dtype; stf.ne = shape[ax] + rp.st_shift; stf.shift = rp.st_shift;
-			stf.mul = rp.st_mul.p ? rp.st_mul.as<double2>() : nullptr;
-			stf.scale = (lastpass ? scale : 1.0)*rp.scale;
-			const int64_t* is = first ? istride : ostride;
-			fft_axis(fc, st, rp.N, rp.forward, other_dims(ax, rshape, is, ostride), is[ax], ostride[ax], ld, stf);
+	const long nh = shape[last]/2 + 1;
+	std::vector<long> rshape(shape, shape+ndim), cshape = rshape;      // real-domain and complex-domain shape: the half spectrum along `last` for r2c / c2r
+	if (kind == 1 || kind == 2) cshape[last] = nh;
+	std::vector<int64_t> cs(ndim); void* scratch = nullptr;            // c2r: the dense complex scratch and its strides
+	if (kind == 2 && naxes > 1) {
+		long acc = 1;
+		for (int k = ndim-1; k >= 0; k--) { cs[k] = acc; acc *= cshape[k]; }
+		DevBuf& sb = stream_scratch(SCR_C2R, device, st);      // (grows only; no synchronisation in the call path)
+		sb.ensure((size_t)acc*sizeof(double2)); scratch = sb.p;
+	}
+	const void* src = in; int src_dtype = in_dtype; const int64_t* sstride = istride;
+	for (int t = 0; t < naxes; t++) {
+		const bool pre = kind == 2 && t < naxes-1;      // c2r: the complex passes that come before the real axis
+		const bool real_axis = kind >= 3 || (kind == 1 && t == 0) || (kind == 2 && !pre);
+		AxisPass p; p.ax = kind == 2 ? (pre ? axes[naxes-2-t] : last) : axes[naxes-1-t];
+		p.n = shape[p.ax]; p.forward = forward != 0; p.shape = real_axis ? &rshape : &cshape;
+		p.ld.ptr = src; p.ld.dtype = src_dtype; p.is = sstride;
+		p.st.ptr = pre ? scratch : out; p.st.dtype = pre ? (int)PX_C128 : out_dtype; p.os = pre ? cs.data() : ostride;
+		if (kind >= 3) {
+			// FFTW r2r kinds (pixell/fft.py:211-290): each is the real part of a complex FFT of an extension of the line --
+			// mirror extension or zero padding with a half-sample phase ramp as a load functor, the other phase ramp, the bin
+			// offset and "2 Re" / "-2 Im" in the store functor.  Only the first n bins are stored.
+			const R2RPlan& rp = r2r_plan(device, kind, p.n);
+			p.ld.mode = rp.mirror ? LD_MIRROR : LD_PLAIN; p.ld.ne = p.n; p.ld.mir_c = rp.mir_c; p.ld.par0 = 0; p.ld.par_step = 0;
+			p.ld.shift = rp.ld_shift; p.ld.mul = rp.ld_mul.p ? rp.ld_mul.as<double2>() : nullptr;
+			p.st.ne = p.n + rp.st_shift; p.st.shift = rp.st_shift; p.st.scale = rp.scale;
+			p.st.mul = rp.st_mul.p ? rp.st_mul.as<double2>() : nullptr;
+			p.n = rp.N; p.forward = rp.forward;
 		}
-	} else if (kind == 0) {
-		{	// 2-D transforms over the last two axes of dense arrays (enmap.fft / ifft) through the chain stages.  Real maps: two rows per
-			// complex line, the Hermitian half carried through the column passes; complex input: rows into a transposed intermediate, columns back
-			const long minpix = [] { const char* e = getenv("PXS_FFT2_FAST_MINPIX"); return e ? atol(e) : (1L << 16); }();    // (-1: never; read per call: the tests switch it)
-			const bool real_in = in_dtype <= PX_F64;
-			bool dense = ndim >= 2 && naxes == 2 && ((axes[0] == ndim-2 && axes[1] == ndim-1) || (axes[0] == ndim-1 && axes[1] == ndim-2)) && (in != out || !real_in)
-				&& (real_in || in_dtype == PX_C128) && out_dtype == PX_C128 && minpix >= 0 && (long)shape[ndim-1]*shape[ndim-2] >= minpix;
-			long acc = 1, npre = 1;
-			for (int k = ndim-1; k >= 0 && dense; k--) { dense = istride[k] == acc && ostride[k] == acc; acc *= shape[k]; if (k < ndim-2) npre *= shape[k]; }
-			if (dense) {
-				const std::shared_ptr<FftChain> ch = f2_chain(device, st, fc);
-				if (real_in ? ch->fft2_real(st, in, in_dtype, (double2*)out, npre, shape[ndim-2], shape[ndim-1], forward != 0, scale)
-				            : ch->fft2_c2c(st, (const double2*)in, (double2*)out, npre, shape[ndim-2], shape[ndim-1], forward != 0, scale)) return 0;
-			}
-		}
-		for (int t = 0; t < naxes; t++) {
-			int ax = axes[naxes-1-t];
-			bool first = (t == 0), lastpass = (t == naxes-1);
-			FftLoad ld; FftStore stf;
-			ld.ptr = first ? in : out; ld.dtype = first ? in_dtype : out_dtype;
-			stf.ptr = out; stf.dtype = out_dtype; stf.scale = lastpass ? scale : 1.0;
-			const int64_t* is = first ? istride : ostride;
-			fft_axis(fc, st, shape[ax], forward != 0, other_dims(ax, cshape, is, ostride), is[ax], ostride[ax], ld, stf);
-		}
-	} else if (kind == 1) {
-		// real axis first (numpy.fft.rfftn order), then c2c over the remaining axes in place on out
-		{
-			FftLoad ld; FftStore stf;
-			ld.ptr = in; ld.dtype = in_dtype; stf.ptr = out; stf.dtype = out_dtype; stf.ne = nh;
-			stf.scale = naxes == 1 ? scale : 1.0;
-			std::vector<long> rshape(shape, shape+ndim);
-			fft_axis(fc, st, nlast, forward != 0, other_dims(last, rshape, istride, ostride), istride[last], ostride[last], ld, stf);
-		}
-		for (int t = 1; t < naxes; t++) {
-			int ax = axes[naxes-1-t];
-			FftLoad ld; FftStore stf;
-			ld.ptr = out; ld.dtype = out_dtype; stf.ptr = out; stf.dtype = out_dtype; stf.scale = (t == naxes-1) ? scale : 1.0;
-			fft_axis(fc, st, shape[ax], forward != 0, other_dims(ax, cshape, ostride, ostride), ostride[ax], ostride[ax], ld, stf);
-		}
-	} else {
-		// c2r: complex transforms over all but the last axis into scratch, then Hermitian c2r on the last axis
-		const void* src = in; int src_dtype = in_dtype; std::vector<int64_t> sstride(istride, istride+ndim);
-		if (naxes > 1) {
-			size_t tot = 1; for (int k = 0; k < ndim; k++) tot *= cshape[k];
-			DevBuf& scratch = stream_scratch(SCR_C2R, device, st);      // (grows only; no synchronisation in the call path)
-			scratch.ensure(tot*sizeof(double2));
-			std::vector<int64_t> cs(ndim); long acc = 1;
-			for (int k = ndim-1; k >= 0; k--) { cs[k] = acc; acc *= cshape[k]; }
-			for (int t = 0; t < naxes-1; t++) {
-				int ax = axes[naxes-2-t];
-				FftLoad ld; FftStore stf;
-				ld.ptr = (t == 0) ? in : scratch.p; ld.dtype = (t == 0) ? in_dtype : PX_C128;
-				stf.ptr = scratch.p; stf.dtype = PX_C128;
-				const int64_t* is = (t == 0) ? istride : cs.data();
-				fft_axis(fc, st, shape[ax], forward != 0, other_dims(ax, cshape, is, cs.data()), is[ax], cs[ax], ld, stf);
-			}
-			src = scratch.p; src_dtype = PX_C128; sstride = cs;
-		}
-		FftLoad ld; FftStore stf;
-		ld.ptr = src; ld.dtype = src_dtype; ld.mode = LD_HERM; ld.ne = nh;
-		stf.ptr = out; stf.dtype = out_dtype; stf.scale = scale;
-		std::vector<long> rshape(shape, shape+ndim);
-		// note: LD_HERM reads indices < nh directly and conj(N-e) otherwise: for even N the Nyquist bin e=N/2 < nh is read directly
-		fft_axis(fc, st, nlast, forward != 0, other_dims(last, rshape, sstride.data(), ostride), sstride[last], ostride[last], ld, stf);
+		else if (kind == 1 && t == 0) p.st.ne = nh;
+		else if (kind == 2 && !pre) { p.ld.mode = LD_HERM; p.ld.ne = nh; }      // (indices < nh read directly, conj(N-e) otherwise: for even N the Nyquist bin N/2 < nh directly)
+		passes.push_back(p);
+		src = p.st.ptr; src_dtype = p.st.dtype; sstride = p.os;
+	}
+	passes.back().st.scale *= scale;
+	for (const AxisPass& p : passes) {
+		std::vector<AxisDim> od;      // the other dims: the lines
+		for (int k = 0; k < ndim; k++) if (k != p.ax) od.push_back({(*p.shape)[k], (long)p.is[k], (long)p.os[k]});
+		fft_axis(fc, st, p.n, p.forward, od, p.is[p.ax], p.os[p.ax], p.ld, p.st);
 	}
 	PXS_CATCH
 }

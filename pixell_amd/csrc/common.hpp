@@ -61,7 +61,7 @@ struct DevBuf {
 // on one stream are ordered by the stream.  The reference is found under the registry's lock and stays valid until the stream is
 // released (entries never move); the caller grows it with ensure() and launches outside the lock.  Growing hands the old block to the
 // arena, which synchronises the device before the block serves anybody else: the stream's earlier kernels may still read it.
-enum ScratchSlot : int { SCR_BLUESTEIN, SCR_C2R, SCR_ALM2CL, SCR_SRC_FIXED, SCR_SRC_PAIRS, SCR_DISTANCE };
+enum ScratchSlot : int { SCR_FOURSTEP, SCR_BLUESTEIN, SCR_C2R, SCR_ALM2CL, SCR_SRC_FIXED, SCR_SRC_PAIRS, SCR_DISTANCE };
 DevBuf& stream_scratch(ScratchSlot slot, int device, void* stream);
 void stream_scratch_release(int device, void* stream);      // a stream is about to be destroyed: a recycled handle must not inherit a stale buffer
 
@@ -86,13 +86,14 @@ inline FastDiv make_fastdiv(uint32_t d) {
 }
 
 enum DType : int { PX_F32 = 0, PX_F64 = 1, PX_C64 = 2, PX_C128 = 3, PX_U8 = 4, PX_I32 = 5 };      // (the integer types: maps that pxm_interpol copies from)
+inline int dtype_bytes(int dt) { return dt == PX_U8 ? 1 : dt == PX_F32 || dt == PX_I32 ? 4 : dt == PX_C128 ? 16 : 8; }      // of one element
 
 // the alm and the maps of an SHT call as the C ABI hands them over: component c of batch member b starts at element
 // b*bstride + c*cstride of `dtype`; from(b): the same arrays from batch member b on
 struct AlmArg { void* ptr; int dtype; long cstride, bstride;
-	AlmArg from(long b) const { return AlmArg{(char*)ptr + (dtype == PX_C64 ? 8 : 16)*(size_t)b*bstride, dtype, cstride, bstride}; } };
+	AlmArg from(long b) const { return AlmArg{(char*)ptr + dtype_bytes(dtype)*(size_t)b*bstride, dtype, cstride, bstride}; } };
 struct MapArg { void* ptr; int dtype; long cstride, bstride;
-	MapArg from(long b) const { return MapArg{(char*)ptr + (dtype == PX_F32 ? 4 : 8)*(size_t)b*bstride, dtype, cstride, bstride}; } };
+	MapArg from(long b) const { return MapArg{(char*)ptr + dtype_bytes(dtype)*(size_t)b*bstride, dtype, cstride, bstride}; } };
 
 // Tuning and experiment switches (tile shapes, ring pairs per lane, planner overrides, alternative paths kept for A/B runs) are read
 // from the environment in LAB builds only (-DPXS_LAB, tools/build_variants.sh); the product build compiles their defaults in.  What

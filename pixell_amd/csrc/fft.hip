@@ -344,40 +344,37 @@ template<int LM, int NT, bool GEN> __global__ __launch_bounds__(NT) void fft_lds
 // across the store loop only) still took 200-260 VGPRs -- the persistent loop makes every load-functor invariant live -- and
 // ran 2x slower (n = 200: 0.19 -> 0.44 ms).  What the attempts left behind: the LDS-only barrier, the per-load-mode instantiation and the pass
 // table in device memory, which keep the argument struct out of scratch.)
-// launch one of the two kernels over nblk tiles
-template<int LM> static void launch_tiles_m(const KArgs& k, long nblk, size_t sh, hipStream_t st, int nt_override) {
+// Threads per workgroup.  Tiles of 2048 points and more (lines of 1025..2048 points: 64 KiB of LDS, 2 workgroups per CU) get 512: at
+// < 64 VGPRs twice the waves fit, measured 1.39 -> 1.86 TB/s at n = 2048; for the 32 KiB tiles 512 threads were 3-8 % slower.
+// The generic-radix kernel (twice the LDS per line) exists with 256 only.
+static int tile_threads(const KArgs& k) { return !k.generic && (long)k.T*k.n >= 2048 ? 512 : 256; }
+// launch one of the three kernels over nblk tiles
+template<int LM> static void launch_tiles_m(const KArgs& k, long nblk, size_t sh, hipStream_t st) {
 #ifdef PXS_HOST_SIM
 	hipLaunchKernelGGL((fft_lds_kernel<LM, 1, true>), dim3((unsigned)nblk), dim3(1), sh, st, k);
 #else
-	// 512 threads per workgroup: LDS allows 4 workgroups of 2048 points per CU, and at < 64 VGPRs twice the waves fit
-	// tiles of more than 2048 points (lines of 1025..2048 points: 64 KiB of LDS, 2 workgroups per CU) get 512 threads:
-	// measured 1.39 -> 1.86 TB/s at n = 2048; for the 32 KiB tiles 512 threads were 3-8 % slower
-	static const int nt_env = [] { const char* e = lab_getenv("PXS_FFT_NT"); return e ? atoi(e) : 0; }();
-	const int nt = nt_override ? nt_override : nt_env ? nt_env : ((long)k.T*k.n >= 2048 ? 512 : 256);
 	static const bool once = [] {
 		(void)hipFuncSetAttribute((const void*)fft_lds_kernel<LM, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
 		(void)hipFuncSetAttribute((const void*)fft_lds_kernel<LM, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
 		(void)hipFuncSetAttribute((const void*)fft_lds_kernel<LM, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-		(void)hipFuncSetAttribute((const void*)fft_lds_kernel<LM, 128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
 		return true; }();
 	(void)once;
-	if (k.generic)      hipLaunchKernelGGL((fft_lds_kernel<LM, 256, true>), dim3((unsigned)nblk), dim3(256), sh, st, k);
-	else if (nt == 512) hipLaunchKernelGGL((fft_lds_kernel<LM, 512, false>), dim3((unsigned)nblk), dim3(512), sh, st, k);
-	else if (nt == 128) hipLaunchKernelGGL((fft_lds_kernel<LM, 128, false>), dim3((unsigned)nblk), dim3(128), sh, st, k);
-	else                hipLaunchKernelGGL((fft_lds_kernel<LM, 256, false>), dim3((unsigned)nblk), dim3(256), sh, st, k);
+	if (k.generic)                   hipLaunchKernelGGL((fft_lds_kernel<LM, 256, true>), dim3((unsigned)nblk), dim3(256), sh, st, k);
+	else if (tile_threads(k) == 512) hipLaunchKernelGGL((fft_lds_kernel<LM, 512, false>), dim3((unsigned)nblk), dim3(512), sh, st, k);
+	else                             hipLaunchKernelGGL((fft_lds_kernel<LM, 256, false>), dim3((unsigned)nblk), dim3(256), sh, st, k);
 #endif
 }
-static void launch_tiles(const KArgs& k, long nblk, size_t sh, hipStream_t st, int nt_override = 0) {
+static void launch_tiles(const KArgs& k, long nblk, size_t sh, hipStream_t st) {
 	const int lm = k.mode == 2 ? (int)LD_PLAIN : k.ld.mode;      // pass B reads the four-step scratch, no functor
 	switch (lm) {
-		case LD_PLAIN:       launch_tiles_m<LD_PLAIN>(k, nblk, sh, st, nt_override); break;
-		case LD_HERM:        launch_tiles_m<LD_HERM>(k, nblk, sh, st, nt_override); break;
-		case LD_MIRROR:      launch_tiles_m<LD_MIRROR>(k, nblk, sh, st, nt_override); break;
-		case LD_SPEC:        launch_tiles_m<LD_SPEC>(k, nblk, sh, st, nt_override); break;
-		case LD_SPEC_ADJ:    launch_tiles_m<LD_SPEC_ADJ>(k, nblk, sh, st, nt_override); break;
-		case LD_MIRROR_PAIR: launch_tiles_m<LD_MIRROR_PAIR>(k, nblk, sh, st, nt_override); break;
-		case LD_REAL_PAIR:   launch_tiles_m<LD_REAL_PAIR>(k, nblk, sh, st, nt_override); break;
-		case LD_HERM_PAIR:   launch_tiles_m<LD_HERM_PAIR>(k, nblk, sh, st, nt_override); break;
+		case LD_PLAIN:       launch_tiles_m<LD_PLAIN>(k, nblk, sh, st); break;
+		case LD_HERM:        launch_tiles_m<LD_HERM>(k, nblk, sh, st); break;
+		case LD_MIRROR:      launch_tiles_m<LD_MIRROR>(k, nblk, sh, st); break;
+		case LD_SPEC:        launch_tiles_m<LD_SPEC>(k, nblk, sh, st); break;
+		case LD_SPEC_ADJ:    launch_tiles_m<LD_SPEC_ADJ>(k, nblk, sh, st); break;
+		case LD_MIRROR_PAIR: launch_tiles_m<LD_MIRROR_PAIR>(k, nblk, sh, st); break;
+		case LD_REAL_PAIR:   launch_tiles_m<LD_REAL_PAIR>(k, nblk, sh, st); break;
+		case LD_HERM_PAIR:   launch_tiles_m<LD_HERM_PAIR>(k, nblk, sh, st); break;
 		default: throw Error(PXS_ERR_ARG, "fft: unknown load mode");
 	}
 }
@@ -396,18 +393,11 @@ static std::vector<int> factorize(long n) {
 	// Odd radices first: in the first pass (L = 1) lane b touches points b*R + i, a stride of R points of 16 bytes:
 	// conflict-free over the 64 LDS banks for R = 3, 5 but 4-way for R = 4.  The last radix sets the stride n/R of the
 	// digit-reversed scatter on load; 4 keeps it the least harmful for lengths that are multiples of 8.
-	static const int oddfirst = [] { const char* e = lab_getenv("PXS_FFT_ODDFIRST"); return e ? atoi(e) : 1; }();
-	if (oddfirst) {
-		while (n % 3 == 0) { f.push_back(3); n /= 3; }
-		while (n % 5 == 0) { f.push_back(5); n /= 5; }
-		int twos = 0; while (n % 2 == 0) { twos++; n /= 2; }
-		if (twos & 1) { f.push_back(2); twos--; }
-		while (twos >= 2) { f.push_back(4); twos -= 2; }
-	}
-	while (n % 4 == 0) { f.push_back(4); n /= 4; }
-	while (n % 2 == 0) { f.push_back(2); n /= 2; }
 	while (n % 3 == 0) { f.push_back(3); n /= 3; }
 	while (n % 5 == 0) { f.push_back(5); n /= 5; }
+	int twos = 0; while (n % 2 == 0) { twos++; n /= 2; }
+	if (twos & 1) { f.push_back(2); twos--; }
+	while (twos >= 2) { f.push_back(4); twos -= 2; }
 	for (long p = 7; p*p <= n; p += 2) while (n % p == 0) { f.push_back((int)p); n /= p; }
 	if (n > 1) f.push_back((int)n);
 	return f;
@@ -442,8 +432,7 @@ static bool split_two(long n, long& n1, long& n2) {
 		if (a % 8 == 0 && b % 8 == 0 && 4*a >= b) best8 = a;
 	}
 	if (best < 0) return false;
-	static const int align8 = [] { const char* e = lab_getenv("PXS_FFT_ALIGN8"); return e ? atoi(e) : 1; }();
-	if (best8 > 0 && align8) best = best8;
+	if (best8 > 0) best = best8;
 	n1 = best; n2 = n/best;
 	return n1 <= FFT_NLOC_MAX && n2 <= FFT_NLOC_MAX;
 }
@@ -457,7 +446,7 @@ bool FftContext::supported(long n, std::string* why) {
 	long n1, n2;
 	if (!split_two(n, n1, n2)) {
 		if (why) *why = "FFT length " + std::to_string(n) + " has no factorisation n1*n2 with both factors <= " +
-			std::to_string(FFT_NLOC_MAX) + " (large prime factor; Bluestein not implemented)";
+			std::to_string(FFT_NLOC_MAX) + " (large prime factor: only plain c2c / r2c / c2r transforms of such a length exist, through chirp-z)";
 		return false;
 	}
 	return true;
@@ -471,21 +460,17 @@ long FftContext::good_size(long n) {
 	}
 }
 
-// Fewest passes with radices from {2,3,4,5} and the composite register radices {6,8,9,10,12,15,16} (fft_dev.hpp); PXS_FFT_RADICES
-// restricts the set (tuning); only those up to PXS_COMP_MAXR are compiled in (fft_dev.hpp).  Odd radices go first: in the first passes (small L) consecutive lanes are R points apart, which
-// for an even R puts them on few LDS banks.
+// Fewest passes with radices from {2,3,4,5}, the composite register radices {6,8,9,10,12,15,16} up to maxr (<= PXS_COMP_MAXR, the largest
+// compiled in: fft_dev.hpp) and the plain radix 7 of the chain kernels that have it (maxr >= 9).  Odd radices go first: in the first
+// passes (small L) consecutive lanes are R points apart, which for an even R puts them on few LDS banks.
 static std::vector<int> factorize_comp(long n, int maxr) {
-	static const std::vector<int> allowed = [] {
-		std::vector<int> a; const char* e = lab_getenv("PXS_FFT_RADICES");
-		std::string s = e ? e : "16,15,12,10,9,8,7,6,5,4,3,2";
-		size_t pos = 0;
-		while (pos < s.size()) { size_t c = s.find(',', pos); if (c == std::string::npos) c = s.size(); int v = atoi(s.substr(pos, c-pos).c_str()); if (v >= 2 && (v <= 5 || v <= PXS_COMP_MAXR)) a.push_back(v); pos = c+1; }
-		return a; }();
+	static const int radices[] = {16, 15, 12, 10, 9, 8, 7, 6, 5, 4, 3, 2};
+	const size_t nrad = sizeof(radices)/sizeof(radices[0]);
 	std::vector<int> best, cur;
 	std::function<void(long, size_t)> rec = [&](long m, size_t from) {
 		if (m == 1) { if (best.empty() || cur.size() < best.size()) best = cur; return; }
 		if (!best.empty() && cur.size()+1 >= best.size()) return;
-		for (size_t i = from; i < allowed.size(); i++) if (m % allowed[i] == 0 && (allowed[i] == 7 ? maxr >= 9 : (allowed[i] <= 5 || allowed[i] <= maxr))) { cur.push_back(allowed[i]); rec(m/allowed[i], i); cur.pop_back(); }
+		for (size_t i = from; i < nrad; i++) { const int r = radices[i]; if (m % r == 0 && (r == 7 ? maxr >= 9 : (r <= 5 || r <= maxr))) { cur.push_back(r); rec(m/r, i); cur.pop_back(); } }
 	};
 	rec(n, 0);
 	if (best.empty()) return factorize(n);
@@ -495,8 +480,6 @@ static std::vector<int> factorize_comp(long n, int maxr) {
 
 std::shared_ptr<FftSub> FftContext::sub(long n, bool comp, int maxr) {
 	std::lock_guard<std::mutex> g(mu_);
-	static const bool comp_on = [] { const char* e = lab_getenv("PXS_FFT_COMP"); return e ? atoi(e) != 0 : true; }();
-	comp = comp && comp_on;
 	maxr = std::min(maxr, PXS_COMP_MAXR);
 	const long key = comp ? -(n + ((long)maxr << 40)) : n;
 	auto it = subs_.find(key);
@@ -547,26 +530,18 @@ const double2* FftContext::bigtw(long n) {
 
 static void fill_sub(KArgs& k, const FftSub& s, long maxlines) {
 	k.n = s.n; k.nfac = s.nfac; k.generic = s.generic;
-#ifdef PXS_LAB
-	{ static const int nopass = [] { const char* e = getenv("PXS_FFT_DEBUG_NOPASS"); return e ? atoi(e) : 0; }(); if (nopass) k.nfac = 0; }   // timing experiments only: wrong results
-#endif
 	k.pass = s.d_pass.as<PassDesc>();
 	k.perm = s.perm.as<int>(); k.tw = s.tw.as<double2>();
-	int bufs = s.generic ? 2 : 1;
-	static const long env_pts = [] { const char* e = lab_getenv("PXS_FFT_PTS"); return e ? atol(e) : 0L; }();
-	long pts = s.n <= 1024 ? FFT_LDS_PTS/2 : FFT_LDS_PTS;    // 32 KiB tiles for short lines: 4-5 workgroups per CU
-	if (env_pts > 0 && s.n <= env_pts/2) pts = env_pts;
+	const int bufs = s.generic ? 2 : 1;
+	const long pts = s.n <= 1024 ? FFT_LDS_PTS/2 : FFT_LDS_PTS;    // 32 KiB tiles for short lines: 4-5 workgroups per CU
 	long T = (pts - s.n)/((long)bufs*s.n);
 	if (T < 1) T = 1;
 	if (T > 64) T = 64;
 	// Tiles that run along the contiguous memory direction (four-step column passes, adjacent lines) move T*16-byte
 	// runs: keep them whole 128-byte lines.  Neighbouring tiles are handled by workgroups on different XCDs, so a
 	// line shared by two tiles is fetched from HBM twice (FETCH_SIZE of this kernel was 1.6x its WRITE_SIZE).
-	static const int align8 = [] { const char* e = lab_getenv("PXS_FFT_ALIGN8"); return e ? atoi(e) : 1; }();
-	if (align8) {
-		if (T >= 8) T -= T % 8;
-		else if (T >= 5 && (long)bufs*8*s.n + s.n <= FFT_LDS_PTS) T = 8;
-	}
+	if (T >= 8) T -= T % 8;
+	else if (T >= 5 && (long)bufs*8*s.n + s.n <= FFT_LDS_PTS) T = 8;
 	if (T > maxlines) T = maxlines;
 	k.T = (int)T;
 	k.dn = make_fastdiv(s.n); k.dT = make_fastdiv((uint32_t)T);
@@ -574,45 +549,54 @@ static void fill_sub(KArgs& k, const FftSub& s, long maxlines) {
 	// contiguous memory direction.  With 16-byte points a stride that is a multiple of 8 points (which the 128-byte
 	// alignment rule above makes the normal case: 200, 216, 320) puts 16 lanes on 1-2 bank groups: 8-16-way LDS bank
 	// conflicts (SQ_LDS_BANK_CONFLICT was 1.9x SQ_ACTIVE_INST_LDS).  An odd stride spreads them over all banks.
-	static const int lpad = [] { const char* e = lab_getenv("PXS_FFT_LINEPAD"); return e ? atoi(e) : 1; }();
-	k.ns = lpad ? (s.n | 1) : s.n;
+	k.ns = s.n | 1;
 }
 
 static size_t lds_bytes(const KArgs& k) { const size_t pts = (size_t)k.T*k.ns + 2; return sizeof(double2)*((size_t)k.n + pts*(k.generic ? 2 : 1)); }
+
+// Plan and launch one pass over the `lines` lines i of k: sub-transforms s for every line (mode 0), or for every (line, sub-line) of
+// the four-step split -- sub-lines j2 < n2 in pass A (mode 1: n1-point FFTs over j1, twiddled, into the scratch), k1 < n1 in pass B
+// (mode 2: n2-point FFTs over j2 out of it).  A workgroup's tile runs over the lines (mode 0, or tile_i: lines adjacent in memory) or
+// over the sub-lines (contiguous in memory).  Returns the number of blocks.
+static long launch_pass(KArgs k, hipStream_t st, int mode, const FftSub& s, int tile_i, long lines) {
+	const long nsub = mode == 0 ? 1 : mode == 1 ? k.n2 : k.n1;
+	const long tiled = (mode == 0 || tile_i) ? lines : nsub, other = (mode == 0 || tile_i) ? nsub : lines;
+	fill_sub(k, s, tiled);
+	k.mode = mode; k.tile_i = tile_i; k.i_count = lines;
+	k.ntile = (tiled + k.T - 1)/k.T;
+	// thread -> element maps: the index that is contiguous in memory runs fastest over the lanes.  User arrays of mode 0: the line
+	// index where lines are adjacent (|stride| of the line index smaller than the element stride); the four-step passes: always the
+	// tiled index, but for pass B's read of scratch rows [line][N]
+	k.load_inner_fast  = mode == 0 ? (std::abs(k.d.is_i) < std::abs(k.d.is_e)) : mode == 1 ? 1 : tile_i;
+	k.store_inner_fast = mode == 0 ? (std::abs(k.d.os_i) < std::abs(k.d.os_e)) : 1;
+	const long nblk = k.ntile*other*k.d.n_o1*k.d.n_o2;
+	launch_tiles(k, nblk, lds_bytes(k), st);
+	return nblk;
+}
 
 void FftContext::exec(hipStream_t st, long n, bool forward, const FftDims& d, const FftLoad& ld, const FftStore& stf) {
 	std::string why;
 	if (!supported(n, &why)) throw Error(PXS_ERR_UNSUPPORTED, why);
 	if (d.n_i <= 0 || d.n_o1 <= 0 || d.n_o2 <= 0) return;
 	KArgs k; memset(&k, 0, sizeof(k));
-	k.N = n; k.forward = forward ? 1 : 0; k.d = d; k.ld = ld; k.st = stf; k.i_base = 0; k.i_count = d.n_i;
+	k.N = n; k.forward = forward ? 1 : 0; k.d = d; k.ld = ld; k.st = stf; k.i_base = 0;
 	if (n <= FFT_NLOC_MAX) {
-		auto s = sub(n);
-		fill_sub(k, *s, d.n_i);
-		k.mode = 0; k.n1 = (int)n; k.n2 = 1;
-		k.ntile = (d.n_i + k.T - 1)/k.T;
-		// lines adjacent in memory (|stride| of the line index smaller than the element stride) => line index fastest
-		k.load_inner_fast  = (std::abs(d.is_i) < std::abs(d.is_e)) ? 1 : 0;
-		k.store_inner_fast = (std::abs(d.os_i) < std::abs(d.os_e)) ? 1 : 0;
-		long nblk = k.ntile*d.n_o1*d.n_o2;
-		size_t sh = lds_bytes(k);
-		launch_tiles(k, nblk, sh, st);
+		k.n1 = (int)n; k.n2 = 1;
+		launch_pass(k, st, 0, *sub(n), 0, d.n_i);
 		PXS_HIP(hipGetLastError());
 		return;
 	}
 	long n1, n2; split_two(n, n1, n2);
 	auto s1 = sub(n1); auto s2 = sub(n2);
-	const double2* btw = bigtw(n);
+	k.bigtw = bigtw(n); k.n1 = (int)n1; k.n2 = (int)n2;
 	// chunk lines so that the scratch stays below temp_budget
 	size_t budget = temp_budget; env_budget("PXS_FFT_TEMP_MB", 20, budget);
 	long lines_budget = std::max<long>(1, (long)(budget/(sizeof(double2)*n)));
-	DevBuf* tbuf = nullptr;
-	{
-		std::lock_guard<std::mutex> g(mu_);
-		size_t want = sizeof(double2)*n*std::min<long>(lines_budget, d.n_i*d.n_o1*d.n_o2);
-		tbuf = &temps_[st];     // one scratch per stream: transforms issued on different streams may overlap
-		tbuf->ensure(want);
-	}
+	// one scratch per stream (transforms issued on different streams may overlap), grown on demand and kept (common.hpp stream_scratch)
+	DevBuf& tbuf = stream_scratch(SCR_FOURSTEP, device_, st);
+	tbuf.ensure(sizeof(double2)*n*std::min<long>(lines_budget, d.n_i*d.n_o1*d.n_o2));
+	k.temp = tbuf.as<double2>();
+	const int tile_i = (std::abs(d.is_i) < std::abs(d.is_e)) ? 1 : 0;      // lines adjacent in memory
 	// iterate over o2, o1 chunks, i chunks
 	long o1_per = 1, i_per = d.n_i;
 	if (d.n_i <= lines_budget) { o1_per = std::min<long>(d.n_o1, std::max<long>(1, lines_budget/d.n_i)); }
@@ -624,27 +608,14 @@ void FftContext::exec(hipStream_t st, long n, bool forward, const FftDims& d, co
 		long no1 = std::min(o1_per, d.n_o1 - o1), ni = std::min(i_per, d.n_i - i0);
 		pass_lines.add(no1*ni);
 		KArgs a = k;
-		a.d.n_o1 = no1; a.d.n_o2 = 1; a.i_base = i0; a.i_count = ni;
+		a.d.n_o1 = no1; a.d.n_o2 = 1; a.i_base = i0;
 		// shift base pointers
-		auto esz = [](int dt) { return dt == PX_F32 ? 4 : dt == PX_F64 ? 8 : dt == PX_C64 ? 8 : 16; };
 		const long lmul = (ld.mode == LD_MIRROR_PAIR || ld.mode == LD_REAL_PAIR || ld.mode == LD_HERM_PAIR) ? 2 : 1;   // packed input lines
 		const long smul = stf.real_pair ? 2 : 1;
-		a.ld.ptr = (const char*)ld.ptr + esz(ld.dtype)*(o2*d.is_o2 + o1*d.is_o1 + lmul*i0*d.is_i);
-		a.st.ptr = (char*)stf.ptr + esz(stf.dtype)*(o2*d.os_o2 + o1*d.os_o1 + smul*i0*d.os_i);
-		a.temp = tbuf->as<double2>(); a.bigtw = btw; a.n1 = (int)n1; a.n2 = (int)n2;
-		const int tile_i = (std::abs(d.is_i) < std::abs(d.is_e)) ? 1 : 0;
-		// pass A: n1-point FFTs over j1 for each (i, j2); tile over j2 (lines contiguous) or over i (lines adjacent)
-		KArgs pa = a; fill_sub(pa, *s1, tile_i ? ni : n2); pa.mode = 1; pa.tile_i = tile_i;
-		pa.ntile = ((tile_i ? ni : n2) + pa.T - 1)/pa.T;
-		pa.load_inner_fast = 1; pa.store_inner_fast = 1;
-		long nblkA = pa.ntile*(tile_i ? n2 : ni)*no1;
-		launch_tiles(pa, nblkA, lds_bytes(pa), st);
-		// pass B: n2-point FFTs over j2 for each (i, k1)
-		KArgs pb = a; fill_sub(pb, *s2, tile_i ? ni : n1); pb.mode = 2; pb.tile_i = tile_i;
-		pb.ntile = ((tile_i ? ni : n1) + pb.T - 1)/pb.T;
-		pb.load_inner_fast = tile_i ? 1 : 0; pb.store_inner_fast = 1;
-		long nblkB = pb.ntile*(tile_i ? n1 : ni)*no1;
-		launch_tiles(pb, nblkB, lds_bytes(pb), st);
+		a.ld.ptr = (const char*)ld.ptr + dtype_bytes(ld.dtype)*(o2*d.is_o2 + o1*d.is_o1 + lmul*i0*d.is_i);
+		a.st.ptr = (char*)stf.ptr + dtype_bytes(stf.dtype)*(o2*d.os_o2 + o1*d.os_o1 + smul*i0*d.os_i);
+		launch_pass(a, st, 1, *s1, tile_i, ni);
+		launch_pass(a, st, 2, *s2, tile_i, ni);
 		PXS_HIP(hipGetLastError());
 	}
 }

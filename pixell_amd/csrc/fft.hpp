@@ -59,21 +59,20 @@ public:
 	// out = FFT_n(in) along e for every line; forward: e^{-2 pi i jk/n}; unnormalised.
 	void exec(hipStream_t st, long n, bool forward, const FftDims& d, const FftLoad& ld, const FftStore& stf);
 	static long good_size(long n);          // smallest 2^a 3^b 5^c >= n that the engine can factor
-	static bool supported(long n, std::string* why = nullptr);
-	// views for the fused chain kernels (fftchain.hip): LDS sub-transform tables of length n (radices 2,3,4,5 only:
-	// `ok` false otherwise) and the four-step twiddle table e^{-2 pi i k/n}, k < n
+	static bool supported(long n, std::string* why = nullptr);      // false: no n1*n2 with both <= FFT_NLOC_MAX (a large prime factor); plain c2c / r2c / c2r of such a length go through chirp-z (api_fft.hip), nothing else does
+	int device() const { return device_; }  // the device the tables (and every transform of this context) live on
+	// views for the fused chain kernels (fftchain.hip): LDS sub-transform tables of length n, factorised over the radices 2,3,4,5,7 and the
+	// composite register radices up to maxr (`generic` set when a factor is none of them), and the four-step twiddle table e^{-2 pi i k/n}, k < n
 	struct SubView { int n, nfac, ns, generic; const void* pass; const int* perm; const double2* tw; const int* hfac; const int* hperm; };      // hfac, hperm: host copies of the radices and of perm
 	SubView view(long n, int maxr = 1000);      // maxr: largest composite register radix the calling kernel has compiled in
 	const double2* twiddle_table(long n) { return bigtw(n); }
-	void release_stream(hipStream_t st) { std::lock_guard<std::mutex> g(mu_); temps_.erase(st); }   // four-step scratch of a stream that is going away
-	size_t temp_budget = size_t(4) << 30;   // bytes of four-step scratch per stream (set from the free memory in the constructor; PXS_FFT_TEMP_MB, read per exec, overrides)
+	size_t temp_budget = size_t(4) << 30;   // bytes of four-step scratch per stream (stream_scratch(SCR_FOURSTEP); set from the free memory in the constructor; PXS_FFT_TEMP_MB, read per exec, overrides)
 	PassLog pass_lines;                     // passes of the most recent four-step exec on this device, lines per pass (pxs_plan_query(NULL, "passes_fft"))
 private:
 	int device_;
 	std::mutex mu_;
 	std::map<long, std::shared_ptr<FftSub>> subs_;
 	std::map<long, DevBuf> bigtw_;
-	std::map<hipStream_t, DevBuf> temps_;
 	std::shared_ptr<FftSub> sub(long n, bool comp = false, int maxr = 1000);   // comp: factorisation with the composite register radices (chain kernels)
 	const double2* bigtw(long n);
 };

@@ -451,7 +451,7 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 		}
 		evs.clear();
 	};
-	auto field = [&](long q) -> char* { const long b = q/ncm, c = q - b*ncm; return (char*)map.from(b).ptr + (map.dtype == PX_F32 ? 4 : 8)*c*map.cstride; };
+	auto field = [&](long q) -> char* { const long b = q/ncm, c = q - b*ncm; return (char*)map.from(b).ptr + dtype_bytes(map.dtype)*c*map.cstride; };
 	if (!adjoint) {
 		timed(PT_ST_CC, [&] {
 			const int rc = pxs_synthesis(grid, spin, mode, 0, nb, alm.ptr, alm.dtype, alm.cstride, alm.bstride, f, PX_F64, npix, ncm*npix, st);

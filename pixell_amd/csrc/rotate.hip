@@ -288,8 +288,8 @@ extern "C" int pxa_rotate_alm(int lmax, int ncomp, const void* alm_in, int64_t i
 	for (int c0 = 0, g = 0; c0 < ncomp; g++) {
 		const int nc = std::min(gmax, ncomp - c0);
 		RotK q = p;
-		q.in = (const char*)alm_in + (size_t)c0*in_cstride*(alm_dtype == PX_C64 ? 8 : 16); q.in_cstride = in_cstride;
-		q.out = (char*)alm_out + (size_t)c0*out_cstride*(alm_dtype == PX_C64 ? 8 : 16); q.out_cstride = out_cstride;
+		q.in = (const char*)alm_in + (size_t)c0*in_cstride*dtype_bytes(alm_dtype); q.in_cstride = in_cstride;
+		q.out = (char*)alm_out + (size_t)c0*out_cstride*dtype_bytes(alm_dtype); q.out_cstride = out_cstride;
 		q.ang_in = psi;
 		switch (nc) {
 			case 1: rot_group<1>(q, coef, g == 0, x1, x2, theta, phi, st); break;

@@ -177,14 +177,13 @@ void leg_to_h(pxs_plan* p, hipStream_t st, const double2* leg, long ldleg, long 
 		(long)nm*ldleg, (long)nr*ldh, ldleg, ldh, (const double2*)p->phase.p, 1, 1.0);
 }
 
-static int map_esz(int dt) { return dt == PX_F32 ? 4 : 8; }
 // n lines of an FFT of the generic engine, dense along the line: line i reads from i*is and writes to i*os
 static FftDims lines(long n, long is, long os) { FftDims d; d.n_i = n; d.is_i = is; d.os_i = os; return d; }
 
 // (the unfused ring FFT of a map sizes its own packed spectra in hbuf; rings shorter than 2 mmax + 1 alias and go unpaired)
 void unfused_map2leg(pxs_plan* p, hipStream_t st, const MapArg& m, int nc, double2* leg) {
 	const int nm = p->mmax + 1, nr = p->nring;
-	FftLoad ld; ld.ptr = (const char*)m.ptr + map_esz(m.dtype)*p->ring_off0; ld.dtype = m.dtype;
+	FftLoad ld; ld.ptr = (const char*)m.ptr + dtype_bytes(m.dtype)*p->ring_off0; ld.dtype = m.dtype;
 	FftStore sf;
 	if (2L*p->mmax < p->nphi) {
 		// two real rings per complex transform; the pruned two-sided spectrum (|k| <= mmax) is unpacked in the transpose
@@ -216,7 +215,7 @@ void unfused_h2map(pxs_plan* p, hipStream_t st, const MapArg& m, int nc) {
 	const bool pairs = 2L*p->mmax < p->nphi;      // two rings per complex transform: Z = X_a + i X_b, real part -> ring 2q, imaginary part -> ring 2q+1
 	FftDims d = lines(pairs ? (nr + 1)/2 : nr, nm, p->ring_stride); d.n_o1 = nc; d.is_o1 = (long)nr*nm; d.os_o1 = m.cstride; d.os_e = p->pix_stride;
 	FftLoad ld; ld.ptr = p->hbuf.p; ld.ne = nm;
-	FftStore sf; sf.ptr = (char*)m.ptr + map_esz(m.dtype)*p->ring_off0; sf.dtype = m.dtype;
+	FftStore sf; sf.ptr = (char*)m.ptr + dtype_bytes(m.dtype)*p->ring_off0; sf.dtype = m.dtype;
 	if (pairs) { ld.mode = LD_HERM_PAIR; ld.pair_lines = nr; sf.real_pair = 1; sf.pair_lines = nr; }
 	else { ld.mode = LD_HERM; ld.herm_fold = 1; }
 	p->fc->exec(st, p->nphi, false, d, ld, sf);

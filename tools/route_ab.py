@@ -1,12 +1,13 @@
 """A/B of two builds of the library, route by route: the same seeded calls through each (one fresh process per library, selected with
 PIXELL_AMD_LIB), outputs dumped and compared.  The case list reaches every value of the route enum of csrc/sht_plan.hpp, both directions.
 
-  PIXELL_AMD_LIB=<lib> PXS_CHAIN_VERBOSE=1 python tools/route_ab.py run OUT.npz [--split] 2> OUT.log
+  PIXELL_AMD_LIB=<lib> PXS_CHAIN_VERBOSE=1 python tools/route_ab.py run OUT.npz [--split | --fft] 2> OUT.log
   python tools/route_ab.py compare A.npz B.npz B.log     # B.log: the verbose log of a build that prints its routes
   python tools/route_ab.py merge SIM_TABLE GPU_TABLE...   # compare outputs -> the table of profiles/route_refactor_ab.txt
 
 Maps must agree bit for bit; alm bit for bit with the deterministic option (and on the simulator), to 1e-13 relative rms with the
-default atomic sums on the GPU (the bound of tests/test_streams.py); scratch_bytes, analysis_form and theta_line must be equal."""
+default atomic sums on the GPU (the bound of tests/test_streams.py); scratch_bytes, analysis_form and theta_line must be equal.
+--fft: the generic N-d FFT engine instead (csrc/fft.hip, api_fft.hip), which has no atomic sums: every output bit for bit, everywhere."""
 import os, sys, json
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,20 +100,67 @@ def cases(split):
 	cs += [points("alm2map_pos s2", False), points("alm2map_pos adjoint s2", True)]
 	return cs
 
-def run(out, split):
+def fft_cases():
+	"""pixell_amd.fft on seeded arrays: single-pass lines (the direct-DFT radix pass at 7 and 61, 2048 the longest), four-step lines (2304 the
+	shortest), chirp-z by the min-prime rule (131) and for want of a factorisation (4099), every kind, strided views, the budget seam"""
+	import torch
+	from pixell_amd import fft as pfft, _lib
+	rng = np.random.default_rng(4321)
+	dev = "cpu" if _lib.is_hostsim() else "cuda"
+	def arr(*sh, dt=np.complex128):
+		x = rng.standard_normal(sh)+(1j*rng.standard_normal(sh) if np.dtype(dt).kind == "c" else 0)
+		return torch.from_numpy(x.astype(dt)).to(dev)
+	def out(*sh, dt=np.complex128): return torch.zeros(sh, dtype=getattr(torch, np.dtype(dt).name), device=dev)
+	cs = []
+	def case(name, fn, env=None):
+		def run():
+			for k, v in (env or {}).items(): os.environ[k] = v
+			try: o = fn().cpu().numpy()
+			except _lib.PxsError as e: o = np.array([e.code])      # (a refusal is an outcome too: the same code from both builds)
+			finally:
+				for k in (env or {}): del os.environ[k]
+			return o, None
+		cs.append(("fft "+name, run))
+	for n in (1, 2, 7, 36, 61, 131, 216, 2048, 2304, 4099, 10800):
+		x = arr(3, n)
+		case("c2c forward n=%d" % n, lambda x=x: pfft.fft(x)); case("c2c backward n=%d" % n, lambda x=x: pfft.ifft(x))
+	for n in (9, 16):
+		x = arr(3, n, dt=np.float64); h = arr(3, n//2+1); h2 = arr(6, n//2+1)
+		case("r2c n=%d" % n, lambda x=x: pfft.rfft(x)); case("c2r n=%d" % n, lambda h=h, n=n: pfft.irfft(h, n=n))
+		case("c2r two axes 6 x %d" % n, lambda h2=h2, n=n: pfft.irfft(h2, n=n, axes=[-2, -1]))
+	x = arr(2, 5, 12); case("middle axis of (2, 5, 12)", lambda x=x: pfft.fft(x, axes=[1]))
+	x = arr(8, 21)[::2, 1::3]; case("non-contiguous input view", lambda x=x: pfft.fft(x))
+	x = arr(4, 10); o = out(4, 20)
+	def strided_out(x=x, o=o): pfft.fft(x, o[:, ::2]); return o      # (the whole base array: what lies between must stay untouched)
+	case("output into a strided view", strided_out)
+	x = arr(4, 6, 10); case("three axes", lambda x=x: pfft.fft(x, axes=[0, 1, 2]))
+	x = arr(3, 36, dt=np.complex64); case("c2c complex64", lambda x=x: pfft.fft(x))
+	x = arr(3, 16, dt=np.float32); case("r2c float32", lambda x=x: pfft.rfft(x))
+	# 3000: the extended length 6000 is a four-step line; DCT-I and DST-I extend to 2 (n -+ 1), which has it at 3001 and 2999 and is refused
+	# at 3000 (5998 = 2 x 2999, 6002 = 2 x 3001: no chirp-z for r2r)
+	kinds = ("DCT-I", "DCT-II", "DCT-III", "DCT-IV", "DST-I", "DST-II", "DST-III", "DST-IV")
+	for n, t in [(n, t) for n in (5, 16, 31, 3000) for t in kinds]+[(3001, "DCT-I"), (2999, "DST-I")]:
+		case("%s n=%d" % (t, n), lambda x=arr(2, n, dt=np.float64), t=t: pfft.dct(x, type=t))
+	x = arr(24, 40, dt=np.float64); case("real 2-D, generic engine", lambda x=x: pfft.fft(x, axes=[-2, -1]), env={"PXS_FFT2_FAST_MINPIX": "-1"})
+	x = arr(40, 2304); case("four-step in passes of 14 lines", lambda x=x: pfft.fft(x), env={"PXS_FFT_TEMP_MB": "0.5"})
+	return cs
+
+def run(out, split, fft=False):
 	from pixell_amd import sht, _lib
 	res = {}; meta = {"hostsim": bool(_lib.is_hostsim()), "version": _lib.load().pxs_version().decode(), "cases": []}
-	for det in (False, True):
+	for det in ((False,) if fft else (False, True)):
 		sht.set_deterministic(det); sht.clear_plans()
-		for name, fn in cases(split):
+		for name, fn in (fft_cases() if fft else cases(split)):
 			key = name+(" [det]" if det else "")
 			os.write(2, ("CASE %s\n" % key).encode())
 			o, plan = fn()
 			if not _lib.is_hostsim():
 				import torch; torch.cuda.synchronize()
 			res[key] = np.array(o, copy=True)
-			meta["cases"].append(dict(name=key, scratch=plan.info()["scratch_bytes"], nring_syn=plan.info()["nring_syn"], nring_ana=plan.info()["nring_ana"],
-				form=plan.query("analysis_form"), line=plan.query("theta_line"), alm=bool(np.iscomplexobj(o))))
+			info = plan.info() if plan is not None else dict(scratch_bytes=0, nring_syn=0, nring_ana=0)      # (the FFT cases have no plan)
+			meta["cases"].append(dict(name=key, scratch=info["scratch_bytes"], nring_syn=info["nring_syn"], nring_ana=info["nring_ana"],
+				form=plan.query("analysis_form") if plan is not None else 0, line=plan.query("theta_line") if plan is not None else 0,
+				alm=bool(plan is not None and np.iscomplexobj(o))))
 	np.savez(out, **{k.replace("/", "|"): v for k, v in res.items()})
 	with open(out+".json", "w") as f: json.dump(meta, f)
 
@@ -161,6 +209,6 @@ def merge(sim_table, gpu_tables):
 	return bad
 
 if __name__ == "__main__":
-	if sys.argv[1] == "run": run(sys.argv[2], "--split" in sys.argv)
+	if sys.argv[1] == "run": run(sys.argv[2], "--split" in sys.argv, "--fft" in sys.argv)
 	elif sys.argv[1] == "merge": sys.exit(1 if merge(sys.argv[2], sys.argv[3:]) else 0)
 	else: sys.exit(1 if compare(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else None) else 0)
