@@ -130,6 +130,9 @@ int pxs_analysis(pxs_plan* plan, int spin, int adjoint, int nbatch,
  * "leg_max_batch" (value = n >= 0; default 0 = no bound): at most n maps per launch of the single-map (VALU) Legendre kernels and 8 n per
  *   launch of the FP64-MFMA kernels.  The only limit otherwise is the grid size (2^31 blocks: tens of thousands of maps in one call);
  *   the option exists so that the launch loop can be tested.  Same results.
+ * "leg_ana_k" (value = K >= 0; default 0 = the library's rule): ring pairs per lane of the single-map (VALU) Legendre analysis kernels.  The rule
+ *   takes 8 (spin 0) / 4 (spin s), fewer on small ring sets, and 6 for spin s where the ring set gives at least 8 waves per m; the option exists
+ *   so that every compiled kernel can be tested on a small ring set.  A K without a compiled kernel is an error of the call.  Same results to rounding.
  * Memory budgets from the environment (PXS_BATCH_GB, PXS_PART_GB, PXS_SEED_GB, PXS_CHAIN_SCRATCH_GB in GB; PXS_FFT_TEMP_MB,
  *   PXS_RESAMPLE_MB, PXS_RING_CHUNK_MB in MB) are real numbers of their unit (0.004 GB = 4 MB), read as the plan is made (PXS_PART_GB,
  *   PXS_RESAMPLE_MB), per call (the others) or per transform of the FFT engine (PXS_FFT_TEMP_MB: pxf_fft_nd and plans alike).
@@ -140,6 +143,7 @@ int pxs_plan_option(pxs_plan* plan, const char* name, int64_t value);
  * route), "ncc_circle" = N_cc, the circle of the CC grid of the Legendre stage (0: none), "ducc_ncc_circle" = ducc0's N_cc for
  * the plan's lmax, "theta_line" = 1 if the theta resampling of pxs_analysis runs as one kernel with the line resident on a CU
  * (the circle sizes compiled into thetaline.hip; PXS_THETA_LINE=0 switches it off), 0 if as the five-stage chain: same results.
+ * "leg_ana_k": ring pairs per lane of the single-map Legendre analysis kernels in the plan's most recent analysis or adjoint synthesis (0: none yet).
  * "chain_stages": the distinct FFT chain stage shapes (stage, transform lengths, lines per tile) of the plan's standard calls (analysis
  * under its current option, synthesis of spin 0 and 2); "chain_static": how many of them have a compile-time-planned kernel
  * (csrc/chain_static_table.hpp; PXS_CHAIN_STATIC=0, read per call, runs the run-time kernel for all: same results to rounding);

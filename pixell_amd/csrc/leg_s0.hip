@@ -178,6 +178,28 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 	kk += 2; \
 	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*kbase, lane, LEG_FSTEPS, a.atomic); kk = 0; kbase = k+2; } }
 
+// one step of the spin-0 analysis on the step coefficients themselves: the four lane sums of the step into T0..T3, LA the current values, LB the previous ones (-> the next)
+#define S0_ANA_STEP_C(ca, cb, LA, LB, T0, T1, T2, T3) { \
+	PXS_VCOPY(vb, cb); \
+	_Pragma("unroll") for (int s = 0; s < K; s++) { \
+		T0 = fma(LA[s], d1r[s], T0); T1 = fma(LA[s], d1i[s], T1); T2 = fma(LA[s], d2r[s], T2); T3 = fma(LA[s], d2i[s], T3); \
+		LB[s] = fma(fma(ca, csq[s], vb), LA[s], LB[s]); \
+	} }
+// two fast steps of phase C from step kfirst on: the drain of the scalar rows between the two, the flush of a full tile and the request of the next rows (NEXT) at it
+#define S0_ANA_PAIR_D(ca0, cb0, ca1, cb1, kfirst, NEXT) { \
+	double t0 = 0, t1 = 0, t2 = 0, t3 = 0, u0 = 0, u1 = 0, u2 = 0, u3 = 0; \
+	S0_ANA_STEP_C(ca0, cb0, lam2, lam1, t0, t1, t2, t3) \
+	_Pragma("unroll") for (int s = 0; s < K; s++) PXS_DONE(lam1[s]); \
+	PXS_DONE(t0); PXS_DONE(t1); PXS_DONE(t2); PXS_DONE(t3); \
+	PXS_ROWS_DRAIN(); \
+	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*kbase, lane, LEG_FSTEPS, a.atomic); kk = 0; kbase = (kfirst); } \
+	NEXT; \
+	PXS_ROWS_ISSUED(); \
+	S0_ANA_STEP_C(ca1, cb1, lam1, lam2, u0, u1, u2, u3) \
+	LEG_RED_PUT(kk, t0, t1, t2, t3) \
+	LEG_RED_PUT(kk+1, u0, u1, u2, u3) \
+	kk += 2; }
+
 template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 {
 	PXS_SHARED(double, red);
@@ -194,7 +216,7 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 	const bool polar = leg_wave_polar(a, wv, K);
 	// ring data of slot s: sum and (difference x cos theta) of the north and south ring
 	auto load_data = [&](int s) {
-		const int p = leg_pair(a, wv, K, s, lane);
+		const int p = leg_pair(a, wv, K, s, PXS_LATE_INT(lane));
 		const bool valid = leg_pair_valid(a, p);
 		const int rn = valid ? a.ring_n[p] : -1, rs = valid ? a.ring_s[p] : -1;
 		const double x = valid ? a.cth[p] : 0.0;
@@ -245,22 +267,24 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 				if (++sc[s] == 0) load_data(s);
 			}
 	}
-	// phase C: every lane at scale 0 (or without data): next coefficients prefetched with scalar loads (the one-drain loop of leg_syn_s0, the drain between the two steps of
-	// a pair and the flush at that drain: 24.1 -> 23.5 ms at C3, inside three times the spread; not in the tree -- legendre_dev.hpp, "Row prefetch")
-	double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1);
+	// phase C: every lane at scale 0 (or without data).  The one-drain loop of leg_syn_s0 on the compact rows (a, b'), with the drain BETWEEN the two steps of a pair -- the
+	// ds_writes of the reduction count on lgkmcnt too and are a step old there -- and the flush of a full tile at that drain.  A row set therefore spans the second step of
+	// a pair and the first step of the next one: it is requested at one drain, complete at the next and read from there to the one after (legendre_dev.hpp, "Row prefetch")
+	const double2* __restrict__ cf = (const double2*)PXS_UNIFORM_LONG((long)((polar ? a.coef2p : a.coef2) + row0));
+	coef2x2_t n = LDC2(cf, k), f = LDC2(cf, k+1);
+	PXS_ROWS_DRAIN();
+	n.a1 = n.a0; n.b1 = n.b0;      // (n.a1, n.b1): the row of the first step of the next pair (the row of step k + 1 that came with it is dropped: one 16-byte row per wave and m)
 	while (k + 3 < nk) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
-		double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3);
-		S0_ANA_PAIR(c0, c1)
-		k += 2;
-		c0 = LDC(coef, k+2); c1 = LDC(coef, k+3);
-		S0_ANA_PAIR(n0, n1)
+		S0_ANA_PAIR_D(n.a1, n.b1, f.a0, f.b0, k, n = LDC2(cf, k+3))
+		S0_ANA_PAIR_D(f.a1, f.b1, n.a0, n.b0, k+2, f = LDC2(cf, k+5))
+		k += 4;
+	}
+	if (k + 1 < nk) {
+		S0_ANA_PAIR_D(n.a1, n.b1, f.a0, f.b0, k, (void)0)
 		k += 2;
 	}
-	for (; k + 1 < nk; k += 2) {
-		const double4_t n0 = LDC(coef, k+2), n1 = LDC(coef, k+3);
-		S0_ANA_PAIR(c0, c1)
-		c0 = n0; c1 = n1;
-	}
+	PXS_ROWS_DRAIN();
+	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*kbase, lane, LEG_FSTEPS, a.atomic); kk = 0; kbase = k; }
 	if (k < nk) {
 		double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
 #pragma unroll
@@ -397,8 +421,10 @@ template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_s0_mm(const Le
 // ---- launches: the kernel of (direction, form, K or ng); the ring pairs per lane the host's rules select are 4 and 2 (synthesis), 8, 4 and 2 (analysis) ----
 void launch_leg_s0(bool analysis, int ng, int K, dim3 grid, hipStream_t st, const LegK& a) {
 	static const bool once = leg_mm_lds_optin({leg_ana_s0_mm<2, MM_WAVES>, leg_ana_s0_mm<1, MM_WAVES>}); (void)once;
-	const LegKernel k = analysis ? (ng == 2 ? leg_ana_s0_mm<2, MM_WAVES> : ng ? leg_ana_s0_mm<1, MM_WAVES> : K == 8 ? leg_ana_s0<8> : K == 2 ? leg_ana_s0<2> : leg_ana_s0<4>)
-	                             : (ng == 2 ? leg_syn_s0_mm<2> : ng ? leg_syn_s0_mm<1> : K == 2 ? leg_syn_s0<2> : leg_syn_s0<4>);
+	// (a K without a compiled kernel is an error, not another kernel: the grid, the seeds and the partial moments were laid out for the K asked for)
+	const LegKernel k = analysis ? (ng == 2 ? leg_ana_s0_mm<2, MM_WAVES> : ng ? leg_ana_s0_mm<1, MM_WAVES> : K == 8 ? leg_ana_s0<8> : K == 4 ? leg_ana_s0<4> : K == 2 ? leg_ana_s0<2> : nullptr)
+	                             : (ng == 2 ? leg_syn_s0_mm<2> : ng ? leg_syn_s0_mm<1> : K == 4 ? leg_syn_s0<4> : K == 2 ? leg_syn_s0<2> : nullptr);
+	PXS_REQUIRE(k != nullptr, "internal: no spin-0 Legendre kernel compiled for this number of ring pairs per lane");
 	leg_launch(k, analysis, ng, grid, st, a);
 }
 

@@ -101,13 +101,25 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 		} \
 	}
 
+// Row sets of the phase-C loops (legendre_dev.hpp, "Row prefetch"): the 32-byte rows of two consecutive steps, requested together.  SPIN_ROW0(r) / SPIN_ROW1(r):
+// (ca, c1, c2) of the first / second step of set r, (a, b, -b) in plain waves and the columns (a, c, d) in polar ones -- written where the row is used, behind the
+// drain: anything computed from a row at its request would make the compiler wait there.  (Plain waves on the compact rows (a, b), in a loop of their own next to the
+// polar waves' loop, had every load at its distance too, but the kernels then held the chains and the sums of both loops in registers of their own:
+// leg_syn_spin<3> 103 -> 168 VGPRs, leg_ana_spin<4> 152 -> 178, a wave per SIMD less each.)
+struct spin_rows_t { double4_t r0, r1; };
+__device__ __forceinline__ spin_rows_t spin_rows(const double4_t* coef, long i) { spin_rows_t r; r.r0 = LDC(coef, i); r.r1 = LDC(coef, i+1); return r; }
+#define SPIN_ROW0(r) r.r0.a, polar ? r.r0.c : r.r0.b, polar ? r.r0.d : -r.r0.b
+#define SPIN_ROW1(r) r.r1.a, polar ? r.r1.c : r.r1.b, polar ? r.r1.d : -r.r1.b
+
 // (step coefficient a x +- b as one FMA with the additive constant copied to a VGPR once per step -- gfx950 allows one
 // scalar source per VALU op -- instead of a multiply shared by two adds: 12 + 2/K instead of 13 VALU ops per ring pair and l)
 // two fast steps of the spin synthesis (G1/G2 swap roles).  The south-ring sums take (-1)^(l+m) a: they are
 // accumulated with sign +1 on even steps and -1 on odd steps and multiplied by the sign of the first step at the end.
-#define SPIN_SYN_PAIR(f0, f1, a0, a1) { \
+#define SPIN_SYN_PAIR(f0, f1, a0, a1) SPIN_SYN_PAIR_C(f0.a, polar ? f0.c : f0.b, polar ? f0.d : -f0.b, f1.a, polar ? f1.c : f1.b, polar ? f1.d : -f1.b, a0, a1)
+// ... on the step coefficients themselves: (ca, c1, c2) of a step = a and the additive constants of the G+ and the G- chain
+#define SPIN_SYN_PAIR_C(ca0, c10, c20, ca1, c11, c21, a0, a1) { \
 	{ \
-		const double ca = f0.a, c1 = polar ? f0.c : f0.b, c2 = polar ? f0.d : -f0.b; \
+		const double ca = ca0, c1 = c10, c2 = c20; \
 		PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
 		_Pragma("unroll") for (int s = 0; s < K; s++) { \
 			const double gp = S.gp2[s], gm = S.gm2[s]; \
@@ -119,7 +131,7 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 		} \
 	} \
 	{ \
-		const double ca = f1.a, c1 = polar ? f1.c : f1.b, c2 = polar ? f1.d : -f1.b; \
+		const double ca = ca1, c1 = c11, c2 = c21; \
 		PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
 		_Pragma("unroll") for (int s = 0; s < K; s++) { \
 			const double gp = S.gp1[s], gm = S.gm1[s]; \
@@ -130,6 +142,31 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 			S.gp2[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp2[s]); S.gm2[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm2[s]); \
 		} \
 	} }
+
+#define SPIN_SYN_PAIR_R(s0, s1, a0, a1) SPIN_SYN_PAIR_C(s0, s1, a0, a1)
+// phase C of the spin synthesis (the row sets above; here a set is the two steps of a pair): one drain per step pair, the rows of the next pair
+// (table and pre-scaled alm) requested right behind it, two pairs per trip on alternating row sets (leg_syn_s0)
+#define SPIN_SYN_PHASE_C { \
+	spin_rows_t f = spin_rows(coef, j); a0 = LDC(at, j); a1 = LDC(at, j+1); \
+	while (j + 3 < nl) { \
+		PXS_ROWS_DRAIN(); \
+		spin_rows_t n = spin_rows(coef, j+2); double4_t m0 = LDC(at, j+2), m1 = LDC(at, j+3); \
+		PXS_ROWS_ISSUED(); \
+		SPIN_SYN_PAIR_R(SPIN_ROW0(f), SPIN_ROW1(f), a0, a1) \
+		PXS_ROWS_DRAIN(); \
+		f = spin_rows(coef, j+4); a0 = LDC(at, j+4); a1 = LDC(at, j+5); \
+		PXS_ROWS_ISSUED(); \
+		SPIN_SYN_PAIR_R(SPIN_ROW0(n), SPIN_ROW1(n), m0, m1) \
+		j += 4; \
+	} \
+	for (; j + 1 < nl; j += 2) { \
+		PXS_ROWS_DRAIN(); \
+		const spin_rows_t n = spin_rows(coef, j+2); const double4_t m0 = LDC(at, j+2), m1 = LDC(at, j+3); \
+		PXS_ROWS_ISSUED(); \
+		SPIN_SYN_PAIR_R(SPIN_ROW0(f), SPIN_ROW1(f), a0, a1) \
+		f = n; a0 = m0; a1 = m1; \
+	} \
+	PXS_ROWS_DRAIN(); }
 
 // (leg_syn_spin<3> must stay below 128 VGPRs = 4 waves per SIMD; computing the lane as threadIdx.x & 63 for multi-wave
 // workgroups once pushed it to 132 = 3 waves and leg_syn from 120 to 151 ms at config 3 -- keep an eye on that cliff.)
@@ -184,21 +221,9 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 				pnr[s] = pni[s] = mnr[s] = mni[s] = qsr[s] = qsi[s] = nsr[s] = nsi[s] = 0;
 				S.gp1[s] = S.gp2[s] = S.gm1[s] = S.gm2[s] = 0;
 			}
-		// phase C: fast loop, next coefficients prefetched (with one drain per step pair and the next rows requested right behind it, as in leg_syn_s0: 67.8 -> 66.4 ms at C3, about three times the spread; not in the tree -- legendre_dev.hpp, "Row prefetch")
-		double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1), a0 = LDC(at, j), a1 = LDC(at, j+1);
-		while (j + 3 < nl) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
-			double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3), m0 = LDC(at, j+2), m1 = LDC(at, j+3);
-			SPIN_SYN_PAIR(f0, f1, a0, a1)
-			j += 2;
-			f0 = LDC(coef, j+2); f1 = LDC(coef, j+3); a0 = LDC(at, j+2); a1 = LDC(at, j+3);
-			SPIN_SYN_PAIR(n0, n1, m0, m1)
-			j += 2;
-		}
-		for (; j + 1 < nl; j += 2) {
-			const double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3), m0 = LDC(at, j+2), m1 = LDC(at, j+3);
-			SPIN_SYN_PAIR(f0, f1, a0, a1)
-			f0 = n0; f1 = n1; a0 = m0; a1 = m1;
-		}
+		// phase C: fast loop, the one-drain loop of leg_syn_s0 on the 32-byte rows (legendre_dev.hpp, "Row prefetch")
+		double4_t a0, a1;
+		SPIN_SYN_PHASE_C
 		if (j < nl) {
 #pragma unroll
 			for (int s = 0; s < K; s++) {
@@ -262,7 +287,62 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 	kk += 2; \
 	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*jbase, lane, LEG_FSTEPS, a.atomic); kk = 0; jbase = j+2; } }
 
-template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
+// the two steps of SPIN_ANA_PAIR on the step coefficients themselves, (ca, c1, c2) = a and the additive constants of the G+ and the G- chain: the first step of a
+// pair (south-ring sign +, sums into t0..t3), the second (sign -, sums into u0..u3)
+#define SPIN_ANA_STEP0_C(ca, c1, c2) { \
+	PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
+	_Pragma("unroll") for (int s = 0; s < K; s++) { \
+		const double gp = S.gp2[s], gm = S.gm2[s]; \
+		t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0); \
+		t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1); \
+		t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2); \
+		t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3); \
+		S.gp1[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp1[s]); S.gm1[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm1[s]); \
+	} }
+#define SPIN_ANA_STEP1_C(ca, c1, c2) { \
+	PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
+	_Pragma("unroll") for (int s = 0; s < K; s++) { \
+		const double gp = S.gp1[s], gm = S.gm1[s]; \
+		u0 = fma(gp, tpnr[s], u0); u0 = fma(-gm, tpsr[s], u0); \
+		u1 = fma(gp, tpni[s], u1); u1 = fma(-gm, tpsi[s], u1); \
+		u2 = fma(gm, tmnr[s], u2); u2 = fma(-gp, tmsr[s], u2); \
+		u3 = fma(gm, tmni[s], u3); u3 = fma(-gp, tmsi[s], u3); \
+		S.gp2[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp2[s]); S.gm2[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm2[s]); \
+	} }
+// two fast steps of phase C from step jfirst on: the drain of the scalar rows between the two, the flush of a full tile and the request of the next rows (NEXT) at it
+// (leg_ana_s0, S0_ANA_PAIR_D)
+#define SPIN_ANA_PAIR_D(ca0, c10, c20, ca1, c11, c21, jfirst, NEXT) { \
+	double t0 = 0, t1 = 0, t2 = 0, t3 = 0, u0 = 0, u1 = 0, u2 = 0, u3 = 0; \
+	SPIN_ANA_STEP0_C(ca0, c10, c20) \
+	_Pragma("unroll") for (int s = 0; s < K; s++) { PXS_DONE(S.gp1[s]); PXS_DONE(S.gm1[s]); } \
+	PXS_DONE(t0); PXS_DONE(t1); PXS_DONE(t2); PXS_DONE(t3); \
+	PXS_ROWS_DRAIN(); \
+	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*jbase, lane, LEG_FSTEPS, a.atomic); kk = 0; jbase = (jfirst); } \
+	NEXT; \
+	PXS_ROWS_ISSUED(); \
+	SPIN_ANA_STEP1_C(ca1, c11, c21) \
+	LEG_RED_PUT(kk, t0, t1, t2, t3) \
+	LEG_RED_PUT(kk+1, u0, u1, u2, u3) \
+	kk += 2; }
+// phase C of the spin analysis.  A row set spans the second step of a pair and the first of the next one (leg_ana_s0): the loop enters with the row of step j in
+// the place of "the first step of the next pair"
+#define SPIN_ANA_PHASE_C { \
+	spin_rows_t n = spin_rows(coef, j), f = spin_rows(coef, j+1); \
+	PXS_ROWS_DRAIN(); \
+	n.r1 = n.r0; \
+	while (j + 3 < nl) {      /* (two pairs per iteration on alternating row sets, see leg_syn_s0) */ \
+		SPIN_ANA_PAIR_R(SPIN_ROW1(n), SPIN_ROW0(f), j, n = spin_rows(coef, j+3)) \
+		SPIN_ANA_PAIR_R(SPIN_ROW1(f), SPIN_ROW0(n), j+2, f = spin_rows(coef, j+5)) \
+		j += 4; \
+	} \
+	if (j + 1 < nl) { \
+		SPIN_ANA_PAIR_R(SPIN_ROW1(n), SPIN_ROW0(f), j, (void)0) \
+		j += 2; \
+	} }
+#define SPIN_ANA_PAIR_R(s0, s1, jfirst, NEXT) SPIN_ANA_PAIR_D(s0, s1, jfirst, NEXT)
+
+// (K = 2 is asked to keep its 5 waves per SIMD: 96 VGPRs; left alone the one-drain loop takes 98 = 4 waves.  No scratch either way)
+template<int K> __global__ __launch_bounds__(64, (K == 2 ? 5 : 1)) void leg_ana_spin(const LegK a)
 {
 	PXS_SHARED(double, red);
 	const int lane = threadIdx.x; int wv, m, bb;
@@ -286,7 +366,7 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 	double tpnr[K], tpni[K], tmnr[K], tmni[K], tpsr[K], tpsi[K], tmsr[K], tmsi[K];
 	auto load_data = [&](int s) {
 		// ring indices are re-read here rather than kept in registers through the loops (the kernel sits at the 256-VGPR line)
-		const int p = leg_pair(a, wv, K, s, lane);
+		const int p = leg_pair(a, wv, K, s, PXS_LATE_INT(lane));
 		const bool valid = leg_pair_valid(a, p);
 		const int rn_ = valid ? a.ring_n[p] : -1, rs_ = valid ? a.ring_s[p] : -1;
 		double2 q = rn_ >= 0 ? inq[rn_] : make_double2(0, 0), u = rn_ >= 0 ? inu[rn_] : make_double2(0, 0);
@@ -324,21 +404,11 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_spin(const LegK a)
 			if (was && S.scp[s] == 0 && S.scm[s] == 0) load_data(s);
 		}
 	}
-	// phase C: next coefficients prefetched (with one drain per step pair, between its two steps, and the flush at that drain: 90.4 -> 89.1 ms at C3, inside three times the spread; not in the tree -- legendre_dev.hpp, "Row prefetch")
-	double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1);
-	while (j + 3 < nl) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
-		double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3);
-		SPIN_ANA_PAIR(f0, f1)
-		j += 2;
-		f0 = LDC(coef, j+2); f1 = LDC(coef, j+3);
-		SPIN_ANA_PAIR(n0, n1)
-		j += 2;
-	}
-	for (; j + 1 < nl; j += 2) {
-		const double4_t n0 = LDC(coef, j+2), n1 = LDC(coef, j+3);
-		SPIN_ANA_PAIR(f0, f1)
-		f0 = n0; f1 = n1;
-	}
+	// phase C: the one-drain loop of leg_syn_s0 with the drain between the two steps of a pair and the flush of a full tile at that drain, as in leg_ana_s0, on the
+	// 32-byte rows (legendre_dev.hpp, "Row prefetch")
+	SPIN_ANA_PHASE_C
+	PXS_ROWS_DRAIN();
+	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*jbase, lane, LEG_FSTEPS, a.atomic); kk = 0; jbase = j; }
 	if (j < nl) {
 		double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
 #pragma unroll
@@ -483,11 +553,13 @@ template<int NG, int W> __global__ __launch_bounds__(64*W, 4) void leg_ana_spin_
 // rows as (P', M).  The shape of leg_syn_s0_mm: one P tile, 4 x 8 accumulator VGPRs per group of 4 maps, one wave per workgroup, no cross-wave step.
 template<int NG> __global__ __launch_bounds__(64, 4) void leg_syn_spin_mm(const LegK a) { leg_syn_mm<SpinMm, NG>(a); }
 
-// ---- launches: the kernel of (direction, form, K or ng); the ring pairs per lane the host's rules select are 3 and 2 (synthesis), 4, 3 and 2 (analysis) ----
+// ---- launches: the kernel of (direction, form, K or ng); the ring pairs per lane the host's rules select are 3 and 2 (synthesis), 6, 4, 3 and 2 (analysis) ----
 void launch_leg_spin(bool analysis, int ng, int K, dim3 grid, hipStream_t st, const LegK& a) {
 	static const bool once = leg_mm_lds_optin({leg_ana_spin_mm<2, MM_WAVES>, leg_ana_spin_mm<1, MM_WAVES>}); (void)once;
-	const LegKernel k = analysis ? (ng == 2 ? leg_ana_spin_mm<2, MM_WAVES> : ng ? leg_ana_spin_mm<1, MM_WAVES> : K >= 4 ? leg_ana_spin<4> : K == 3 ? leg_ana_spin<3> : leg_ana_spin<2>)
-	                             : (ng == 2 ? leg_syn_spin_mm<2> : ng ? leg_syn_spin_mm<1> : K == 3 ? leg_syn_spin<3> : leg_syn_spin<2>);
+	// (a K without a compiled kernel is an error, not another kernel: the grid, the seeds and the partial moments were laid out for the K asked for)
+	const LegKernel k = analysis ? (ng == 2 ? leg_ana_spin_mm<2, MM_WAVES> : ng ? leg_ana_spin_mm<1, MM_WAVES> : K == 6 ? leg_ana_spin<6> : K == 4 ? leg_ana_spin<4> : K == 3 ? leg_ana_spin<3> : K == 2 ? leg_ana_spin<2> : nullptr)
+	                             : (ng == 2 ? leg_syn_spin_mm<2> : ng ? leg_syn_spin_mm<1> : K == 3 ? leg_syn_spin<3> : K == 2 ? leg_syn_spin<2> : nullptr);
+	PXS_REQUIRE(k != nullptr, "internal: no spin-s Legendre kernel compiled for this number of ring pairs per lane");
 	leg_launch(k, analysis, ng, grid, st, a);
 }
 

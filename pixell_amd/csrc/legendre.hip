@@ -39,7 +39,8 @@
 namespace pxs {
 
 // ring pairs per lane (K) of the VALU kernels: chosen by measurement on MI355X (profiles/r04_ktune_c3.txt, profiles/r05_dp_rate_and_k_waves.txt;
-// leg_ana_spin<4>: 3 waves per SIMD, K = 6 has 2: 146.9 against 150.5 ms at config 3); k_small_grid lowers them on small ring sets
+// leg_ana_spin<4>: 3 waves per SIMD, K = 6 has 2: 146.9 against 150.5 ms at config 3, before the one-drain row prefetch); k_small_grid lowers them on small ring
+// sets, leg_ana_k raises the analysis ones on large ring sets
 static constexpr int K_SYN0 = 4, K_ANA0 = 8, K_SYNS = 3, K_ANAS = 4;
 
 // ---------------------------------------------------------------------------------
@@ -499,6 +500,8 @@ void LegTables::build(int lmax_, int mmax_, int spin_) {
 	}
 	d_row = upload(row);
 	DevBuf d_start = upload(start);
+	// (4 rows of padding: the phase-C loops of the VALU kernels request rows up to 2 past the end of an m (leg_syn_s0, leg_syn_spin) or 3 (the analysis kernels, whose
+	// row sets start a step late), the pre-scaled alm (leg_almt_stride) up to 2)
 	d_coef.alloc(sizeof(double4_t)*(size_t)(nrows + 4)); d_alpha.alloc(sizeof(double)*(size_t)(nrows + 4));
 	// (+4 rows: the fast loops prefetch up to 3 rows ahead)
 	PXS_HIP(hipMemset((char*)d_coef.p + sizeof(double4_t)*(size_t)nrows, 0, sizeof(double4_t)*4)); PXS_HIP(hipMemset((char*)d_alpha.p + sizeof(double)*(size_t)nrows, 0, sizeof(double)*4));
@@ -634,6 +637,17 @@ static int k_small_grid(const RingSet& rs, int kdef, std::initializer_list<int> 
 	for (int k : smaller) if (k < kdef && eligible(k)) return k;
 	return kdef;
 }
+// Ring pairs per lane of the VALU analysis.  Spin s: where k_small_grid leaves the default and the ring set gives LEG_BIG_MIN_WAVES waves per m with it (1793 ring
+// pairs), K_ANAS_BIG: the lane reduce-scatter of a step (10 VALU instructions whatever K is) is then shared by half as many FMAs again, at two waves per SIMD
+// instead of three; on smaller ring sets the padded polar wave and the fewer, longer waves cost more than that saves.  C3: leg_ana_spin<4> 91.41 -> leg_ana_spin<6>
+// 87.48 ms per launch (spreads 0.5 / 1.0), C2 leg_ana 8.72 -> 8.65.  Spin 0 keeps K_ANA0: leg_ana_s0<12> (217 VGPRs, two waves per SIMD)
+// was measured without per-block starts, which are not built, and gained 0.4 ms of 24, inside its spread; it is not in the tree (profiles/README.md, "Analysis K").
+static constexpr int K_ANAS_BIG = 6, LEG_BIG_MIN_WAVES = 8;
+static int leg_ana_k(const RingSet& rs, int spin) {
+	if (spin == 0) return k_small_grid(rs, K_ANA0, {4, 2}, 4);
+	const int k = k_small_grid(rs, K_ANAS, {3, 2});
+	return (k == K_ANAS && (rs.npairs + 64*K_ANAS - 1)/(64*K_ANAS) >= LEG_BIG_MIN_WAVES) ? K_ANAS_BIG : k;
+}
 // ---- batch planner ----
 // A call of nb maps goes out as an ordered list of launches.  With 4 or more maps (PXS_SYN_MM_MIN / PXS_ANA_MM_MIN) the maps share one recurrence in the FP64-MFMA
 // kernels (leg_*_mm): groups of 8 maps per wave (synthesis) or workgroup (analysis); a remainder of more than 4 maps as one more 8-map group, of 4 or fewer as a
@@ -762,7 +776,8 @@ void leg_analysis(hipStream_t st, const RingSet& rs, const LegTables& tb, LegWor
 {
 	PXS_REQUIRE(alm_dtype == PX_C64 || alm_dtype == PX_C128, "alm must be complex64 or complex128");
 	PXS_REQUIRE(nb >= 1, "leg_analysis: nb must be >= 1");
-	const int K = tb.spin == 0 ? k_small_grid(rs, K_ANA0, {4, 2}, 4) : k_small_grid(rs, K_ANAS, {3, 2});
+	const int K = wk.ana_k > 0 ? wk.ana_k : leg_ana_k(rs, tb.spin);
+	wk.last_ana_k = K;
 	const int nm = tb.mmax+1;
 	const int mm_pairs = (tb.spin == 0 ? 64 : 32)*MM_WAVES;      // ring pairs per workgroup of the MFMA form
 	const std::vector<LegLaunch> plan = leg_batch_plan(nb, tb.spin, true, deriv1, wk.deterministic, [&] { return seeds_pending(wk, rs, tb, 1, K); },

@@ -53,6 +53,8 @@ struct LegWork {     // scratch owned by the SHT plan
 	std::map<std::tuple<const void*, int, int, int>, Seeds> seeds;
 	size_t seed_budget = size_t(16) << 30, seed_bytes = 0;     // PXS_SEED_GB; 0 turns the seeds off
 	DevBuf count; bool count_on = false;                       // executed-work counters of the Legendre kernels (LegK::count), while profiling
+	int ana_k = 0;           // pxs_plan_option("leg_ana_k"): ring pairs per lane of the VALU analysis kernels, for tests; 0: the host's rule (leg_ana_k, legendre.hip).  A value without a compiled kernel is an error at the launch
+	int last_ana_k = 0;      // pxs_plan_query("leg_ana_k"): the ring pairs per lane the most recent leg_analysis ran (or would have run) its VALU launches with
 	int max_batch = 0;       // pxs_plan_option("leg_max_batch"): upper bound on what leg_max_batch allows one launch (maps; groups of 8 maps for the MFMA form); 0: the grid limit alone
 	// what the most recent leg_synthesis / leg_analysis launched: the m ranges of its last VALU analysis launch sequence (size: m per
 	// range), its VALU launches and its MFMA launches (size: maps)

@@ -74,15 +74,15 @@ __device__ __forceinline__ double ldc_double(const double* p, long i) {
 // (tools/leg_prefetch_distance.py reads the distances off the assembly: 0-4 FMAs before, 12 K after).  The arithmetic is the same expression on the same values in
 // the same order.  Measured on MI355X at C3, parent and result in one session, launches with the seeds loaded (profiles/leg_prefetch_ab.txt): leg_syn_s0<4>
 // 20.29 -> 16.89 ms, its waitcnt share of the wave cycles 46 -> 25 %.
-// The same loop was built for the other three VALU kernels and is not in the tree: spin-s rows as (a, b) compact / three columns of the 32-byte rows in polar waves, the
-// analysis kernels with the drain BETWEEN the two steps of a pair (the ds_writes of the reduction, which count on lgkmcnt too, a step old there) and the flush of a full
-// tile at that drain.  Every load had its step pair of distance (24 K / 12 K FMAs), registers and waves per SIMD were the parent's, results bit for bit the parent's,
-// and the waitcnt share fell (leg_syn_spin<3> 29 -> 19 %, leg_ana_spin<4> 16 -> 7 %, leg_ana_s0<8> 21 -> 12 %) with the issue stalls rising by as much: at 3-4 waves per
-// SIMD the VALU-active share of a wave's cycles times the waves is 0.94-0.96 before and 0.98-1.0 after -- the other waves of the SIMD already issue into most of the
-// time one wave waits.  Kernel traces, parent / that build / parent in one session: leg_syn_spin<3> 67.85 / 66.37 / 67.71 ms, leg_ana_spin<4> 90.39 / 89.13 / 90.48,
-// leg_ana_s0<8> 24.01 / 23.51 / 24.16 (spreads 0.2-0.6): 0.6-1.4 ms each, at or inside three times the spread.  bench.py, parent / this code / that build alternating
-// in one session: C3 step 279.48 / 276.95 / 275.18 ms (spreads 1.3 / 1.1 / 0.9).  That build was measured and compared bit for bit on the Legendre-only calls but has
-// not been through the whole GPU suite: the three kernels keep their loops here, and putting them on this one is the next step (profiles/README.md).
+// The other three VALU kernels run the same loop.  leg_ana_s0 reads the compact rows too; the spin-s kernels read the 32-byte rows, of which polar waves need the
+// columns a, c, d (a loop of their own for plain waves on the compact rows cost a wave per SIMD: leg_spin.hip, "Row sets").  The analysis kernels have the drain
+// BETWEEN the two steps of a pair -- the ds_writes of the reduction count on lgkmcnt too and are a step old there -- and flush a full tile at that drain; a row set
+// there spans the second step of a pair and the first of the next.  The flush is conditional, and a scheduling barrier holds within its basic block only: PXS_DONE
+// keeps the FMAs of the step in front of the drain in front of it.  Every load has its step pair of distance (24 K / 12 K FMAs), results are bit for bit what the
+// former loops gave.  When first built, at 3-4 waves per SIMD, these three loops gained 0.6-1.4 ms each at C3, at or inside three times the spread: the waitcnt share
+// fell (leg_syn_spin<3> 29 -> 19 %, leg_ana_spin<4> 16 -> 7 %, leg_ana_s0<8> 21 -> 12 %) and the issue stalls rose by as much, the other waves of the SIMD already
+// issuing into most of the time one wave waits.  They are what lets the analysis run at TWO waves per SIMD with more ring pairs per lane (leg_ana_k, legendre.hip);
+// figures: profiles/README.md, "Analysis K".
 struct coef2x2_t { double a0, b0, a1, b1; };
 #ifdef PXS_HOST_SIM
 #define LDC2(p, i) (coef2x2_t{(p)[i].x, (p)[i].y, (p)[(i)+1].x, (p)[(i)+1].y})
@@ -98,6 +98,14 @@ __device__ __forceinline__ coef2x2_t ldc_row2(const double2* p, long i) {
 // s_waitcnt lgkmcnt(0) (vmcnt and expcnt left open), as an instruction the compiler's own wait insertion sees
 #define PXS_ROWS_DRAIN() do { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PXS_ROWS_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#endif
+// A per-lane double that has to be computed by this point.  The analysis kernels put their conditional flush behind the drain, and a scheduling barrier holds within
+// its basic block only: without this the compiler sinks the FMAs of the step in front of the drain past the flush's branch, and the rows they read stay live across
+// the point where the next ones are to be requested (the requests then follow a step late).  No instruction.
+#ifdef PXS_HOST_SIM
+#define PXS_DONE(x)
+#else
+#define PXS_DONE(x) asm volatile("" : "+v"(x))
 #endif
 
 struct LegK {
@@ -245,6 +253,15 @@ __device__ __forceinline__ bool leg_wave_polar(const LegK& a, int wv, int K) { r
 #else
 __device__ __forceinline__ int pxs_fresh_int(int x) { asm("" : "+v"(x)); return x; }
 #define PXS_FRESH_INT(x) pxs_fresh_int(x)
+#endif
+// ... and one the compiler may not compute ahead of this point either: the analysis kernels take the lane through it where a slot fetches its ring data in phase B.
+// Computed from the lane itself, the addresses of every slot's ring indices were kept from the head of the phase-B loop on (leg_ana_spin<3> 132 -> 122 VGPRs
+// and a fourth wave per SIMD with it, leg_ana_spin<6> 230 -> 206, leg_ana_s0<8> 159 -> 156)
+#ifdef PXS_HOST_SIM
+#define PXS_LATE_INT(x) (x)
+#else
+__device__ __forceinline__ int pxs_late_int(int x) { asm volatile("" : "+v"(x)); return x; }
+#define PXS_LATE_INT(x) pxs_late_int(x)
 #endif
 
 // (An L2 prefetch of the coefficient streams via global_load_lds into an LDS sink was tried to hide SMEM

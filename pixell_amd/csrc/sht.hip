@@ -288,6 +288,9 @@ int pxs_plan_option(pxs_plan* p, const char* name, int64_t value) {
 	} else if (std::string(name) == "leg_max_batch") {      // upper bound on the maps of one Legendre launch (8 x as many for the MFMA form); 0: the grid limit alone
 		PXS_REQUIRE(value >= 0 && value <= (1 << 20), "pxs_plan_option: leg_max_batch takes 0 (no bound) or a number of maps");
 		p->wk.max_batch = (int)value;
+	} else if (std::string(name) == "leg_ana_k") {      // ring pairs per lane of the VALU analysis kernels; 0: the host's rule -- for tests (a value without a compiled kernel fails at the launch)
+		PXS_REQUIRE(value >= 0 && value <= 64, "pxs_plan_option: leg_ana_k takes 0 (the host's rule) or a number of ring pairs per lane");
+		p->wk.ana_k = (int)value;
 	} else throw Error(PXS_ERR_ARG, std::string("pxs_plan_option: unknown option '") + name + "'");
 	PXS_CATCH
 }
@@ -367,6 +370,7 @@ int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	PXS_REQUIRE(p, "pxs_plan_query: null argument");
 	if (p->pts) *value = points_query(p->pts, n);
 	else if (n == "analysis_form") { const Route r = analysis_route_now(p); *value = (r.kind == R_RING_WEIGHTS || r.kind == R_CC_WEIGHTS) ? 1 : (r.form->fine ? 2 : 0); }
+	else if (n == "leg_ana_k") *value = p->wk.last_ana_k;      // ring pairs per lane of the VALU launches of the most recent Legendre analysis on the plan (0: none yet)
 	else if (n == "ncc_circle") *value = p->th.ncc > 0 ? p->th.Ncc : 0;
 	else if (n == "ducc_ncc_circle") *value = FftChain::ducc_ncc(p->lmax);
 	else if (n == "theta_line") *value = analysis_route_now(p).line ? 1 : 0;      // 1: its theta resampling runs as ONE kernel per call (thetaline.hip), 0: as the stage chain

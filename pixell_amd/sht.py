@@ -95,11 +95,12 @@ class Plan:
 	def set_option(self, name, value):
 		"""pxs_plan_option: "analysis" = 2 (ducc0's route, the default) | 0 (full theta-interpolant) | 1 (ring weights + adjoint synthesis where ntheta >= 2 lmax + 2);
 		"deterministic" = 0 | 1 (ordered, bitwise repeatable analysis sums; see set_deterministic);
-		"leg_max_batch" = n (at most n maps per single-map Legendre launch, 8 n per FP64-MFMA launch; 0: the grid limit alone -- for tests)"""
+		"leg_max_batch" = n (at most n maps per single-map Legendre launch, 8 n per FP64-MFMA launch; 0: the grid limit alone -- for tests);
+		"leg_ana_k" = K (ring pairs per lane of the single-map Legendre analysis kernels; 0: the library's rule -- for tests)"""
 		_lib.check(_lib.load().pxs_plan_option(self.handle, name.encode(), int(value)))
 	def query(self, name):
-		"""pxs_plan_query: "analysis_form", "ncc_circle", "ducc_ncc_circle", "theta_line", "chain_stages", "chain_static", "chain_static_table",
-		"passes_<seam>" (see passes) """
+		"""pxs_plan_query: "analysis_form", "ncc_circle", "ducc_ncc_circle", "theta_line", "chain_stages", "chain_static", "chain_static_table", "leg_ana_k" (ring pairs per lane of the plan's
+		most recent single-map Legendre analysis), "passes_<seam>" (see passes) """
 		v = ctypes.c_int64()
 		_lib.check(_lib.load().pxs_plan_query(self.handle, name.encode(), ctypes.byref(v)))
 		return int(v.value)

@@ -2,7 +2,9 @@
 // the accumulating wave-steps and FMA counts of leg_syn_s0<4>, leg_ana_s0<8>, leg_syn_spin<3>, leg_ana_spin<4> on a CC ring set, with the
 // library's own tables (LegTables::build_host), start values (pow_scaled / to_scaled, spin_init), m-limit and 4-step test, and the largest
 // term a threshold drops.  Plain (non-polar) form of the recurrences throughout: the polar form is the same algebra.
-//   g++ -O2 -fopenmp -o leg_live_count tools/leg_live_count.cpp && ./leg_live_count [lmax 10000] [Ncc 20160] [m stride 1]
+//   g++ -O2 -fopenmp -o leg_live_count tools/leg_live_count.cpp && ./leg_live_count [lmax 10000] [Ncc 20160] [m stride 1] [K of leg_ana_s0] [K of leg_ana_spin]
+// The analysis K default to what the host picks for the ring set (leg_ana_k, legendre.hip: 8 for spin 0; 6 for spin 2 where 4 gives at least 8 waves per m, else 4; k_small_grid's
+// rules for small ring sets are not modelled), so that the counts are those of the kernels as built and can be set against PXS_COUNT.
 // Prints, per kernel and threshold, sum over (m, wave) of (steps - start step) x K x FMAs per step (what PXS_COUNT adds up in a
 // seeded launch) and its ratio to the scale-0 rule, then log2 of the largest |lambda| (chain value x alpha) any chain has at a step
 // before it is live itself -- an upper bound of what its wave drops, since a wave starts no later than any of its lanes.
@@ -10,6 +12,7 @@
 // (the partition until leg_pair_of existed), (b) the padding in front of pair 0, in wave 0 (leg_pair_of: what the kernels do and PXS_COUNT adds up), (c) = (b) and
 // a block of 64 pairs accumulates only from the first 4-step test at which one of its chains, or of a more polar block of the wave, is live: the recurrence FMAs
 // (2 of 6, 4 of 12) from the wave's start, the accumulation FMAs from the block's.  (c) is modelled, not built: no kernel does it.
+// Last, per kernel, the share of the accumulating wave-steps that lie in phase B (some lane of the wave still below scale 0: the steps with the rescale sweep).
 // Runtime on 16 cores: lmax 10^4 at stride 1 about 10 minutes, at stride 7 a minute and a half (the ratios agree to four digits); lmax 4000 (C2: Ncc 8064) at stride 1 a minute.
 #include <cmath>
 #include <cstdio>
@@ -39,15 +42,20 @@ static bool live(double v, int sc, int t) { return sc == 0 && (t == 0 ? v != 0.0
 static double lg(double v, int sc, double alpha) { return (v == 0.0 || alpha == 0.0) ? -1e9 : log2(fabs(v)) + 800.0*sc + log2(fabs(alpha)); }
 
 static const int TLIVE = 4;      // index of LEG_LIVE = 2^-140 in THR
-static void run(const int lmax, const long Ncc, const int mstride) {
+static void run(const int lmax, const long Ncc, const int mstride, int kana0, int kanas) {
 	const LDb PIl = 3.141592653589793238462643383279502884L;
 	const int ncc = (int)(Ncc/2 + 1), npairs = (ncc + 1)/2;
 	std::vector<double> cth(npairs), sth(npairs), sh2(npairs), ch2(npairs);
 	for (int p = 0; p < npairs; p++) { const LDb th = 2*PIl*p/Ncc; cth[p] = (double)cosl(th); sth[p] = (double)sinl(th); sh2[p] = (double)sinl(th/2); ch2[p] = (double)cosl(th/2); }
 	const double ofs = std::max(100.0, 0.01*lmax);
-	const int KS[2][2] = {{4, 8}, {3, 4}};      // [spin 0 / spin 2][synthesis / analysis]
-	const char* KN[2][2] = {{"leg_syn_s0<4>", "leg_ana_s0<8>"}, {"leg_syn_spin<3>", "leg_ana_spin<4>"}};
-	double fma_sum[2][2][NT] = {}, steps_sum[2][2][NT] = {}, part_sum[2][2][3] = {}; double dropmax[2][NT]; double grow4[2] = {0, 0};
+	if (kana0 <= 0) kana0 = 8;
+	if (kanas <= 0) kanas = (npairs + 64*4 - 1)/(64*4) >= 8 ? 6 : 4;
+	const int KMAX = 16;      // (blocks per wave the model takes; the kernels compile K up to 8 / 6)
+	if (kana0 > KMAX || kanas > KMAX) { fprintf(stderr, "K up to %d\n", KMAX); exit(1); }
+	const int KS[2][2] = {{4, kana0}, {3, kanas}};      // [spin 0 / spin 2][synthesis / analysis]
+	char kn[2][32]; snprintf(kn[0], 32, "leg_ana_s0<%d>", kana0); snprintf(kn[1], 32, "leg_ana_spin<%d>", kanas);
+	const char* KN[2][2] = {{"leg_syn_s0<4>", kn[0]}, {"leg_syn_spin<3>", kn[1]}};
+	double fma_sum[2][2][NT] = {}, steps_sum[2][2][NT] = {}, part_sum[2][2][3] = {}, phb_sum[2][2][2] = {}; double dropmax[2][NT]; double grow4[2] = {0, 0};
 	for (int i = 0; i < 2; i++) for (int t = 0; t < NT; t++) dropmax[i][t] = -1e9;
 	// sectoral normalisations (build_host)
 	std::vector<LDb> cms(lmax + 1), nrm(lmax + 1);
@@ -87,7 +95,7 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 				}
 			}
 			const int kend = 4*(n/4);      // where phase A stops whatever the chains do
-			std::vector<int> klive(NT*(size_t)npairs), ktrue(npairs, INT_MAX); std::vector<char> alive(npairs);      // ktrue: the test at which the chain IS live at LEG_LIVE (klive: or phase A ran out of steps)
+			std::vector<int> klive(NT*(size_t)npairs), ktrue(npairs, INT_MAX), kzero(npairs, 0); std::vector<char> alive(npairs);      // kzero: the 4-step test at which every chain of the pair is at scale 0 (n: never);      // ktrue: the test at which the chain IS live at LEG_LIVE (klive: or phase A ran out of steps)
 			double dm[NT]; for (int t = 0; t < NT; t++) dm[t] = -1e9; double g4 = 0;
 			for (int p = 0; p < npairs; p++) {
 				// nc chains: spin 0 one (v2 current, v1 previous), spin 2 two
@@ -108,11 +116,13 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 				}
 				int* kl = &klive[NT*(size_t)p]; for (int t = 0; t < NT; t++) kl[t] = -1;
 				const double x = sp ? cth[p] : cth[p]*cth[p];
-				int k = 0, found = 0;
+				int k = 0, found = 0; kzero[p] = n;
 				if (!alive[p]) { for (int t = 0; t < NT; t++) kl[t] = kend; continue; }
 				while (true) {
 					for (int t = 0; t < NT; t++) if (kl[t] < 0) { bool lv = false; for (int h = 0; h < nc; h++) lv |= live(v2[h], sc[h], t); if (lv || k + 4 > n) { kl[t] = k; found++; if (lv && t == TLIVE) ktrue[p] = k; } }
-					if (found == NT) break;
+					bool below = false; for (int h = 0; h < nc; h++) below |= sc[h] < 0;
+					if (!below) kzero[p] = std::min(kzero[p], k);
+					if (found == NT && (!below || k + 4 > n)) break;
 					double before = 0; for (int h = 0; h < nc; h++) if (sc[h] == 0) before = fmax(before, fabs(v2[h]));
 					// four steps; the values of these steps are dropped by every threshold not yet reached
 					for (int i = 0; i < 4; i++) {
@@ -125,7 +135,7 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 						}
 					}
 					for (int h = 0; h < nc; h++) {
-						if (sc[h] == 0 && before > 0 && before < 0x1p-90) g4 = fmax(g4, fabs(v2[h])/before);
+						if (found < NT && sc[h] == 0 && before > 0 && before < 0x1p-90) g4 = fmax(g4, fabs(v2[h])/before);
 						if (sc[h] < 0 && fabs(v2[h]) > SC_BIG) { v1[h] *= SC_SMALL; v2[h] *= SC_SMALL; sc[h]++; }
 					}
 					k += 4;
@@ -143,20 +153,21 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 				}
 			}
 			// the partitions at LEG_LIVE: pt = 0 padding behind the last pair, 1 in front of pair 0, 2 the same and blocks from their own step
-			double ps[2][3] = {};
+			double ps[2][3] = {}, pb[2][2] = {};
 			for (int d = 0; d < 2; d++) {
 				const int K = KS[sp][d], per = 64*K, nwave = (npairs + per - 1)/per, frec = sp ? 4 : 2, facc = sp ? 8 : 4;
 				for (int pt = 0; pt < 3; pt++) {
 					const int pad = pt ? nwave*per - npairs : 0;
 					for (int w = 0; w < nwave; w++) {
-						bool any = false; int k0 = kend; int bs[8];
+						bool any = false; int k0 = kend, kz = 0; int bs[KMAX];
 						for (int b = 0; b < K; b++) {
 							bs[b] = INT_MAX;
 							for (int p = std::max(0, w*per + 64*b - pad); p < std::min(npairs, w*per + 64*b + 64 - pad); p++)
-								if (alive[p]) { any = true; bs[b] = std::min(bs[b], ktrue[p]); }
+								if (alive[p]) { any = true; bs[b] = std::min(bs[b], ktrue[p]); kz = std::max(kz, kzero[p]); }
 							k0 = std::min(k0, bs[b]);
 						}
 						if (!any) continue;
+						if (pt == 1) { pb[d][0] += std::max(0, std::min(kz, n) - k0); pb[d][1] += n - k0; }
 						if (pt < 2) { ps[d][pt] += (double)(n - k0)*K*(frec + facc); continue; }
 						double f = (double)(n - k0)*K*frec; int eff = INT_MAX;
 						for (int b = 0; b < K; b++) {
@@ -171,6 +182,7 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 #pragma omp critical
 			{
 				for (int d = 0; d < 2; d++) for (int pt = 0; pt < 3; pt++) part_sum[sp][d][pt] += ps[d][pt];
+				for (int d = 0; d < 2; d++) for (int i = 0; i < 2; i++) phb_sum[sp][d][i] += pb[d][i];
 				for (int d = 0; d < 2; d++) for (int t = 0; t < NT; t++) { fma_sum[sp][d][t] += fs[d][t]; steps_sum[sp][d][t] += ss[d][t]; }
 				for (int t = 0; t < NT; t++) dropmax[sp][t] = fmax(dropmax[sp][t], dm[t]);
 				grow4[sp] = fmax(grow4[sp], g4);
@@ -192,6 +204,9 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 		printf("  %-16s %.5e | %.5e | %.5e   (%.4f, %.4f)\n", KN[sp][d], q[0]*128*mstride, q[1]*128*mstride, q[2]*128*mstride, q[1]/q[0], q[2]/q[0]); }
 	for (int d = 0; d < 2; d++) { double q[3]; for (int pt = 0; pt < 3; pt++) q[pt] = part_sum[0][d][pt] + part_sum[1][d][pt];
 		printf("  %-16s %.5e | %.5e | %.5e   (%.4f, %.4f)\n", d ? "analysis, both" : "synthesis, both", q[0]*128*mstride, q[1]*128*mstride, q[2]*128*mstride, q[1]/q[0], q[2]/q[0]); }
+	printf("phase B share of the accumulating wave-steps (padding in wave 0):");
+	for (int sp = 0; sp < 2; sp++) for (int d = 0; d < 2; d++) printf("  %s %.2f %%", KN[sp][d], 100*phb_sum[sp][d][0]/phb_sum[sp][d][1]);
+	printf("\n");
 	for (int sp = 0; sp < 2; sp++) {
 		printf("spin %d: largest 4-step growth of a scale-0 chain below 2^-90: 2^%.1f; log2 of the largest |lambda| before a chain is live:", sp ? 2 : 0, log2(grow4[sp]));
 		for (int t = 0; t < NT; t++) printf("  %s: %.1f", THRN[t], dropmax[sp][t]);
@@ -200,6 +215,6 @@ static void run(const int lmax, const long Ncc, const int mstride) {
 }
 
 int main(int argc, char** argv) {
-	run(argc > 1 ? atoi(argv[1]) : 10000, argc > 2 ? atol(argv[2]) : 20160, argc > 3 ? atoi(argv[3]) : 1);
+	run(argc > 1 ? atoi(argv[1]) : 10000, argc > 2 ? atol(argv[2]) : 20160, argc > 3 ? atoi(argv[3]) : 1, argc > 4 ? atoi(argv[4]) : 0, argc > 5 ? atoi(argv[5]) : 0);
 	return 0;
 }
