@@ -144,6 +144,7 @@ int pxs_plan_option(pxs_plan* plan, const char* name, int64_t value);
  * the plan's lmax, "theta_line" = 1 if the theta resampling of pxs_analysis runs as one kernel with the line resident on a CU
  * (the circle sizes compiled into thetaline.hip; PXS_THETA_LINE=0 switches it off), 0 if as the five-stage chain: same results.
  * "leg_ana_k": ring pairs per lane of the single-map Legendre analysis kernels in the plan's most recent analysis or adjoint synthesis (0: none yet).
+ * "leg_executed_flops_ana": FP64 flops the Legendre analysis kernels executed while profiling was on (see pxs_profile_flops).
  * "chain_stages": the distinct FFT chain stage shapes (stage, transform lengths, lines per tile) of the plan's standard calls (analysis
  * under its current option, synthesis of spin 0 and 2); "chain_static": how many of them have a compile-time-planned kernel
  * (csrc/chain_static_table.hpp; PXS_CHAIN_STATIC=0, read per call, runs the run-time kernel for all: same results to rounding);
@@ -191,6 +192,9 @@ int pxs_profile_read(pxs_plan* plan, double* ms, int* counts, int reset);
  * quote the hardware FMA utilisation next to the algorithmic flop count of SURVEY 8(d) (which credits rings and degrees the
  * kernels skip as polar-dead).  No reference counterpart. */
 int pxs_profile_flops(pxs_plan* plan, double* flops, int reset);
+/* A wave of the single-map kernels holds K blocks of 64 ring pairs, and the figures above count every block from the step at which its wave starts.  The
+ * analysis kernels start the accumulation of a block at the block's own live step: what they executed with that taken into account is
+ * pxs_plan_query "leg_executed_flops_ana" (flops, an exact integer; reset together with pxs_profile_flops).  bench.py quotes flops[1], which at C3 is 3.2 % above it. */
 
 /* N-d FFT over `naxes` axes of a strided array: the engine behind fft.engines["hip"].FFTW(a,b,axes,
  * direction) (pixell/fft.py:8-64,133-209) and enmap.fft/ifft (enmap.py:1307-1337).

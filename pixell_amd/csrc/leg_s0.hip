@@ -26,7 +26,8 @@ namespace pxs {
 		} \
 		k += 4; \
 	}
-// phase A with the recurrence seeds (legendre_dev.hpp, "Recurrence seeds"): mode 2 loads the state and the step reached, mode 1 records them
+// phase A with the recurrence seeds (legendre_dev.hpp, "Recurrence seeds"): mode 2 loads the state, the step reached and the start steps of the blocks (the seed
+// tail, knext; legendre_dev.hpp, "Block starts"), mode 1 records them (the start steps as the blocks start: S0_BLOCK_BEGIN; LEG_NEVER until then)
 #define S0_SEEDED_PHASE_A \
 	if (a.seed_mode == 2) { \
 		const double* sd = a.seed_d + ((long)m*a.nwave + wv)*(2*K*64); const int* si = a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64); \
@@ -37,9 +38,17 @@ namespace pxs {
 		if (a.seed_mode == 1) { \
 			double* sd = a.seed_d + ((long)m*a.nwave + wv)*(2*K*64); int* si = a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64); \
 			_Pragma("unroll") for (int s = 0; s < K; s++) { sd[s*64 + lane] = lam1[s]; sd[(K+s)*64 + lane] = lam2[s]; si[s*64 + lane] = sc[s]; } \
-			if (lane == 0) si[K*64] = k; \
+			if (lane == 0) si[K*64] = k; else if (lane <= K) si[K*64 + lane] = LEG_NEVER; \
 		} \
 	}
+// does block c start at this 4-step test (one of its chains, or one of a more polar block, is live)?  Seeded launches read it off the seed tail.  Tests are
+// at multiples of 4 steps (phase A ends at one): a phase B that ends on a lone pair leaves the last steps of the wave without a test
+#define S0_BLOCK_STARTS(c) ((k & 3) == 0 && (a.seed_mode == 2 ? k >= knext : __any(leg_live_upto<c>(lam2, sc))))
+// the seed tail of this (wave, m): [0] the step phase A reached, [1 + c] the start step of block c
+#define S0_SEED_TAIL (a.seed_i + ((long)m*a.nwave + wv)*((K+1)*64) + K*64)
+// block c starts at step k: counted from here on; recorded in the seed tail by the lane that wrote LEG_NEVER there.  NEXT_START(c): a seeded launch reads the start of block c
+#define S0_BLOCK_BEGIN(c) { PXS_COUNT_BLOCK(DIR, (long)(nk - k)*4); if (a.seed_mode == 1 && lane == (c) + 1) S0_SEED_TAIL[(c) + 1] = k; }
+#define S0_NEXT_START(c) if (a.seed_mode == 2) knext = PXS_UNIFORM_INT(S0_SEED_TAIL[(c) + 1]);
 
 // two fast steps of the spin-0 synthesis (lam1/lam2 swap roles)
 #define S0_SYN_PAIR(c0, c1, a0, a1) S0_SYN_PAIR_C(c0.a, polar ? c0.c : c0.b, c1.a, polar ? c1.c : c1.b, a0, a1)
@@ -159,17 +168,17 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 	}
 }
 
-// two fast steps of the spin-0 analysis: 2 x 4 lane sums into the LDS reduction tile, flush every 4 steps
+// two fast steps of the spin-0 analysis: 2 x 4 lane sums into the LDS reduction tile, flush every 4 steps.  Blocks SLO .. K - 1 have started and take part in the sums
 #define S0_ANA_PAIR(c0, c1) { \
 	PXS_VCOPY(vb0, polar ? c0.c : c0.b); \
 	PXS_VCOPY(vb1, polar ? c1.c : c1.b); \
 	double t0 = 0, t1 = 0, t2 = 0, t3 = 0, u0 = 0, u1 = 0, u2 = 0, u3 = 0; \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
-		t0 = fma(lam2[s], d1r[s], t0); t1 = fma(lam2[s], d1i[s], t1); t2 = fma(lam2[s], d2r[s], t2); t3 = fma(lam2[s], d2i[s], t3); \
+		if (s >= SLO) { t0 = fma(lam2[s], d1r[s], t0); t1 = fma(lam2[s], d1i[s], t1); t2 = fma(lam2[s], d2r[s], t2); t3 = fma(lam2[s], d2i[s], t3); } \
 		lam1[s] = fma(fma(c0.a, csq[s], vb0), lam2[s], lam1[s]); \
 	} \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
-		u0 = fma(lam1[s], d1r[s], u0); u1 = fma(lam1[s], d1i[s], u1); u2 = fma(lam1[s], d2r[s], u2); u3 = fma(lam1[s], d2i[s], u3); \
+		if (s >= SLO) { u0 = fma(lam1[s], d1r[s], u0); u1 = fma(lam1[s], d1i[s], u1); u2 = fma(lam1[s], d2r[s], u2); u3 = fma(lam1[s], d2i[s], u3); } \
 		lam2[s] = fma(fma(c1.a, csq[s], vb1), lam1[s], lam2[s]); \
 	} \
 	/* steps come in aligned pairs (phase A advances by 4, phases B and C by 2): kk is even here */ \
@@ -182,7 +191,7 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 #define S0_ANA_STEP_C(ca, cb, LA, LB, T0, T1, T2, T3) { \
 	PXS_VCOPY(vb, cb); \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
-		T0 = fma(LA[s], d1r[s], T0); T1 = fma(LA[s], d1i[s], T1); T2 = fma(LA[s], d2r[s], T2); T3 = fma(LA[s], d2i[s], T3); \
+		if (s >= SLO) { T0 = fma(LA[s], d1r[s], T0); T1 = fma(LA[s], d1i[s], T1); T2 = fma(LA[s], d2r[s], T2); T3 = fma(LA[s], d2i[s], T3); } \
 		LB[s] = fma(fma(ca, csq[s], vb), LA[s], LB[s]); \
 	} }
 // two fast steps of phase C from step kfirst on: the drain of the scalar rows between the two, the flush of a full tile and the request of the next rows (NEXT) at it
@@ -199,6 +208,72 @@ template<int K> __global__ __launch_bounds__(64, (K == 4 ? 7 : 1)) void leg_syn_
 	LEG_RED_PUT(kk, t0, t1, t2, t3) \
 	LEG_RED_PUT(kk+1, u0, u1, u2, u3) \
 	kk += 2; }
+
+// Phases B and C of the spin-0 analysis with NB started blocks (SLO = K - NB: the first of them; legendre_dev.hpp, "Block starts").  A wave enters at nb = 1 and
+// walks through the stages in order; `more`: block SLO - 1 starts at this 4-step test, on to the next stage.  inC: phase B is over (wave-wide, whatever the stage).
+// A block fetches its ring data when it starts (the lanes of it at scale 0; the others when they get there), until then it takes no part in the lane sums.
+// (The synthesis kernel keeps one loop for all blocks: with stages of the same kind it came out level, see legendre_dev.hpp.)
+// phase B: plain fast steps; every 4 steps the lanes below scale 0 are rescaled, and a lane of a started block that reaches scale 0 fetches its ring data (its
+// true terms before that are < 2^-340 of the result).
+// phase C: every lane at scale 0 (or without data).  The one-drain loop of leg_syn_s0 on the compact rows (a, b'), with the drain BETWEEN the two steps of a pair -- the
+// ds_writes of the reduction count on lgkmcnt too and are a step old there -- and the flush of a full tile at that drain.  A row set therefore spans the second step of
+// a pair and the first step of the next one: it is requested at one drain, complete at the next and read from there to the one after (legendre_dev.hpp, "Row prefetch").
+// At the top of a trip (n.a1, n.b1) is the row of step k and f the rows of steps k + 1, k + 2: a stage that ends there leaves them to the next.
+#define S0_ANA_STAGE(NB) if constexpr ((NB) <= K) { if (nb == (NB)) { \
+	constexpr int SLO = K - (NB); \
+	bool more = false; \
+	if (!inC) { \
+	while (k + 1 < nk) { \
+		if constexpr ((NB) < K) if (k < nk && S0_BLOCK_STARTS(SLO - 1)) { more = true; break; } \
+		bool pend = false; \
+		_Pragma("unroll") for (int s = 0; s < K; s++) pend |= (sc[s] < 0); \
+		if (!__any(pend)) break; \
+		for (int it = 0; it < 2 && k + 1 < nk; it++, k += 2) { \
+			const double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1); \
+			S0_ANA_PAIR(c0, c1) \
+		} \
+		_Pragma("unroll") for (int s = 0; s < K; s++) \
+			if (sc[s] < 0 && fabs(lam2[s]) > SC_BIG) { \
+				lam1[s] *= SC_SMALL; lam2[s] *= SC_SMALL; \
+				if (++sc[s] == 0 && s >= SLO) load_data(s); \
+			} \
+	} \
+	if (!more) { \
+		n = LDC2(cf, k); f = LDC2(cf, k+1); \
+		PXS_ROWS_DRAIN(); \
+		n.a1 = n.a0; n.b1 = n.b0;      /* (n.a1, n.b1): the row of the first step of the next pair (the row of step k + 1 that came with it is dropped: one 16-byte row per wave and m) */ \
+		inC = 1; \
+	} } \
+	if (!more) { \
+		for (;;) {      /* (two pairs per iteration on alternating row sets, see leg_syn_s0) */ \
+			if constexpr ((NB) < K) if (k < nk && S0_BLOCK_STARTS(SLO - 1)) { more = true; break; } \
+			if (!(k + 3 < nk)) break; \
+			S0_ANA_PAIR_D(n.a1, n.b1, f.a0, f.b0, k, n = LDC2(cf, k+3)) \
+			S0_ANA_PAIR_D(f.a1, f.b1, n.a0, n.b0, k+2, f = LDC2(cf, k+5)) \
+			k += 4; \
+		} \
+	} \
+	if (!more) { \
+		slo = SLO; \
+		nb = K + 1; \
+	} else if constexpr ((NB) < K) { S0_BLOCK_BEGIN(SLO - 1) if (sc[SLO - 1] == 0) load_data(SLO - 1); if constexpr ((NB) + 1 < K) { S0_NEXT_START(SLO - 2) } nb = (NB) + 1; } \
+} }
+// The last steps of a wave, fewer than four, with the blocks from `slo` on started, whichever stage ended: one copy, the started blocks tested at run time.  (A copy
+// per stage cost registers, not time: the single-pair loop of every stage kept the chains in a register set of its own -- leg_ana_s0<8> 156 -> 176 VGPRs, a wave per SIMD.)
+#define S0_ANA_TAIL { const int SLO = slo; \
+		if (k + 1 < nk) { \
+			S0_ANA_PAIR_D(n.a1, n.b1, f.a0, f.b0, k, (void)0) \
+			k += 2; \
+		} \
+		PXS_ROWS_DRAIN(); \
+		if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*kbase, lane, LEG_FSTEPS, a.atomic); kk = 0; kbase = k; } \
+		if (k < nk) { \
+			double t0 = 0, t1 = 0, t2 = 0, t3 = 0; \
+			_Pragma("unroll") for (int s = 0; s < K; s++) if (s >= SLO) { t0 = fma(lam2[s], d1r[s], t0); t1 = fma(lam2[s], d1i[s], t1); t2 = fma(lam2[s], d2r[s], t2); t3 = fma(lam2[s], d2i[s], t3); } \
+			LEG_RED_PUT(kk, t0, t1, t2, t3) \
+			kk++; \
+		} }
+
 
 template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 {
@@ -243,55 +318,23 @@ template<int K> __global__ __launch_bounds__(64) void leg_ana_s0(const LegK a)
 	int k = 0;
 	S0_SEEDED_PHASE_A
 	k = PXS_UNIFORM_INT(k); coef = (const double4_t*)PXS_UNIFORM_LONG((long)coef);
-	PXS_COUNT(1, (long)(nk - k)*K*6 + (a.seed_mode != 2 ? (long)k*K*2 : 0L));
+	// executed work: the recurrence FMAs of every block from here on (and of phase A where it ran), the accumulation FMAs of block K - 1, which starts with the
+	// wave; the other blocks add theirs as they start (S0_BLOCK_BEGIN)
+	constexpr int DIR = 1;
+	PXS_COUNT2(DIR, (long)(nk - k)*K*2 + (a.seed_mode != 2 ? (long)k*K*2 : 0L), (long)(nk - k)*4, K);
+	int knext = LEG_NEVER;      // seeded launches: the start step of the next block to start (the seed tail)
+	if constexpr (K > 1) { S0_NEXT_START(K - 2) }
 	if (lane == 0 && !a.atomic) a.first[wv*a.nmc + (m - a.m0)] = k + 1;      // rows before k are not written (reduce_partials skips them)
-	// ring data of the lanes that start at scale 0 or reached it during phase A (rings without signal have lam = 0)
-#pragma unroll
-	for (int s = 0; s < K; s++) if (sc[s] == 0) load_data(s);
+	// ring data of block K - 1: the lanes that start at scale 0 or reached it during phase A (rings without signal have lam = 0)
+	if (sc[K - 1] == 0) load_data(K - 1);
 	int kk = 0, kbase = k;
-	// phase B: plain fast steps; every 4 steps the lanes below scale 0 are rescaled, and a lane that reaches scale 0
-	// fetches its ring data (its true terms before that are < 2^-340 of the result)
-	while (k + 1 < nk) {
-		bool pend = false;
-#pragma unroll
-		for (int s = 0; s < K; s++) pend |= (sc[s] < 0);
-		if (!__any(pend)) break;
-		for (int it = 0; it < 2 && k + 1 < nk; it++, k += 2) {
-			const double4_t c0 = LDC(coef, k), c1 = LDC(coef, k+1);
-			S0_ANA_PAIR(c0, c1)
-		}
-#pragma unroll
-		for (int s = 0; s < K; s++)
-			if (sc[s] < 0 && fabs(lam2[s]) > SC_BIG) {
-				lam1[s] *= SC_SMALL; lam2[s] *= SC_SMALL;
-				if (++sc[s] == 0) load_data(s);
-			}
-	}
-	// phase C: every lane at scale 0 (or without data).  The one-drain loop of leg_syn_s0 on the compact rows (a, b'), with the drain BETWEEN the two steps of a pair -- the
-	// ds_writes of the reduction count on lgkmcnt too and are a step old there -- and the flush of a full tile at that drain.  A row set therefore spans the second step of
-	// a pair and the first step of the next one: it is requested at one drain, complete at the next and read from there to the one after (legendre_dev.hpp, "Row prefetch")
+	// phases B and C, by number of started blocks (S0_ANA_STAGE)
 	const double2* __restrict__ cf = (const double2*)PXS_UNIFORM_LONG((long)((polar ? a.coef2p : a.coef2) + row0));
-	coef2x2_t n = LDC2(cf, k), f = LDC2(cf, k+1);
-	PXS_ROWS_DRAIN();
-	n.a1 = n.a0; n.b1 = n.b0;      // (n.a1, n.b1): the row of the first step of the next pair (the row of step k + 1 that came with it is dropped: one 16-byte row per wave and m)
-	while (k + 3 < nk) {      // (two pairs per iteration on alternating row sets, see leg_syn_s0)
-		S0_ANA_PAIR_D(n.a1, n.b1, f.a0, f.b0, k, n = LDC2(cf, k+3))
-		S0_ANA_PAIR_D(f.a1, f.b1, n.a0, n.b0, k+2, f = LDC2(cf, k+5))
-		k += 4;
-	}
-	if (k + 1 < nk) {
-		S0_ANA_PAIR_D(n.a1, n.b1, f.a0, f.b0, k, (void)0)
-		k += 2;
-	}
-	PXS_ROWS_DRAIN();
-	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*kbase, lane, LEG_FSTEPS, a.atomic); kk = 0; kbase = k; }
-	if (k < nk) {
-		double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-#pragma unroll
-		for (int s = 0; s < K; s++) { t0 = fma(lam2[s], d1r[s], t0); t1 = fma(lam2[s], d1i[s], t1); t2 = fma(lam2[s], d2r[s], t2); t3 = fma(lam2[s], d2i[s], t3); }
-		LEG_RED_PUT(kk, t0, t1, t2, t3)
-		kk++;
-	}
+	coef2x2_t n, f;
+	int nb = 1, inC = 0, slo = 0;
+	S0_ANA_STAGE(1) S0_ANA_STAGE(2) S0_ANA_STAGE(3) S0_ANA_STAGE(4) S0_ANA_STAGE(5) S0_ANA_STAGE(6) S0_ANA_STAGE(7) S0_ANA_STAGE(8)
+	static_assert(K <= 8, "leg_ana_s0: one S0_ANA_STAGE per block (K = 12 takes four more and was measured with them: profiles/README.md, \"Block starts\")");
+	S0_ANA_TAIL
 	if (kk > 0) leg_flush(red, pout + 4*kbase, lane, kk, a.atomic);
 }
 

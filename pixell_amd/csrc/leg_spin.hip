@@ -82,7 +82,8 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 		j += 4; \
 	}
 
-// phase A with the recurrence seeds (legendre_dev.hpp): mode 2 loads the state and the step reached, mode 1 records them after running phase A
+// phase A with the recurrence seeds (legendre_dev.hpp): mode 2 loads the state, the step reached and the start steps of the blocks (the seed tail, knext;
+// legendre_dev.hpp, "Block starts"), mode 1 records them after running phase A (the start steps as the blocks start: SPIN_BLOCK_BEGIN; LEG_NEVER until then)
 #define SPIN_SEEDED_PHASE_A \
 	if (a.seed_mode == 2) { \
 		const double* sd = a.seed_d + ((long)m*a.nwave + wv)*(4*K*64); const int* si = a.seed_i + ((long)m*a.nwave + wv)*((2*K+1)*64); \
@@ -97,9 +98,17 @@ template<int K> __device__ __forceinline__ bool spin_init(const LegK& a, int wv,
 			_Pragma("unroll") for (int s = 0; s < K; s++) { \
 				sd[s*64 + lane] = S.gp1[s]; sd[(K+s)*64 + lane] = S.gp2[s]; sd[(2*K+s)*64 + lane] = S.gm1[s]; sd[(3*K+s)*64 + lane] = S.gm2[s]; \
 				si[s*64 + lane] = S.scp[s]; si[(K+s)*64 + lane] = S.scm[s]; } \
-			if (lane == 0) si[2*K*64] = j; \
+			if (lane == 0) si[2*K*64] = j; else if (lane <= K) si[2*K*64 + lane] = LEG_NEVER; \
 		} \
 	}
+// does block c start at this 4-step test (one of its chains, or one of a more polar block, is live)?  Seeded launches read it off the seed tail.  Tests are
+// at multiples of 4 steps (phase A ends at one): a phase B that ends on a lone pair leaves the last steps of the wave without a test
+#define SPIN_BLOCK_STARTS(c) ((j & 3) == 0 && (a.seed_mode == 2 ? j >= knext : __any(leg_live_upto<c>(S.gp2, S.scp) || leg_live_upto<c>(S.gm2, S.scm))))
+// the seed tail of this (wave, m): [0] the step phase A reached, [1 + c] the start step of block c
+#define SPIN_SEED_TAIL (a.seed_i + ((long)m*a.nwave + wv)*((2*K+1)*64) + 2*K*64)
+// block c starts at step j: counted from here on; recorded in the seed tail by the lane that wrote LEG_NEVER there.  NEXT_START(c): a seeded launch reads the start of block c
+#define SPIN_BLOCK_BEGIN(c) { PXS_COUNT_BLOCK(DIR, (long)(nl - j)*8); if (a.seed_mode == 1 && lane == (c) + 1) SPIN_SEED_TAIL[(c) + 1] = j; }
+#define SPIN_NEXT_START(c) if (a.seed_mode == 2) knext = PXS_UNIFORM_INT(SPIN_SEED_TAIL[(c) + 1]);
 
 // Row sets of the phase-C loops (legendre_dev.hpp, "Row prefetch"): the 32-byte rows of two consecutive steps, requested together.  SPIN_ROW0(r) / SPIN_ROW1(r):
 // (ca, c1, c2) of the first / second step of set r, (a, b, -b) in plain waves and the columns (a, c, d) in polar ones -- written where the row is used, behind the
@@ -262,10 +271,12 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 		PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
 		_Pragma("unroll") for (int s = 0; s < K; s++) { \
 			const double gp = S.gp2[s], gm = S.gm2[s]; \
-			t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0); \
-			t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1); \
-			t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2); \
-			t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3); \
+			if (s >= SLO) { \
+				t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0); \
+				t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1); \
+				t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2); \
+				t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3); \
+			} \
 			S.gp1[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp1[s]); S.gm1[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm1[s]); \
 		} \
 	} \
@@ -274,10 +285,12 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 		PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
 		_Pragma("unroll") for (int s = 0; s < K; s++) { \
 			const double gp = S.gp1[s], gm = S.gm1[s]; \
-			u0 = fma(gp, tpnr[s], u0); u0 = fma(-gm, tpsr[s], u0); \
-			u1 = fma(gp, tpni[s], u1); u1 = fma(-gm, tpsi[s], u1); \
-			u2 = fma(gm, tmnr[s], u2); u2 = fma(-gp, tmsr[s], u2); \
-			u3 = fma(gm, tmni[s], u3); u3 = fma(-gp, tmsi[s], u3); \
+			if (s >= SLO) { \
+				u0 = fma(gp, tpnr[s], u0); u0 = fma(-gm, tpsr[s], u0); \
+				u1 = fma(gp, tpni[s], u1); u1 = fma(-gm, tpsi[s], u1); \
+				u2 = fma(gm, tmnr[s], u2); u2 = fma(-gp, tmsr[s], u2); \
+				u3 = fma(gm, tmni[s], u3); u3 = fma(-gp, tmsi[s], u3); \
+			} \
 			S.gp2[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp2[s]); S.gm2[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm2[s]); \
 		} \
 	} \
@@ -293,20 +306,24 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 	PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
 		const double gp = S.gp2[s], gm = S.gm2[s]; \
-		t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0); \
-		t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1); \
-		t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2); \
-		t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3); \
+		if (s >= SLO) { \
+			t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0); \
+			t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1); \
+			t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2); \
+			t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3); \
+		} \
 		S.gp1[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp1[s]); S.gm1[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm1[s]); \
 	} }
 #define SPIN_ANA_STEP1_C(ca, c1, c2) { \
 	PXS_VCOPY(v1, c1); PXS_VCOPY(v2, c2); \
 	_Pragma("unroll") for (int s = 0; s < K; s++) { \
 		const double gp = S.gp1[s], gm = S.gm1[s]; \
-		u0 = fma(gp, tpnr[s], u0); u0 = fma(-gm, tpsr[s], u0); \
-		u1 = fma(gp, tpni[s], u1); u1 = fma(-gm, tpsi[s], u1); \
-		u2 = fma(gm, tmnr[s], u2); u2 = fma(-gp, tmsr[s], u2); \
-		u3 = fma(gm, tmni[s], u3); u3 = fma(-gp, tmsi[s], u3); \
+		if (s >= SLO) { \
+			u0 = fma(gp, tpnr[s], u0); u0 = fma(-gm, tpsr[s], u0); \
+			u1 = fma(gp, tpni[s], u1); u1 = fma(-gm, tpsi[s], u1); \
+			u2 = fma(gm, tmnr[s], u2); u2 = fma(-gp, tmsr[s], u2); \
+			u3 = fma(gm, tmni[s], u3); u3 = fma(-gp, tmsi[s], u3); \
+		} \
 		S.gp2[s] = fma(fma(ca, S.x[s], v1), gp, -S.gp2[s]); S.gm2[s] = fma(fma(ca, S.x[s], v2), gm, -S.gm2[s]); \
 	} }
 // two fast steps of phase C from step jfirst on: the drain of the scalar rows between the two, the flush of a full tile and the request of the next rows (NEXT) at it
@@ -324,21 +341,74 @@ template<int K> __global__ __launch_bounds__(64) void leg_syn_spin(const LegK a)
 	LEG_RED_PUT(kk, t0, t1, t2, t3) \
 	LEG_RED_PUT(kk+1, u0, u1, u2, u3) \
 	kk += 2; }
-// phase C of the spin analysis.  A row set spans the second step of a pair and the first of the next one (leg_ana_s0): the loop enters with the row of step j in
-// the place of "the first step of the next pair"
-#define SPIN_ANA_PHASE_C { \
-	spin_rows_t n = spin_rows(coef, j), f = spin_rows(coef, j+1); \
-	PXS_ROWS_DRAIN(); \
-	n.r1 = n.r0; \
-	while (j + 3 < nl) {      /* (two pairs per iteration on alternating row sets, see leg_syn_s0) */ \
-		SPIN_ANA_PAIR_R(SPIN_ROW1(n), SPIN_ROW0(f), j, n = spin_rows(coef, j+3)) \
-		SPIN_ANA_PAIR_R(SPIN_ROW1(f), SPIN_ROW0(n), j+2, f = spin_rows(coef, j+5)) \
-		j += 4; \
+// Phases B and C of the spin analysis with NB started blocks (SLO = K - NB; leg_s0.hip, S0_ANA_STAGE; the synthesis keeps one loop for all blocks).  A block fetches its ring data when it
+// starts (the lanes of it with both chains at scale 0; the others when they get there), until then it takes no part in the lane sums.
+// phase B: plain fast steps; every 4 steps the chains below scale 0 are rescaled, and a lane of a started block whose two chains have both reached scale 0
+// fetches its ring data (true terms before that: < 2^-340 of the result).
+// phase C: the one-drain loop of leg_syn_s0 with the drain between the two steps of a pair and the flush of a full tile at that drain, as in leg_ana_s0, on the
+// 32-byte rows (legendre_dev.hpp, "Row prefetch").  A row set spans the second step of a pair and the first of the next one (leg_ana_s0): at the top of a trip
+// n.r1 is the row of step j, f the rows of steps j + 1, j + 2; a stage that ends there leaves them to the next.
+#define SPIN_ANA_STAGE(NB) if constexpr ((NB) <= K) { if (nb == (NB)) { \
+	constexpr int SLO = K - (NB); \
+	bool more = false; \
+	if (!inC) { \
+	while (j + 1 < nl) { \
+		if constexpr ((NB) < K) if (j < nl && SPIN_BLOCK_STARTS(SLO - 1)) { more = true; break; } \
+		bool pend = false; \
+		_Pragma("unroll") for (int s = 0; s < K; s++) pend |= (S.scp[s] < 0) || (S.scm[s] < 0); \
+		if (!__any(pend)) break; \
+		for (int it = 0; it < 2 && j + 1 < nl; it++, j += 2) { \
+			const double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1); \
+			SPIN_ANA_PAIR(f0, f1) \
+		} \
+		_Pragma("unroll") for (int s = 0; s < K; s++) { \
+			const bool was = (S.scp[s] < 0) || (S.scm[s] < 0); \
+			if (S.scp[s] < 0 && fabs(S.gp2[s]) > SC_BIG) { S.gp1[s] *= SC_SMALL; S.gp2[s] *= SC_SMALL; S.scp[s]++; } \
+			if (S.scm[s] < 0 && fabs(S.gm2[s]) > SC_BIG) { S.gm1[s] *= SC_SMALL; S.gm2[s] *= SC_SMALL; S.scm[s]++; } \
+			if (s >= SLO && was && S.scp[s] == 0 && S.scm[s] == 0) load_data(s); \
+		} \
 	} \
-	if (j + 1 < nl) { \
-		SPIN_ANA_PAIR_R(SPIN_ROW1(n), SPIN_ROW0(f), j, (void)0) \
-		j += 2; \
-	} }
+	if (!more) { \
+		n = spin_rows(coef, j); f = spin_rows(coef, j+1); \
+		PXS_ROWS_DRAIN(); \
+		n.r1 = n.r0; \
+		inC = 1; \
+	} } \
+	if (!more) { \
+		for (;;) {      /* (two pairs per iteration on alternating row sets, see leg_syn_s0) */ \
+			if constexpr ((NB) < K) if (j < nl && SPIN_BLOCK_STARTS(SLO - 1)) { more = true; break; } \
+			if (!(j + 3 < nl)) break; \
+			SPIN_ANA_PAIR_R(SPIN_ROW1(n), SPIN_ROW0(f), j, n = spin_rows(coef, j+3)) \
+			SPIN_ANA_PAIR_R(SPIN_ROW1(f), SPIN_ROW0(n), j+2, f = spin_rows(coef, j+5)) \
+			j += 4; \
+		} \
+	} \
+	if (!more) { \
+		slo = SLO; \
+		nb = K + 1; \
+	} else if constexpr ((NB) < K) { SPIN_BLOCK_BEGIN(SLO - 1) if (S.scp[SLO - 1] == 0 && S.scm[SLO - 1] == 0) load_data(SLO - 1); if constexpr ((NB) + 1 < K) { SPIN_NEXT_START(SLO - 2) } nb = (NB) + 1; } \
+} }
+// (the last steps, fewer than four, with the blocks from `slo` on started: one copy for all stages, leg_s0.hip, S0_ANA_TAIL)
+#define SPIN_ANA_TAIL { const int SLO = slo; \
+		if (j + 1 < nl) { \
+			SPIN_ANA_PAIR_R(SPIN_ROW1(n), SPIN_ROW0(f), j, (void)0) \
+			j += 2; \
+		} \
+		PXS_ROWS_DRAIN(); \
+		if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*jbase, lane, LEG_FSTEPS, a.atomic); kk = 0; jbase = j; } \
+		if (j < nl) { \
+			double t0 = 0, t1 = 0, t2 = 0, t3 = 0; \
+			_Pragma("unroll") for (int s = 0; s < K; s++) if (s >= SLO) { \
+				const double gp = S.gp2[s], gm = S.gm2[s]; \
+				t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0); \
+				t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1); \
+				t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2); \
+				t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3); \
+			} \
+			LEG_RED_PUT(kk, t0, t1, t2, t3) \
+			kk++; \
+		} }
+
 #define SPIN_ANA_PAIR_R(s0, s1, jfirst, NEXT) SPIN_ANA_PAIR_D(s0, s1, jfirst, NEXT)
 
 // (K = 2 is asked to keep its 5 waves per SIMD: 96 VGPRs; left alone the one-drain loop takes 98 = 4 waves.  No scratch either way)
@@ -379,49 +449,22 @@ template<int K> __global__ __launch_bounds__(64, (K == 2 ? 5 : 1)) void leg_ana_
 	int j = 0;
 	SPIN_SEEDED_PHASE_A
 	j = PXS_UNIFORM_INT(j); coef = (const double4_t*)PXS_UNIFORM_LONG((long)coef);
-	PXS_COUNT(1, (long)(nl - j)*K*12 + (a.seed_mode != 2 ? (long)j*K*4 : 0L));
+	// executed work: the recurrence FMAs of every block from here on (and of phase A where it ran), the accumulation FMAs of block K - 1, which starts with the
+	// wave; the other blocks add theirs as they start (SPIN_BLOCK_BEGIN)
+	constexpr int DIR = 1;
+	PXS_COUNT2(DIR, (long)(nl - j)*K*4 + (a.seed_mode != 2 ? (long)j*K*4 : 0L), (long)(nl - j)*8, K);
+	int knext = LEG_NEVER;      // seeded launches: the start step of the next block to start (the seed tail)
+	if constexpr (K > 1) { SPIN_NEXT_START(K - 2) }
 	if (lane == 0 && !a.atomic) a.first[wv*a.nmc + (m - a.m0)] = j + 1;      // rows before j are not written (reduce_partials skips them)
-	// ring data of the lanes whose chains start at scale 0 or both reached it during phase A
-#pragma unroll
-	for (int s = 0; s < K; s++) if (S.scp[s] == 0 && S.scm[s] == 0) load_data(s);
+	// ring data of block K - 1: the lanes whose chains start at scale 0 or both reached it during phase A
+	if (S.scp[K - 1] == 0 && S.scm[K - 1] == 0) load_data(K - 1);
 	int kk = 0, jbase = j;
-	// phase B: plain fast steps; every 4 steps the chains below scale 0 are rescaled, and a lane whose two chains
-	// have both reached scale 0 fetches its ring data (true terms before that: < 2^-340 of the result)
-	while (j + 1 < nl) {
-		bool pend = false;
-#pragma unroll
-		for (int s = 0; s < K; s++) pend |= (S.scp[s] < 0) || (S.scm[s] < 0);
-		if (!__any(pend)) break;
-		for (int it = 0; it < 2 && j + 1 < nl; it++, j += 2) {
-			const double4_t f0 = LDC(coef, j), f1 = LDC(coef, j+1);
-			SPIN_ANA_PAIR(f0, f1)
-		}
-#pragma unroll
-		for (int s = 0; s < K; s++) {
-			const bool was = (S.scp[s] < 0) || (S.scm[s] < 0);
-			if (S.scp[s] < 0 && fabs(S.gp2[s]) > SC_BIG) { S.gp1[s] *= SC_SMALL; S.gp2[s] *= SC_SMALL; S.scp[s]++; }
-			if (S.scm[s] < 0 && fabs(S.gm2[s]) > SC_BIG) { S.gm1[s] *= SC_SMALL; S.gm2[s] *= SC_SMALL; S.scm[s]++; }
-			if (was && S.scp[s] == 0 && S.scm[s] == 0) load_data(s);
-		}
-	}
-	// phase C: the one-drain loop of leg_syn_s0 with the drain between the two steps of a pair and the flush of a full tile at that drain, as in leg_ana_s0, on the
-	// 32-byte rows (legendre_dev.hpp, "Row prefetch")
-	SPIN_ANA_PHASE_C
-	PXS_ROWS_DRAIN();
-	if (kk == LEG_FSTEPS) { leg_flush(red, pout + 4*jbase, lane, LEG_FSTEPS, a.atomic); kk = 0; jbase = j; }
-	if (j < nl) {
-		double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-#pragma unroll
-		for (int s = 0; s < K; s++) {
-			const double gp = S.gp2[s], gm = S.gm2[s];
-			t0 = fma(gp, tpnr[s], t0); t0 = fma(gm, tpsr[s], t0);
-			t1 = fma(gp, tpni[s], t1); t1 = fma(gm, tpsi[s], t1);
-			t2 = fma(gm, tmnr[s], t2); t2 = fma(gp, tmsr[s], t2);
-			t3 = fma(gm, tmni[s], t3); t3 = fma(gp, tmsi[s], t3);
-		}
-		LEG_RED_PUT(kk, t0, t1, t2, t3)
-		kk++;
-	}
+	// phases B and C, by number of started blocks (SPIN_ANA_STAGE)
+	spin_rows_t n, f;
+	int nb = 1, inC = 0, slo = 0;
+	SPIN_ANA_STAGE(1) SPIN_ANA_STAGE(2) SPIN_ANA_STAGE(3) SPIN_ANA_STAGE(4) SPIN_ANA_STAGE(5) SPIN_ANA_STAGE(6)
+	static_assert(K <= 6, "leg_ana_spin: one SPIN_ANA_STAGE per block");
+	SPIN_ANA_TAIL
 	if (kk > 0) leg_flush(red, pout + 4*jbase, lane, kk, a.atomic);
 }
 

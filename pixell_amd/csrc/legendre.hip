@@ -641,7 +641,9 @@ static int k_small_grid(const RingSet& rs, int kdef, std::initializer_list<int> 
 // pairs), K_ANAS_BIG: the lane reduce-scatter of a step (10 VALU instructions whatever K is) is then shared by half as many FMAs again, at two waves per SIMD
 // instead of three; on smaller ring sets the padded polar wave and the fewer, longer waves cost more than that saves.  C3: leg_ana_spin<4> 91.41 -> leg_ana_spin<6>
 // 87.48 ms per launch (spreads 0.5 / 1.0), C2 leg_ana 8.72 -> 8.65.  Spin 0 keeps K_ANA0: leg_ana_s0<12> (217 VGPRs, two waves per SIMD)
-// was measured without per-block starts, which are not built, and gained 0.4 ms of 24, inside its spread; it is not in the tree (profiles/README.md, "Analysis K").
+// was measured without per-block starts and gained 0.4 ms of 24, inside its spread, and again with them (four more stages; the same 217 VGPRs, no scratch), behind a
+// rule that took it where K_ANA0 leaves LEG_BIG_MIN_WAVES waves per m (C3): leg_ana_s0<8> 23.77 -> leg_ana_s0<12> 23.15 ms per launch at spreads of 0.13 / 0.33, C3 leg_ana
+// 110.89 -> 110.35 at spreads of 0.76 / 0.54 -- under three times the spread both ways; instance and rule are out again (profiles/README.md, "Block starts").
 static constexpr int K_ANAS_BIG = 6, LEG_BIG_MIN_WAVES = 8;
 static int leg_ana_k(const RingSet& rs, int spin) {
 	if (spin == 0) return k_small_grid(rs, K_ANA0, {4, 2}, 4);

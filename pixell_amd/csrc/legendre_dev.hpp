@@ -39,6 +39,27 @@ static constexpr int    SC_STEP  = 800;
 static constexpr double LEG_LIVE = 0x1p-140;
 #define LEG_IS_LIVE(v, sc) ((sc) == 0 && fabs(v) >= LEG_LIVE)
 
+// Block starts.  A wave holds K blocks of 64 ring pairs, block K - 1 the most equatorial.  It leaves phase A when its first chain is live, which is almost always one of
+// block K - 1; the more polar blocks then hold zeros or values below LEG_LIVE for hundreds of steps more.  Every block runs its recurrence FMAs from the wave's
+// start on, but its ACCUMULATION FMAs (4 of 6 per step for spin 0, 8 of 12 for spin s) only from its own start: the first 4-step test, counted from the wave's
+// start, at which one of its own chains or a chain of a more polar block of the wave is live (leg_live_upto; tools/leg_live_count.cpp, column (c), is the same rule on
+// the CPU).  Starts are wave-uniform and monotone -- block K - 1 with the wave, then K - 2, ... -- so a wave runs its phases B and C as a sequence of loops
+// compiled for NB = 1 .. K started blocks (the *_ANA_STAGE macros of leg_s0.hip / leg_spin.hip), switching at a 4-step test; loop NB = K is the former loop.  What
+// this drops is bounded as what LEG_LIVE drops (above): values of chains that are not live.  An analysis block fetches its ring data when it starts.
+// The ANALYSIS kernels do this.  Measured on MI355X at C3, parent and result alternating (profiles/README.md, "Block starts", table "the tree as it is"): leg_ana
+// 112.03 -> 109.25 ms per step (spreads 0.50 / 0.58), C2 leg_ana 8.71 -> 8.26.  The synthesis kernels were built the same way, passed the same tests and came out level
+// (same section, table "all four kernels gated": leg_syn 84.62 -> 84.11 ms at spreads of 1.0 / 1.1, leg_syn_spin<3> 68.48 -> 69.05 ms in the kernel trace) with fewer blocks per wave to gate (K = 4 / 3); they keep the one loop
+// for all blocks, and the seed tail of a synthesis record is written (LEG_NEVER) and not read.
+// Seeded launches read the starts off the seed record instead of testing: the last 64 ints of a (wave, m) record held the step reached in [0] and nothing else;
+// [1 + c] now holds the start step of block c (LEG_NEVER: none), written by lane c + 1 both times so that the two stores stay in order.  No byte is added.
+#define LEG_NEVER 0x7fffffff
+template<int C, int K> __device__ __forceinline__ bool leg_live_upto(const double (&v)[K], const int (&sc)[K]) {
+	bool act = false;
+#pragma unroll
+	for (int s = 0; s <= C; s++) act |= LEG_IS_LIVE(v[s], sc[s]);
+	return act;
+}
+
 struct double4_t { double a, b, c, d; };
 // Wave-uniform table rows are fetched through the constant address space: that makes them scalar loads (s_load_dwordx8)
 // even in kernels that also store to global memory inside their loops.  Without it the analysis kernels, whose flush
@@ -124,10 +145,10 @@ struct LegK {
 	// recurrence seeds: the state of every chain at the end of phase A, per (m, wave): [nd][K][64] doubles, [ni][K][64] + 64 ints
 	// (the first of the last 64: the step reached).  mode 0: off, 1: run phase A and record, 2: load instead of running it
 	int seed_mode; double* seed_d; int* seed_i;
-	// executed-work counters (profiling on: pxs_profile; null otherwise): count[0] synthesis, count[1] analysis, in FMA instructions
-	// per lane: every wave adds (steps it ran) x K x (FMAs per ring pair and step: 6 per two degrees for spin 0, 12 per degree for
-	// spin s; 2 / 4 in the recurrence-only phase A).  x 64 lanes x 2 = the FP64 flops the hardware executed in the recurrences and
-	// accumulations (rings dropped as polar-dead and (wave, m) pairs skipped entirely are not in it, masked-off lanes are).
+	// executed-work counters (profiling on: pxs_profile; null otherwise): per slot count[0] synthesis, count[1] analysis (wave counts), count[2], count[3] (not executed; PXS_COUNT_AT), in FMA instructions
+	// per lane: every wave adds (steps it ran) x K x (recurrence FMAs per ring pair and step: 2 per two degrees for spin 0, 4 per degree for spin s; phase A
+	// included where it ran) + per block (steps from the block's start) x (accumulation FMAs: 4 / 8).  x 64 lanes x 2 = the FP64 flops the hardware executed in
+	// the recurrences and accumulations (rings dropped as polar-dead and (wave, m) pairs skipped entirely are not in it, masked-off lanes are).
 	double* count;
 	// maps of a batched call in one launch: the waves of one m of ALL maps sit next to each other in an XCD's queue, so the maps
 	// share the coefficient rows in L2 and the scalar cache.  Strides in elements of leg (double2), almt and mom (double).
@@ -137,11 +158,21 @@ struct LegK {
 };
 // (PXS_NCOUNT slots, one picked by the block index: 200 000 waves adding to ONE address cost ~10 ms per C3 step and 24 ms per C4 step)
 #define PXS_NCOUNT 1024
+// A slot holds four sums: [dir] the wave count -- every block of a wave counted with all its FMAs from the wave's start, the figure pxs_profile_flops has always
+// reported and bench.py and tests/test_leg_ana_blocks.py set against the model's column (b) -- and [2 + dir] what of it was NOT executed: the accumulation FMAs of
+// the blocks of the analysis kernels between the wave's start and their own ("Block starts" above).  Wave count minus that is the executed count, column (c): plan
+// query "leg_executed_flops_ana".  A kernel whose blocks all start with the wave adds to [dir] alone, one atomic per wave as before.
 #ifdef PXS_HOST_SIM
-#define PXS_COUNT(dir, expr) if (a.count != nullptr && lane == 0) atomicAdd(a.count + 2*(blockIdx.x & (PXS_NCOUNT - 1)) + (dir), (double)(expr))
+#define PXS_COUNT_AT(i, expr) if (a.count != nullptr && lane == 0) atomicAdd(a.count + 4*(blockIdx.x & (PXS_NCOUNT - 1)) + (i), (double)(expr))
 #else
-#define PXS_COUNT(dir, expr) if (a.count != nullptr && lane == 0) unsafeAtomicAdd(a.count + 2*(blockIdx.x & (PXS_NCOUNT - 1)) + (dir), (double)(expr))
+#define PXS_COUNT_AT(i, expr) if (a.count != nullptr && lane == 0) unsafeAtomicAdd(a.count + 4*(blockIdx.x & (PXS_NCOUNT - 1)) + (i), (double)(expr))
 #endif
+#define PXS_COUNT(dir, expr) PXS_COUNT_AT(dir, expr)
+// ... of the kernels with block starts, at the wave's start: wave count = the recurrence FMAs `rec` (every block, from here on, and phase A where it ran) + the accumulation
+// FMAs `acc` of each of the K blocks from here on; not executed: those of K - 1 blocks (block K - 1 starts with the wave), less what a block still runs when it starts
+// (PXS_COUNT_BLOCK: its accumulation FMAs from there on)
+#define PXS_COUNT2(dir, rec, acc, K_) { PXS_COUNT_AT(dir, (rec) + (K_)*(acc)); if ((K_) > 1) PXS_COUNT_AT(2 + (dir), ((K_) - 1)*(acc)); }
+#define PXS_COUNT_BLOCK(dir, acc) PXS_COUNT_AT(2 + (dir), -(acc))
 
 // Block -> (m, ring chunk).  Every wave of one m streams the same coefficient rows (32 B per l) through the
 // scalar cache; workgroups are dealt round-robin to the 8 XCDs, each with a private L2.  With the plain

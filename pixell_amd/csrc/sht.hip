@@ -370,6 +370,15 @@ int pxs_plan_query(const pxs_plan* p, const char* name, int64_t* value) {
 	PXS_REQUIRE(p, "pxs_plan_query: null argument");
 	if (p->pts) *value = points_query(p->pts, n);
 	else if (n == "analysis_form") { const Route r = analysis_route_now(p); *value = (r.kind == R_RING_WEIGHTS || r.kind == R_CC_WEIGHTS) ? 1 : (r.form->fine ? 2 : 0); }
+	else if (n == "leg_executed_flops_ana") {      // wave count less what was not executed (legendre_dev.hpp, PXS_COUNT_AT): blocks of the analysis kernels from their own start; reset with pxs_profile_flops
+		double sum = 0;
+		if (p->wk.count.p) {
+			PXS_HIP(hipSetDevice(p->device)); PXS_HIP(hipDeviceSynchronize());
+			std::vector<double> c(p->wk.count.bytes/sizeof(double)); PXS_HIP(hipMemcpy(c.data(), p->wk.count.p, p->wk.count.bytes, hipMemcpyDeviceToHost));
+			for (size_t i = 1; i + 2 < c.size(); i += 4) sum += (c[i] - c[i + 2])*128.0;
+		}
+		*value = (int64_t)sum;
+	}
 	else if (n == "leg_ana_k") *value = p->wk.last_ana_k;      // ring pairs per lane of the VALU launches of the most recent Legendre analysis on the plan (0: none yet)
 	else if (n == "ncc_circle") *value = p->th.ncc > 0 ? p->th.Ncc : 0;
 	else if (n == "ducc_ncc_circle") *value = FftChain::ducc_ncc(p->lmax);
@@ -445,7 +454,7 @@ int pxs_profile(pxs_plan* p, int enable) {
 	PXS_TRY
 	PXS_REQUIRE(p, "pxs_profile: null plan");
 	p->prof.enabled = enable != 0;
-	if (enable && !p->wk.count.p) { PXS_HIP(hipSetDevice(p->device)); p->wk.count.alloc(2*1024*sizeof(double)); PXS_HIP(hipMemset(p->wk.count.p, 0, p->wk.count.bytes)); }
+	if (enable && !p->wk.count.p) { PXS_HIP(hipSetDevice(p->device)); p->wk.count.alloc(4*1024*sizeof(double)); /* PXS_NCOUNT slots of four sums: legendre_dev.hpp */ PXS_HIP(hipMemset(p->wk.count.p, 0, p->wk.count.bytes)); }
 	p->wk.count_on = enable != 0;
 	PXS_CATCH
 }
@@ -458,7 +467,7 @@ int pxs_profile_flops(pxs_plan* p, double* flops, int reset) {
 	PXS_HIP(hipSetDevice(p->device));
 	PXS_HIP(hipDeviceSynchronize());
 	std::vector<double> c(p->wk.count.bytes/sizeof(double)); PXS_HIP(hipMemcpy(c.data(), p->wk.count.p, p->wk.count.bytes, hipMemcpyDeviceToHost));
-	for (size_t i = 0; i + 1 < c.size(); i += 2) { flops[0] += c[i]*128.0; flops[1] += c[i+1]*128.0; }     // FMA instructions per lane x 64 lanes x 2 flops
+	for (size_t i = 0; i + 3 < c.size(); i += 4) { flops[0] += c[i]*128.0; flops[1] += c[i+1]*128.0; }     // FMA instructions per lane x 64 lanes x 2 flops (the wave counts of a slot: legendre_dev.hpp, PXS_COUNT_AT)
 	if (reset) PXS_HIP(hipMemset(p->wk.count.p, 0, p->wk.count.bytes));
 	PXS_CATCH
 }

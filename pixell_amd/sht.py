@@ -87,11 +87,14 @@ class Plan:
 		_lib.check(_lib.load().pxs_profile_read(self.handle, ms, cnt, int(bool(reset))))
 		names = ["leg_syn", "leg_ana", "ring_fft", "resample"]
 		return {n: (ms[i], cnt[i]) for i, n in enumerate(names)}
-	def profile_flops(self, reset=True):
-		"""FP64 flops the Legendre kernels executed while profiling was on: (synthesis, analysis) (pxs_profile_flops)"""
+	def profile_flops(self, reset=True, executed=False):
+		"""FP64 flops of the Legendre kernels while profiling was on: (synthesis, analysis).  Default: the wave count of pxs_profile_flops, every block of a wave
+		counted from the wave's start.  executed=True: what the kernels executed, the blocks of the analysis kernels counted from their own start (plan query
+		"leg_executed_flops_ana"; the synthesis kernels start all blocks with the wave, so their two counts are one)"""
+		ana = float(self.query("leg_executed_flops_ana")) if executed else None
 		f = (ctypes.c_double*2)()
 		_lib.check(_lib.load().pxs_profile_flops(self.handle, f, int(bool(reset))))
-		return f[0], f[1]
+		return (f[0], ana) if executed else (f[0], f[1])
 	def set_option(self, name, value):
 		"""pxs_plan_option: "analysis" = 2 (ducc0's route, the default) | 0 (full theta-interpolant) | 1 (ring weights + adjoint synthesis where ntheta >= 2 lmax + 2);
 		"deterministic" = 0 | 1 (ordered, bitwise repeatable analysis sums; see set_deterministic);

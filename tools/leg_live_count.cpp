@@ -3,15 +3,18 @@
 // library's own tables (LegTables::build_host), start values (pow_scaled / to_scaled, spin_init), m-limit and 4-step test, and the largest
 // term a threshold drops.  Plain (non-polar) form of the recurrences throughout: the polar form is the same algebra.
 //   g++ -O2 -fopenmp -o leg_live_count tools/leg_live_count.cpp && ./leg_live_count [lmax 10000] [Ncc 20160] [m stride 1] [K of leg_ana_s0] [K of leg_ana_spin]
+//                                                                                  [K of leg_syn_s0 4] [K of leg_syn_spin 3] [first pair 0]
 // The analysis K default to what the host picks for the ring set (leg_ana_k, legendre.hip: 8 for spin 0; 6 for spin 2 where 4 gives at least 8 waves per m, else 4; k_small_grid's
-// rules for small ring sets are not modelled), so that the counts are those of the kernels as built and can be set against PXS_COUNT.
+// rules for small ring sets are not modelled: give the K), so that the counts are those of the kernels as built and can be set against PXS_COUNT.
+// first pair: the ring set is the band of the CC rings from that pair to the equator (a declination cut: no polar cap).
 // Prints, per kernel and threshold, sum over (m, wave) of (steps - start step) x K x FMAs per step (what PXS_COUNT adds up in a
 // seeded launch) and its ratio to the scale-0 rule, then log2 of the largest |lambda| (chain value x alpha) any chain has at a step
 // before it is live itself -- an upper bound of what its wave drops, since a wave starts no later than any of its lanes.
 // Then, at LEG_LIVE = 2^-140, three ways of dealing ring pairs to waves and blocks: (a) 64 K consecutive pairs per wave with the padding behind the last pair
 // (the partition until leg_pair_of existed), (b) the padding in front of pair 0, in wave 0 (leg_pair_of: what the kernels do and PXS_COUNT adds up), (c) = (b) and
 // a block of 64 pairs accumulates only from the first 4-step test at which one of its chains, or of a more polar block of the wave, is live: the recurrence FMAs
-// (2 of 6, 4 of 12) from the wave's start, the accumulation FMAs from the block's.  (c) is modelled, not built: no kernel does it.
+// (2 of 6, 4 of 12) from the wave's start, the accumulation FMAs from the block's.  (c) is what the kernels do (legendre_dev.hpp, "Block starts") and what PXS_COUNT adds up
+// in a seeded launch; the last lines print (b) and (c) as exact integers (FMAs per lane; x 128 = pxs_profile_flops), for tests/test_leg_block_starts.py.
 // Last, per kernel, the share of the accumulating wave-steps that lie in phase B (some lane of the wave still below scale 0: the steps with the rescale sweep).
 // Runtime on 16 cores: lmax 10^4 at stride 1 about 10 minutes, at stride 7 a minute and a half (the ratios agree to four digits); lmax 4000 (C2: Ncc 8064) at stride 1 a minute.
 #include <cmath>
@@ -42,19 +45,22 @@ static bool live(double v, int sc, int t) { return sc == 0 && (t == 0 ? v != 0.0
 static double lg(double v, int sc, double alpha) { return (v == 0.0 || alpha == 0.0) ? -1e9 : log2(fabs(v)) + 800.0*sc + log2(fabs(alpha)); }
 
 static const int TLIVE = 4;      // index of LEG_LIVE = 2^-140 in THR
-static void run(const int lmax, const long Ncc, const int mstride, int kana0, int kanas) {
+static void run(const int lmax, const long Ncc, const int mstride, int kana0, int kanas, int ksyn0, int ksyns, const int pair0) {
 	const LDb PIl = 3.141592653589793238462643383279502884L;
-	const int ncc = (int)(Ncc/2 + 1), npairs = (ncc + 1)/2;
+	const int ncc = (int)(Ncc/2 + 1), npairs = (ncc + 1)/2 - pair0;
+	if (npairs <= 0) { fprintf(stderr, "no ring pair left\n"); exit(1); }
 	std::vector<double> cth(npairs), sth(npairs), sh2(npairs), ch2(npairs);
-	for (int p = 0; p < npairs; p++) { const LDb th = 2*PIl*p/Ncc; cth[p] = (double)cosl(th); sth[p] = (double)sinl(th); sh2[p] = (double)sinl(th/2); ch2[p] = (double)cosl(th/2); }
+	for (int p = 0; p < npairs; p++) { const LDb th = 2*PIl*(p + pair0)/Ncc; cth[p] = (double)cosl(th); sth[p] = (double)sinl(th); sh2[p] = (double)sinl(th/2); ch2[p] = (double)cosl(th/2); }
 	const double ofs = std::max(100.0, 0.01*lmax);
 	if (kana0 <= 0) kana0 = 8;
 	if (kanas <= 0) kanas = (npairs + 64*4 - 1)/(64*4) >= 8 ? 6 : 4;
 	const int KMAX = 16;      // (blocks per wave the model takes; the kernels compile K up to 8 / 6)
-	if (kana0 > KMAX || kanas > KMAX) { fprintf(stderr, "K up to %d\n", KMAX); exit(1); }
-	const int KS[2][2] = {{4, kana0}, {3, kanas}};      // [spin 0 / spin 2][synthesis / analysis]
-	char kn[2][32]; snprintf(kn[0], 32, "leg_ana_s0<%d>", kana0); snprintf(kn[1], 32, "leg_ana_spin<%d>", kanas);
-	const char* KN[2][2] = {{"leg_syn_s0<4>", kn[0]}, {"leg_syn_spin<3>", kn[1]}};
+	if (ksyn0 <= 0) ksyn0 = 4;
+	if (ksyns <= 0) ksyns = 3;
+	if (kana0 > KMAX || kanas > KMAX || ksyn0 > KMAX || ksyns > KMAX) { fprintf(stderr, "K up to %d\n", KMAX); exit(1); }
+	const int KS[2][2] = {{ksyn0, kana0}, {ksyns, kanas}};      // [spin 0 / spin 2][synthesis / analysis]
+	char kn[4][32]; snprintf(kn[0], 32, "leg_ana_s0<%d>", kana0); snprintf(kn[1], 32, "leg_ana_spin<%d>", kanas); snprintf(kn[2], 32, "leg_syn_s0<%d>", ksyn0); snprintf(kn[3], 32, "leg_syn_spin<%d>", ksyns);
+	const char* KN[2][2] = {{kn[2], kn[0]}, {kn[3], kn[1]}};
 	double fma_sum[2][2][NT] = {}, steps_sum[2][2][NT] = {}, part_sum[2][2][3] = {}, phb_sum[2][2][2] = {}; double dropmax[2][NT]; double grow4[2] = {0, 0};
 	for (int i = 0; i < 2; i++) for (int t = 0; t < NT; t++) dropmax[i][t] = -1e9;
 	// sectoral normalisations (build_host)
@@ -189,7 +195,7 @@ static void run(const int lmax, const long Ncc, const int mstride, int kana0, in
 			}
 		}
 	}
-	printf("lmax %d, Ncc %ld: %d ring pairs, every %d-th m (sums x %d)\n", lmax, Ncc, npairs, mstride, mstride);
+	printf("lmax %d, Ncc %ld: %d ring pairs from pair %d on, every %d-th m (sums x %d)\n", lmax, Ncc, npairs, pair0, mstride, mstride);
 	for (int sp = 0; sp < 2; sp++) for (int d = 0; d < 2; d++) {
 		printf("%s  (x 128 = FP64 flops; the T/Q/U round trip runs it once)\n", KN[sp][d]);
 		for (int t = 0; t < NT; t++) printf("  live at %-8s wave-steps %.6e  FMA per lane %.6e  ratio %.4f\n", THRN[t], steps_sum[sp][d][t]*mstride, fma_sum[sp][d][t]*mstride, fma_sum[sp][d][t]/fma_sum[sp][d][0]);
@@ -204,6 +210,8 @@ static void run(const int lmax, const long Ncc, const int mstride, int kana0, in
 		printf("  %-16s %.5e | %.5e | %.5e   (%.4f, %.4f)\n", KN[sp][d], q[0]*128*mstride, q[1]*128*mstride, q[2]*128*mstride, q[1]/q[0], q[2]/q[0]); }
 	for (int d = 0; d < 2; d++) { double q[3]; for (int pt = 0; pt < 3; pt++) q[pt] = part_sum[0][d][pt] + part_sum[1][d][pt];
 		printf("  %-16s %.5e | %.5e | %.5e   (%.4f, %.4f)\n", d ? "analysis, both" : "synthesis, both", q[0]*128*mstride, q[1]*128*mstride, q[2]*128*mstride, q[1]/q[0], q[2]/q[0]); }
+	printf("FMAs per lane of a seeded launch, exact: all blocks from the wave's start (b) | blocks from their own step (c)\n");
+	for (int sp = 0; sp < 2; sp++) for (int d = 0; d < 2; d++) printf("  %-16s %.0f | %.0f\n", KN[sp][d], part_sum[sp][d][1]*mstride, part_sum[sp][d][2]*mstride);
 	printf("phase B share of the accumulating wave-steps (padding in wave 0):");
 	for (int sp = 0; sp < 2; sp++) for (int d = 0; d < 2; d++) printf("  %s %.2f %%", KN[sp][d], 100*phb_sum[sp][d][0]/phb_sum[sp][d][1]);
 	printf("\n");
@@ -215,6 +223,7 @@ static void run(const int lmax, const long Ncc, const int mstride, int kana0, in
 }
 
 int main(int argc, char** argv) {
-	run(argc > 1 ? atoi(argv[1]) : 10000, argc > 2 ? atol(argv[2]) : 20160, argc > 3 ? atoi(argv[3]) : 1, argc > 4 ? atoi(argv[4]) : 0, argc > 5 ? atoi(argv[5]) : 0);
+	run(argc > 1 ? atoi(argv[1]) : 10000, argc > 2 ? atol(argv[2]) : 20160, argc > 3 ? atoi(argv[3]) : 1, argc > 4 ? atoi(argv[4]) : 0, argc > 5 ? atoi(argv[5]) : 0,
+		argc > 6 ? atoi(argv[6]) : 0, argc > 7 ? atoi(argv[7]) : 0, argc > 8 ? atoi(argv[8]) : 0);
 	return 0;
 }
