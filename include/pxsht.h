@@ -335,12 +335,35 @@ int pxm_distance_from(int ny, int nx, double dec0, double ddec, double ra0, doub
  *   [0, n-1]; 1 "mirror": indices mirrored with period 2(n-1); 2 "constant": cval where x < 0 or x > n-1 on an axis, indices mirrored;
  *   3 "wrap" (scipy's legacy rule): x outside [0, n-1] folded with period n-1, indices mirrored; 4 "grid-wrap": indices modulo n.  Taps:
  *   floor(x + 1/2) (order 0), floor(x), floor(x) + 1 (order 1), floor(x) - 1 .. floor(x) + 2 (order 3).  A coordinate that is not a number
- *   gives cval. */
+ *   gives cval.
+ * pxm_spline_filter_axes: pxm_spline_filter with one extension rule per axis (a map that goes round the sky: periodic along x, mirror along
+ *   y); pxm_spline_filter is this call with its rule given twice. */
 int pxm_spline_filter(int nmap, int ny, int nx, const void* d_in, int in_dtype, int64_t in_mstride, double* d_tmp, double* d_out, int extension,
                       int device, void* stream);
 int pxm_interpol(int nmap, int ny, int nx, const void* d_maps, int map_dtype, int64_t mstride, int64_t npts, const double* d_pts, int ony, int onx,
                  double yoff, double yscale, double xoff, double xscale, double yref, double yper, double xref, double xper,
                  int order, int border, double cval, void* d_out, int device, void* stream);
+int pxm_spline_filter_axes(int nmap, int ny, int nx, const void* d_in, int in_dtype, int64_t in_mstride, double* d_tmp, double* d_out,
+                           int extension_y, int extension_x, int device, void* stream);
+
+/* catalogue cut-outs (pixell/reproject.py:10-116 thumbnails / thumbnails_ivar, with coordinates.recenter and the polarisation angle of
+ * coordinates.transform(pol=True), coordinates.py:25-122, 289-305).  All arrays DEVICE, FP64 arithmetic, no wait (the first call of a
+ * stream, or a larger thumbnail than any before on it, allocates the direction table).
+ * pxm_thumbnails: d_out[o][m][j][i] = map m, interpolated, where thumbnail pixel (j, i) lies once the thumbnail's centre is put on object o;
+ *   d_out: [nobj][nmap][oy][ox] in the maps' dtype.  Maps, dtypes, order, the affine map from (dec, ra) in radians to pixels and the rewind
+ *   (ref, per): as in pxm_interpol.  d_obj: f64 [nobj][2] = (dec, ra) in radians.  The thumbnail geometry has crval = (0, 0): pixel (j, i)
+ *   has the intermediate coordinates x = (i + 1 - crpix_x) cdelt_x, y = (j + 1 - crpix_y) cdelt_y in degrees and the direction
+ *   v = unit vector of (dec = y, ra = x) (proj 0, CAR) or v = (1, x, y)/|.| with x, y in radians (proj 1, TAN: gnomonic about (0, 0)).
+ *   Object o at (dec_o, ra_o) turns it into V = Rz(ra_o) Ry(-dec_o) v, read at dec = atan2(V_z, hypot(V_x, V_y)), ra = atan2(V_y, V_x).
+ *   border_y, border_x: the border codes of pxm_interpol, one per axis.  A pixel whose position is not a number, or outside a "constant"
+ *   axis, gets cval in every map.  pol != 0: components qcomp and ucomp (different, in [0, nmap), float maps) are rotated by -2 psi,
+ *   Q' = cos 2psi Q + sin 2psi U, U' = -sin 2psi Q + cos 2psi U, psi = atan2(Re . N, Re . E) the angle of the rotated east vector e of
+ *   the thumbnail pixel in the (east, north) frame of the sky position (enmap.rotate_pol(., -psi), reproject.py:93-101); pixels that got
+ *   cval are not rotated.  nobj times the workgroups per thumbnail (ceil(oy ox / 256)) must stay below 2^31. */
+int pxm_thumbnails(int nmap, int ny, int nx, const void* d_maps, int map_dtype, int64_t mstride,
+                   double yoff, double yscale, double xoff, double xscale, double yref, double yper, double xref, double xper,
+                   int64_t nobj, const double* d_obj, int oy, int ox, int proj, double cdelt_y, double crpix_y, double cdelt_x, double crpix_x,
+                   int order, int border_y, int border_x, double cval, int pol, int qcomp, int ucomp, void* d_out, int device, void* stream);
 
 /* 1 if the engine can transform this length (2,3,5-smooth or prime factors small enough) */
 int pxf_fft_supported(int64_t n);

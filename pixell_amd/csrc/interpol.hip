@@ -1,8 +1,8 @@
 // Spline interpolation of maps [ny][nx] at arbitrary positions: what the reference's utils.interpol / SplineInterpolator (pixell/utils.py:630-783:
 // scipy.ndimage.spline_filter followed by map_coordinates(prefilter=False)) gives enmap.at and enmap.project.  Two steps:
 //
-// pxm_spline_filter   the cubic B-spline coefficients c of the samples f: along each axis B c = f, B the (1/6, 4/6, 1/6) collocation matrix under the
-//   axis' extension rule (whole-sample mirror, half-sample reflect or periodic).  With z = sqrt(3) - 2 the solution is the two-sided sum
+// pxm_spline_filter(_axes)   the cubic B-spline coefficients c of the samples f: along each axis B c = f, B the (1/6, 4/6, 1/6) collocation matrix under the
+//   axis' extension rule (whole-sample mirror, half-sample reflect or periodic; _axes: one rule per axis, as a full-sky map wants them).  With z = sqrt(3) - 2 the solution is the two-sided sum
 //   c[k] = G sum_j z^|j| f[k - j], G = -6z/(1 - z^2), over the extended samples, which the usual pair of recursions evaluates:
 //       C+[k] = f[k] + z C+[k-1]             (causal)            c[k1] = G (C+[k1] + z C-[k1+1])      C-[k] = f[k] + z C-[k+1]
 //       c[k]  = z (c[k+1] - 6 C+[k])         (anticausal)
@@ -19,6 +19,7 @@
 //   read that the caller did not have already.  Every tap index goes through the border's index rule, whatever the coordinate was.
 #include "../../include/pxsht.h"
 #include "common.hpp"
+#include "interpol_dev.hpp"
 
 namespace pxs {
 namespace ipl {
@@ -32,20 +33,6 @@ static_assert(CHUNK % XT == 0 && HALO % XT == 0, "the tiles of the x pass must t
 
 static constexpr double POLE = -0.26794919243112270647;      // sqrt(3) - 2
 static constexpr double GAIN = -6.0*POLE/(1.0 - POLE*POLE);
-
-enum : int { EXT_MIRROR = 0, EXT_REFLECT = 1, EXT_PERIODIC = 2, EXT_CLAMP = 3 };
-enum : int { B_NEAREST = 0, B_MIRROR = 1, B_CONSTANT = 2, B_WRAP = 3, B_GRIDWRAP = 4 };
-
-// sample i of a line of n under the extension rule: always in [0, n)
-__device__ __forceinline__ int ext_index(int ext, long i, int n) {
-	if (i >= 0 && i < n) return (int)i;
-	if (n == 1) return 0;
-	if (ext == EXT_CLAMP) return i < 0 ? 0 : n - 1;
-	const long P = ext == EXT_MIRROR ? 2l*(n - 1) : (ext == EXT_REFLECT ? 2l*n : (long)n);
-	long m = i % P; if (m < 0) m += P;
-	if (m < n) return (int)m;
-	return (int)(ext == EXT_MIRROR ? P - m : P - 1 - m);
-}
 
 // the y pass: in [nmap][ny][nx] of T, maps in_ms apart -> out [nmap][ny][nx] f64.  grid (ceil(nx/256), chunks of rows, nmap)
 template<class T> __global__ __launch_bounds__(256) void filter_y_kernel(int ny, int nx, int ext, const T* __restrict__ in, long in_ms, double* out)
@@ -109,47 +96,7 @@ __global__ __launch_bounds__(64) void filter_x_kernel(int ny, int nx, int ext, c
 }
 
 // ---- the gather ---------------------------------------------------------------------------------------------------------------------
-struct Axis { int n; double off, scale, ref, per; };
 struct Gather { Axis y, x; long npts; int onx; int order, border; };
-
-// the pixel coordinate of p on an axis under the border rule; false: the point takes cval
-__device__ __forceinline__ bool axis_coord(const Axis& a, double p, int order, int border, double& xo) {
-	double x = fma(a.scale, p, a.off);
-	if (a.per > 0) {
-		double m = fmod(x - a.ref + 0.5*a.per, a.per);
-		if (m < 0) m += a.per;
-		x = a.ref + m - 0.5*a.per;
-	}
-	if (!(fabs(x) < 1e15)) return false;      // (not a number, or no pixel at all)
-	const double L = (double)(a.n - 1);
-	if (border == B_CONSTANT) { if (x < 0 || x > L) return false; }
-	else if (border == B_WRAP) {
-		if (a.n == 1) x = 0;
-		else if (x < 0) x += L*(double)((long)(-x/L) + 1);
-		else if (x > L) x -= L*(double)(long)(x/L);
-	} else if (border == B_MIRROR && order == 0) {
-		if (a.n == 1) x = 0;
-		else { x = fabs(x); x -= 2*L*floor(x/(2*L)); if (x > L) x = 2*L - x; }
-	}
-	xo = x;
-	return true;
-}
-// the order + 1 taps of an axis at x: indices under the border's index rule, weights
-__device__ __forceinline__ void axis_taps(int n, double x, int order, int border, int* idx, double* w) {
-	const int ext = border == B_NEAREST ? EXT_CLAMP : (border == B_GRIDWRAP ? EXT_PERIODIC : EXT_MIRROR);
-	if (order == 0) { idx[0] = ext_index(ext, (long)floor(x + 0.5), n); w[0] = 1.0; return; }
-	const double fl = floor(x), t = x - fl;
-	const long i0 = (long)fl;
-	if (order == 1) {
-		idx[0] = ext_index(ext, i0, n); idx[1] = ext_index(ext, i0 + 1, n);
-		w[0] = 1.0 - t; w[1] = t;
-		return;
-	}
-	for (int k = 0; k < 4; k++) idx[k] = ext_index(ext, i0 - 1 + k, n);
-	const double u = 1.0 - t;
-	w[0] = u*u*u*(1.0/6.0); w[3] = t*t*t*(1.0/6.0);
-	w[1] = (4.0 - 6.0*t*t + 3.0*t*t*t)*(1.0/6.0); w[2] = (4.0 - 6.0*u*u + 3.0*u*u*u)*(1.0/6.0);
-}
 
 // maps [nmap][ny][nx] of T, mstride apart -> out [nmap][npts] of T.  pts: f64 [2][npts], or null: point i is (i / onx, i % onx)
 template<class T> __global__ __launch_bounds__(256) void gather_kernel(Gather g, int nmap, const T* __restrict__ maps, long mstride, const double* __restrict__ pts,
@@ -196,13 +143,14 @@ using namespace pxs::ipl;
 
 extern "C" {
 
-int pxm_spline_filter(int nmap, int ny, int nx, const void* d_in, int in_dtype, int64_t in_mstride, double* d_tmp, double* d_out, int extension,
-                      int device, void* stream)
+int pxm_spline_filter_axes(int nmap, int ny, int nx, const void* d_in, int in_dtype, int64_t in_mstride, double* d_tmp, double* d_out,
+                           int extension_y, int extension_x, int device, void* stream)
 {
 	PXS_TRY
 	PXS_REQUIRE(nmap >= 0 && ny >= 1 && nx >= 1, "pxm_spline_filter: bad sizes");
 	PXS_REQUIRE(in_dtype == PX_F32 || in_dtype == PX_F64, "pxm_spline_filter: the maps must be float32 or float64");
-	PXS_REQUIRE(extension == EXT_MIRROR || extension == EXT_REFLECT || extension == EXT_PERIODIC, "pxm_spline_filter: unknown extension rule");
+	for (int extension : {extension_y, extension_x})
+		PXS_REQUIRE(extension == EXT_MIRROR || extension == EXT_REFLECT || extension == EXT_PERIODIC, "pxm_spline_filter: unknown extension rule");
 	PXS_REQUIRE(nmap == 0 || (d_in && d_tmp && d_out && d_tmp != d_out && (const void*)d_tmp != d_in), "pxm_spline_filter: the input, the scratch and the output are three arrays");
 	PXS_REQUIRE(nmap <= 1 || in_mstride >= (int64_t)ny*nx, "pxm_spline_filter: the maps overlap");
 	const long ncy = (ny + CHUNK - 1)/CHUNK, ncx = (nx + CHUNK - 1)/CHUNK, nry = (ny + XROWS - 1)/XROWS;
@@ -211,11 +159,17 @@ int pxm_spline_filter(int nmap, int ny, int nx, const void* d_in, int in_dtype, 
 	if (nmap == 0) return 0;
 	hipStream_t st = (hipStream_t)stream;
 	const dim3 gy(blocks_of(nx), (unsigned)ncy, (unsigned)nmap), gx((unsigned)ncx, (unsigned)nry, (unsigned)nmap);
-	if (in_dtype == PX_F32) hipLaunchKernelGGL((filter_y_kernel<float>), gy, dim3(256), 0, st, ny, nx, extension, (const float*)d_in, (long)in_mstride, d_tmp);
-	else hipLaunchKernelGGL((filter_y_kernel<double>), gy, dim3(256), 0, st, ny, nx, extension, (const double*)d_in, (long)in_mstride, d_tmp);
-	hipLaunchKernelGGL(filter_x_kernel, gx, dim3(XROWS), sizeof(double)*XROWS*XLD, st, ny, nx, extension, (const double*)d_tmp, d_out);
+	if (in_dtype == PX_F32) hipLaunchKernelGGL((filter_y_kernel<float>), gy, dim3(256), 0, st, ny, nx, extension_y, (const float*)d_in, (long)in_mstride, d_tmp);
+	else hipLaunchKernelGGL((filter_y_kernel<double>), gy, dim3(256), 0, st, ny, nx, extension_y, (const double*)d_in, (long)in_mstride, d_tmp);
+	hipLaunchKernelGGL(filter_x_kernel, gx, dim3(XROWS), sizeof(double)*XROWS*XLD, st, ny, nx, extension_x, (const double*)d_tmp, d_out);
 	PXS_HIP(hipGetLastError());
 	PXS_CATCH
+}
+
+int pxm_spline_filter(int nmap, int ny, int nx, const void* d_in, int in_dtype, int64_t in_mstride, double* d_tmp, double* d_out, int extension,
+                      int device, void* stream)
+{
+	return pxm_spline_filter_axes(nmap, ny, nx, d_in, in_dtype, in_mstride, d_tmp, d_out, extension, extension, device, stream);
 }
 
 int pxm_interpol(int nmap, int ny, int nx, const void* d_maps, int map_dtype, int64_t mstride, int64_t npts, const double* d_pts, int ony, int onx,

@@ -114,6 +114,39 @@ def band_geometry(dec_cut, res=None, shape=None, dims=(), proj="car", variant="f
 	w = fwcs.deepcopy(); w.wcs.crpix[1] -= first
 	return tuple(dims)+(last-first, fshape[-1]), w
 
+def thumbnail_geometry(r=None, res=None, shape=None, dims=(), proj="tan"):
+	"""(shape, wcs) of a geometry in projection proj ("car" or "tan") centred on (0, 0), which lies exactly on pixel shape//2 of an odd
+	shape, cdelt = (-res, res): the geometry of reproject.thumbnails (enmap.thumbnail_geometry, enmap.py:1770-1820).  Two of r (the
+	radius from the centre to the edges), res and shape, in radians."""
+	proj = str(proj).lower()
+	if proj not in ("car", "tan"): raise NotImplementedError("thumbnail_geometry: projections \"car\" and \"tan\", not \"%s\"" % proj)
+	make = CarWCS if proj == "car" else wcsutils.TanWCS
+	dirs = np.array([1.0, -1.0])
+	def odd(shape): return np.rint(np.zeros(2)+np.asarray(shape[-2:], float)).astype(int)//2*2+1
+	def rpix(wcs, r):      # |pixel offset| {y,x} of the point (dec, ra) = r from the centre
+		x, y = wcs.wcs_world2pix(r[1]/degree, r[0]/degree, 0)
+		return np.abs(np.array([float(y), float(x)]))
+	def expand(res):
+		res = np.atleast_1d(np.asarray(res, float))
+		return dirs*res[0] if res.size == 1 else res
+	if r is None:
+		if res is None or shape is None: raise ValueError("Two of r, res and shape must be given")
+		res, shape = expand(res), odd(shape)
+		wcs = make(cdelt=res[::-1]/degree, crval=[0, 0], crpix=shape[::-1]//2+1)
+	elif shape is None:
+		if res is None: raise ValueError("Two of r, res and shape must be given")
+		res, r = expand(res), np.zeros(2)+r
+		wcs = make(cdelt=res[::-1]/degree, crval=[0, 0], crpix=[1, 1])
+		shape = 2*np.rint(rpix(wcs, r)).astype(int)+1
+		wcs.wcs.crpix = np.array(shape[::-1]//2+1, float)
+	else:
+		shape, r = odd(shape), np.zeros(2)+r
+		wcs = make(cdelt=[1, 1], crval=[0, 0], crpix=[1, 1])
+		ratio = (shape-1)/(2*rpix(wcs, r))*dirs
+		wcs.wcs.cdelt = wcs.wcs.cdelt/ratio[::-1]
+		wcs.wcs.crpix = np.array(shape[::-1]//2+1, float)
+	return tuple(dims)+tuple(int(n) for n in shape), wcs
+
 def spin_helper(spin, n):
 	"""Walk the n components of a map / alm stack in spin groups: yields (spin, first, last+1); spin 0 takes one component,
 	any other spin a pair; the spin list is cycled (enmap.spin_helper, enmap.py:3378-3388).  IndexError if a pair is cut."""
@@ -138,6 +171,24 @@ def area(shape, wcs):
 	lo, hi, _ = _dec_span(shape, wcs)
 	return (np.sin(hi)-np.sin(lo))*abs(wcs.wcs.cdelt[0])*degree*shape[-1]
 def pixsize(shape, wcs): return area(shape, wcs)/np.prod(shape[-2:])
+
+def pixshapes_cyl(shape, wcs, signed=False):
+	"""[{height,width}, ny] of the pixels of each row of a separable cylindrical geometry, radians: a row from dec1 to dec2 is dec2 - dec1
+	high and, its pixels having the area dRA (sin dec2 - sin dec1), area/height wide (enmap.pixshapes_cyl, enmap.py:1150-1175)"""
+	if not wcsutils.is_separable(wcs): raise NotImplementedError("pixshapes_cyl: only separable cylindrical geometries")
+	ny = int(shape[-2])
+	dec = np.clip(pix2sky(shape, wcs, [np.arange(ny+1)-0.5, np.zeros(ny+1)])[0], -np.pi/2, np.pi/2)
+	heights = dec[1:]-dec[:-1]
+	sdec = np.sin(dec)
+	res = np.array([heights, wcs.wcs.cdelt[0]*degree*(sdec[1:]-sdec[:-1])/heights])
+	return res if signed else np.abs(res)
+
+def pixsizemap(shape, wcs, broadcastable=False):
+	"""the area of every pixel in steradians, [ny, nx] (broadcastable: [ny, 1]), a host ndmap: exact per row for separable cylindrical
+	geometries (enmap.pixsizemap, enmap.py:1177-1204)"""
+	psize = np.prod(pixshapes_cyl(shape, wcs), 0)[:, None]
+	if not broadcastable: psize = np.broadcast_to(psize, tuple(shape[-2:]))
+	return ndmap(psize, wcs)
 
 def _norm(emap, normalize, sign, dct=False):
 	norm = 1.0
@@ -541,6 +592,7 @@ for _cls in (ndmap, dmap):
 	_cls.posmap   = lambda self, **kw: posmap(self.shape, self.wcs, **kw)
 	_cls.at       = lambda self, pos, **kw: at(self, pos, **kw)
 	_cls.project  = lambda self, shape, wcs, **kw: project(self, shape, wcs, **kw)
+	_cls.pixsizemap = lambda self, **kw: pixsizemap(self.shape, self.wcs, **kw)
 
 # ---------------------------------------------------------------------------------------
 # bounding boxes and pixel sizes of separable CAR geometries (what pixell_amd.wavelets builds its per-scale geometries from)

@@ -34,6 +34,10 @@ def _ip_get_mode(mode, order):
 	return mode, int(order)
 
 def _check_border(border):
+	"""a border name, or a pair of them (y, x): what reproject.thumbnails reads a map that goes round the sky with"""
+	if isinstance(border, (tuple, list)):
+		if len(border) != 2: raise ValueError("a border per axis is a pair (y, x)")
+		return tuple(_check_border(b) for b in border)
 	if border not in BORDERS: raise ValueError("Unrecognized border '%s'" % str(border))
 	return border
 
@@ -48,6 +52,10 @@ def _filter(d, border):
 	ny, nx = int(d.shape[-2]), int(d.shape[-1])
 	nmap = int(np.prod(d.shape[:-2], dtype=np.int64))
 	tmp, out = A.empty(d.shape, np.float64, like=d), A.empty(d.shape, np.float64, like=d)
+	if isinstance(border, tuple):
+		_lib.check(_lib.load().pxm_spline_filter_axes(nmap, ny, nx, A.ptr(d), _DT[A.np_dtype(d)], ny*nx, A.ptr(tmp), A.ptr(out), _EXTENSION[border[0]],
+			_EXTENSION[border[1]], A.device_index(), A.current_stream()))
+		return out
 	_lib.check(_lib.load().pxm_spline_filter(nmap, ny, nx, A.ptr(d), _DT[A.np_dtype(d)], ny*nx, A.ptr(tmp), A.ptr(out), _EXTENSION[border],
 		A.device_index(), A.current_stream()))
 	return out
@@ -59,8 +67,9 @@ def _as_kind(work, device):
 
 def spline_filter(arr, order=3, border="nearest"):
 	"""The B-spline coefficients of arr [..., ny, nx] over its last two axes, float64: scipy.ndimage.spline_filter(arr[I], order,
-	mode=border) for every leading index I.  Orders 0 and 1 have no filter: a float64 copy.  A map comes back as a map."""
-	_, order = _ip_get_mode("spline", order); _check_border(border)
+	mode=border) for every leading index I.  Orders 0 and 1 have no filter: a float64 copy.  A map comes back as a map.  border may be
+	a pair (y, x): each axis is then filtered under its own border's extension."""
+	_, order = _ip_get_mode("spline", order); border = _check_border(border)
 	data = _raw(arr)
 	if data.ndim < 2: raise ValueError("spline_filter needs at least two axes")
 	device = A.device_of(data)
@@ -72,7 +81,7 @@ def spline_filter(arr, order=3, border="nearest"):
 
 class SplineInterpolator:
 	"""arr [{pre}, ny, nx] prepared for interpolation at many sets of positions: utils.SplineInterpolator (utils.py:696-720).  The
-	prefilter (order 3) runs once, here; every call is one launch."""
+	prefilter (order 3) runs once, here; every call is one launch.  border: a name, or a pair (y, x) for reproject.thumbnails."""
 	prefiltered = True
 	def __init__(self, arr, npre=0, mode="spline", border="nearest", order=3, cval=0.0):
 		self.mode, self.order = _ip_get_mode(mode, order)
@@ -99,6 +108,7 @@ class SplineInterpolator:
 		"""The values [{pre}, oshape] at the points pts [2, oshape] or, without pts, at the pixels of a grid oshape = (ony, onx).  A
 		point's pixel coordinate on axis a is affine[a][0] + affine[a][1]*p, rewound into rewind[a][1] pixels around rewind[a][0] where
 		that period is positive.  out: an array of the result's shape and dtype to fill."""
+		if isinstance(self.border, tuple): raise NotImplementedError("an interpolator with a border per axis is read by reproject.thumbnails only")
 		oshape = tuple(int(n) for n in oshape)
 		pre = tuple(self.arr.shape[:self.npre]); ny, nx = int(self.arr.shape[-2]), int(self.arr.shape[-1])
 		nmap, npts = int(np.prod(pre, dtype=np.int64)), int(np.prod(oshape, dtype=np.int64))

@@ -32,6 +32,35 @@ class CarWCS:
 	def __repr__(self):
 		return "car:{cdelt:%s,crval:%s,crpix:%s}" % (list(self.wcs.cdelt), list(self.wcs.crval), list(self.wcs.crpix))
 
+class TanWCS:
+	"""Gnomonic (TAN) stand-in about crval = (0, 0) only, which is what a thumbnail geometry is: the intermediate coordinates
+	x = (pix_x + 1 - crpix_x) cdelt_x, y = (pix_y + 1 - crpix_y) cdelt_y, in radians, are the standard coordinates (xi, eta) of the direction
+	(1, xi, eta): ra = atan(xi), dec = atan2(eta, hypot(1, xi)), and back xi = tan(ra), eta = tan(dec)/cos(ra) on the hemisphere that faces
+	(0, 0) (not a number on the other).  Not separable: everything that needs a separable geometry raises for it."""
+	def __init__(self, cdelt=None, crval=None, crpix=None, ctype=None):
+		self.wcs = _Prm()
+		self.wcs.ctype = ["RA---TAN", "DEC--TAN"] if ctype is None else list(ctype)
+		if cdelt is not None: self.wcs.cdelt = np.array(cdelt, float)
+		if crpix is not None: self.wcs.crpix = np.array(crpix, float)
+		if crval is not None and np.any(np.asarray(crval, float) != 0): raise ValueError("TanWCS is gnomonic about crval = (0, 0) only")
+		if get_proj(self) != "tan": raise ValueError("TanWCS needs TAN ctypes")
+	def deepcopy(self):
+		return TanWCS(self.wcs.cdelt, self.wcs.crval, self.wcs.crpix, self.wcs.ctype)
+	def wcs_pix2world(self, x, y, origin):
+		w = self.wcs; degree = np.pi/180
+		xi = (np.asarray(x, float)+1-origin-w.crpix[0])*w.cdelt[0]*degree
+		eta = (np.asarray(y, float)+1-origin-w.crpix[1])*w.cdelt[1]*degree
+		return [np.arctan2(xi, 1.0)/degree, np.arctan2(eta, np.hypot(1.0, xi))/degree]
+	def wcs_world2pix(self, ra, dec, origin):
+		w = self.wcs; degree = np.pi/180
+		ra, dec = np.asarray(ra, float)*degree, np.asarray(dec, float)*degree
+		with np.errstate(invalid="ignore", divide="ignore"):
+			front = np.cos(dec)*np.cos(ra) > 0
+			xi, eta = np.where(front, np.tan(ra), np.nan), np.where(front, np.tan(dec)/np.cos(ra), np.nan)
+		return [xi/degree/w.cdelt[0]+w.crpix[0]-1+origin, eta/degree/w.cdelt[1]+w.crpix[1]-1+origin]
+	def __repr__(self):
+		return "tan:{cdelt:%s,crval:%s,crpix:%s}" % (list(self.wcs.cdelt), list(self.wcs.crval), list(self.wcs.crpix))
+
 def get_proj(wcs):
 	ct = wcs.wcs.ctype[0]
 	return ct[-3:].lower() if len(ct) >= 3 else ""
