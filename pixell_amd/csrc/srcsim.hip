@@ -4,7 +4,8 @@
 //   r(p, i)   = 2 asin(sqrt(min(h, 1))),  h = sin^2((dec_p - dec_i)/2) + cos dec_p cos dec_i sin^2((ra_p - ra_i)/2)       (no cancellation for close points)
 //   P_i(r)    = the linear interpolation of the object's profile samples (rs, vs): vs[0] below rs[0], 0 from rs[n-1] on
 //   rcut_i    = rs[min(k+1, n-1)], k the last sample with |vs[k]| >= vmin / max_c |amps[c,i]| (0 if none), capped by rmax > 0
-//   forward   : map[c,p] = op(map[c,p], amps[c,i] P_i(r)) for every object with r <= rcut_i, for `add` in ascending i
+//   forward   : map[c,p] = op(map[c,p], amps[c,i] P_i(r)) for every object with r <= rcut_i; for `add` the terms are summed in ascending i and the
+//               sum is added to the map once, so what the map held is rounded against once, not once per object
 //   transpose : amps[c,i] += sum_{p: r <= rcut_i} map[c,p] P_i(r)
 //   radial sum: oprofs[i,c,k] += sum map[c,p] over bins[k] <= r < bins[k+1]
 // Pixel p = (y, x) sits at float(dec0 + y ddec), float(ra0 + x dra), objects at float coordinates, as the reference takes them.
@@ -38,8 +39,12 @@ __device__ __forceinline__ float pix_decf(const PixGeo& g, int y) { return (floa
 __device__ __forceinline__ float pix_raf(const PixGeo& g, int x) { return (float)pix_ra(g, x); }
 __device__ __forceinline__ int prof_id(const Prof& pr, const int* pid, long i) { const int q = pid ? pid[i] : 0; return q < 0 ? 0 : (q >= pr.nprof ? pr.nprof - 1 : q); }
 
+// The RA difference is brought into [-pi, pi] in double before it is rounded to float: across the seam of a map that covers the whole
+// circle the two coordinates differ by 2 pi, and a float difference there is good to 2^-24 of 2 pi, not of the separation (paint_kernel takes
+// its separable terms in double and has no such case).  Away from the seam nothing changes: the double difference rounds to the float one.
 __device__ __forceinline__ float pair_dist(float pdec, float pra, float cp, float odec, float ora, float co) {
-	const float sd = sinf(0.5f*(pdec - odec)), sr = sinf(0.5f*(pra - ora));
+	const double dra = (double)pra - (double)ora;
+	const float sd = sinf(0.5f*(pdec - odec)), sr = sinf((float)(0.5*(dra - 2*PXS_PI*rint(dra*(0.5/PXS_PI)))));
 	const float h = sd*sd + cp*co*(sr*sr);
 	return 2.0f*asinf(sqrtf(fminf(h, 1.0f)));
 }
@@ -215,7 +220,7 @@ template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(Pi
 		for (int c0 = 0; c0 < ncomp; c0 += NCC) {
 			const int nc = ncomp - c0 < NCC ? ncomp - c0 : NCC;
 			T acc[NCC];
-			for (int c = 0; c < NCC; c++) acc[c] = (inside && c < nc) ? map[(c0 + c)*cstride + p] : T(0);
+			for (int c = 0; c < NCC; c++) acc[c] = (OP != 0 && inside && c < nc) ? map[(c0 + c)*cstride + p] : T(0);      // add: the objects' sum starts from zero and meets the map once, at the end
 			for (int j0 = 0; j0 < n; j0 += NCH) {
 				const int m = n - j0 < NCH ? n - j0 : NCH;
 				__syncthreads();      // (the readers of the previous step are done)
@@ -243,7 +248,7 @@ template<class T, int OP> __global__ __launch_bounds__(256) void paint_kernel(Pi
 					}
 				}
 			}
-			if (inside) for (int c = 0; c < nc; c++) map[(c0 + c)*cstride + p] = acc[c];
+			if (inside) for (int c = 0; c < nc; c++) { T& mv = map[(c0 + c)*cstride + p]; mv = OP == 0 ? mv + acc[c] : acc[c]; }
 		}
 	}
 }

@@ -44,9 +44,10 @@ def split_reference(ainfo, alm, filters, lmaxs):
 		res.append(np.asarray(small.lmul(a, f[:li+1])))
 	return res
 
-def check_split(lmax, kind, npre, dtype, seed=0):
+def check_split(lmax, kind, npre, dtype, seed=0, scales=None):
+	"""scales: (lmaxs, Ls) in place of scales_of(lmax); entries 2 and 3 must share an L"""
 	rng = np.random.default_rng(seed)
-	ainfo = layout(kind, lmax); lmaxs, Ls = scales_of(lmax)
+	ainfo = layout(kind, lmax); lmaxs, Ls = scales_of(lmax) if scales is None else scales
 	alm = rand_c(rng, (npre, ainfo.nelem) if npre > 1 else (ainfo.nelem,), dtype)
 	filters = filters_of(rng, lmaxs, lmax)
 	got = ainfo.bank_split(alm, filters, lmaxs, Ls)
@@ -76,9 +77,9 @@ def small_l(info):
 	for m in range(info.mmax+1): l[info.lm2ind(np.arange(m, info.lmax+1), m)] = np.arange(m, info.lmax+1)
 	return l
 
-def check_merge(lmax, kind, npre, dtype, seed=1):
+def check_merge(lmax, kind, npre, dtype, seed=1, scales=None):
 	rng = np.random.default_rng(seed)
-	ainfo = layout(kind, lmax); lmaxs, Ls = scales_of(lmax)
+	ainfo = layout(kind, lmax); lmaxs, Ls = scales_of(lmax) if scales is None else scales
 	pre = (npre,) if npre > 1 else ()
 	alms = [rand_c(rng, pre+(almops.tri_nelem(L),), dtype) for L in Ls]
 	filters = filters_of(rng, lmaxs, lmax)
