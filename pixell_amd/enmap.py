@@ -45,7 +45,10 @@ class dmap:
 		res = _sliced(self, self.tensor[sel], sel)
 		if not isinstance(res, dmap): raise IndexError("indexing a pixel axis of a dmap leaves no map geometry: slice the tensor itself")
 		return res
-	def copy(self): return dmap(self.tensor.clone(), self.wcs)
+	def copy(self):
+		"""a dmap of a clone of the tensor, which keeps the strides of a dense permuted tensor (torch.clone preserves the memory format):
+		code that computes addresses from the copy asks for a C-contiguous one itself, as harm2map does"""
+		return dmap(self.tensor.clone(), self.wcs)
 	def pixsize(self): return pixsize(self.shape, self.wcs)
 
 def _sliced(parent, res, sel):
@@ -317,6 +320,7 @@ def _rotate_pairs(hmap, spin, iau, inverse):
 	"""rotate every spin-s pair of a contiguous complex harmonic map [...,ncomp,ny,nx] in place"""
 	data = _data(hmap)
 	if data.ndim <= 2: return
+	if not A.is_contiguous(data): raise ValueError("_rotate_pairs: the harmonic map must be C-contiguous (component addresses are computed from its shape)")
 	ny, nx = data.shape[-2:]; nc = data.shape[-3]
 	lib = _lib.load(); dev = A.device_index(); st = A.current_stream()
 	dt = A.DT[A.np_dtype(data)]; esz = A.np_dtype(data).itemsize
@@ -341,7 +345,9 @@ def harm2map(emap, nthread=0, normalize=True, iau=False, spin=[0, 2], keep_imag=
 	"""E/B -> Q/U rotation + inverse 2-D FFT (enmap.harm2map, enmap.py:1376-1389)"""
 	dev, was_host = _to_device(emap)
 	if dev.ndim > 2:
-		dev = dev.copy()
+		# the working copy is C-contiguous whatever the caller's strides: _rotate_pairs addresses components from the shape
+		d = _data(dev)
+		dev = _wrap(d.clone(memory_format=A.torch().contiguous_format) if A.is_tensor(d) else np.array(d, order="C"), dev)
 		_rotate_pairs(dev, spin, iau, inverse=True)
 	res = ifft(dev, nthread=nthread, normalize=normalize, adjoint_fft=adjoint_map2harm)
 	if not keep_imag:
