@@ -142,7 +142,7 @@ int pxs_plan_option(pxs_plan* plan, const char* name, int64_t value);
 /* What a plan does: "analysis_form" = the form pxs_analysis runs now (0 interpolant, 1 ring weights, 2 fine-CC form of ducc0's
  * route), "ncc_circle" = N_cc, the circle of the CC grid of the Legendre stage (0: none), "ducc_ncc_circle" = ducc0's N_cc for
  * the plan's lmax, "theta_line" = 1 if the theta resampling of pxs_analysis runs as one kernel with the line resident on a CU
- * (the circle sizes compiled into thetaline.hip; PXS_THETA_LINE=0 switches it off), 0 if as the five-stage chain: same results.
+ * (the fine-CC form and the ring-weights form on the circle sizes compiled into thetaline.hip; PXS_THETA_LINE=0 switches it off), 0 if as the five-stage chain: same results.
  * "leg_ana_k": ring pairs per lane of the single-map Legendre analysis kernels in the plan's most recent analysis or adjoint synthesis (0: none yet).
  * "leg_executed_flops_ana": FP64 flops the Legendre analysis kernels executed while profiling was on (see pxs_profile_flops).
  * "chain_stages": the distinct FFT chain stage shapes (stage, transform lengths, lines per tile) of the plan's standard calls (analysis

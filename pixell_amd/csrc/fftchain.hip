@@ -1108,7 +1108,7 @@ void FftChain::theta(hipStream_t st, ThetaOp op, const ThetaCall& c) {
 }
 
 void FftChain::to_cc(hipStream_t st, const ThetaCall& c) {
-	if (dry_ ? line_takes(*c.tp, true) : line_analysis(st, true, c)) return;
+	if (line_takes(*c.tp, true, c.sig_half)) { if (!dry_) line_analysis(st, true, c); return; }
 	const ThetaPlan& tp = *c.tp; const long npair = (c.nm + 1)/2, g = tp.g, bN = tp.bN, g2 = tp.g2, ac = tp.ac;
 	const double2* ph = c.ph;
 #ifdef PXS_LAB
@@ -1131,7 +1131,7 @@ void FftChain::to_cc(hipStream_t st, const ThetaCall& c) {
 // operator A that commutes with the reflection (E': mirror extension of the ring samples, R: restriction to the CC rings) except
 // at the CC pole rings, which E' counts twice: weight 1/2 there (c.wcc).  So: RA1, the resize N -> N_cc directly, RA5.
 void FftChain::from_cc_adjoint(hipStream_t st, const ThetaCall& c) {
-	if (dry_ ? line_takes(*c.tp, false) : line_analysis(st, false, c)) return;
+	if (line_takes(*c.tp, false, nullptr)) { if (!dry_) line_analysis(st, false, c); return; }
 	const ThetaPlan& tp = *c.tp; const long npair = (c.nm + 1)/2, g = tp.g, bN = tp.bN, ac = tp.ac;
 	theta_chunks(TH_FROM_CC_ADJ, c, [&](int c0, long ncl) {
 		// (wring: quadrature weights of the map's rings: the weights form of the analysis)

@@ -38,6 +38,7 @@ struct ThetaCall {
 	// tables: shift phase per k; pointwise table on the M circle; weight (.x) per CC ring (TH_FROM_CC_ADJ: 1/N_cc, half at the poles;
 	// TH_TO_CC_ADJ: the TH_TO_CC weights halved off the poles); optional weight (.x) per ring of the map; h = ... * conj(tab[m]) * scale
 	const double2 *ph = nullptr, *sigma = nullptr, *wcc = nullptr, *wring = nullptr, *tab = nullptr; double scale = 1.0;
+	const double* sig_half = nullptr;      // the fine-CC form: entries i <= M/2 of its sigma, which is real and mirror-symmetric (AnaForm::sig_half)
 };
 
 class FftChain {
@@ -72,9 +73,10 @@ public:
 	// 2-D FFT of complex128 [npre][ny][nx] (in == out allowed); false if nx or ny has no usable factorisation
 	bool fft2_c2c(hipStream_t st, const double2* in, double2* out, long npre, long ny, long nx, bool forward, double scale);
 	// single-kernel form of TH_TO_CC (has_mid) / TH_FROM_CC_ADJ for lines that fit a CU (thetaline.hip): one workgroup per pair of columns,
-	// no HBM intermediates.  false: not eligible (sizes, radices) or switched off (PXS_THETA_LINE=0) -- the caller runs the stage chain.
-	bool line_analysis(hipStream_t st, bool has_mid, const ThetaCall& c);
-	static bool line_takes(const ThetaPlan& tp, bool has_mid);      // ... would it (then the call needs no theta scratch)
+	// no HBM intermediates.  line_takes: THE test of whether it runs the call -- the circles are a compiled configuration, a middle circle
+	// comes with ThetaCall::sig_half, and PXS_THETA_LINE is not 0; the route (which then sizes no theta scratch), the dry run and the launch ask it.
+	static bool line_takes(const ThetaPlan& tp, bool has_mid, const double* sig_half);
+	void line_analysis(hipStream_t st, bool has_mid, const ThetaCall& c);      // (throws on a call line_takes refuses)
 	// single-kernel form of h2map for ring lengths compiled into ringline.hip: one workgroup per ring pair, no HBM intermediate
 	bool line_h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& m, int nc, int mmax, long hcomp);
 	static bool line_h2map_takes(long nphi, int mmax);
@@ -119,7 +121,6 @@ private:
 	Split ra_, rs_;           // ring FFT splits: analysis, synthesis
 	long nphi_ = 0;
 	DevBuf s1_, s2_;          // ping-pong scratch
-	std::shared_ptr<struct ThetaLine> tl_;     // plans of the single-kernel theta engine
 };
 
 // where the pixels of a map live, in the form the ring-FFT kernels take it (fftchain.hip, ringline.hip)

@@ -2,8 +2,9 @@
 // registers (PMAX points per thread at most) and transforms it with Stockham decimation-in-frequency passes whose butterflies
 // (radix 2 ... 16) run entirely in registers.  Between two passes the line goes through the LDS ONE COMPONENT AT A TIME
 // (re, then im): the LDS holds n doubles, so a line of 16 128 points (258 KB) fits a CU -- 129 KB in the LDS during an exchange,
-// the other component in registers.  Used by the single-kernel theta resampling engine (thetaline.hip); host model of the same
-// index arithmetic: tools/regfft_model.py.
+// the other component in registers; LDS word i holds line index i (padded and rotated layouts were measured and lost to their address
+// arithmetic: DESIGN.md).  Used by the single-kernel engines (thetaline.hip, ringline.hip), whose shared host side is at the end of
+// this file; host model of the same index arithmetic: tools/regfft_model.py.
 //
 // Pass p (radix R, s = product of the earlier radices, nb = n / R butterflies, butterfly b = q + s*pp, q = b mod s):
 //   reads   a_k = x[b + nb*k]                            -- the same pattern for every pass: thread t holds butterflies t + NT*i
@@ -25,11 +26,18 @@
 //    every slot of every pass) is hoisted out of the line loop into registers that are then spilled.
 #pragma once
 #include "fft_dev.hpp"
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <map>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 namespace pxs {
 
 static constexpr int RF_TWL = 128;         // two-level twiddles: W_n^e = lo[e mod 128] * hi[e / 128]
+static constexpr int rf_twlen(int count) { return RF_TWL + (count + RF_TWL - 1)/RF_TWL; }      // entries of the table for e < count
 
 // compile-time loop: f(std::integral_constant<int, I>) for I = A ... B-1
 template<int A, int B, class F> __device__ __forceinline__ void sfor(F&& f) {
@@ -77,6 +85,10 @@ template<class S, int P, int NT> struct RfPassT {
 	static constexpr int R = S::rad(P), s = S::stride(P), n = S::N, nb = n/R, K = (nb + NT - 1)/NT, slots = K*R;
 	static constexpr bool twiddled = s < nb;
 };
+// the most register slots a pass of sequence S takes
+template<class S, int NT, int P = 0> constexpr int rf_slots() {
+	if constexpr (P >= S::NP) return 0; else return std::max(RfPassT<S, P, NT>::slots, rf_slots<S, NT, P + 1>());
+}
 
 // R-point butterfly on a local array; output j is left in position slot(j) (the composite radices of fft_dev.hpp permute)
 template<int R> struct RfB;
@@ -145,20 +157,6 @@ PXS_RFLEAN(3, 2) PXS_RFLEAN(4, 2) PXS_RFLEAN(3, 3) PXS_RFLEAN(5, 2) PXS_RFLEAN(4
 
 template<int NT, int PMAX> struct RegFft {
 	using Regs = double2 (&)[PMAX];
-	// LDS word of line index i: the index itself.  Measured on the C4 configuration (tools/tl_lab.sh, shader clocks per line): no padding
-	// 265 000, one padding word per 16 -- the first form -- 296 000, the words of each block of 16 rotated by the block's number 292 000.
-	// A bank model (ds_write_b64: 16 lanes x 16 banks, ds_read_b64: 32 x 32) gives the plain layout 3x the conflict-free write cycles and
-	// the padded ones 1.25x, but with the plain layout every LDS address of a phase is one base register plus a compile-time offset
-	// (base + s*j for the writes of a butterfly, tid + constant for the reads), and the address arithmetic of the other two -- ten integer
-	// operations per point and exchange -- costs more than the conflicts.
-#if defined(PXS_LAB_TL_PAD16)      /* lab builds: the other two layouts (the line area is sized for n + 32 words: pad16 on small lines only) */
-	static __device__ __forceinline__ int pad(int i) { return i + (i >> 4); }
-#elif defined(PXS_LAB_TL_ROT16)
-	static __device__ __forceinline__ int pad(int i) { return (i & ~15) | ((i + (i >> 4)) & 15); }
-#else
-	static __device__ __forceinline__ int pad(int i) { return i; }
-#endif
-
 	// read pattern of pass PS: slot c = i*R + k holds x[tid + NT*i + nb*k] (threads with tid + NT*i >= nb: no element; they get f(0)).
 	// Every slot of the pass is overwritten for every lane, so that the compiler sees the old contents die.
 	template<class PS, class F> static __device__ __forceinline__ void fill(Regs v, int tid, F&& f) {
@@ -177,7 +175,7 @@ template<int NT, int PMAX> struct RegFft {
 		sfor<0, PS::slots>([&](auto C) RF_INL {
 			constexpr int c = RF_IDX(C), i = c/PS::R, k = c % PS::R;
 			const bool ok = (i + 1)*NT <= PS::nb || tid < PS::nb - NT*i;
-			const double x = line[pad(ok ? tid + (NT*i + PS::nb*k) : 0)];
+			const double x = line[ok ? tid + (NT*i + PS::nb*k) : 0];
 			if (COMP) v[c].y = x; else v[c].x = x;
 			RF_FENCE_SLOT(c);
 		});
@@ -190,7 +188,7 @@ template<int NT, int PMAX> struct RegFft {
 			const int b = tid + NT*i;
 			if ((i + 1)*NT <= PS::nb || b < PS::nb) {
 				const int base = PS::R*b - (PS::R - 1)*(b % PS::s);
-				sfor<0, PS::R>([&](auto J) RF_INL { constexpr int j = RF_IDX(J); line[pad(base + PS::s*j)] = COMP ? v[i*PS::R + j].y : v[i*PS::R + j].x; });
+				sfor<0, PS::R>([&](auto J) RF_INL { constexpr int j = RF_IDX(J); line[base + PS::s*j] = COMP ? v[i*PS::R + j].y : v[i*PS::R + j].x; });
 			}
 		});
 	}
@@ -202,16 +200,13 @@ template<int NT, int PMAX> struct RegFft {
 			const int b = tid + NT*i;
 			if ((i + 1)*NT <= PS::nb || b < PS::nb) {
 				const int base = PS::R*b - (PS::R - 1)*(b % PS::s);
-				sfor<0, PS::R>([&](auto J) RF_INL { constexpr int j = RF_IDX(J); line[pad(base + PS::s*j)] = v[i*PS::R + j]; });
+				sfor<0, PS::R>([&](auto J) RF_INL { constexpr int j = RF_IDX(J); line[base + PS::s*j] = v[i*PS::R + j]; });
 			}
 		});
 	}
 	// the butterflies of a pass and their Stockham twiddles (tw: this length's two-level table in the LDS)
 	template<class PS> static __device__ __forceinline__ void compute(Regs v, int tid, const double2* tw) {
 		constexpr int R = PS::R;
-#ifdef PXS_LAB_TL_NOCOMP      /* lab builds: timing without the butterflies (wrong results) */
-		return;
-#endif
 		RF_OPAQUE(tid);
 		sfor<0, PS::K>([&](auto I) RF_INL {
 			constexpr int i = RF_IDX(I);
@@ -259,6 +254,7 @@ template<int NT, int PMAX> struct RegFft {
 			constexpr int c = RF_IDX(C), i = c/PS::R, j = c % PS::R;
 			const int b = min(tid + NT*i, PS::nb - 1);
 			v[c] = f(v[c], b + PS::nb*j);
+			RF_PIN2(v[c]);      // (a value of its own, as between two stages of the chain: a product fused into the adds of the next butterfly rounds differently)
 			RF_FENCE_SLOT(c);
 		});
 	}
@@ -271,9 +267,6 @@ template<int NT, int PMAX> struct RegFft {
 	// maps of the row layout cost the boundary steps more than the passes gained: 305 000 clocks per line against 272 000.
 	// tools/xchg_probe2.hip keeps the measurement.)
 	template<class PP, class PN, bool SYNC = true> static __device__ __forceinline__ void exchange(Regs v, int tid, double* line) {
-#ifdef PXS_LAB_TL_NOXCHG      /* lab builds: timing without the LDS exchanges between the passes (wrong results) */
-		return;
-#endif
 		if (SYNC) RF_BARRIER(); else RF_WAVE_SYNC();
 		write_comp<PP, 0>(v, tid, line);
 		if (SYNC) RF_BARRIER(); else RF_WAVE_SYNC();
@@ -295,5 +288,51 @@ template<int NT, int PMAX> struct RegFft {
 		});
 	}
 };
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side shared by the line engines: twiddle tables, grid, launch
+// ---------------------------------------------------------------------------------------------------------------
+// two-level table at t[off]: lo[l] = W_n^{mult l}, l < 128, then hi[h] = W_n^{128 mult h}, 128 h < count
+inline void rf_fill_tw(std::vector<double2>& t, int off, long n, long mult, long count) {
+	const long double tpi = 6.283185307179586476925286766559L;
+	auto w = [&](long e) { const long double ang = tpi*(long double)((mult*e) % n)/(long double)n; return make_double2((double)cosl(ang), (double)(-sinl(ang))); };
+	for (int l = 0; l < RF_TWL; l++) t[off + l] = w(l);
+	for (long h = 0; h*RF_TWL < count; h++) t[off + RF_TWL + h] = w(h*RF_TWL);
+}
+struct RfHost {      // per process, under one lock: CUs per device; twiddle tables per device and identity (the lengths and the shift they are made of)
+	std::mutex mu; std::map<int, int> ncu; std::map<std::pair<int, std::array<long, 4>>, DevBuf> tw;
+};
+inline RfHost& rf_host() { static RfHost h; return h; }
+// the current device's copy of the table `id` of ntw entries, filled by fill(t) on first use
+template<class F> const double2* rf_twiddles(const std::array<long, 4>& id, int ntw, F&& fill) {
+	int dev = 0; PXS_HIP(hipGetDevice(&dev));
+	RfHost& h = rf_host(); std::lock_guard<std::mutex> g(h.mu);
+	DevBuf& b = h.tw[std::make_pair(dev, id)];
+	if (!b.p) { std::vector<double2> t((size_t)ntw, make_double2(1, 0)); fill(t); b = upload(t); }
+	return b.as<double2>();
+}
+// workgroups of a kernel that loops over ntask lines: what the current device holds at once (a CU: 2048 threads, 160 KB of LDS), one per task at most
+inline long rf_grid(long ntask, int nt, size_t lds) {
+	int dev = 0; PXS_HIP(hipGetDevice(&dev));
+	RfHost& h = rf_host(); std::lock_guard<std::mutex> g(h.mu);
+	int& ncu = h.ncu[dev];
+	if (ncu == 0) {
+#ifdef PXS_HOST_SIM
+		ncu = 2;
+#else
+		hipDeviceProp_t pr; PXS_HIP(hipGetDeviceProperties(&pr, dev)); ncu = std::max(1, pr.multiProcessorCount);
+#endif
+	}
+	const long per_cu = std::max<long>(1, std::min<long>(2048/nt, (long)(160*1024)/(long)lds));
+	return std::min<long>(ntask, (long)ncu*per_cu);
+}
+// launch of the kernel of configuration CFG (CFG::NT threads, CFG::lds bytes of dynamic LDS: past the default limit, raised on the first launch)
+template<class CFG, class Args> void rf_launch(void (*kernel)(Args), const Args& a, long nwg, hipStream_t st) {
+	static_assert(CFG::lds <= 160*1024 - 256, "the line does not fit the LDS");
+	static const bool once = [&] { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024); return true; }();
+	(void)once;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(CFG::NT), CFG::lds, st, a);
+	PXS_HIP(hipGetLastError());
+}
 
 } // namespace pxs

@@ -13,11 +13,6 @@
 #include "fftchain.hpp"
 #include "chain_dev.hpp"
 #include "regfft_dev.hpp"
-#include <algorithm>
-#include <map>
-#include <utility>
-#include <memory>
-#include <vector>
 
 namespace pxs {
 
@@ -27,15 +22,11 @@ struct RingArgs {
 	MapAddr m;
 };
 
-static constexpr int rl_twlen(int count) { return RF_TWL + (count + RF_TWL - 1)/RF_TWL; }
-template<class S, int NT, int P = 0> constexpr int rl_slots() {
-	if constexpr (P >= S::NP) return 0; else { constexpr int a = RfPassT<S, P, NT>::slots, b = rl_slots<S, NT, P + 1>(); return a > b ? a : b; }
-}
 template<int NT_, int MMAX_CAP, class S_> struct RingCfg {
 	static constexpr int NT = NT_, X = S_::N, MCAP = MMAX_CAP;      // ring length; the rows of h hold at most MCAP + 1 coefficients
 	using S = S_;
-	static constexpr int PMAX = rl_slots<S, NT>();
-	static constexpr int ntw = rl_twlen(X);
+	static constexpr int PMAX = rf_slots<S, NT>();
+	static constexpr int ntw = rf_twlen(X);
 	static constexpr int words = (X > 4*(MCAP + 1) ? X : 4*(MCAP + 1)) + 16;      // doubles: one component of the line, or both rows of h (complex)
 	static constexpr size_t lds = sizeof(double2)*ntw + sizeof(double)*words + 16;
 	static_assert(2*MCAP < X, "the Hermitian image of the coefficients overlaps them");
@@ -108,17 +99,9 @@ template<class CFG> __global__ PXS_RL_BOUNDS void ring_line_kernel(const RingArg
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct RingEntry { long X; int mcap, nt, ntw; size_t lds; void (*launch)(const RingArgs&, size_t, long, hipStream_t); };
-template<class CFG> static void launch_ring(const RingArgs& a, size_t lds, long nwg, hipStream_t st) {
-#ifndef PXS_HOST_SIM
-	static const bool once = [] { (void)hipFuncSetAttribute((const void*)ring_line_kernel<CFG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024); return true; }();
-	(void)once;
-#endif
-	hipLaunchKernelGGL((ring_line_kernel<CFG>), dim3((unsigned)nwg), dim3(CFG::NT), lds, st, a);
-}
+struct RingEntry { long X; int mcap, nt, ntw; size_t lds; void (*launch)(const RingArgs&, long nwg, hipStream_t); };
 template<class CFG> static RingEntry ring_entry() {
-	static_assert(CFG::lds <= 160*1024 - 256, "the ring pair does not fit the LDS");
-	return RingEntry{CFG::X, CFG::MCAP, CFG::NT, CFG::ntw, CFG::lds, &launch_ring<CFG>};
+	return RingEntry{CFG::X, CFG::MCAP, CFG::NT, CFG::ntw, CFG::lds, [](const RingArgs& a, long nwg, hipStream_t st) { rf_launch<CFG>(ring_line_kernel<CFG>, a, nwg, st); }};
 }
 // Ring lengths compiled in (a plan takes the kernel when nphi matches and mmax is within the configuration's cap):
 //   10 800 pixels per ring (BASELINE C2 / C4, mmax <= 4000): 16 15 15 3 on 1024 threads, <= 16 points per thread
@@ -130,10 +113,6 @@ using RingC4 = RingCfg<1024, 4000, RfSeq<16, 15, 15, 3>>;
 static const RingEntry RING_CONFIGS[] = { ring_entry<RingC4>() };
 #endif
 
-struct RingLineState { std::map<std::pair<int, long>, DevBuf> tw; std::map<int, int> ncu; };      // twiddle tables and CU counts per (device, ring length)
-static std::mutex g_ring_mu;
-static RingLineState& ring_state() { static RingLineState s; return s; }
-
 // PXS_RING_LINE=0 keeps the stage chain (read per call: the tests compare the two paths)
 static bool ring_line_enabled() { const char* e = getenv("PXS_RING_LINE"); return e ? atoi(e) != 0 : true; }
 
@@ -144,53 +123,20 @@ static const RingEntry* ring_find(long nphi, int mmax) {
 }
 bool FftChain::line_h2map_takes(long nphi, int mmax) { return ring_find(nphi, mmax) != nullptr; }
 
-static void ring_tables(const RingEntry* e, const double2*& tw, int& ncu);
-
 bool FftChain::line_h2map(hipStream_t st, const double2* h, long ldh, const MapDesc& m, int nc, int mmax, long hcomp)
 {
 	const RingEntry* e = ring_find(m.nphi, mmax);
 	if (!e) return false;
-	const double2* tw; int ncu; ring_tables(e, tw, ncu);
 	const long npair = (m.nring + 1)/2;
 	RingArgs a; memset(&a, 0, sizeof(a));
-	a.tw = tw; a.ntw = e->ntw; a.h = h; a.ldh = ldh; a.hcomp = hcomp > 0 ? hcomp : m.nring; a.mmax = mmax; a.npair = (int)npair; a.nring = m.nring;
+	a.tw = rf_twiddles({e->X, 0, 0, 0}, e->ntw, [&](std::vector<double2>& t) { rf_fill_tw(t, 0, e->X, 1, e->X); });      // (the identities of the theta engine's tables have N_cc > 0 in the third place)
+	a.ntw = e->ntw; a.h = h; a.ldh = ldh; a.hcomp = hcomp > 0 ? hcomp : m.nring; a.mmax = mmax; a.npair = (int)npair; a.nring = m.nring;
 	const long ntask = (long)nc*npair;
 	PXS_REQUIRE(ntask < (1L << 31), "internal: ring line grid too large");
 	a.ntask = (int)ntask; a.dnp = make_fastdiv((uint32_t)npair);
 	a.m = map_addr(m);
-	const long per_cu = std::max<long>(1, std::min<long>(2048/e->nt, (long)(160*1024)/(long)e->lds));
-	e->launch(a, e->lds, std::min<long>(ntask, (long)ncu*per_cu), st);
-	PXS_HIP(hipGetLastError());
+	e->launch(a, rf_grid(ntask, e->nt, e->lds), st);
 	return true;
-}
-
-static void ring_tables(const RingEntry* e, const double2*& tw, int& ncu)
-{
-	{	std::lock_guard<std::mutex> g(g_ring_mu);
-		RingLineState& s = ring_state();
-		int dev = 0;
-#ifndef PXS_HOST_SIM
-		PXS_HIP(hipGetDevice(&dev));
-#endif
-		DevBuf& b = s.tw[std::make_pair(dev, e->X)];
-		if (!b.p) {
-			std::vector<double2> t((size_t)e->ntw, make_double2(1, 0));
-			const long double tpi = 6.283185307179586476925286766559L;
-			for (int l = 0; l < RF_TWL; l++) { const long double ang = tpi*(long double)(l % e->X)/(long double)e->X; t[l] = make_double2((double)cosl(ang), (double)(-sinl(ang))); }
-			for (long hh = 0; hh*RF_TWL < e->X; hh++) { const long double ang = tpi*(long double)((hh*RF_TWL) % e->X)/(long double)e->X; t[RF_TWL + hh] = make_double2((double)cosl(ang), (double)(-sinl(ang))); }
-			b = upload(t);
-		}
-		tw = b.as<double2>();
-		int& n = s.ncu[dev];
-		if (n == 0) {
-#ifdef PXS_HOST_SIM
-			n = 2;
-#else
-			hipDeviceProp_t pr; PXS_HIP(hipGetDeviceProperties(&pr, dev)); n = std::max(1, pr.multiProcessorCount);
-#endif
-		}
-		ncu = n;
-	}
 }
 
 } // namespace pxs

@@ -136,6 +136,7 @@ void setup_resampling(pxs_plan* p) {
 			sg[i] = make_double2((double)(wr*(LDb)Mf/(2*PIl)), 0.0);
 		}
 		af.sigma = upload(sg);
+		{ std::vector<double> sh((size_t)nf); for (int i = 0; i < nf; i++) sh[i] = sg[i].x; af.sig_half = upload(sh); }      // sg[i] = sg[Mf - i], real
 		const double f = (double)ai.M/(double)Mf;       // the FFT normalisation 1/(N M) of the weights, for this M
 		std::vector<double2> wf(w), whf(w);
 		for (int j = 0; j < t.ncc; j++) { wf[j].x *= f; whf[j].x *= (j == 0 || j == t.ncc-1) ? f : 0.5*f; }
@@ -309,7 +310,7 @@ static void run_theta(pxs_plan* p, hipStream_t st, const Route& r, int nct, int 
 	c.map = (to_h ? p->hbuf : p->leg).as<double2>(); c.ldmap = to_h ? r.ld_h : r.ld_leg; c.nr = to_h ? r.nr_h : r.nr_th;
 	c.cc = p->leg2.as<double2>(); c.ldcc = r.ld_leg2; c.ncc = t.ncc;
 	c.ph = (r.theta == TH_FROM_CC ? t.ph_up : t.ph_shift).as<double2>();
-	if (mid) c.sigma = f.sigma.as<double2>();
+	if (mid) { c.sigma = f.sigma.as<double2>(); c.sig_half = f.sig_half.as<double>(); }
 	if (r.theta != TH_FROM_CC) c.wcc = (r.theta == TH_TO_CC ? f.wcc : r.theta == TH_TO_CC_ADJ ? f.whalf : t.wadj).as<double2>();
 	c.wring = wring;
 	if (to_h) { c.tab = p->phase.as<double2>(); c.scale = mid ? 2.0 : 1.0/(double)t.Ncc; }
@@ -529,7 +530,7 @@ static Route route_of(const pxs_plan* p, bool analysis, int spin, int mode, bool
 	const bool unfused = r.kind == R_VIA_CC_UNFUSED || r.kind == R_VIA_CC_UNFUSED_H || r.kind == R_UNFUSED;
 	r.batched = !unfused;
 	r.theta_fused = r.theta != TH_NONE && !unfused;
-	r.line = r.theta_fused && r.theta <= TH_FROM_CC_ADJ && FftChain::line_takes(r.form->tp, r.theta == TH_TO_CC);
+	r.line = r.theta_fused && r.theta <= TH_FROM_CC_ADJ && FftChain::line_takes(r.form->tp, r.theta == TH_TO_CC, r.form->sig_half.as<double>());
 	// the ring chain's scratch is reserved with the call (the unfused analysis leaves it to the chain's own launches, as it always did)
 	r.reserve_chain = p->chain_rings && r.kind != R_UNFUSED;
 	return r;

@@ -43,8 +43,9 @@ DevBuf ring_weight_table(const std::string& g, int n, int nphi);    // ... / nph
 inline bool self_mirrored(long r, int mir_c, long N) { const long t = 2*r + mir_c; return t == 0 || t == N || t == 2*N; }
 
 // one form of the interpolating analysis: the fine circle of M points, the pointwise table on it, the CC weights (whalf: halved off
-// the two pole rings, for the adjoint) and the fused theta chain that holds the circle (tp.ok) -- the unfused engine takes any M
-struct AnaForm { ThetaPlan tp; DevBuf sigma, wcc, whalf; long M = 0; bool fine = false; };
+// the two pole rings, for the adjoint) and the fused theta chain that holds the circle (tp.ok) -- the unfused engine takes any M.
+// sig_half: the fine-CC form's table is real and mirror-symmetric; its entries i <= M/2 as doubles, for the single-kernel engine
+struct AnaForm { ThetaPlan tp; DevBuf sigma, sig_half, wcc, whalf; long M = 0; bool fine = false; };
 // tables of the theta resampling between the map's grid (circle of N samples, mirror constant mir_c) and the CC grid (circle N_cc, ncc rings)
 struct ThetaTables {
 	long N = 0; int mir_c = 0; long Ncc = 0; int ncc = 0;

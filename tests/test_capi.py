@@ -60,7 +60,7 @@ def test_default_build_carries_no_lab_switches():
 	from pixell_amd import _build
 	blob = open(_build.build(), "rb").read()
 	for name in (b"PXS_CH_NOFFT", b"PXS_CH_NOTW", b"PXS_CH_NOPH", b"PXS_FFT_DEBUG_NOPASS", b"PXS_CHAIN_V2", b"PXS_CH2_", b"PXS_SYN_SHARE", b"chain2_kernel", b"leg_syn_s0b",
-			b"PXS_FFT_NT", b"PXS_FFT_ODDFIRST", b"PXS_FFT_ALIGN8", b"PXS_FFT_RADICES", b"PXS_FFT_COMP", b"PXS_FFT_PTS", b"PXS_FFT_LINEPAD", b"PXS_BLUESTEIN_MINPRIME"):
+			b"PXS_FFT_NT", b"PXS_FFT_ODDFIRST", b"PXS_FFT_ALIGN8", b"PXS_FFT_RADICES", b"PXS_FFT_COMP", b"PXS_FFT_PTS", b"PXS_FFT_LINEPAD", b"PXS_BLUESTEIN_MINPRIME", b"PXS_TL_"):
 		assert name not in blob, name
 
 def test_docs_agree_with_the_header():

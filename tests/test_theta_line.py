@@ -30,7 +30,7 @@ def run_pair(nt, nph, lmax, spin, nb, monkeypatch, seed=3, mmax=None):
 	assert np.abs(out["0"][0]).max() > 0 and np.abs(out["0"][1]).max() > 0
 
 @pytest.mark.hostsim
-@pytest.mark.parametrize("spin,nb,mmax", [(0, 1, 24), (1, 1, 24), (2, 1, 250), (0, 3, 250)])      # (mmax = 24: 25 columns, the last pair has one member; spin 1: the odd column first)
+@pytest.mark.parametrize("spin,nb,mmax", [(0, 1, 24), (1, 1, 24), (2, 1, 250), (0, 3, 250), (2, 1, 24)])      # (mmax = 24: 25 columns, the last pair has one member; spin 1: the odd column first; spin 2 with 25 columns: two components of 13 tasks each)
 def test_line_engine_hostsim(monkeypatch, spin, nb, mmax):
 	assert _lib.is_hostsim()
 	run_pair(360, 720, 250, spin, nb, monkeypatch, mmax=mmax)
@@ -40,6 +40,54 @@ def test_line_engine_hostsim(monkeypatch, spin, nb, mmax):
 def test_line_engine_c2_size_gpu(monkeypatch, spin, nb):
 	"""BASELINE C2 / C4 grid: 5400 x 10800, lmax 4000 (N = 10 800, N_cc = 8064, M = 16 128)"""
 	run_pair(5400, 10800, 4000, spin, nb, monkeypatch)
+
+def check_interpolant_keeps_the_chain(nt, nph, lmax, monkeypatch, run):
+	"""The engine's middle circle is always M = 2 N_cc, the fine-CC form: the interpolant form (M >= N + 2 lmax + 2) of a compiled
+	grid matches no configuration and runs the stage chain, whatever PXS_THETA_LINE says."""
+	ms = sht.tri_mstart(lmax, lmax); nalm = int(ms[-1]) + lmax + 1
+	monkeypatch.setenv("PXS_THETA_LINE", "1")
+	plan = sht.grid_plan("F1", nt, nph, 0.1, (False, False), lmax, lmax, ms, 1)
+	plan.set_option("analysis", sht.ANALYSIS_MODES["interpolant"])
+	assert plan.query("analysis_form") == 0 and plan.query("theta_line") == 0
+	plan.set_option("analysis", sht.ANALYSIS_MODES["ducc0"])
+	assert plan.query("analysis_form") == 2 and plan.query("theta_line") == 1
+	if not run: return
+	noise = np.random.default_rng(5).standard_normal((1, nt, nph))
+	out = {}
+	for line in ("1", "0"):
+		monkeypatch.setenv("PXS_THETA_LINE", line)
+		out[line] = np.zeros((1, nalm), complex)
+		sht.analysis_2d(alm=out[line], map=noise, spin=0, lmax=lmax, mmax=lmax, geometry="F1", phi0=0.1, mstart=ms, analysis="interpolant")
+	assert np.abs(out["0"]).max() > 0 and np.array_equal(out["1"], out["0"])
+
+@pytest.mark.hostsim
+def test_interpolant_form_keeps_the_chain_hostsim(monkeypatch): check_interpolant_keeps_the_chain(360, 720, 250, monkeypatch, run=True)
+@pytest.mark.gpu
+def test_interpolant_form_keeps_the_chain_gpu(monkeypatch): check_interpolant_keeps_the_chain(5400, 10800, 4000, monkeypatch, run=False)      # (the plan and its queries only)
+
+def check_second_plan_same_circle(nt, nph, lmax, monkeypatch):
+	"""a plan is dropped with its device memory and built again: the engine's tables belong to the plan, so the second plan's call
+	gives the first one's alm, bit for bit, and both agree with the stage chain.  (The plans are made with ordered Legendre sums: in
+	arrival order, the default, an analysis repeats to ~1e-14 only, whatever its theta stage.)"""
+	monkeypatch.setenv("PXS_DETERMINISTIC", "1")
+	ms = sht.tri_mstart(lmax, lmax); nalm = int(ms[-1]) + lmax + 1
+	kw = dict(spin=0, lmax=lmax, mmax=lmax, geometry="F1", phi0=0.1, mstart=ms)
+	noise = np.random.default_rng(6).standard_normal((1, nt, nph))
+	out = []
+	for line in ("1", "1", "0"):
+		monkeypatch.setenv("PXS_THETA_LINE", line)
+		sht.clear_plans(release=True)
+		assert sht.grid_plan("F1", nt, nph, 0.1, (False, False), lmax, lmax, ms, 1).query("theta_line") == int(line)
+		out.append(np.zeros((1, nalm), complex))
+		sht.analysis_2d(alm=out[-1], map=noise, **kw)
+	sht.clear_plans()      # (the cache keeps no plan made under this test's environment)
+	assert np.abs(out[2]).max() > 0 and np.array_equal(out[0], out[1])
+	assert relrms(out[1], out[2]) < 1e-13, relrms(out[1], out[2])
+
+@pytest.mark.hostsim
+def test_line_engine_second_plan_same_circle_hostsim(monkeypatch): check_second_plan_same_circle(360, 720, 250, monkeypatch)
+@pytest.mark.gpu
+def test_line_engine_second_plan_same_circle_gpu(monkeypatch): check_second_plan_same_circle(5400, 10800, 4000, monkeypatch)
 
 def run_ring_pair(nt, nph, lmax, spin, monkeypatch, dtype=np.float64, flip=(False, False), mmax=None):
 	"""synthesis_2d with the single-kernel ring FFT (ringline.hip) and with the two-stage chain: the same map"""
