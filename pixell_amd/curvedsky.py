@@ -136,6 +136,35 @@ def _contig(x):
 	if A.is_tensor(x): return x if x.is_contiguous() else x.contiguous()
 	return x
 
+def _copy(x): return None if x is None else (x.clone() if A.is_tensor(x) else x.copy())
+
+def _copy_out(alm, map, copy, alm_is_out):
+	"""(alm, map) with the one the call overwrites replaced by a copy of it when `copy` (copy=True of every transform)"""
+	if not copy: return alm, map
+	return (_copy(alm), map) if alm_is_out else (alm, _copy(map))
+
+def _layout_kwargs(ainfo):
+	"""where the library finds element (l, m): the alm layout keywords of every sht call"""
+	return dict(lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride)
+
+def _check_shapes(alm_full, map_full, deriv, pixdims=2, exc=AssertionError, text=None):
+	"""alm [..., ncomp, nelem] and map [..., ncomp, pixels] (deriv: alm [..., nelem], map [..., 2, pixels]) must agree on the leading
+	dimensions; raises exc, with `text` for either failure where the caller has one of its own"""
+	if deriv and map_full.shape[-pixdims-1] != 2:
+		raise exc(text or "map must have shape [...,2,%s] when deriv is True" % ("nloc" if pixdims == 1 else "ny,nx"))
+	if tuple(map_full.shape[:map_full.ndim-pixdims-bool(deriv)]) != tuple(alm_full.shape[:-1]):
+		raise exc(text or "map and alm must agree on pre-dimensions")
+
+def _weights_like(weights, like):
+	"""pixel weights where `like` lives (a scalar stays a scalar)"""
+	if np.isscalar(weights) or not A.is_tensor(like): return weights
+	return A.torch().as_tensor(np.asarray(weights), device=like.device)
+
+def _dec_sign(like, pixdims):
+	"""[-1, 1] along the component axis of a gradient map [2, pixels...]: d/dtheta <-> d/ddec"""
+	f = np.array([-1.0, 1.0]).reshape((2,)+(1,)*pixdims)
+	return A.torch().as_tensor(f, dtype=like.dtype, device=like.device) if A.is_tensor(like) else f.astype(like.dtype)
+
 def _batched_jobs(spin, alm_full, map_full):
 	"""[(spin, alm [nb, nca, nelem], map [nb, ncm, ny, nx])]: the reference loops over the pre-dimensions and the spin groups
 	(curvedsky.py:910-924, 1038-1046) with one ducc call each; here every spin group is ONE library call over all pre-dimension
@@ -161,20 +190,21 @@ def _as_view(x, shape):
 # ---------------------------------------------------------------------------------------
 # public API
 # ---------------------------------------------------------------------------------------
+def _by_method(map, method, pix_tol, funcs):
+	"""(funcs[method], minfo) for the map's geometry; "auto" picks the method of the geometry"""
+	minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
+	if method == "auto": method = get_method(map.shape, map.wcs, minfo=minfo)
+	if method in funcs: return funcs[method], minfo
+	if method == "general":
+		raise NotImplementedError("method 'general' (non-cylindrical pixelisations, ducc synthesis_general) is outside the accelerated path")
+	raise ValueError("Unrecognized alm2map method '%s'" % str(method))
+
 def alm2map(alm, map, spin=[0, 2], deriv=False, adjoint=False, copy=False, method="auto", ainfo=None,
 		verbose=False, nthread=None, epsilon=1e-6, pix_tol=1e-6, locinfo=None, tweak=False):
 	"""Spherical harmonics synthesis (curvedsky.alm2map, curvedsky.py:83-164).  See the reference
 	docstring for the argument meaning; `map` is overwritten unless copy=True and returned."""
-	minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
-	if method == "auto": method = get_method(map.shape, map.wcs, minfo=minfo)
-	if   method == "2d":
-		return alm2map_2d(alm, map, ainfo=ainfo, minfo=minfo, spin=spin, deriv=deriv, copy=copy, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol)
-	elif method == "cyl":
-		return alm2map_cyl(alm, map, ainfo=ainfo, minfo=minfo, spin=spin, deriv=deriv, copy=copy, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol)
-	elif method == "general":
-		raise NotImplementedError("method 'general' (non-cylindrical pixelisations, ducc synthesis_general) is outside the accelerated path")
-	else:
-		raise ValueError("Unrecognized alm2map method '%s'" % str(method))
+	func, minfo = _by_method(map, method, pix_tol, {"2d": alm2map_2d, "cyl": alm2map_cyl})
+	return func(alm, map, ainfo=ainfo, minfo=minfo, spin=spin, deriv=deriv, copy=copy, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol)
 
 def alm2map_adjoint(map, alm=None, spin=[0, 2], deriv=False, copy=False, method="auto", ainfo=None, verbose=False, nthread=None, epsilon=None, pix_tol=1e-6, locinfo=None):
 	return alm2map(alm, map, spin=spin, deriv=deriv, adjoint=True, copy=copy, method=method, ainfo=ainfo, verbose=verbose, nthread=nthread, epsilon=epsilon, pix_tol=pix_tol, locinfo=locinfo)
@@ -187,29 +217,84 @@ def map2alm(map, alm=None, lmax=None, spin=[0, 2], deriv=False, adjoint=False, c
 	curvedsky.py:852-861) on full grids with ny >= 2 lmax + 2: identical alm for band-limited maps (see pixell_amd.sht.analysis_2d).
 	weights_order (ours, method "cyl" only): "reference" (default) applies weights to rows exactly as the reference does, including its
 	mirrored pixel areas for maps stored north-to-south off a named grid; "map": weight i belongs to map row i (see map2alm_cyl)."""
-	minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
-	if method == "auto": method = get_method(map.shape, map.wcs, minfo=minfo)
-	if   method == "2d":
-		return map2alm_2d(map, alm, ainfo=ainfo, minfo=minfo, lmax=lmax, spin=spin, deriv=deriv, copy=copy, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol, analysis=analysis)
-	elif method == "cyl":
-		return map2alm_cyl(map, alm, ainfo=ainfo, minfo=minfo, lmax=lmax, spin=spin, deriv=deriv, copy=copy, verbose=verbose, adjoint=adjoint, nthread=nthread, niter=niter, pix_tol=pix_tol, weights=weights, weights_order=weights_order)
-	elif method == "general":
-		raise NotImplementedError("method 'general' (non-cylindrical pixelisations, ducc synthesis_general) is outside the accelerated path")
-	else:
-		raise ValueError("Unrecognized alm2map method '%s'" % str(method))
+	func, minfo = _by_method(map, method, pix_tol, {"2d": map2alm_2d, "cyl": map2alm_cyl})
+	more = dict(analysis=analysis) if func is map2alm_2d else dict(niter=niter, weights=weights, weights_order=weights_order)
+	return func(map, alm, ainfo=ainfo, minfo=minfo, lmax=lmax, spin=spin, deriv=deriv, copy=copy, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol, **more)
 
 def map2alm_adjoint(alm, map, lmax=None, spin=[0, 2], deriv=False, copy=False, method="auto", ainfo=None, verbose=False, nthread=None, niter=0, epsilon=1e-6, pix_tol=1e-6, weights=None, locinfo=None, analysis=None):
 	"""curvedsky.map2alm_adjoint (curvedsky.py:304-310); analysis (ours): the form of map2alm whose transpose this is"""
 	return map2alm(map=map, alm=alm, lmax=lmax, spin=spin, deriv=deriv, adjoint=True, copy=copy, method=method, ainfo=ainfo, verbose=verbose, nthread=nthread, niter=niter, epsilon=epsilon, pix_tol=pix_tol, weights=weights, locinfo=locinfo, analysis=analysis)
 
-# ---- 2d ---------------------------------------------------------------------------------
-def _check_shapes(alm_full, map_full, deriv):
-	if deriv:
-		assert map_full.ndim >= 3 and map_full.shape[-3] == 2, "map must have shape [...,2,ny,nx] when deriv is True"
-		assert tuple(map_full.shape[:-3]) == tuple(alm_full.shape[:-1]), "map and alm must agree on pre-dimensions"
-	else:
-		assert tuple(map_full.shape[:-2]) == tuple(alm_full.shape[:-1]), "map and alm must agree on pre-dimensions"
+# ---- transform families: what differs between the 2d DERIV1 path, cyl rings, healpix rings and points, and the loops they share ----
+class _Family:
+	"""One kind of pixelisation as the two drivers below see it.
+	syn, adj: the forward and adjoint sht function; kw: their fixed keywords; pixdims: the pixel axes of a map.
+	to_lib: a map slice [nc, pixels...] as the library takes it (the solver shapes results back to the slice).
+	contig_read: a map slice that the library reads is made contiguous first.
+	zeroed_map: the solver's synthesis is handed a zeroed map of the slice's size instead of allocating one (the rings of a theta
+	window do not cover the map).
+	signed_adjoint: an adjoint DERIV1 call applies the declination sign to a COPY of its input.  Points do: their adjoint is the exact
+	transpose of the forward call, which signs its output, and leaves the input alone.  The 2d, cyl and healpix adjoints apply no
+	sign.  The reference signs the caller's map after the call; the difference is deliberate."""
+	def __init__(self, syn, adj, kw, pixdims, to_lib=lambda m: m, contig_read=False, zeroed_map=False, signed_adjoint=False):
+		self.syn, self.adj, self.kw, self.pixdims, self.to_lib = syn, adj, kw, pixdims, to_lib
+		self.contig_read, self.zeroed_map, self.signed_adjoint = contig_read, zeroed_map, signed_adjoint
 
+def _groups(pre, spin, ncomp, deriv):
+	"""(spin, mode, alm index, map index) of every library call over the pre-dimensions `pre`, as the reference loops
+	(curvedsky.py:910-924): with deriv one DERIV1 / spin-1 call per entry (the alm gains its component axis), else its spin groups"""
+	for I in nditer(pre):
+		if deriv: yield 1, "DERIV1", I+(None,), I
+		else:
+			for s, j1, j2 in enmap.spin_helper(spin, ncomp):
+				yield int(s), "STANDARD", I+(slice(j1, j2),), I+(slice(j1, j2),)
+
+def _full_groups(fam, alm_full, map_full, spin, deriv):
+	return _groups(map_full.shape[:map_full.ndim-fam.pixdims-1], spin, None if deriv else alm_full.shape[-2], deriv)
+
+def _direct(fam, alm_full, map_full, spin, deriv, adjoint):
+	"""alm -> map (adjoint: map -> alm), one library call per group, written into map_full (alm_full)"""
+	func = fam.adj if adjoint else fam.syn
+	for s, mode, ai, mi in _full_groups(fam, alm_full, map_full, spin, deriv):
+		v = alm_full[ai]; a = _contig(v); m = map_full[mi]
+		if adjoint and deriv and fam.signed_adjoint: m = m*_dec_sign(m, fam.pixdims)
+		if adjoint and fam.contig_read: m = _contig(m)
+		func(alm=a, map=fam.to_lib(m), spin=s, mode=mode, **fam.kw)
+		if adjoint:
+			if a is not v: v[...] = a             # (the library wrote a contiguous staging copy of a strided alm slice)
+		elif deriv: map_full[mi+(0,)] *= -1       # theta derivative -> dec derivative (curvedsky.py:919)
+
+def jacobi_inverse(forward, approx_backward, y, niter=0):
+	"""Solve forward(x) = y given an approximate inverse B: x_0 = B y, x_{k+1} = x_k + B (y - forward(x_k))
+	(Jacobi / Richardson refinement; what curvedsky.jacobi_inverse, curvedsky.py:1122-1136, does around the ring transforms)"""
+	x = approx_backward(y)
+	for _ in range(int(niter)):
+		x = x+approx_backward(y-forward(x))
+	return x
+
+def _operators(fam, s, mode, like, weights):
+	"""Y, YT, YTW, WY of one group: synthesis onto a map like `like`, its transpose, and both with the pixel weights"""
+	kw = dict(fam.kw, spin=s, mode=mode); shp = tuple(like.shape)
+	def Y(a):   return fam.syn(alm=_contig(a), map=A.zeros(shp, A.np_dtype(like), like) if fam.zeroed_map else None, **kw).reshape(shp)
+	def YT(m):  return fam.adj(map=fam.to_lib(_contig(m)), **kw)
+	def YTW(m): return YT(m*weights)
+	def WY(a):  return Y(a)*weights
+	return Y, YT, YTW, WY
+
+def _solve(fam, alm_full, map_full, spin, deriv, adjoint, niter, weights):
+	"""map -> alm by weighted adjoint synthesis + `niter` Jacobi refinements (curvedsky.py:1067-1084), written into alm_full;
+	adjoint: the transpose of that operator, alm -> map_full.  deriv: gradient maps [ddec, dra] through the DERIV1 transforms."""
+	for s, mode, ai, mi in _full_groups(fam, alm_full, map_full, spin, deriv):
+		m = map_full[mi]
+		Y, YT, YTW, WY = _operators(fam, s, mode, m, weights)
+		if adjoint:
+			res = jacobi_inverse(YT, WY, _contig(alm_full[ai]), niter=niter)
+			map_full[mi] = res*_dec_sign(m, fam.pixdims) if deriv else res
+		else:
+			alm_full[ai] = jacobi_inverse(Y, YTW, m*_dec_sign(m, fam.pixdims) if deriv else m, niter=niter)
+
+# ---- 2d ---------------------------------------------------------------------------------
+_NO_PADS = ((0, 0), (0, 0))
 def _native_pads(minfo, use_y):
 	"""((y_before, y_after), (x_before, x_after)) in the map's own pixel order.  minfo.ypad/xpad are in
 	ducc orientation, i.e. after the flips of map2buffer (curvedsky.py:1384-1403)."""
@@ -231,38 +316,32 @@ def _padded_like(map, pads, fill):
 	if fill: buf[..., y0:y0+map.shape[-2], x0:x0+map.shape[-1]] = mdata
 	return (enmap.dmap(buf, w) if isinstance(map, enmap.dmap) else enmap.ndmap(buf, w))
 
-def _crop_into(map, pmap, pads):
+def _on_padded(map, pads, map_is_input, run):
+	"""run(pmap) on the map padded to its full grid / full rings, as the reference does (curvedsky.py:766-772, 786-792, 866-871):
+	an input map is copied into the padding, an output map is cropped back out of it and returned"""
 	(y0, y1), (x0, x1) = pads
+	pmap = _padded_like(map, pads, fill=map_is_input)
+	res = run(pmap)
+	if map_is_input: return res
 	_mdata(map)[...] = _mdata(pmap)[..., y0:y0+map.shape[-2], x0:x0+map.shape[-1]]
+	return map
 
 def alm2map_2d(alm, map, ainfo=None, minfo=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, pix_tol=1e-6):
 	"""curvedsky.alm2map_2d + alm2map_raw_2d (curvedsky.py:756-774, 900-926)"""
-	if copy:
-		if adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
-		elif not adjoint: map = map.copy()
+	alm, map = _copy_out(alm, map, copy, alm_is_out=adjoint)
 	mdata = _mdata(map)
-	if adjoint: alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=False, like=mdata)
-	else:       alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=True, like=mdata)
+	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=not adjoint, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	pads = _native_pads(minfo, use_y=True)
-	if pads != ((0, 0), (0, 0)):
-		# pad to the full grid as the reference does (curvedsky.py:766-772); the padded geometry is case "2d"
-		pmap = _padded_like(map, pads, fill=adjoint)
-		res = alm2map_2d(alm, pmap, ainfo=ainfo, spin=spin, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol)
-		if adjoint: return res
-		_crop_into(map, pmap, pads)
-		return map
+	if pads != _NO_PADS:      # (the padded geometry is case "2d")
+		return _on_padded(map, pads, adjoint, lambda pmap: alm2map_2d(alm, pmap, ainfo=ainfo, spin=spin, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol))
 	alm_full = _atleast(alm, 2 if deriv else 3)
 	map_full = _atleast(mdata, 4)
 	_check_shapes(alm_full, map_full, deriv)
 	func = sht.adjoint_synthesis_2d if adjoint else sht.synthesis_2d
-	kwargs = dict(phi0=minfo.phi0, lmax=ainfo.lmax, mmax=ainfo.mmax, geometry=minfo.ducc_geo.name, mstart=ainfo.mstart, lstride=ainfo.stride, flip=minfo.flip)
+	kwargs = dict(_layout_kwargs(ainfo), phi0=minfo.phi0, geometry=minfo.ducc_geo.name, flip=minfo.flip)
 	if deriv:
-		for I in nditer(map_full.shape[:-3]):
-			a = _contig(alm_full[I][None]); m = map_full[I]
-			func(alm=a, map=m, mode="DERIV1", spin=1, **kwargs)
-			if adjoint: alm_full[I] = a[0]
-			else: map_full[I+(0,)] *= -1       # theta derivative -> dec derivative (curvedsky.py:919)
+		_direct(_Family(sht.synthesis_2d, sht.adjoint_synthesis_2d, kwargs, pixdims=2), alm_full, map_full, spin, True, adjoint)
 	else:
 		jobs = _batched_jobs(spin, alm_full, map_full)
 		# numpy arrays: the inputs of all spin groups start uploading now, outputs come back while the next group runs (pixell_amd/hostio.py).
@@ -270,27 +349,19 @@ def alm2map_2d(alm, map, ainfo=None, minfo=None, spin=[0, 2], deriv=False, copy=
 		if adjoint: jobs = sorted(jobs, key=lambda j: -j[2].shape[-3])
 		with sht.host_pipeline([m if adjoint else a for s, a, m in jobs], [a if adjoint else m for s, a, m in jobs]):
 			for s, a, m in jobs: func(alm=a, map=m, spin=s, **kwargs)
-	if adjoint: return alm
-	else:       return map
+	return alm if adjoint else map
 
 def map2alm_2d(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, pix_tol=1e-6, analysis=None):
 	"""curvedsky.map2alm_2d + map2alm_raw_2d (curvedsky.py:822-841, 1018-1048)"""
-	if adjoint:
-		if copy and map is not None: map = map.copy()
-	else:
-		if copy and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
+	alm, map = _copy_out(alm, map, copy, alm_is_out=not adjoint)
 	mdata = _mdata(map)
 	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=adjoint, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	if deriv:
 		raise NotImplementedError("ducc does not support derivatives for map2alm operations. Can be worked around if necessary.")
 	pads = _native_pads(minfo, use_y=True)
-	if pads != ((0, 0), (0, 0)):
-		pmap = _padded_like(map, pads, fill=not adjoint)
-		res = map2alm_2d(pmap, alm=alm, ainfo=ainfo, lmax=lmax, spin=spin, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol, analysis=analysis)
-		if not adjoint: return res
-		_crop_into(map, pmap, pads)
-		return map
+	if pads != _NO_PADS:
+		return _on_padded(map, pads, not adjoint, lambda pmap: map2alm_2d(pmap, alm=alm, ainfo=ainfo, lmax=lmax, spin=spin, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol, analysis=analysis))
 	alm_full = _atleast(alm, 3)
 	map_full = _atleast(mdata, 4)
 	_check_shapes(alm_full, map_full, False)
@@ -303,76 +374,47 @@ def map2alm_2d(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], de
 	if not adjoint: jobs = sorted(jobs, key=lambda j: -j[2].shape[-3])      # (see alm2map_2d: map -> alm takes the largest group first)
 	with sht.host_pipeline([a if adjoint else m for s, a, m in jobs], [m if adjoint else a for s, a, m in jobs]):
 		for s, a, m in jobs: func(alm=a, map=m, spin=s, **kwargs)
-	if adjoint: return map
-	else:       return alm
+	return map if adjoint else alm
 
 # ---- cyl --------------------------------------------------------------------------------
-def _ring_kwargs(map, minfo, ainfo):
-	"""ring tables of the map in ducc orientation, with the flips of map2buffer expressed as
-	a descending ringstart / negative pixel stride (no copy)."""
-	assert not np.any(np.array(minfo.xpad) != 0), "partial-width maps are padded by the callers"
-	shape = map.shape; ny, nx = shape[-2:]
-	fshape, fwcs = wcsutils.flipped(shape, map.wcs, minfo.flip)
-	rinfo = get_ring_info(fshape, fwcs)
-	rows = np.arange(ny)[::-1] if minfo.flip[0] else np.arange(ny)
-	start = rows*nx + (nx-1 if minfo.flip[1] else 0)
-	return dict(theta=rinfo.theta, nphi=rinfo.nphi, phi0=rinfo.phi0, ringstart=start.astype(np.uint64),
-		pixstride=-1 if minfo.flip[1] else 1, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride)
+def _ring_kwargs(rinfo, ainfo, **more):
+	"""the keywords of the ring transforms for the ring tables rinfo (ringstart: their offsets unless given)"""
+	return dict(dict(_layout_kwargs(ainfo), theta=rinfo.theta, nphi=rinfo.nphi, phi0=rinfo.phi0, ringstart=rinfo.offsets), **more)
 
 def _flat(m):
 	return m.reshape(m.shape[:-2]+(m.shape[-2]*m.shape[-1],))
 
+def _cyl_family(map, minfo, ainfo):
+	"""the rows of the map as rings in ducc orientation, with the flips of map2buffer expressed as a descending ringstart / negative
+	pixel stride (no copy)"""
+	assert not np.any(np.array(minfo.xpad) != 0), "partial-width maps are padded by the callers"
+	shape = map.shape; ny, nx = shape[-2:]
+	fshape, fwcs = wcsutils.flipped(shape, map.wcs, minfo.flip)
+	rows = np.arange(ny)[::-1] if minfo.flip[0] else np.arange(ny)
+	start = rows*nx + (nx-1 if minfo.flip[1] else 0)
+	kw = _ring_kwargs(get_ring_info(fshape, fwcs), ainfo, ringstart=start.astype(np.uint64), pixstride=-1 if minfo.flip[1] else 1)
+	return _Family(sht.synthesis, sht.adjoint_synthesis, kw, pixdims=2, to_lib=_flat)
+
 def alm2map_cyl(alm, map, ainfo=None, minfo=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, pix_tol=1e-6):
 	"""curvedsky.alm2map_cyl + alm2map_raw_cyl (curvedsky.py:776-794, 928-962)"""
-	if copy:
-		if adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
-		elif not adjoint: map = map.copy()
+	alm, map = _copy_out(alm, map, copy, alm_is_out=adjoint)
 	mdata = _mdata(map)
 	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, pre=map.shape[:-2], dtype=A.np_dtype(mdata), convert=not adjoint, like=mdata)
 	if minfo is None: minfo = analyse_geometry(map.shape, map.wcs, tol=pix_tol)
 	pads = _native_pads(minfo, use_y=False)
-	if pads != ((0, 0), (0, 0)):
-		# partial-width map: extend the rings to the full circle (curvedsky.py:786-792)
-		pmap = _padded_like(map, pads, fill=adjoint)
-		res = alm2map_cyl(alm, pmap, ainfo=ainfo, spin=spin, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol)
-		if adjoint: return res
-		_crop_into(map, pmap, pads)
-		return map
-	kwargs = _ring_kwargs(map, minfo, ainfo)
+	if pads != _NO_PADS:      # partial-width map: the rings are extended to the full circle
+		return _on_padded(map, pads, adjoint, lambda pmap: alm2map_cyl(alm, pmap, ainfo=ainfo, spin=spin, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol))
+	fam = _cyl_family(map, minfo, ainfo)
 	alm_full = _atleast(alm, 2 if deriv else 3)
 	map_full = _atleast(mdata, 4)
 	_check_shapes(alm_full, map_full, deriv)
-	func = sht.adjoint_synthesis if adjoint else sht.synthesis
-	for I in nditer(map_full.shape[:-3]):
-		if deriv:
-			a = _contig(alm_full[I][None]); m = _flat(map_full[I])
-			func(alm=a, map=m, mode="DERIV1", spin=1, **kwargs)
-			if adjoint: alm_full[I] = a[0]
-			else: map_full[I+(0,)] *= -1
-		else:
-			for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
-				Ij = I+(slice(j1, j2),)
-				v = alm_full[Ij]; a = _contig(v)
-				func(alm=a, map=_flat(map_full[Ij]), spin=int(s), **kwargs)
-				if adjoint and a is not v: v[...] = a
-	if adjoint: return alm
-	else:       return map
-
-def jacobi_inverse(forward, approx_backward, y, niter=0):
-	"""Solve forward(x) = y given an approximate inverse B: x_0 = B y, x_{k+1} = x_k + B (y - forward(x_k))
-	(Jacobi / Richardson refinement; what curvedsky.jacobi_inverse, curvedsky.py:1122-1136, does around the ring transforms)"""
-	x = approx_backward(y)
-	for _ in range(int(niter)):
-		x = x+approx_backward(y-forward(x))
-	return x
+	_direct(fam, alm_full, map_full, spin, deriv, adjoint)
+	return alm if adjoint else map
 
 def map2alm_cyl(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], weights=None, deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, pix_tol=1e-6, niter=0, weights_order="reference"):
 	"""curvedsky.map2alm_cyl + map2alm_raw_cyl (curvedsky.py:843-873, 1050-1086): quadrature
 	weights (exact grid weights where available) + Jacobi refinement around the HIP transforms."""
-	if adjoint:
-		if copy and map is not None: map = map.copy()
-	else:
-		if copy and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
+	alm, map = _copy_out(alm, map, copy, alm_is_out=not adjoint)
 	mdata = _mdata(map)
 	# (with deriv the alm has no component axis; the reference allocates [2,nelem] here and then fails its shape check)
 	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=map.shape[:-3] if deriv else map.shape[:-2], dtype=A.np_dtype(mdata), convert=adjoint, like=mdata)
@@ -400,44 +442,14 @@ def map2alm_cyl(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], w
 		if ref_order and minfo.flip[0]: weights = weights[::-1]
 	weights = np.ascontiguousarray(weights, dtype=A.np_dtype(mdata))
 	pads = _native_pads(minfo, use_y=False)
-	if pads != ((0, 0), (0, 0)):
-		# partial-width map: zero-extend the rings to the full circle (curvedsky.py:866-871); weights are per row
-		pmap = _padded_like(map, pads, fill=not adjoint)
-		res = map2alm_cyl(pmap, alm=alm, ainfo=ainfo, lmax=lmax, spin=spin, weights=weights, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol, niter=niter, weights_order="map")
-		if not adjoint: return res
-		_crop_into(map, pmap, pads)
-		return map
-	kwargs = _ring_kwargs(map, minfo, ainfo)
+	if pads != _NO_PADS:      # partial-width map: the rings are zero-extended to the full circle; weights are per row
+		return _on_padded(map, pads, not adjoint, lambda pmap: map2alm_cyl(pmap, alm=alm, ainfo=ainfo, lmax=lmax, spin=spin, weights=weights, deriv=deriv, copy=False, verbose=verbose, adjoint=adjoint, nthread=nthread, pix_tol=pix_tol, niter=niter, weights_order="map"))
+	fam = _cyl_family(map, minfo, ainfo)
 	alm_full = _atleast(alm, 2 if deriv else 3)
 	map_full = _atleast(mdata, 4)
 	_check_shapes(alm_full, map_full, deriv)
-	if A.is_tensor(mdata): w = A.torch().as_tensor(weights, device=mdata.device)[:, None]
-	else: w = weights[:, None]
-	def wmul(m): return m*w
-	if deriv:
-		# gradient maps [ddec, dra] <-> alm through the DERIV1 transforms (curvedsky.py:1067-1076)
-		decflip = (A.torch().as_tensor([-1.0, 1.0], device=mdata.device, dtype=mdata.dtype) if A.is_tensor(mdata) else np.array([-1.0, 1.0], A.np_dtype(mdata)))[:, None, None]
-		for I in nditer(map_full.shape[:-3]):
-			shp = map_full[I].shape
-			def Y(a):   return sht.synthesis(alm=_contig(a), spin=1, mode="DERIV1", **kwargs).reshape(shp)
-			def YT(m):  return sht.adjoint_synthesis(map=_flat(_contig(m)), spin=1, mode="DERIV1", **kwargs)
-			def YTW(m): return YT(wmul(m))
-			def WY(a):  return wmul(Y(a))
-			if adjoint: map_full[I] = jacobi_inverse(YT, WY, _contig(alm_full[I][None]), niter=niter)*decflip
-			else:       alm_full[I] = jacobi_inverse(Y, YTW, map_full[I]*decflip, niter=niter)[0]
-		return map if adjoint else alm
-	for I in nditer(map_full.shape[:-3]):
-		for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
-			Ij = I+(slice(j1, j2),)
-			shp = map_full[Ij].shape
-			def Y(a):   return sht.synthesis(alm=_contig(a), spin=int(s), **kwargs).reshape(shp)
-			def YT(m):  return sht.adjoint_synthesis(map=_flat(_contig(m)), spin=int(s), **kwargs)
-			def YTW(m): return YT(wmul(m))
-			def WY(a):  return wmul(Y(a))
-			if adjoint: map_full[Ij] = jacobi_inverse(YT, WY, _contig(alm_full[Ij]), niter=niter)
-			else:       alm_full[Ij] = jacobi_inverse(Y, YTW, map_full[Ij], niter=niter)
-	if adjoint: return map
-	else:       return alm
+	_solve(fam, alm_full, map_full, spin, deriv, adjoint, niter, _weights_like(weights, mdata)[:, None])
+	return map if adjoint else alm
 
 # ---------------------------------------------------------------------------------------
 # The reference's helper entry points around the transforms, by name (curvedsky.py:900-1086, 1236-1250, 1349-1353, 1384-1473).
@@ -447,7 +459,6 @@ def map2alm_cyl(map, alm=None, ainfo=None, minfo=None, lmax=None, spin=[0, 2], w
 # ---------------------------------------------------------------------------------------
 class ShapeError(Exception): pass
 
-def get_ducc_maxlmax(name, ny): return _geo.grid_maxlmax(name, ny)
 def dangerous_dtype(dtype): return np.dtype(dtype).byteorder not in ("=", "|")
 
 def flip2slice(flips):
@@ -479,11 +490,7 @@ def prepare_raw(alm, map, ainfo=None, lmax=None, deriv=False, verbose=False, nth
 	mdata = _mdata(map)
 	alm, ainfo = prepare_alm(alm, ainfo, lmax=lmax, pre=map.shape[:-pixdims], dtype=A.np_dtype(mdata), convert=convert_alm, like=mdata)
 	alm_full = _atleast(alm, 2 if deriv else 3); map_full = _atleast(mdata, pixdims+2)
-	if deriv:
-		assert map_full.shape[-pixdims-1] == 2, "map must have shape [...,2,%s] when deriv is True" % ("nloc" if pixdims == 1 else "ny,nx")
-		assert tuple(map_full.shape[:-1-pixdims]) == tuple(alm_full.shape[:-1]), "map and alm must agree on pre-dimensions"
-	else:
-		assert tuple(map_full.shape[:-pixdims]) == tuple(alm_full.shape[:-1]), "map and alm must agree on pre-dimensions"
+	_check_shapes(alm_full, map_full, deriv, pixdims)
 	env = os.environ.get("OMP_NUM_THREADS")
 	return alm_full, map_full, ainfo, int(env) if env else int(nthread or 0)
 
@@ -533,71 +540,41 @@ def prepare_healmap(healmap, nside=None, pre=(), dtype=np.float64, like=None):
 	if healmap is not None: return healmap
 	return A.zeros(tuple(pre)+(12*int(nside)**2,), dtype, like)
 
-def _healpix_kwargs(npix, ainfo, theta_min, theta_max):
+def _healpix_family(npix, ainfo, theta_min, theta_max):
+	"""(ring tables, family) of a healpix map of npix pixels in RING order, restricted to the rings of the theta window"""
 	rinfo = apply_minfo_theta_lim(get_ring_info_healpix(npix2nside(npix)), theta_min, theta_max)
-	return rinfo, dict(theta=rinfo.theta, nphi=rinfo.nphi, phi0=rinfo.phi0, ringstart=rinfo.offsets, lmax=ainfo.lmax, mmax=ainfo.mmax,
-		mstart=ainfo.mstart, lstride=ainfo.stride)
+	return rinfo, _Family(sht.synthesis, sht.adjoint_synthesis, _ring_kwargs(rinfo, ainfo), pixdims=1, zeroed_map=True)
 
 def alm2map_healpix(alm, healmap=None, spin=[0, 2], deriv=False, adjoint=False, copy=False, ainfo=None, nside=None, theta_min=None, theta_max=None, nthread=None):
 	"""alm[..., ncomp, nelem] -> healpix map[..., ncomp, 12 nside^2] in RING order (curvedsky.alm2map_healpix, curvedsky.py:312-351);
 	adjoint: the transpose, map -> alm.  With deriv the map is [..., 2, npix] = (d/ddec, d/dra / cos dec)."""
-	if copy:
-		if adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
-		elif not adjoint and healmap is not None: healmap = healmap.clone() if A.is_tensor(healmap) else healmap.copy()
+	alm, healmap = _copy_out(alm, healmap, copy, alm_is_out=adjoint)
 	rdt = real_dtype(A.np_dtype(alm))
 	alm, ainfo = prepare_alm(alm, ainfo, dtype=rdt, convert=not adjoint, like=alm)
 	healmap = prepare_healmap(healmap, nside, alm.shape[:-2]+(2,) if deriv else alm.shape[:-1], rdt, like=alm)
 	alm_full = _atleast(alm, 2 if deriv else 3); map_full = _atleast(healmap, 3)
-	if deriv and (tuple(alm_full.shape[:-1]) != tuple(map_full.shape[:-2]) or map_full.shape[-2] != 2):
-		raise ValueError("When deriv is True, alm must have shape [...,nelem] and map shape [...,2,npix]")
-	if not deriv and tuple(alm_full.shape[:-1]) != tuple(map_full.shape[:-1]):
-		raise ValueError("alm must have shape [...,[ncomp,]nelem] and map shape [...,[ncomp,]npix]")
-	rinfo, kwargs = _healpix_kwargs(map_full.shape[-1], ainfo, theta_min, theta_max)
+	_check_shapes(alm_full, map_full, deriv, 1, ValueError, "When deriv is True, alm must have shape [...,nelem] and map shape [...,2,npix]" if deriv
+		else "alm must have shape [...,[ncomp,]nelem] and map shape [...,[ncomp,]npix]")
+	rinfo, fam = _healpix_family(map_full.shape[-1], ainfo, theta_min, theta_max)
 	if (theta_min is not None or theta_max is not None) and not adjoint: map_full[...] = 0     # rings outside the window are not written
-	func = sht.adjoint_synthesis if adjoint else sht.synthesis
-	for I in nditer(map_full.shape[:-2]):
-		if deriv:
-			a = _contig(alm_full[I][None])
-			func(alm=a, map=map_full[I], mode="DERIV1", spin=1, **kwargs)
-			if adjoint: alm_full[I] = a[0]
-			else: map_full[I+(0,)] *= -1                   # d/dtheta -> d/ddec
-		else:
-			for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
-				Ij = I+(slice(j1, j2),)
-				v = alm_full[Ij]; a = _contig(v)
-				func(alm=a, map=map_full[Ij], spin=int(s), **kwargs)
-				if adjoint and a is not v: v[...] = a
+	_direct(fam, alm_full, map_full, spin, deriv, adjoint)
 	return alm if adjoint else healmap
 
 def map2alm_healpix(healmap, alm=None, ainfo=None, lmax=None, spin=[0, 2], weights=None, deriv=False, copy=False, verbose=False, adjoint=False, niter=0, theta_min=None, theta_max=None, nthread=None):
 	"""healpix map -> alm with pixel-area weights 4 pi / npix (or `weights`) and `niter` Jacobi refinements
 	(curvedsky.map2alm_healpix, curvedsky.py:353-403; like healpy.map2alm).  adjoint: the transpose of that operator, alm -> map."""
-	if copy:
-		if adjoint and healmap is not None: healmap = healmap.clone() if A.is_tensor(healmap) else healmap.copy()
-		elif not adjoint and alm is not None: alm = alm.clone() if A.is_tensor(alm) else alm.copy()
+	alm, healmap = _copy_out(alm, healmap, copy, alm_is_out=not adjoint)
 	if deriv: raise NotImplementedError("map2alm_healpix with deriv=True is broken")          # (as in the reference, curvedsky.py:378)
 	alm, ainfo = prepare_alm(alm=alm, ainfo=ainfo, lmax=lmax, pre=healmap.shape[:-1], dtype=A.np_dtype(healmap), convert=adjoint, like=healmap)
 	alm_full = _atleast(alm, 3); map_full = _atleast(healmap, 3)
-	rinfo, kwargs = _healpix_kwargs(map_full.shape[-1], ainfo, theta_min, theta_max)
+	rinfo, fam = _healpix_family(map_full.shape[-1], ainfo, theta_min, theta_max)
 	if weights is None: weights = 4*np.pi/rinfo.npix
-	if A.is_tensor(healmap) and not np.isscalar(weights): weights = A.torch().as_tensor(np.asarray(weights), device=healmap.device)
-	for I in nditer(map_full.shape[:-2]):
-		for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
-			Ij = I+(slice(j1, j2),)
-			like = map_full[Ij]
-			def Y(a):   return sht.synthesis(alm=_contig(a), map=A.zeros(tuple(like.shape), A.np_dtype(like), like), spin=int(s), **kwargs)
-			def YT(m):  return sht.adjoint_synthesis(map=_contig(m), spin=int(s), **kwargs)
-			def YTW(m): return YT(m*weights)
-			def WY(a):  return Y(a)*weights
-			if adjoint: map_full[Ij] = jacobi_inverse(YT, WY, _contig(alm_full[Ij]), niter=niter)
-			else:       alm_full[Ij] = jacobi_inverse(Y, YTW, map_full[Ij], niter=niter)
+	_solve(fam, alm_full, map_full, spin, False, adjoint, niter, _weights_like(weights, healmap))
 	return healmap if adjoint else alm
 
 # ---------------------------------------------------------------------------------------
 # arbitrary positions: the point transforms of sht.synthesis_general (curvedsky.py:174-207, 993-1016, 1088-1120)
 # ---------------------------------------------------------------------------------------
-def _copy(x): return None if x is None else (x.clone() if A.is_tensor(x) else x.copy())
-
 def _loc_from_pos(pos):
 	"""pos [{dec,ra}, ...] -> loc [..., {codec, ra}] with ra made positive (curvedsky.py:185-193)"""
 	if A.is_tensor(pos):
@@ -615,10 +592,7 @@ def alm2map_pos(alm, pos=None, loc=None, ainfo=None, map=None, spin=[0, 2], deri
 	loc: [..., {codec,ra}].  The pre-dimensions of pos / loc come back as trailing dimensions of the map: alm [..., nelem] ->
 	map [..., npts...] (deriv: [..., 2, npts...], the declination derivative first).  adjoint: map -> alm, returns alm (with deriv
 	the exact transpose: the sign of the declination component is applied before the transform and the input is left alone)."""
-	if adjoint:
-		if copy and alm is not None: alm = _copy(alm)
-	else:
-		if copy and map is not None: map = _copy(map)
+	alm, map = _copy_out(alm, map, copy, alm_is_out=adjoint)
 	if loc is None: loc = _loc_from_pos(pos)
 	lpre = tuple(loc.shape[:-1])
 	loc = loc.reshape(-1, 2)
@@ -631,77 +605,34 @@ def alm2map_pos(alm, pos=None, loc=None, ainfo=None, map=None, spin=[0, 2], deri
 	if adjoint: return res
 	return mflat.reshape(tuple(mflat.shape[:-1])+lpre)
 
+def _points_family(loc, ainfo, epsilon, map_dtype):
+	"""the points loc [npts, 2] with ONE binning of them (sht.points_plan) for every spin group and Jacobi step"""
+	if epsilon is None: epsilon = 1e-10 if map_dtype == np.float64 else 1e-6
+	kw = dict(_layout_kwargs(ainfo), loc=loc, epsilon=epsilon, plan=sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon))
+	return _Family(sht.synthesis_general, sht.adjoint_synthesis_general, kw, pixdims=1, contig_read=True, signed_adjoint=True)
+
 def alm2map_raw_general(alm, map, loc, ainfo=None, spin=[0, 2], deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, epsilon=None):
 	"""alm [..., ncomp, nelem] -> map [..., ncomp, npts] at loc [npts, 2] (curvedsky.alm2map_raw_general, curvedsky.py:993-1016); adjoint: the
 	transpose.  deriv: alm [..., nelem] -> map [..., 2, npts] = (d/ddec, d/dra / cos dec)."""
-	if copy:
-		if adjoint: alm = _copy(alm)
-		else: map = _copy(map)
+	alm, map = _copy_out(alm, map, copy, alm_is_out=adjoint)
 	alm_full, map_full, ainfo, nthread = prepare_raw(alm, map, ainfo=ainfo, deriv=deriv, nthread=nthread, pixdims=1, convert_alm=not adjoint)
-	if epsilon is None: epsilon = 1e-10 if A.np_dtype(map_full) == np.float64 else 1e-6
-	kw = dict(loc=loc, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride, epsilon=epsilon)
-	kw["plan"] = sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon)     # one binning of the points for every spin group
-	func = sht.adjoint_synthesis_general if adjoint else sht.synthesis_general
-	for I in nditer(map_full.shape[:-2]):
-		if deriv:
-			a = _contig(alm_full[I][None])
-			if adjoint:
-				m = map_full[I]*_dec_flip(map_full)
-				func(alm=a, map=_contig(m), mode="DERIV1", spin=1, **kw); alm_full[I] = a[0]
-			else:
-				func(alm=a, map=map_full[I], mode="DERIV1", spin=1, **kw)
-				map_full[I+(0,)] *= -1                   # d/dtheta -> d/ddec
-		else:
-			for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
-				Ij = I+(slice(j1, j2),)
-				v = alm_full[Ij]; a = _contig(v)
-				func(alm=a, map=_contig(map_full[Ij]) if adjoint else map_full[Ij], spin=int(s), **kw)
-				if adjoint and a is not v: v[...] = a
+	_direct(_points_family(loc, ainfo, epsilon, A.np_dtype(map_full)), alm_full, map_full, spin, deriv, adjoint)
 	return alm if adjoint else map
-
-def _dec_flip(like):
-	f = np.array([-1.0, 1.0])[:, None]
-	return A.torch().as_tensor(f, dtype=like.dtype, device=like.device) if A.is_tensor(like) else f.astype(like.dtype)
 
 def map2alm_raw_general(map, loc, alm=None, ainfo=None, lmax=None, spin=[0, 2], weights=None, deriv=False, copy=False, verbose=False, adjoint=False, nthread=None, niter=0, epsilon=None):
 	"""values at loc [npts, 2] -> alm: weighted adjoint synthesis (pixel weights `weights`, default 1) with `niter` Jacobi refinements
 	(curvedsky.map2alm_raw_general, curvedsky.py:1088-1120).  adjoint: the transpose of that operator, alm -> map."""
-	if adjoint:
-		if copy and map is not None: map = _copy(map)
-	else:
-		if copy and alm is not None: alm = _copy(alm)
-	if epsilon is None: epsilon = 1e-10 if A.np_dtype(_mdata(map)) == np.float64 else 1e-6
+	alm, map = _copy_out(alm, map, copy, alm_is_out=not adjoint)
 	alm_full, map_full, ainfo, nthread = prepare_raw(alm, map, ainfo=ainfo, lmax=lmax, deriv=deriv, nthread=nthread, pixdims=1, convert_alm=adjoint)
-	kw = dict(loc=loc, lmax=ainfo.lmax, mmax=ainfo.mmax, mstart=ainfo.mstart, lstride=ainfo.stride, epsilon=epsilon)
-	kw["plan"] = sht.points_plan(loc, ainfo.lmax, ainfo.mmax, ainfo.mstart, ainfo.stride, epsilon)     # shared by the spin groups and the Jacobi steps
-	if weights is None: weights = 1.0
-	if A.is_tensor(map_full) and not np.isscalar(weights): weights = A.torch().as_tensor(np.asarray(weights), device=map_full.device)
-	for I in nditer(map_full.shape[:-2]):
-		if deriv:
-			def Y(a):   return sht.synthesis_general(alm=_contig(a), mode="DERIV1", spin=1, **kw)
-			def YT(m):  return sht.adjoint_synthesis_general(map=_contig(m), mode="DERIV1", spin=1, **kw)
-			def YTW(m): return YT(m*weights)
-			def WY(a):  return Y(a)*weights
-			flip = _dec_flip(map_full)
-			if adjoint: map_full[I] = jacobi_inverse(YT, WY, _contig(alm_full[I][None]), niter=niter)*flip
-			else:       alm_full[I] = jacobi_inverse(Y, YTW, map_full[I]*flip, niter=niter)[0]
-		else:
-			for s, j1, j2 in enmap.spin_helper(spin, alm_full.shape[-2]):
-				Ij = I+(slice(j1, j2),)
-				def Y(a, s=s):   return sht.synthesis_general(alm=_contig(a), spin=int(s), **kw)
-				def YT(m, s=s):  return sht.adjoint_synthesis_general(map=_contig(m), spin=int(s), **kw)
-				def YTW(m): return YT(m*weights)
-				def WY(a):  return Y(a)*weights
-				if adjoint: map_full[Ij] = jacobi_inverse(YT, WY, _contig(alm_full[Ij]), niter=niter)
-				else:       alm_full[Ij] = jacobi_inverse(Y, YTW, map_full[Ij], niter=niter)
+	fam = _points_family(loc, ainfo, epsilon, A.np_dtype(map_full))
+	_solve(fam, alm_full, map_full, spin, deriv, adjoint, niter, _weights_like(1.0 if weights is None else weights, map_full))
 	return map if adjoint else alm
 
 # ---------------------------------------------------------------------------------------
 # 1-D transforms: radial profiles <-> functions of l, as m = 0 transforms on rings of one pixel (curvedsky.py:510-554)
 # ---------------------------------------------------------------------------------------
 def _m0_kwargs(theta, lmax):
-	rinfo = get_ring_info_radial(theta)
-	return dict(theta=rinfo.theta, nphi=rinfo.nphi, phi0=rinfo.phi0, ringstart=rinfo.offsets, spin=0, lmax=int(lmax), mmax=0, mstart=np.zeros(1, np.uint64))
+	return _ring_kwargs(get_ring_info_radial(theta), alm_info(lmax=lmax, mmax=0), spin=0)
 
 def profile2harm(br, r, lmax=None, oversample=1, left=None, right=None):
 	"""br[..., nr] sampled at ascending radii r (radians) -> bl[..., lmax+1] with b(r) = sum_l (2l+1)/(4 pi) b_l P_l(cos r): the

@@ -237,12 +237,13 @@ def ring_plan(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride=1, pixst
 	return _cached_plan(key, make)
 
 def _ncomp(spin, mode):
+	"""(alm components, map components) of a call; the one place that refuses an unknown mode"""
 	if mode == "DERIV1": return 1, 2
+	if mode != "STANDARD": raise ValueError("unknown mode '%s'" % str(mode))
 	return (1, 1) if spin == 0 else (2, 2)
 
 def _check_pair(alm, map, spin, mode, pixdims):
 	nca, ncm = _ncomp(spin, mode)
-	if mode not in ("STANDARD", "DERIV1"): raise ValueError("unknown mode '%s'" % str(mode))
 	if alm.ndim == 3 and map.ndim == 2+pixdims:          # a batch of independent maps (ours; ducc takes one map per call)
 		if alm.shape[0] != map.shape[0]: raise ValueError("batched call: alm and map disagree on the batch size")
 		alm, map = alm[0], map[0]
@@ -347,20 +348,26 @@ def adjoint_analysis_2d(*, alm, map, spin, lmax, geometry, mmax=None, mstart=Non
 	_run_ana(plan, map, alm, spin, True, analysis)
 	return plan if return_plan else map
 
-def _ring_args(alm, map, theta, nphi, phi0, ringstart, lmax, mmax, mstart, spin, lstride, pixstride, mode):
+def _missing_map(alm, shape):
+	"""the map a call without one returns: zeros of the real type of alm, next to it"""
+	return A.zeros(shape, np.float32 if A.np_dtype(alm) == np.complex64 else np.float64, like=alm)
+
+def _missing_alm(map, pre, lmax, mstart, lstride):
+	"""the alm a call without one returns: zeros [pre..., nelem] of the layout, of the complex type of map, next to it"""
+	nelem = int(np.max(np.asarray(mstart).astype(np.int64))+lmax*lstride+1)
+	return A.zeros(tuple(pre)+(nelem,), np.complex64 if A.np_dtype(map) == np.float32 else np.complex128, like=map)
+
+def _ring_args(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride, pixstride):
 	if mmax is None: mmax = lmax
 	if mstart is None: mstart = tri_mstart(lmax, mmax)
-	return ring_plan(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride, pixstride), mmax, mstart
+	return ring_plan(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride, pixstride), mstart
 
 def synthesis(*, alm, theta, nphi, phi0, ringstart, lmax, mmax=None, mstart=None, spin=0, map=None, lstride=1, pixstride=1, nthreads=0, mode="STANDARD"):
 	"""ducc0.sht.experimental.synthesis as called at curvedsky.py:936-960 (map[nc, npix])"""
-	plan, mmax, mstart = _ring_args(alm, map, theta, nphi, phi0, ringstart, lmax, mmax, mstart, spin, lstride, pixstride, mode)
-	nca, ncm = _ncomp(spin, mode)
+	plan, mstart = _ring_args(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride, pixstride)
 	if map is None:
 		rs_ = np.asarray(ringstart).astype(np.int64); last_ = rs_+(np.asarray(nphi).astype(np.int64)-1)*pixstride
-		npix = int(max(rs_.max(), last_.max())+1)
-		rdt = np.float32 if A.np_dtype(alm) == np.complex64 else np.float64
-		map = A.zeros((ncm, npix), rdt, like=alm)
+		map = _missing_map(alm, (_ncomp(spin, mode)[1], int(max(rs_.max(), last_.max())+1)))
 	_check_pair(alm, map, spin, mode, 1)
 	_run_syn(plan, alm, map, spin, mode, False)
 	synthesis.last_plan = plan
@@ -368,12 +375,8 @@ def synthesis(*, alm, theta, nphi, phi0, ringstart, lmax, mmax=None, mstart=None
 
 def adjoint_synthesis(*, map, theta, nphi, phi0, ringstart, lmax, mmax=None, mstart=None, spin=0, alm=None, lstride=1, pixstride=1, nthreads=0, mode="STANDARD"):
 	"""ducc0.sht.experimental.adjoint_synthesis as called at curvedsky.py:1068-1084"""
-	plan, mmax, mstart = _ring_args(alm, map, theta, nphi, phi0, ringstart, lmax, mmax, mstart, spin, lstride, pixstride, mode)
-	nca, ncm = _ncomp(spin, mode)
-	if alm is None:
-		nelem = int(np.max(np.asarray(mstart).astype(np.int64))+lmax*lstride+1)
-		cdt = np.complex64 if A.np_dtype(map) == np.float32 else np.complex128
-		alm = A.zeros((nca, nelem), cdt, like=map)
+	plan, mstart = _ring_args(theta, nphi, phi0, ringstart, lmax, mmax, mstart, lstride, pixstride)
+	if alm is None: alm = _missing_alm(map, (_ncomp(spin, mode)[0],), lmax, mstart, lstride)
 	_check_pair(alm, map, spin, mode, 1)
 	_run_syn(plan, alm, map, spin, mode, True)
 	adjoint_synthesis.last_plan = plan
@@ -446,13 +449,8 @@ def synthesis_general(*, alm, loc, spin, lmax, mmax=None, mstart=None, lstride=1
 	map [ncm, npts] (or [nb, ncm, npts]) at loc [npts, 2] = (theta, phi).  numpy in, numpy out; a CUDA tensor stays on its device.
 	epsilon: relative L2 accuracy (default 1e-10 for float64 maps, 1e-6 for float32), within [1e-13, 0.1].
 	plan (ours): a points_plan of these points to reuse (its epsilon and layout apply)."""
-	nca, ncm = _ncomp(spin, mode)
-	if mode not in ("STANDARD", "DERIV1"): raise ValueError("unknown mode '%s'" % str(mode))
 	npts = int(loc.shape[0])
-	if map is None:
-		rdt = np.float32 if A.np_dtype(alm) == np.complex64 else np.float64
-		shape = tuple(alm.shape[:-2])+(ncm, npts)
-		map = A.zeros(shape, rdt, like=alm)
+	if map is None: map = _missing_map(alm, tuple(alm.shape[:-2])+(_ncomp(spin, mode)[1], npts))
 	_check_pair(alm, map, spin, mode, 1)
 	if map.shape[-1] != npts: raise ValueError("map has %d points, loc %d" % (map.shape[-1], npts))
 	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, A.np_dtype(map))
@@ -463,16 +461,10 @@ def synthesis_general(*, alm, loc, spin, lmax, mmax=None, mstart=None, lstride=1
 def adjoint_synthesis_general(*, map, loc, spin, lmax, mmax=None, mstart=None, lstride=1, epsilon=None, mode="STANDARD", alm=None, nthreads=0, plan=None):
 	"""ducc0.sht.experimental.adjoint_synthesis_general as called at curvedsky.py:1104-1115: the exact transpose of synthesis_general,
 	map [ncm, npts] -> alm [nca, nelem] (overwritten; allocated when None)"""
-	nca, ncm = _ncomp(spin, mode)
-	if mode not in ("STANDARD", "DERIV1"): raise ValueError("unknown mode '%s'" % str(mode))
 	if mmax is None: mmax = lmax
 	if mstart is None: mstart = tri_mstart(lmax, mmax)
 	npts = int(loc.shape[0])
-	if alm is None:
-		nelem = int(np.max(np.asarray(mstart).astype(np.int64))+lmax*lstride+1)
-		cdt = np.complex64 if A.np_dtype(map) == np.float32 else np.complex128
-		shape = tuple(map.shape[:-2])+(nca, nelem)
-		alm = A.zeros(shape, cdt, like=map)
+	if alm is None: alm = _missing_alm(map, tuple(map.shape[:-2])+(_ncomp(spin, mode)[0],), lmax, mstart, lstride)
 	_check_pair(alm, map, spin, mode, 1)
 	if map.shape[-1] != npts: raise ValueError("map has %d points, loc %d" % (map.shape[-1], npts))
 	plan = _use_plan(plan, loc, lmax, mmax, mstart, lstride, epsilon, A.np_dtype(map))
@@ -481,6 +473,7 @@ def adjoint_synthesis_general(*, map, loc, spin, lmax, mmax=None, mstart=None, l
 		return alm
 	_run_points(plan, alm, map, spin, mode, True)
 	return alm
+
 
 _gridweights_cache = {}
 def rotate_alm(alm, lmax, psi, theta, phi, nthreads=1):
