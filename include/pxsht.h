@@ -365,6 +365,28 @@ int pxm_thumbnails(int nmap, int ny, int nx, const void* d_maps, int map_dtype, 
                    int64_t nobj, const double* d_obj, int oy, int ox, int proj, double cdelt_y, double crpix_y, double cdelt_x, double crpix_x,
                    int order, int border_y, int border_x, double cval, int pol, int qcomp, int ucomp, void* d_out, int device, void* stream);
 
+/* connected components, per-label reductions and the per-pixel solve of the source finder (pixell/analysis.py:553-564: scipy.ndimage.label,
+ * center_of_mass, maximum; :1052-1060 solve_mapsys: np.linalg.solve / inv per pixel).  All arrays DEVICE unless marked HOST.
+ * pxm_label: d_labels (int32 [ny][nx], 16-byte aligned) = 0 where d_mask (uint8 [ny][nx]) is 0 and 1 .. n on its n connected components,
+ *   numbered in ascending order of their lowest flat pixel index (scipy.ndimage.label's numbering: a raster-order flood fill): a pure
+ *   function of the mask, the same bit for bit from run to run.  connectivity 1: 4-neighbours, 2: 8-neighbours.  wrap_x = 1: column nx-1
+ *   is a neighbour of column 0.  ny nx < 2^31.  *count (HOST, may be NULL) receives n, and the call waits for the stream to read it.
+ * pxm_label_stats: reductions over the pixels of every label 1 .. nlabel of d_labels (int32 [ny][nx], values 0 .. nlabel, 0 is skipped, from
+ *   any source).  d_v, d_w: value and weight maps [ny][nx], f32 | f64 each by its dtype code, or NULL (w = 1; without d_v: sum_v 0, vmax
+ *   and vmin NaN, the args -1).  Per label l, at index l-1: d_count (int64) pixels; d_box (int32 [4][nlabel]) ymin, ymax, xmin, xmax;
+ *   d_sums (f64 [4][nlabel]) sum w, sum w y, sum w x, sum v; d_vmax, d_vmin (f64) and d_argmax, d_argmin (int64: the lowest flat index
+ *   that holds the value; -0 counts as +0).  A label without pixels: count 0, box (ny, -1, nx, -1), NaN, -1.  Everything but the four
+ *   sums is independent of the order of execution; the sums are FP64 atomic adds in arrival order.  A label outside 0 .. nlabel makes the
+ *   call fail (that pixel is skipped, nothing is written out of range).  The call waits for the stream to learn this.
+ * pxm_solve_mapsys: d_flux[a][p] = (K_p^-1 r_p)[a], d_dflux[a][p] = sqrt((K_p^-1)[a][a]) for K_p[a][b] = d_kappa[a][b][p] and
+ *   r_p[a] = d_rho[a][p], p < npix, n = 2 .. 8 (others: unsupported); all four arrays of one dtype, f32 | f64, FP64 arithmetic:
+ *   Gauss-Jordan elimination with partial pivoting.  A pixel with a zero pivot gets NaN in all its outputs.  No wait. */
+int pxm_label(int ny, int nx, const void* d_mask, int connectivity, int wrap_x, int32_t* d_labels, int64_t* count, int device, void* stream);
+int pxm_label_stats(int ny, int nx, const int32_t* d_labels, int64_t nlabel, const void* d_v, int v_dtype, const void* d_w, int w_dtype,
+                    int64_t* d_count, int32_t* d_box, double* d_sums, double* d_vmax, double* d_vmin, int64_t* d_argmax, int64_t* d_argmin,
+                    int device, void* stream);
+int pxm_solve_mapsys(int n, int64_t npix, const void* d_kappa, const void* d_rho, void* d_flux, void* d_dflux, int dtype, int device, void* stream);
+
 /* 1 if the engine can transform this length (2,3,5-smooth or prime factors small enough) */
 int pxf_fft_supported(int64_t n);
 int64_t pxf_fft_good_size(int64_t n);

@@ -61,7 +61,7 @@ struct DevBuf {
 // on one stream are ordered by the stream.  The reference is found under the registry's lock and stays valid until the stream is
 // released (entries never move); the caller grows it with ensure() and launches outside the lock.  Growing hands the old block to the
 // arena, which synchronises the device before the block serves anybody else: the stream's earlier kernels may still read it.
-enum ScratchSlot : int { SCR_FOURSTEP, SCR_BLUESTEIN, SCR_C2R, SCR_ALM2CL, SCR_SRC_FIXED, SCR_SRC_PAIRS, SCR_DISTANCE, SCR_THUMBS };
+enum ScratchSlot : int { SCR_FOURSTEP, SCR_BLUESTEIN, SCR_C2R, SCR_ALM2CL, SCR_SRC_FIXED, SCR_SRC_PAIRS, SCR_DISTANCE, SCR_THUMBS, SCR_LABEL };
 DevBuf& stream_scratch(ScratchSlot slot, int device, void* stream);
 void stream_scratch_release(int device, void* stream);      // a stream is about to be destroyed: a recycled handle must not inherit a stale buffer
 

@@ -183,6 +183,14 @@ static inline int atomicMin(int* p, int v) { int old = __atomic_load_n(p, __ATOM
 static inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 static inline int atomicMax(int* p, int v) { int old = __atomic_load_n(p, __ATOMIC_RELAXED); while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {} return old; }
 static inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) { unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED); while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {} return old; }
+static inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) { unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED); while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {} return old; }
+static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+// relaxed atomic loads (label.hip: the find loops of a union-find that other lanes link with atomicMin); the scope has no meaning here
+#define __HIP_MEMORY_SCOPE_WORKGROUP 3
+#define __HIP_MEMORY_SCOPE_AGENT 4
+#define __hip_atomic_load(p, order, scope) __atomic_load_n((p), (order))
+static inline int __shfl_xor(int v, int mask) { return (int)pxsim::xchg((uint64_t)(uint32_t)v, pxsim::lane_id() ^ mask); }
+static inline long long __shfl_xor(long long v, int mask) { return (long long)pxsim::xchg((uint64_t)v, pxsim::lane_id() ^ mask); }
 static inline float __fmul_rn(float a, float b) { volatile float r = a*b; return r; }
 static inline float __fadd_rn(float a, float b) { volatile float r = a+b; return r; }
 static inline int __shfl(int v, int src) { return (int)pxsim::xchg((uint64_t)(uint32_t)v, src); }

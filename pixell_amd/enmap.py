@@ -824,6 +824,16 @@ def labeled_distance_transform(labels, omap=None, odomains=None, rmax=None, meth
 	do = odomains if odomains is not None else _wrap(dd.reshape(full), labels)
 	return oo, do
 
+def map_mul(mat, vec):
+	"""Elementwise matrix multiplication mat*vec along the last non-pixel axes; the result has the shape of vec (enmap.map_mul,
+	enmap.py:1418-1427).  A mat of three axes or fewer is a plain product.  Host maps or device maps (an einsum of torch's there)."""
+	m, v = _data(mat), _data(vec)
+	like = mat if hasattr(mat, "wcs") else vec
+	if not hasattr(m, "ndim"): m = np.asarray(m)
+	if m.ndim <= 3: return _wrap(m*v, like) if hasattr(like, "wcs") else m*v
+	res = A.torch().einsum("...abyx,...byx->...ayx", m, v) if A.is_tensor(m) else np.einsum("...abyx,...byx->...ayx", m, v)
+	return _wrap(res, like) if hasattr(like, "wcs") else res
+
 def _mask_not(mask): return _wrap(_data(mask) == 0, mask)
 
 def grow_mask(mask, r):
@@ -904,3 +914,8 @@ for _cls in (ndmap, dmap):
 	_cls.shrink_mask  = lambda self, r: shrink_mask(self, r)
 	_cls.apod_mask    = lambda self, **kw: apod_mask(self, **kw)
 	_cls.apod         = lambda self, width, **kw: apod(self, width, **kw)
+	_cls.label        = lambda self, **kw: _label(self, **kw)
+
+def _label(mask, **kw):
+	from . import labels
+	return labels.label(mask, **kw)
