@@ -276,6 +276,34 @@ int pxm_deflect(int64_t npts, int ny, int nx, double dec0, double ddec, double r
                 const void* d_grad, int grad_dtype, int64_t grad_cstride, int geodesic, double* d_loc, double* d_psi, int device, void* stream);
 int pxm_rotate_pol(int64_t npts, int npair, void* a, void* b, int64_t pair_stride, int dtype, const double* d_psi, int spin, int device, void* stream);
 
+/* the Doppler boost of maps (pixell/aberration.py): the values of pixel maps at displaced pixels, and the modulation.
+ * pxm_plan_map_points: a plan for the trigonometric interpolation of maps [ny][nx] at npts points (aberration.interpol_map, aberration.py:246-270,
+ *   whose ducc0.nufft.u2nu this replaces).  d_pix: DEVICE f64 [{y, x}][npts] in pixels, any finite value (wrapped onto the periodic grid), read
+ *   while the plan is made (sorted into the plan).  With g = the map (ydouble = 0, N1 = ny), or the map continued over the pole (ydouble = 1,
+ *   N1 = 2 ny: g[ny + r][x] = map[ny - 1 - r][x - nx/2]), N2 = nx and G = fft2(g), the value at (y, x) is
+ *   Re sum_{j1, j2} G[j1][j2] exp(2 pi i (k(j1, N1) y / N1 + k(j2, N2) x / N2)) / (N1 N2), k(j, N) = j for j <= (N - 1)/2, j - N above: the whole
+ *   band, the Nyquist terms of an even axis split between +N/2 and -N/2 so that real maps give this number with no imaginary part to drop
+ *   (two maps travel as one complex grid): half and half, and the corner G[N1/2][N2/2] of two even axes as cos(pi (y + x)).
+ *   epsilon in [1e-13, 0.1]: relative L2 accuracy.  N1 and nx must be transformable by the FFT engine.  Synchronises `stream` once.  The plan is
+ *   a pxs_plan: pxs_plan_destroy frees it, pxs_plan_query knows "kernel_width", "fine_ntheta", "fine_nphi", "npts", "plan_us" and
+ *   "stage_us_fft" / "_grid" / "_interp" as for pxs_plan_points, pxs_plan_option "profile"; pxs_synthesis refuses it.
+ * pxm_map_points: d_out[c][i] = the value of map c at point i, for ncomp maps (f32 | f64, ny*nx contiguous pixels each, map_cstride elements
+ *   apart) into d_out (f32 | f64, components out_cstride elements apart).  Pairs of maps go through one complex grid each, one pair at a
+ *   time: pack (and double), 2-D FFT, deapodise and zero-pad to the fine grid (oversampling 2), inverse FFT, interpolate; the plan keeps
+ *   16 B x fine_ntheta x fine_nphi + 16 B x N1 x nx of scratch and 24 B per point.  FP64 arithmetic for both dtypes.  Asynchronous: calls on
+ *   one plan from different streams are ordered by the plan's last-use event.  Forward only.
+ * pxm_modulate: in place, aberration.apply_modulation (aberration.py:285-354) on ncomp <= 64 maps (f32 | f64, npix contiguous pixels each,
+ *   map_cstride elements apart) under the modulation d_A (npix values of the maps' dtype).  mode: PXM_MOD_NONE; PXM_MOD_T2T: map *= A, with
+ *   dipole != 0 component 0 gets (A - 1) T0 / map_unit added; PXM_MOD_T2LIN / PXM_MOD_LIN2T: true temperature <-> linearised units (proportional to
+ *   flux density at `freq` Hz, about the monopole T0 K, maps in units of map_unit K); PXM_MOD_LIN2LIN: LIN2T under A = 1, then T2LIN.  Bit c of
+ *   spin0_mask says component c is a scalar: with dipole != 0 those keep the monopole's own boost (the CMB dipole).  LIN2T takes off
+ *   utils.T_cmb = 2.72548 K, not T0, as the reference does.  FP64 arithmetic for both dtypes, differences of Planck functions in closed form. */
+enum { PXM_MOD_NONE = 0, PXM_MOD_T2T = 1, PXM_MOD_T2LIN = 2, PXM_MOD_LIN2T = 3, PXM_MOD_LIN2LIN = 4 };
+int pxm_plan_map_points(pxs_plan** plan, int ny, int nx, int ydouble, int64_t npts, const double* d_pix, double epsilon, int device, void* stream);
+int pxm_map_points(pxs_plan* plan, int ncomp, const void* d_maps, int map_dtype, int64_t map_cstride, void* d_out, int out_dtype, int64_t out_cstride, void* stream);
+int pxm_modulate(int64_t npix, int ncomp, void* d_map, int dtype, int64_t map_cstride, const void* d_A, uint64_t spin0_mask,
+                 int mode, int dipole, double T0, double freq, double map_unit, int device, void* stream);
+
 /* radially symmetric objects painted into a map, and radial sums read back out around a catalogue (pixell/pointsrcs.py:35-210 sim_objects /
  * radial_sum; cython/srcsim_core.c).  The map is [ncomp][ny][nx] on the separable CAR grid dec0 + y ddec, ra0 + x dra (radians, as in
  * the deflection call above; nx |dra| = 2 pi: the columns wrap), f32 | f64, components map_cstride elements apart.  Pixel and object

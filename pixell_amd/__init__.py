@@ -6,6 +6,7 @@
   pixell_amd.enmap      the few enmap pieces the path needs (ndmap, fullsky_geometry, fft, ifft)
   pixell_amd.pointsrcs  sim_objects / radial_sum / radial_bin: painting catalogues, radial profiles
   pixell_amd.reproject  thumbnails / thumbnails_ivar: catalogue cut-outs for stacking, the whole catalogue in one launch
+  pixell_amd.aberration boost_map / deboost_map / Aberrator / Modulator: the Doppler boost of maps (aberration + modulation)
   pixell_amd.distances  find_edges / distance_from_points behind enmap.distance_from, distance_transform, apod_mask
 All arithmetic runs in hand-written HIP kernels (pixell_amd/csrc) behind include/pxsht.h.
 """

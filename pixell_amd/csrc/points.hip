@@ -7,6 +7,9 @@
 //   adjoint   the exact transpose of every step, in reverse order (spread, FFT, truncate + deapodise, inverse FFT, fold, adjoint
 //             CC synthesis)
 //
+//   map pts   a pixel map instead of an alm (pxm_plan_map_points; aberration.interpol_map): map [ny][nx] --continued over the pole (ydouble)
+//             or as it is--> g --2-D FFT--> the whole band, Nyquist terms split, deapodised and zero-padded --> the same last two steps
+//
 // g is exactly a 2-D trigonometric polynomial with |k_theta| <= lmax, |m| <= mmax: sLambda_lm(-theta) = (-1)^(m+s) sLambda_lm(theta),
 // and (-theta, phi) is the point (theta, phi + pi), so the continuation of ring j past the pole is ring j shifted by half a turn
 // times (-1)^s.  Two real fields travel in one complex grid (Q + iU, or two spin-0 maps).
@@ -209,6 +212,54 @@ __global__ void pt_trunc(long n1, long n2, long N1, long N2, int lmax, int mmax,
 	c[idx] = v;
 }
 
+// ---- pixel maps as the source (pxm_plan_map_points): the trigonometric interpolant of a map [ny][nx] at pixel coordinates ------------
+// pix[{y, x}][npts] in pixels, any finite value: wrapped onto the periodic grid N1 x N2 before the tile key is formed
+__global__ void mp_bin(long npts, const double* pix, long N1, long N2, long n1, long n2, int W, int nt2, double2* xu, uint32_t* key, int* bad)
+{
+	const long i = (long)blockIdx.x*blockDim.x + threadIdx.x;
+	if (i >= npts) return;
+	double y = pix[i], x = pix[npts + i];
+	if (!(fabs(y) <= 1e300) || !(fabs(x) <= 1e300)) { *bad = 1; y = 0.0; x = 0.0; }
+	y /= (double)N1; y -= floor(y);
+	x /= (double)N2; x -= floor(x);
+	const double x1 = y*(double)n1, x2 = x*(double)n2;
+	double s;
+	const long i0 = pt_first(x1, n1, W, &s), j0 = pt_first(x2, n2, W, &s);
+	xu[i] = make_double2(x1, x2);
+	key[i] = (uint32_t)((i0/PT_T)*nt2 + j0/PT_T);
+}
+// two real maps (fb may be null) -> one complex grid g[N1][nx]; ydouble: rows ny .. 2 ny - 1 are the rows ny - 1 .. 0 continued over the
+// pole, g[ny + r][k] = f[ny - 1 - r][k - nx/2] (aberration.interpol_map)
+__global__ void mp_pack(int ny, int nx, int ydouble, const void* fa, const void* fb, int dt, double2* g)
+{
+	const long N1 = ydouble ? 2L*ny : ny, idx = (long)blockIdx.x*blockDim.x + threadIdx.x;
+	if (idx >= N1*nx) return;
+	const long j = idx/nx, k = idx - j*nx;
+	const long src = j < ny ? idx : (N1 - 1 - j)*nx + (k + nx - nx/2)%nx;
+	g[idx] = make_double2(ld_real(fa, dt, src), fb ? ld_real(fb, dt, src) : 0.0);
+}
+// coarse spectrum (N1 x N2, the whole band) -> fine spectrum (n1 x n2), deapodised.  The Nyquist coefficient of an even axis goes half
+// and half to +N/2 and -N/2: the operator stays real-to-real, so the two maps packed into one complex grid do not mix.  Where both axes
+// are even the corner coefficient G[N1/2][N2/2] (real for a real map) stands for cos(pi (y + x)), the real part of its one-sided term:
+// half each to (+N1/2, +N2/2) and (-N1/2, -N2/2), nothing to the other two corners.
+__global__ void mp_pad(long n1, long n2, long N1, long N2, const double2* c, const double* d1, const double* d2, double scale, double2* f)
+{
+	const long idx = (long)blockIdx.x*blockDim.x + threadIdx.x;
+	if (idx >= n1*n2) return;
+	const long r1 = idx/n2, r2 = idx - r1*n2;
+	const long k1 = r1 <= n1/2 ? r1 : r1 - n1, k2 = r2 <= n2/2 ? r2 : r2 - n2;
+	const long a1 = k1 < 0 ? -k1 : k1, a2 = k2 < 0 ? -k2 : k2;
+	double2 v = make_double2(0.0, 0.0);
+	if (2*a1 <= N1 && 2*a2 <= N2) {
+		const double2 x = c[(k1 < 0 ? k1 + N1 : k1)*N2 + (k2 < 0 ? k2 + N2 : k2)];
+		const bool ny1 = 2*a1 == N1, ny2 = 2*a2 == N2;
+		const double share = ny1 && ny2 ? ((k1 < 0) == (k2 < 0) ? 0.5 : 0.0) : (ny1 || ny2 ? 0.5 : 1.0);
+		const double w = d1[a1]*d2[a2]*scale*share;
+		v = make_double2(x.x*w, x.y*w);
+	}
+	f[idx] = v;
+}
+
 // ---- interpolation (forward) and spreading (adjoint) -----------------------------------------------------------------------
 // one lane per point, in tile order (neighbouring lanes read neighbouring cells: the taps of a wave stay in L2), W x W taps straight
 // from the fine grid; the result goes to the point's original index
@@ -311,6 +362,7 @@ __global__ void pt_gather(long n1, long n2, int nt1, int nt2, int P, const doubl
 struct PointsState {
 	int device = 0; long npts = 0; double eps = 0, beta = 0; int W = 0;
 	int ntheta = 0, nphi = 0, lmax = 0, mmax = 0; long N1 = 0, n1 = 0, n2 = 0; int nt1 = 0, nt2 = 0;
+	bool from_map = false, ydouble = false;      // a map points plan: the coarse grid is a pixel map [ntheta][nphi] (ydouble: continued over the pole), not a CC synthesis
 	DevBuf xs, perm, off, d1, d2;       // point state: sorted fine coordinates, sorted -> original index, tile offsets, deapodisation
 	DevBuf fbuf, cbuf, fine, slab;      // scratch of a call
 	// stage timers (pxs_plan_option "profile"): device-event ms per stage, summed over the calls since enabled; plan_ms: host wall time
@@ -365,24 +417,17 @@ static long fine_size(long n) {      // >= 2n (sigma = 2), a multiple of the til
 	return PT_T*(long)pxf_fft_good_size(m);
 }
 
-PointsState* points_create(int ntheta, int nphi, int lmax, int mmax, int device, long npts, const double* d_loc, double eps, hipStream_t st)
+// The point state of a plan whose fine grid (n1, n2, W) is set: bin(xu, key, bad) launches the kernel that writes every point's fine
+// coordinates and tile key (and sets *bad for a point it refuses); the points are then sorted by tile into s->xs, s->perm, s->off.
+// Synchronises the stream once; `refused`: the error of a refused point.
+template<class Bin> static void sort_points(PointsState* s, Bin&& bin, const char* refused, hipStream_t st)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	std::unique_ptr<PointsState> s(new PointsState());
-	s->device = device; s->npts = npts; s->eps = eps; s->ntheta = ntheta; s->nphi = nphi; s->lmax = lmax; s->mmax = mmax;
-	points_kernel_params(eps, &s->W, &s->beta);
-	s->N1 = 2L*ntheta - 2;
-	s->n1 = fine_size(s->N1); s->n2 = fine_size(nphi);
-	s->nt1 = (int)(s->n1/PT_T); s->nt2 = (int)(s->n2/PT_T);
-	const long ntiles = (long)s->nt1*s->nt2;
-	PXS_REQUIRE(ntiles < (1L << 31), "pxs_plan_points: fine grid too large");
-	s->d1 = upload(deapod_table(lmax, s->n1, s->W, s->beta));
-	s->d2 = upload(deapod_table(mmax, s->n2, s->W, s->beta));
+	const long npts = s->npts, ntiles = (long)s->nt1*s->nt2;
 	s->off.alloc(sizeof(int64_t)*(ntiles + 1));
-	if (npts == 0) { PXS_HIP(hipMemsetAsync(s->off.p, 0, s->off.bytes, st)); return s.release(); }
+	if (npts == 0) { PXS_HIP(hipMemsetAsync(s->off.p, 0, s->off.bytes, st)); return; }
 	DevBuf xu(sizeof(double2)*npts), k0(sizeof(uint32_t)*npts), k1(sizeof(uint32_t)*npts), v0(sizeof(int64_t)*npts), v1(sizeof(int64_t)*npts), bad(sizeof(int));
 	PXS_HIP(hipMemsetAsync(bad.p, 0, sizeof(int), st));
-	hipLaunchKernelGGL(pt_bin, dim3(nblocks(npts, 256)), dim3(256), 0, st, npts, d_loc, s->n1, s->n2, s->W, s->nt2, xu.as<double2>(), k0.as<uint32_t>(), bad.as<int>());
+	bin(xu.as<double2>(), k0.as<uint32_t>(), bad.as<int>());
 	PXS_HIP(hipGetLastError());
 	// LSD radix sort of (tile, index), 8 bits a pass
 	int bits = 1; while ((1L << bits) < ntiles) bits++;
@@ -408,12 +453,52 @@ PointsState* points_create(int ntheta, int nphi, int lmax, int mmax, int device,
 	int hbad = 0;
 	PXS_HIP(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
 	PXS_HIP(hipStreamSynchronize(st));      // (the temporaries above are released on return)
-	PXS_REQUIRE(!hbad, "pxs_plan_points: theta outside [0, pi] or non-finite phi");
+	PXS_REQUIRE(!hbad, refused);
+}
+
+PointsState* points_create(int ntheta, int nphi, int lmax, int mmax, int device, long npts, const double* d_loc, double eps, hipStream_t st)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::unique_ptr<PointsState> s(new PointsState());
+	s->device = device; s->npts = npts; s->eps = eps; s->ntheta = ntheta; s->nphi = nphi; s->lmax = lmax; s->mmax = mmax;
+	points_kernel_params(eps, &s->W, &s->beta);
+	s->N1 = 2L*ntheta - 2;
+	s->n1 = fine_size(s->N1); s->n2 = fine_size(nphi);
+	s->nt1 = (int)(s->n1/PT_T); s->nt2 = (int)(s->n2/PT_T);
+	PXS_REQUIRE((long)s->nt1*s->nt2 < (1L << 31), "pxs_plan_points: fine grid too large");
+	s->d1 = upload(deapod_table(lmax, s->n1, s->W, s->beta));
+	s->d2 = upload(deapod_table(mmax, s->n2, s->W, s->beta));
+	PointsState* q = s.get();
+	sort_points(q, [&](double2* xu, uint32_t* key, int* bad) {
+		hipLaunchKernelGGL(pt_bin, dim3(nblocks(npts, 256)), dim3(256), 0, st, npts, d_loc, q->n1, q->n2, q->W, q->nt2, xu, key, bad); },
+		"pxs_plan_points: theta outside [0, pi] or non-finite phi", st);
 	s->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	return s.release();
 }
 
 void points_free(PointsState* s) { delete s; }
+
+// the stage timers of one call: run(stage, fn) puts fn between two events when the plan is profiled, collect() waits for them and adds
+// the times to the plan's
+struct StageTimer {
+	PointsState* s; hipStream_t st;
+	struct Ev { int stage; hipEvent_t a, b; };
+	std::vector<Ev> evs;
+	template<class F> void run(int stage, F&& fn) {
+		if (!s->prof) { fn(); return; }
+		Ev e{stage, nullptr, nullptr};
+		PXS_HIP(hipEventCreate(&e.a)); PXS_HIP(hipEventCreate(&e.b));
+		PXS_HIP(hipEventRecord(e.a, st)); fn(); PXS_HIP(hipEventRecord(e.b, st));
+		evs.push_back(e);
+	}
+	void collect() {
+		for (auto& e : evs) {
+			float ms = 0; PXS_HIP(hipEventSynchronize(e.b)); PXS_HIP(hipEventElapsedTime(&ms, e.a, e.b));
+			s->stage_ms[e.stage] += ms; (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b);
+		}
+		evs.clear();
+	}
+};
 
 static void fft2(PointsState* s, hipStream_t st, long na, long nb, double2* data, bool forward) {
 	const int64_t shape[2] = {na, nb}, strides[2] = {nb, 1};
@@ -435,22 +520,9 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 	s->cbuf.ensure(sizeof(double2)*ncoarse);
 	s->fine.ensure(sizeof(double2)*nfine);
 	double* f = s->fbuf.as<double>();
-	struct Ev { int stage; hipEvent_t a, b; };
-	std::vector<Ev> evs;
-	auto timed = [&](int stage, auto&& fn) {
-		if (!s->prof) { fn(); return; }
-		Ev e{stage, nullptr, nullptr};
-		PXS_HIP(hipEventCreate(&e.a)); PXS_HIP(hipEventCreate(&e.b));
-		PXS_HIP(hipEventRecord(e.a, st)); fn(); PXS_HIP(hipEventRecord(e.b, st));
-		evs.push_back(e);
-	};
-	auto collect = [&]() {
-		for (auto& e : evs) {
-			float ms = 0; PXS_HIP(hipEventSynchronize(e.b)); PXS_HIP(hipEventElapsedTime(&ms, e.a, e.b));
-			s->stage_ms[e.stage] += ms; (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b);
-		}
-		evs.clear();
-	};
+	StageTimer timer{s, st};
+	auto timed = [&](int stage, auto&& fn) { timer.run(stage, fn); };
+	auto collect = [&]() { timer.collect(); };
 	auto field = [&](long q) -> char* { const long b = q/ncm, c = q - b*ncm; return (char*)map.from(b).ptr + dtype_bytes(map.dtype)*c*map.cstride; };
 	if (!adjoint) {
 		timed(PT_ST_CC, [&] {
@@ -491,6 +563,61 @@ void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint,
 			if (rc != 0) throw Error(rc, pxs_last_error()); });
 	}
 	collect();
+}
+
+// ---- map points plans (pxm_plan_map_points): the same point state, fine grid and interpolation; the coarse grid is a pixel map's -----
+PointsState* mappoints_create(int ny, int nx, int ydouble, int device, long npts, const double* d_pix, double eps, hipStream_t st)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::unique_ptr<PointsState> s(new PointsState());
+	s->device = device; s->npts = npts; s->eps = eps; s->ntheta = ny; s->nphi = nx; s->from_map = true; s->ydouble = ydouble != 0;
+	points_kernel_params(eps, &s->W, &s->beta);
+	s->N1 = ydouble ? 2L*ny : ny;
+	s->lmax = (int)(s->N1/2); s->mmax = nx/2;      // (the whole band: the tables reach the Nyquist frequency)
+	s->n1 = fine_size(s->N1); s->n2 = fine_size(nx);
+	s->nt1 = (int)(s->n1/PT_T); s->nt2 = (int)(s->n2/PT_T);
+	PXS_REQUIRE((long)s->nt1*s->nt2 < (1L << 31), "pxm_plan_map_points: fine grid too large");
+	s->d1 = upload(deapod_table(s->lmax, s->n1, s->W, s->beta));
+	s->d2 = upload(deapod_table(s->mmax, s->n2, s->W, s->beta));
+	PointsState* q = s.get();
+	sort_points(q, [&](double2* xu, uint32_t* key, int* bad) {
+		hipLaunchKernelGGL(mp_bin, dim3(nblocks(npts, 256)), dim3(256), 0, st, npts, d_pix, q->N1, (long)nx, q->n1, q->n2, q->W, q->nt2, xu, key, bad); },
+		"pxm_plan_map_points: non-finite pixel coordinates", st);
+	s->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return s.release();
+}
+
+bool points_from_map(const PointsState* s) { return s->from_map; }
+
+// out[c][i] = the interpolant of map c at point i, for ncomp maps mstride elements apart (out: ostride), two maps per pass
+void mappoints_run(PointsState* s, int ncomp, const void* maps, int mdt, long mstride, void* out, int odt, long ostride, hipStream_t st)
+{
+	const long npix = (long)s->ntheta*s->nphi;
+	PXS_REQUIRE(ncomp <= 1 || ((mstride >= npix || mstride <= -npix) && (ostride >= s->npts || ostride <= -s->npts)), "pxm_map_points: the components overlap");
+	if (s->npts == 0 || ncomp == 0) return;
+	const long ncoarse = s->N1*s->nphi, nfine = s->n1*s->n2;
+	const double scale = 1.0/((double)s->N1*s->nphi);
+	try { s->cbuf.ensure(sizeof(double2)*ncoarse); s->fine.ensure(sizeof(double2)*nfine); }
+	catch (const Error& e) {
+		throw Error(e.code, "pxm_map_points: no memory for the grids of a pair of maps: coarse " + std::to_string(s->N1) + " x " + std::to_string(s->nphi) + " (" +
+			std::to_string(sizeof(double2)*ncoarse) + " bytes), fine " + std::to_string(s->n1) + " x " + std::to_string(s->n2) + " (" + std::to_string(sizeof(double2)*nfine) + " bytes): " + e.what());
+	}
+	StageTimer timer{s, st};
+	auto timed = [&](int stage, auto&& fn) { timer.run(stage, fn); };
+	for (int c = 0; c < ncomp; c += 2) {
+		const bool two = c + 1 < ncomp;
+		const char* fa = (const char*)maps + dtype_bytes(mdt)*(size_t)c*mstride; const char* fb = two ? fa + dtype_bytes(mdt)*(size_t)mstride : nullptr;
+		char* oa = (char*)out + dtype_bytes(odt)*(size_t)c*ostride; char* ob = two ? oa + dtype_bytes(odt)*(size_t)ostride : nullptr;
+		timed(PT_ST_GRID, [&] { hipLaunchKernelGGL(mp_pack, dim3(nblocks(ncoarse, 256)), dim3(256), 0, st, s->ntheta, s->nphi, s->ydouble ? 1 : 0, (const void*)fa, (const void*)fb, mdt, s->cbuf.as<double2>()); });
+		timed(PT_ST_FFT, [&] { fft2(s, st, s->N1, s->nphi, s->cbuf.as<double2>(), true); });
+		timed(PT_ST_GRID, [&] { hipLaunchKernelGGL(mp_pad, dim3(nblocks(nfine, 256)), dim3(256), 0, st, s->n1, s->n2, s->N1, (long)s->nphi,
+			s->cbuf.as<double2>(), s->d1.as<double>(), s->d2.as<double>(), scale, s->fine.as<double2>()); });
+		timed(PT_ST_FFT, [&] { fft2(s, st, s->n1, s->n2, s->fine.as<double2>(), false); });
+		timed(PT_ST_INTERP, [&] { hipLaunchKernelGGL(pt_interp, dim3(nblocks(s->npts, 256)), dim3(256), 0, st, s->npts, s->xs.as<double2>(), s->perm.as<int64_t>(),
+			s->fine.as<double2>(), s->n1, s->n2, s->W, s->beta, (void*)oa, (void*)ob, odt); });
+		PXS_HIP(hipGetLastError());
+	}
+	timer.collect();      // (profiling only: the one place a call waits for the device)
 }
 
 void points_profile(PointsState* s, bool on) { s->prof = on; for (int k = 0; k < PT_NSTAGE; k++) s->stage_ms[k] = 0; }

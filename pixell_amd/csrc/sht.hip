@@ -263,6 +263,35 @@ int pxs_plan_points(pxs_plan** plan, const pxs_plan* g, int64_t npts, const doub
 	PXS_CATCH
 }
 
+int pxm_plan_map_points(pxs_plan** plan, int ny, int nx, int ydouble, int64_t npts, const double* d_pix, double epsilon, int device, void* stream)
+{
+	PXS_TRY
+	PXS_REQUIRE(plan && ny >= 1 && nx >= 1 && npts >= 0 && (d_pix || npts == 0), "pxm_plan_map_points: bad arguments");
+	PXS_REQUIRE(ny < (1 << 30) && nx < (1 << 30), "pxm_plan_map_points: map too large");
+	PXS_REQUIRE(FftContext::supported(ydouble ? 2L*ny : ny) && FftContext::supported(nx), "pxm_plan_map_points: map sizes the FFT engine cannot transform");
+	PXS_REQUIRE(epsilon >= 1e-13 && epsilon <= 0.1, "pxm_plan_map_points: epsilon must lie in [1e-13, 0.1]");
+	PXS_HIP(hipSetDevice(device));
+	std::unique_ptr<pxs_plan> p(new pxs_plan());
+	p->device = device;
+	p->pts = mappoints_create(ny, nx, ydouble, device, (long)npts, d_pix, epsilon, (hipStream_t)stream);
+	*plan = p.release();
+	PXS_CATCH
+}
+
+int pxm_map_points(pxs_plan* p, int ncomp, const void* d_maps, int map_dtype, int64_t map_cstride, void* d_out, int out_dtype, int64_t out_cstride, void* stream)
+{
+	PXS_TRY
+	PXS_REQUIRE(p && p->pts && points_from_map(p->pts), "pxm_map_points needs a plan of pxm_plan_map_points");
+	PXS_REQUIRE(ncomp >= 0 && (ncomp == 0 || (d_maps && d_out)), "pxm_map_points: bad arguments");
+	PXS_REQUIRE((map_dtype == PX_F32 || map_dtype == PX_F64) && (out_dtype == PX_F32 || out_dtype == PX_F64), "pxm_map_points: maps and values must be float32 or float64");
+	std::lock_guard<std::mutex> plan_lock(p->call_mu);
+	PXS_HIP(hipSetDevice(p->device));
+	hipStream_t st = (hipStream_t)stream;
+	PlanUse use(p, st);
+	mappoints_run(p->pts, ncomp, d_maps, map_dtype, (long)map_cstride, d_out, out_dtype, (long)out_cstride, st);
+	PXS_CATCH
+}
+
 void pxs_plan_destroy(pxs_plan* plan) { delete plan; }
 
 int pxs_plan_option(pxs_plan* p, const char* name, int64_t value) {
@@ -679,6 +708,7 @@ int pxs_synthesis(pxs_plan* p, int spin, int mode, int adjoint, int nbatch,
 	PXS_TRY
 	PXS_REQUIRE(p && alm && map, "pxs_synthesis: null argument");
 	std::lock_guard<std::mutex> plan_lock(p->call_mu);
+	PXS_REQUIRE(!p->pts || p->pgrid, "pxs_synthesis: a map points plan interpolates maps (pxm_map_points), it has no alm");
 	PXS_REQUIRE(spin >= 0 && spin <= p->lmax + 1, "pxs_synthesis: bad spin");
 	PXS_REQUIRE(mode == PXS_MODE_STANDARD || (mode == PXS_MODE_DERIV1 && spin == 1), "DERIV1 needs spin 1");
 	PXS_REQUIRE(map_dtype == PX_F32 || map_dtype == PX_F64, "map must be float32 or float64");

@@ -29,6 +29,10 @@ void points_free(PointsState* s);
 void points_run(PointsState* s, pxs_plan* grid, int spin, int mode, int adjoint, int nb, const AlmArg& alm, const MapArg& map, hipStream_t st);
 int64_t points_query(const PointsState* s, const std::string& name);
 void points_profile(PointsState* s, bool on);
+// ... of a pixel map [ny][nx] instead of an alm (pxm_plan_map_points): pix [{y, x}][npts] in pixels
+PointsState* mappoints_create(int ny, int nx, int ydouble, int device, long npts, const double* d_pix, double eps, hipStream_t st);
+void mappoints_run(PointsState* s, int ncomp, const void* maps, int mdt, long mstride, void* out, int odt, long ostride, hipStream_t st);
+bool points_from_map(const PointsState* s);
 
 // ---- sht_grids.hip: a grid's circle of N samples, ring j at theta = (c + 2 j) pi / N
 struct GridInfo { long N; int c; bool ok; };
