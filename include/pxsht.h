@@ -393,6 +393,39 @@ int pxm_thumbnails(int nmap, int ny, int nx, const void* d_maps, int map_dtype, 
                    int64_t nobj, const double* d_obj, int oy, int ox, int proj, double cdelt_y, double crpix_y, double cdelt_x, double crpix_x,
                    int order, int border_y, int border_x, double cval, int pol, int qcomp, int ucomp, void* d_out, int device, void* stream);
 
+/* healpix pixel arithmetic (RING scheme, any nside >= 1, Gorski et al. 2005) and healpix <-> CAR reprojection by interpolation
+ * (pixell/reproject.py:118-361 map2healpix / healpix2map with method="spline": healpy.pix2ang / ang2pix / get_interp_val,
+ * coordinates.transform_euler, enmap.at, enmap.rotate_pol).  All arrays DEVICE unless marked HOST, int64 pixel indices, FP64 arithmetic,
+ * no wait.  theta is the colatitude, phi the longitude, radians; phi is taken modulo 2 pi.
+ * pxm_healpix_index: mode 0: d_out (f64 [2][n]) = (theta, phi) of the centres of the pixels d_pix_in [n] (not a number for a pixel
+ *   outside [0, 12 nside^2)); mode 1: d_pix_out [n] = the pixel that holds (d_theta[i], d_phi[i]) (-1 where they are not numbers);
+ *   mode 2: d_pix_out [4][n] and d_out (f64 [4][n]) = the four pixels and weights of the ring-bilinear value there: the two pixels
+ *   around phi on the ring above the point and on the ring below, linear in phi on each ring and in theta between them; north of the
+ *   first ring (south of the last) the four pixels of that ring share the polar part equally.  Weights are >= 0 and sum to 1.
+ * pxm_healpix_interp: d_out[m][i] = map m (ncomp maps [12 nside^2] of f32 | f64, mstride elements apart) at point i: the pixel that
+ *   holds it (order 0) or the ring-bilinear value (order 1), in the maps' dtype; not a number where the point is not a number.
+ * pxm_map2healpix: d_out[m][i] = scale times map m at the centre of healpix pixel first + i, i < n, interpolated; d_out: [ncomp] rows
+ *   ostride elements apart, f32 | f64 by out_dtype (the maps' dtype, or f32 from f64 maps).  Maps, dtypes, order, the affine map from
+ *   (dec, ra) in radians to pixels and the rewind (ref, per): as in pxm_interpol; border_y, border_x: as in pxm_thumbnails (a pixel
+ *   outside a "constant" axis gets scale cval in every map).  rot (HOST, nine doubles, row-major, or NULL): the centre's direction n is
+ *   read at M n, and every pair is rotated by -spin psi, a' = cos(spin psi) a + sin(spin psi) b, b' = -sin(spin psi) a + cos(spin psi) b,
+ *   psi = atan2(M e_ra(n) . e_dec(M n), M e_ra(n) . e_ra(M n)) (enmap.rotate_pol(., -psi, spin), reproject.py:239-243).  pairs (HOST,
+ *   int [npair][2]): (first component, spin) of the pairs (c, c + 1), which do not overlap; without rot they have no effect.
+ *   ncomp <= 32.
+ * pxm_healpix2map: d_out[m][y][x] = healpix map m at pixel (y, x) of the separable geometry dec = dec0 + y ddec, ra = ra0 + x dra
+ *   (wcs.separable_geometry), order 0 | 1 as in pxm_healpix_interp, times d_rowfac[y] (f64 [ny], or NULL); rot and pairs as in
+ *   pxm_map2healpix, with n the direction of the output pixel.  d_out in the maps' dtype.  ncomp <= 32. */
+int pxm_healpix_index(int mode, int64_t nside, int64_t n, const int64_t* d_pix_in, const double* d_theta, const double* d_phi, int64_t* d_pix_out, double* d_out,
+                      int device, void* stream);
+int pxm_healpix_interp(int64_t nside, int ncomp, const void* d_maps, int map_dtype, int64_t mstride, int64_t n, const double* d_theta, const double* d_phi,
+                       int order, void* d_out, int device, void* stream);
+int pxm_map2healpix(int ncomp, int ny, int nx, const void* d_maps, int map_dtype, int64_t mstride,
+                    double yoff, double yscale, double xoff, double xscale, double yref, double yper, double xref, double xper,
+                    int order, int border_y, int border_x, double cval, int64_t nside, int64_t first, int64_t n, const double* rot,
+                    int npair, const int* pairs, double scale, void* d_out, int out_dtype, int64_t ostride, int device, void* stream);
+int pxm_healpix2map(int ncomp, int64_t nside, const void* d_maps, int map_dtype, int64_t mstride, int ny, int nx, double dec0, double ddec, double ra0, double dra,
+                    int order, const double* rot, int npair, const int* pairs, const double* d_rowfac, void* d_out, int device, void* stream);
+
 /* connected components, per-label reductions and the per-pixel solve of the source finder (pixell/analysis.py:553-564: scipy.ndimage.label,
  * center_of_mass, maximum; :1052-1060 solve_mapsys: np.linalg.solve / inv per pixel).  All arrays DEVICE unless marked HOST.
  * pxm_label: d_labels (int32 [ny][nx], 16-byte aligned) = 0 where d_mask (uint8 [ny][nx]) is 0 and 1 .. n on its n connected components,

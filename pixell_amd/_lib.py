@@ -59,6 +59,10 @@ def _declare(lib):
 	lib.pxm_spline_filter_axes.argtypes = [i32, i32, i32, vp, i32, i64, vp, vp, i32, i32, i32, vp]
 	lib.pxm_thumbnails.argtypes = [i32, i32, i32, vp, i32, i64, dbl, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i64, vp, i32, i32, i32, dbl, dbl, dbl, dbl,
 		i32, i32, i32, dbl, i32, i32, i32, vp, i32, vp]
+	lib.pxm_healpix_index.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, i32, vp]
+	lib.pxm_healpix_interp.argtypes = [i64, i32, vp, i32, i64, i64, vp, vp, i32, vp, i32, vp]
+	lib.pxm_map2healpix.argtypes = [i32, i32, i32, vp, i32, i64, dbl, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, i32, i32, dbl, i64, i64, i64, vp, i32, vp, dbl, vp, i32, i64, i32, vp]
+	lib.pxm_healpix2map.argtypes = [i32, i64, vp, i32, i64, i32, i32, dbl, dbl, dbl, dbl, i32, vp, i32, vp, vp, vp, i32, vp]
 	lib.pxm_label.argtypes = [i32, i32, vp, i32, i32, vp, c.POINTER(i64), i32, vp]
 	lib.pxm_label_stats.argtypes = [i32, i32, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
 	lib.pxm_solve_mapsys.argtypes = [i32, i64, vp, vp, vp, vp, i32, i32, vp]
@@ -66,13 +70,13 @@ def _declare(lib):
 	lib.pxf_fft_supported.argtypes = [i64]
 	lib.pxf_fft_good_size.argtypes = [i64]; lib.pxf_fft_good_size.restype = i64
 	for name in ["pxs_plan_rings", "pxs_plan_grid2d", "pxs_plan_points", "pxs_synthesis", "pxs_analysis", "pxs_gridweights",
-			"pxs_grid_maxlmax", "pxs_plan_info", "pxs_plan_option", "pxs_plan_query", "pxf_fft_nd", "pxf_fft_supported", "pxs_profile", "pxs_profile_read", "pxs_profile_flops", "pxs_debug_theta_plan", "pxs_debug_chain", "pxs_memory", "pxa_alm2cl", "pxa_lmatmul", "pxa_rotate_alm", "pxa_bank_split", "pxa_bank_merge", "pxm_rotate_queb", "pxm_ps2d", "pxm_lbin", "pxm_bin_index", "pxm_mul_axis", "pxm_deflect", "pxm_rotate_pol", "pxm_plan_map_points", "pxm_map_points", "pxm_modulate", "pxm_sim_objects", "pxm_radial_sum", "pxm_find_edges", "pxm_distance_from", "pxm_spline_filter", "pxm_interpol", "pxm_spline_filter_axes", "pxm_thumbnails", "pxm_label", "pxm_label_stats", "pxm_solve_mapsys"]:
+			"pxs_grid_maxlmax", "pxs_plan_info", "pxs_plan_option", "pxs_plan_query", "pxf_fft_nd", "pxf_fft_supported", "pxs_profile", "pxs_profile_read", "pxs_profile_flops", "pxs_debug_theta_plan", "pxs_debug_chain", "pxs_memory", "pxa_alm2cl", "pxa_lmatmul", "pxa_rotate_alm", "pxa_bank_split", "pxa_bank_merge", "pxm_rotate_queb", "pxm_ps2d", "pxm_lbin", "pxm_bin_index", "pxm_mul_axis", "pxm_deflect", "pxm_rotate_pol", "pxm_plan_map_points", "pxm_map_points", "pxm_modulate", "pxm_sim_objects", "pxm_radial_sum", "pxm_find_edges", "pxm_distance_from", "pxm_spline_filter", "pxm_interpol", "pxm_spline_filter_axes", "pxm_thumbnails", "pxm_healpix_index", "pxm_healpix_interp", "pxm_map2healpix", "pxm_healpix2map", "pxm_label", "pxm_label_stats", "pxm_solve_mapsys"]:
 		getattr(lib, name).restype = i32
 	return lib
 
 EXPORTS = ["pxs_plan_rings", "pxs_plan_grid2d", "pxs_plan_points", "pxs_plan_destroy", "pxs_synthesis", "pxs_analysis",
 	"pxs_gridweights", "pxs_grid_maxlmax", "pxs_plan_info", "pxs_plan_option", "pxs_plan_query", "pxf_fft_nd", "pxf_fft_supported",
-	"pxf_fft_good_size", "pxs_last_error", "pxs_version", "pxs_profile", "pxs_profile_read", "pxs_profile_flops", "pxs_debug_theta_plan", "pxs_debug_chain", "pxs_memory", "pxa_alm2cl", "pxa_lmatmul", "pxa_rotate_alm", "pxa_bank_split", "pxa_bank_merge", "pxm_rotate_queb", "pxm_ps2d", "pxm_lbin", "pxm_bin_index", "pxm_mul_axis", "pxm_deflect", "pxm_rotate_pol", "pxm_plan_map_points", "pxm_map_points", "pxm_modulate", "pxm_sim_objects", "pxm_radial_sum", "pxm_find_edges", "pxm_distance_from", "pxm_spline_filter", "pxm_interpol", "pxm_spline_filter_axes", "pxm_thumbnails", "pxm_label", "pxm_label_stats", "pxm_solve_mapsys"]
+	"pxf_fft_good_size", "pxs_last_error", "pxs_version", "pxs_profile", "pxs_profile_read", "pxs_profile_flops", "pxs_debug_theta_plan", "pxs_debug_chain", "pxs_memory", "pxa_alm2cl", "pxa_lmatmul", "pxa_rotate_alm", "pxa_bank_split", "pxa_bank_merge", "pxm_rotate_queb", "pxm_ps2d", "pxm_lbin", "pxm_bin_index", "pxm_mul_axis", "pxm_deflect", "pxm_rotate_pol", "pxm_plan_map_points", "pxm_map_points", "pxm_modulate", "pxm_sim_objects", "pxm_radial_sum", "pxm_find_edges", "pxm_distance_from", "pxm_spline_filter", "pxm_interpol", "pxm_spline_filter_axes", "pxm_thumbnails", "pxm_healpix_index", "pxm_healpix_interp", "pxm_map2healpix", "pxm_healpix2map", "pxm_label", "pxm_label_stats", "pxm_solve_mapsys"]
 
 def lib_path():
 	# PIXELL_AMD_LIB: another build of the same library (kernel A/B experiments, tools/build_variants.sh, tools/gpu_v2lab.sh, tools/gpu_leg_ab.sh)
